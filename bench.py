@@ -1,12 +1,22 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the DFMIR `--model registration` train step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
 A "step" = REGISTRATIONModel.set_input + optimize_parameters (reference train.py:46-47): forward,
-backward and Adam of G/F/R on one batch of synthetic pairs already resident in HBM.  Workload at
+backward and Adam of G/F/R on one batch of synthetic pairs already resident in HBM.  Every warm-up and timed step starts
+from the same state, restored by copying the three parameter / Adam-moment arenas before the step: the weight-gradient
+kernels meet in fp32 atomics, whose rounding order differs from run to run, and Adam turns those differences into
+different weights within a few steps.  Restored, the inputs of every step and what it computes from them are the same in
+every run (to the rounding of one step).  The state is the seeded weights after two train steps with deterministic weight
+gradients (ops.set_deterministic_wgrad).  Measured on one MI355X, 2 x 3 runs of 20 steps alternating in one job: the
+restore costs 0.14 ms of a 72.6 ms step (0.2 %) against the same step without it, and steps restored to the untrained
+initial weights instead take 73.5 ms (+1.1 %), which is why the state is trained first.  Workload at
 every N: BASELINE.json configs[1] geometry -- 2-D 256x256, batch 16 PER GPU, ngf 64, fp32 (weak
-scaling; configs[2] is the same thing at N = 8).  One JSON line on rank 0 with
+scaling; configs[2] is the same thing at N = 8).  One JSON line on rank 0.  A plain run sets up, warms up, times the K
+steps and prints the headline (`value`, `ms_per_step`, `step_ms`, host enqueue time, losses).  `--dump-outputs DIR` writes
+what the last timed step handed its caller (visuals and losses) as DIR/<name>.npy.
+`--full` adds every other measurement:
   `roofline`      dominant kernel = conv3x3_split_cs_k (3x3 forward/dgrad convs, fp32 operands split into scaled
                   fp16 pairs, 3 products per MAC on v_mfma_f32_32x32x16_f16), timed live with HIP events on its
                   launch stream; achieved = ALGORITHMIC fp32 FLOP/s, peak = 2.5 PFLOP/s dense fp16;
@@ -24,7 +34,7 @@ scaling; configs[2] is the same thing at N = 8).  One JSON line on rank 0 with
   `cpu_baseline`  (N = 1) the CPU oracle = a port of the reference's PyTorch-CPU path, timed on the host cores on a
                   bounded sample: the 2-D step at 256^2 batch 1, (`also_3d_128`) the 3-D step at 128^3 and (`also_3d_big`) one
                   3-D step at 160x192x224.
-  `step_ms`       median / min / max of the K timed steps (HIP events between steps).
+  `step_ms`       median / min / max of the K timed steps (HIP events between steps; every run).
 """
 import argparse
 import json
@@ -472,6 +482,42 @@ def bench_warp_hbm(dev, pmc, reps=20, nset=4):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 20     # per array (4 MB in float32)
+DUMP_MAX_BYTES = 64 << 20    # in all: with more arrays, each one's sample shrinks to its share
+
+
+def dump_outputs(model, out_dir, seed=1234):
+    """What the last timed step handed its caller, as out_dir/<name>.npy: every visual (float32) and every loss (float64).
+    An array above its share of elements -- DUMP_MAX_ELEMS, or fewer when the files would exceed DUMP_MAX_BYTES together --
+    is replaced by a fixed, seeded sample of that many of its elements (flattened, ascending index order).  The updated
+    weights are not written: parameters whose exact gradient is zero (the biases in front of a non-affine InstanceNorm)
+    receive rounding noise, and Adam moves them by up to ~lr on the sign of that noise."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    visuals = [(n, getattr(model, n, None)) for n in model.visual_names]
+    visuals = [(n, t) for n, t in visuals if torch.is_tensor(t)]
+    losses = model.get_current_losses()
+    n_files = len(visuals) + len(losses)
+    cap = min(DUMP_MAX_ELEMS, (DUMP_MAX_BYTES - 4096 * n_files) // (4 * max(len(visuals), 1)))   # (.npy headers: 128 B)
+
+    def sample(t, k):
+        a = t.detach().float().reshape(-1)
+        if a.numel() > cap:
+            idx = np.sort(np.random.RandomState(seed + k).choice(a.numel(), cap, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+            return a.cpu().numpy()
+        return t.detach().float().cpu().numpy()
+
+    arrays = {}
+    for k, (name, t) in enumerate(visuals):
+        arrays["visual_" + name] = sample(t, k)
+    for name, v in losses.items():
+        arrays["loss_" + name] = np.array([v], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -490,6 +536,12 @@ def main():
     ap.add_argument("--roofline-steps", type=int, default=3, help="eager steps after the timed region that time the dominant kernels")
     ap.add_argument("--host-input-steps", type=int, default=5,
                     help="extra steps fed from pinned HOST memory (PCIe-inclusive rate, reported beside the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed its caller (visuals, losses) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: rooflines (dominant kernels timed over extra eager steps), "
+                         "host- and loader-fed rates, the warp HBM roofline, the 3-D steps and the CPU baselines; the "
+                         "--no-* / --*-steps / --pil-workers options shape these")
     args = ap.parse_args()
 
     from dfmir_amd import distributed as dfdist
@@ -507,7 +559,8 @@ def main():
     torch.manual_seed(0)                      # same weights on every rank (also broadcast in parallelize())
     model = REGISTRATIONModel(opt)
     timer = KernelTimer(["conv3x3_L", "wgrad3x3_L"])
-    ops.set_conv_profiler(timer)
+    if args.full:
+        ops.set_conv_profiler(timer)
 
     batches = [synth_pairs(B, S, S, dev, 1000 * rank + i) for i in range(4)]   # resident in HBM
     paths = [""] * B
@@ -521,10 +574,30 @@ def main():
         model.data_dependent_initialize(feed(0))
         model.setup(opt)
         model.parallelize()
+    # every step starts from one state (see the module docstring): two steps with deterministic weight gradients from the
+    # seeded weights, then the arenas are kept and copied back before each step
+    det_prev = ops.deterministic_wgrad()
+    ops.set_deterministic_wgrad(True)
+    for i in range(2):
+        model.set_input(feed(i))
+        model.optimize_parameters()
+    ops.set_deterministic_wgrad(det_prev)
+    start = [(o, o._steps) + tuple(t.clone() for t in (o.flat_p, o.exp_avg, o.exp_avg_sq)) for o in model.optimizers]
+    if opt.capture_step:
+        model._graph['eager_steps'] = 0           # the capture still follows two eager steps of the timed kernels
+
+    def restore():
+        for o, n, p0, m0, v0 in start:
+            o.flat_p.copy_(p0)
+            o.exp_avg.copy_(m0)
+            o.exp_avg_sq.copy_(v0)
+            o._steps = n
+
     # the step's hipGraph is captured on the third optimize_parameters call: with --warmup < 3 the missing steps are
     # run here as well (untimed), so that the timed region holds K steady-state steps and nothing else
     n_warm = max(args.warmup, 3) if opt.capture_step else args.warmup
     for i in range(n_warm):
+        restore()
         model.set_input(feed(i))
         model.optimize_parameters()
 
@@ -541,13 +614,14 @@ def main():
     if distributed:
         model._collective_timing = []             # event pairs around every wait for a gradient exchange
     fence()
-    timer.enabled = not graphed                   # HIP events cannot be recorded inside a graph replay
+    timer.enabled = args.full and not graphed     # HIP events cannot be recorded inside a graph replay
     # one HIP event between consecutive steps (recorded on the step's stream, no host wait): per-step device times for
     # the median / spread; `value` stays the wall clock of the whole region
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
+        restore()
         model.set_input(feed(i))
         model.optimize_parameters()
         marks[i + 1].record()
@@ -560,7 +634,9 @@ def main():
     model._collective_timing = None
     losses = model.get_current_losses()
     assert all(v == v and abs(v) < 1e6 for v in losses.values()), losses   # finite
-    if graphed:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
+    if graphed and args.full:
         # the dominant kernels, timed live with HIP events on their launch stream over eager steps of the same
         # workload right after the timed region (same process, same weights stream, same kernels and shapes)
         model._graph['force_eager'] = True
@@ -620,7 +696,7 @@ def main():
     # PCIe-inclusive rate: the same step when set_input() is handed pinned host tensors (what a DataLoader with
     # pin_memory delivers, dfmir_amd/data.py): never the headline value, reported as `value_host_inputs`
     host_rate = None
-    if args.host_input_steps > 0:
+    if args.full and args.host_input_steps > 0:
         hb = [tuple(t.cpu().pin_memory() for t in pair) for pair in batches]
         torch.cuda.synchronize()
         th = time.perf_counter()
@@ -635,7 +711,7 @@ def main():
     # bicubic resize 286 -> random crop 256 -> flip -> [-1, 1] -> pinned batch, in DataLoader worker processes beside the
     # training process (dfmir_amd/data.py = data/unaligned_dataset.py + base_dataset.py:82-145) -> `value_pil_loader`
     pil_rate = None
-    if args.host_input_steps > 0 and args.pil_workers > 0:
+    if args.full and args.host_input_steps > 0 and args.pil_workers > 0:
         import copy
         import tempfile
         from PIL import Image
@@ -667,13 +743,13 @@ def main():
         pil_rate = B * world * n_done / (time.perf_counter() - th) if n_done else None
         del it
     pil_by_rank = None
-    if distributed and world > 1:
+    if args.full and distributed and world > 1:
         # every rank's own loader-fed rate (x world, i.e. comparable with `value`): 8 ranks x (1 training process + pil_workers
         # loader processes) share the host's cores
         pil_by_rank = dfdist.allgather_float(float(pil_rate or 0.0), dev)
 
-    ks = ks_overlapped if graphed else timer.summary()
-    ks1 = ks_single if graphed else {}
+    ks = ks_overlapped if (graphed and args.full) else timer.summary()
+    ks1 = ks_single if (graphed and args.full) else {}
     result = None
     if rank == 0:
         pairs = B * world * args.steps
@@ -713,9 +789,6 @@ def main():
                                   "registration_model._step_pieces): every launch returns at once.  DFMIR_NO_STAGED=1 = ONE graph "
                                   "with parallel branches, whose hipGraphLaunch (ROCm 7.2) returns only when the second branch has "
                                   "been handed to the GPU: ~39 ms of a 74 ms step (profiles/r06_ab_staged.txt)"),
-            "value_host_inputs": host_rate,
-            "value_pil_loader": pil_rate,       # fed by dfmir_amd.data's DataLoader (PNG decode + transforms in worker processes)
-            "value_pil_loader_by_rank": pil_by_rank,
             "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None,
             "dtype": ("f32 (fp16x2-split MFMA, fp32 accumulate)" if (split and nprod == 3.0) else
@@ -725,6 +798,15 @@ def main():
                                    "REGISTRATIONModel.set_input+optimize_parameters (ResnetGenerator-9 + PatchNCE + 2-D "
                                    "VoxelMorph + bilinear warps, fwd+bwd+Adam), BASELINE configs[1]" % (S, S, B, args.ngf),
                        "global_batch": B * world, "parallelism": "dp%d" % world},
+            "losses": {k: round(v, 6) for k, v in losses.items()},
+        }
+        if collective is not None:
+            result["collective"] = collective
+    if rank == 0 and args.full:
+        result.update({
+            "value_host_inputs": host_rate,
+            "value_pil_loader": pil_rate,       # fed by dfmir_amd.data's DataLoader (PNG decode + transforms in worker processes)
+            "value_pil_loader_by_rank": pil_by_rank,
             "roofline": {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
                          "frac": ach / peak,
                          "issued_tflops": ach * npm, "issued_frac": ach * npm / peak, "products_per_mac": npm,
@@ -767,13 +849,9 @@ def main():
                          "wgrad_launches_timed": wg["launches"],
                          "whole_step_tflops": step_tflop * args.steps / dt if S == 256 and args.ngf == 64 else None,
                          "whole_step_note": "(%.0f - 3 x %.2f) = %.1f conv GFLOP per pair executed (key-side encoder passes "
-                                            "reused from forward()), x batch / step time" % (STEP_GF_REFERENCE, G_ENC_GF, step_gf)},
-            "losses": {k: round(v, 6) for k, v in losses.items()},
-        }
-        if collective is not None:
-            result["collective"] = collective
+                                            "reused from forward()), x batch / step time" % (STEP_GF_REFERENCE, G_ENC_GF, step_gf)}})
     dfdist.barrier()
-    if rank == 0:
+    if rank == 0 and args.full:
         ops.set_conv_profiler(None)
         if world == 1 and not args.no_3d:
             model = None
@@ -792,6 +870,7 @@ def main():
             result["cpu_baseline"] = cpu_baseline(S)
             result["cpu_baseline"]["also_3d_128"] = cpu_baseline_3d(result["cpu_baseline"]["cores"])
             result["cpu_baseline"]["also_3d_big"] = cpu_baseline_3d_big(result["cpu_baseline"]["cores"])
+    if rank == 0:
         print(json.dumps(result))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

@@ -396,6 +396,10 @@ def set_deterministic_wgrad(on):
     _DET["on"] = bool(on)
 
 
+def deterministic_wgrad():
+    return _DET["on"]
+
+
 class _DetAcc(object):
     def __init__(self, n_dw, n_db, count, x, x_amax, dy, dy_amax):
         head = int(lib().dfmir_det_head_floats())

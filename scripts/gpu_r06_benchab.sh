@@ -5,7 +5,7 @@ for rep in 1 2; do
   for v in new base; do
     unset DFMIR_HIP_LIB DFMIR_CONV3D_NO_FLOW_MARCH
     [ $v = base ] && export DFMIR_HIP_LIB=$PWD/build/ko/libdfmir_hip_r06base.so && export DFMIR_CONV3D_NO_FLOW_MARCH=1
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --pil-workers 0 2>/dev/null | tail -n 1 > $O/line_$v$rep.json
+    python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --pil-workers 0 2>/dev/null | tail -n 1 > $O/line_$v$rep.json
     python - $O/line_$v$rep.json $v <<'PY' | tee -a $O/ab.txt
 import json, sys
 r = json.load(open(sys.argv[1]))

@@ -6,7 +6,7 @@ python scripts/conv3d_step_census.py 2>&1 | grep -v amdgpu.ids > $O/conv3d_step_
 for v in new nos2; do
   unset DFMIR_CONV3D_NO_S2
   [ $v = nos2 ] && export DFMIR_CONV3D_NO_S2=1
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --pil-workers 0 2>/dev/null | tail -n 1 > $O/line_$v.json
+  python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --pil-workers 0 2>/dev/null | tail -n 1 > $O/line_$v.json
   python - $O/line_$v.json $v <<'PY' | tee -a $O/ab.txt
 import json, sys
 r = json.load(open(sys.argv[1]))

@@ -210,7 +210,7 @@ def test_bench_eight_ranks_as_the_driver_launches_it():
     env = dict(os.environ, DFMIR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "3",
-           "--batch", "2", "--size", "64", "--ngf", "8"]
+           "--batch", "2", "--size", "64", "--ngf", "8", "--full"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -277,7 +277,8 @@ def test_bench_two_gpus_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("DFMIR_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "4"]
+           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "4",
+           "--full"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -295,7 +296,7 @@ def test_bench_single_rank_over_rccl():
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     env.pop("DFMIR_DIST_BACKEND", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "4", "--batch", "2",
-           "--size", "64", "--ngf", "8", "--no-3d", "--no-cpu-baseline"]
+           "--size", "64", "--ngf", "8", "--full", "--no-3d", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -356,7 +357,7 @@ def test_bench_two_ranks_as_the_driver_launches_it():
     env = dict(os.environ, DFMIR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3",
-           "--batch", "2", "--size", "64", "--ngf", "8"]
+           "--batch", "2", "--size", "64", "--ngf", "8", "--full"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -1,6 +1,8 @@
 """CPU: pin the oracle (oracle/dfmir_oracle.py) against the golden vectors captured from the
 reference itself (tests/golden/make_golden.py).  Tolerance: 1e-4 relative with a 1e-6 absolute floor
  -- in practice the oracle reproduces the reference to ~1e-6."""
+import copy
+
 import numpy as np
 import pytest
 import torch
@@ -92,9 +94,23 @@ def test_resblock_and_generator(golden):
     for i, f in enumerate(feats):
         close(f, g["feat%d" % i], what="feat%d" % i)
     close(x.grad, g["dx"], rtol=1e-3, what="gen dx")
+    # The bias of a conv whose output only feeds a non-affine InstanceNorm has an exactly zero gradient: its fp32 norm is
+    # rounding noise, which differs from CPU to CPU.  The same pass in float64 tells those biases apart; they must be zero
+    # to rounding (1e-5 of their conv's weight gradient), every other gradient norm must match the reference's.
+    og64 = copy.deepcopy(og).double()
+    for p in og64.parameters():
+        p.grad = None
+    x64 = x.detach().double().requires_grad_()
+    y64, feats64 = og64(x64, [0, 4, 8, 12, 16], encode_only=False)
+    ((y64 * C.randn(53, *y64.shape).double()).sum() + sum((f * c.double()).sum() for f, c in zip(feats64, fc))).backward()
+    grads64 = {k: float(p.grad.norm()) for k, p in og64.named_parameters()}
     for k, p in og.named_parameters():
         ref = float(g["gnorm_" + k.replace(".", "_")])
-        assert abs(float(p.grad.norm()) - ref) <= 1e-3 * max(ref, 1e-6), k
+        wk = k[:-len("bias")] + "weight"
+        if k.endswith(".bias") and grads64[k] <= 1e-9 * grads64[wk]:
+            assert float(p.grad.norm()) <= 1e-5 * float(g["gnorm_" + wk.replace(".", "_")]), k
+        else:
+            assert abs(float(p.grad.norm()) - ref) <= 1e-3 * max(ref, 1e-6), k
     enc = og(x.detach(), [0, 4, 8, 12, 16], encode_only=True)
     assert len(enc) == 5 and enc[4].shape == feats[4].shape
 
