@@ -138,6 +138,9 @@ _SIGS = {
     "dfmir_flow_smooth_fwd_p": [P, P, P] + [c_int] * 6 + [P],
     "dfmir_flow_smooth_bwd_p": [P, P, P] + [c_int] * 6 + [P],
     "dfmir_mul": [P, P, P, c_longlong, P],
+    "dfmir_nmi_ws_floats": [c_longlong, c_int],
+    "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
+    "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],
     "dfmir_ncc_fwd_m": [P, P, P, c_int, P, P, P, P] + [c_int] * 5 + [c_float, P],
     "dfmir_ncc_bwd_m": [P, P, P, c_int, P, P, P, P, P, P] + [c_int] * 5 + [c_float, P],
     "dfmir_ncc_fwd": [P, P, P, P, P, P] + [c_int] * 5 + [c_float, P],
@@ -188,6 +191,7 @@ def lib():
         h.dfmir_conv3d_up_dgrad_ws_floats.restype = c_longlong
         h.dfmir_conv3d_upwgrad_ws_floats.restype = c_longlong
         h.dfmir_flow_smooth_ws_floats.restype = c_longlong
+        h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_warp_bwd_own_ws_floats.restype = c_longlong
         h.dfmir_resize_bwd_ws_floats.restype = c_longlong
         h.dfmir_last_error.argtypes = []

@@ -1,7 +1,8 @@
 """Registration losses with the reference's interfaces: `smooothing_loss`
-(models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` (util/losses.py:81-261) and vxm `NCC` / `Grad`
+(models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `Grad`
 (models/voxelmorph/torchvoxelmorph/losses.py:7-67,93-117; also reachable as `dfmir_amd.voxelmorph.losses`), each one
 fused HIP reduction (dfmir_amd.ops)."""
+import numpy as np
 import torch
 
 from . import ops
@@ -59,6 +60,42 @@ class NCC_Loss(_Loss):
         if len(set(kv)) != 1 or len(kv) != nd:
             raise NotImplementedError("NCC window must be cubic and match the tensor rank")
         return ops.ncc_loss(prediction, target, int(kv[0]), self.eps, mask=mask)
+
+
+class NMI_Loss(_Loss):
+    """util/losses.py:263-348: soft-binned (Parzen) mutual information of two images (Guo; Dalca et al., MedIA 2019),
+    returned as -MI with shape (1,).  sigma = mean(diff(bin_centers)) * sigma_ratio; the centers need not be uniform
+    (2 to 64 of them).  Both inputs are clamped to [0, max_clip] first -- data in [-1, 1] loses its negative half, as in
+    the reference -- and every voxel of the batch and channels goes into ONE histogram.  crop_background=True counts only
+    the voxels where `mask` > 1e-4 (any mask that broadcasts to the inputs); the reference's mask-less crop (a box filter
+    over y_true) fails there with a RuntimeError, and raises a ValueError here.  An empty selection gives NaN.  Gradients
+    go to both y_true and y_pred; the bin centers are constants and get none (`vol_bin_centers.requires_grad` is kept for
+    the reference's attribute, but nothing flows into it).  `patch_size` is stored and unused, as in the reference.
+    One HIP forward (dfmir_nmi_fwd) and one backward (dfmir_nmi_bwd)."""
+
+    def __init__(self, bin_centers, device='cpu', sigma_ratio=0.5, max_clip=1, crop_background=False, patch_size=1,
+                 name='nmi'):
+        super().__init__(name=name)
+        self.max_clip = max_clip
+        self.patch_size = patch_size
+        self.crop_background = crop_background
+        self.bin_centers = [float(c) for c in np.asarray(bin_centers, dtype=np.float64).reshape(-1)]
+        self.num_bins = len(self.bin_centers)
+        if not 2 <= self.num_bins <= 64:
+            raise ValueError("NMI_Loss supports 2 to 64 bin centers (got %d)" % self.num_bins)
+        self.sigma_ratio = sigma_ratio
+        self.sigma = np.mean(np.diff(self.bin_centers)) * sigma_ratio
+        self.preterm = 1 / (2 * np.square(self.sigma))
+        self.vol_bin_centers = torch.tensor(self.bin_centers, requires_grad=True, device=device, dtype=torch.float32)
+
+    def __call__(self, y_true, y_pred, mask=None, padding_size=15, **kwargs):
+        if self.crop_background and mask is None:
+            raise ValueError("NMI_Loss(crop_background=True) needs a mask: the reference's mask-less crop does not run "
+                             "(util/losses.py:298-310 passes conv%dd a stride list of the wrong length)" % (y_true.dim() - 2))
+        return ops.nmi_loss(y_true, y_pred, self.bin_centers, self.sigma_ratio, float(self.max_clip),
+                            mask=mask if self.crop_background else None)
+
+    forward = __call__
 
 
 class NCC(object):

@@ -2405,6 +2405,80 @@ def ncc_loss(I, J, win=9, eps=1e-5, mask=None, reduction='neg_sqrt_mean'):
     return NCCFn.apply(I, J, win, eps, mask, {'neg_sqrt_mean': 0, 'neg_mean': 1}[reduction])
 
 
+class NMIFn(Function):
+    """-MI of one soft-binned joint histogram over every voxel of y_true and y_pred (NMI_Loss, util/losses.py:263-348);
+    result shape (1,).  Gradients go to both inputs; `centers` (a device tensor) is a constant and gets none."""
+
+    @staticmethod
+    def forward(ctx, y_true, y_pred, centers, preterm, max_clip, mask=None):
+        _need(y_true, y_pred, centers, mask)
+        y_true, y_pred = _c(y_true), _c(y_pred)
+        if y_true.shape != y_pred.shape or y_true.dtype != torch.float32 or y_pred.dtype != torch.float32:
+            raise DfmirHipError("NMI: fp32 tensors of one shape (got %s, %s)" % (tuple(y_true.shape), tuple(y_pred.shape)))
+        if mask is not None and (mask.dtype != torch.float32 or mask.shape != y_true.shape or not mask.is_contiguous()):
+            raise DfmirHipError("NMI mask: a contiguous fp32 tensor of the inputs' shape")
+        nb, n = centers.numel(), y_true.numel()
+        ws = torch.empty(int(lib().dfmir_nmi_ws_floats(n, nb)), device=y_true.device, dtype=torch.float32)
+        out = torch.empty(1, device=y_true.device, dtype=torch.float32)
+        check(lib().dfmir_nmi_fwd(_p(y_true), _p(y_pred), _p(mask), _p(centers), nb, float(preterm), float(max_clip), n,
+                                  _p(ws), _p(out), _st()))
+        ctx.save_for_backward(y_true, y_pred, centers, mask, ws)
+        ctx.meta = (nb, float(preterm), float(max_clip), n)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        y_true, y_pred, centers, mask, ws = ctx.saved_tensors
+        nb, preterm, max_clip, n = ctx.meta
+        g = _c(g)
+        dt = torch.empty_like(y_true) if ctx.needs_input_grad[0] else None
+        dp = torch.empty_like(y_pred) if ctx.needs_input_grad[1] else None
+        if dt is not None or dp is not None:
+            check(lib().dfmir_nmi_bwd(_p(y_true), _p(y_pred), _p(mask), _p(centers), nb, preterm, max_clip, n, _p(ws),
+                                      _p(g), _p(dt), _p(dp), _st()))
+        return dt, dp, None, None, None, None
+
+
+_NMI_CENTERS = {}
+
+
+def nmi_preterm(centers, sigma_ratio=0.5):
+    """1 / (2 sigma^2), sigma = mean(diff(centers)) * sigma_ratio, in float64 as the reference (util/losses.py:284-285)."""
+    import numpy as np
+    c = np.asarray(centers, dtype=np.float64).reshape(-1)
+    if not 2 <= c.size <= 64:
+        raise DfmirHipError("NMI supports 2 to 64 bin centers (got %d)" % c.size)
+    sigma = np.mean(np.diff(c)) * sigma_ratio
+    return float(1.0 / (2.0 * np.square(sigma)))
+
+
+def nmi_centers(centers, device):
+    """The bin centers as a float32 device tensor, uploaded once per (values, device) and reused (also inside a captured
+    step, which cannot upload)."""
+    import numpy as np
+    vals = tuple(float(v) for v in np.asarray(centers, dtype=np.float64).reshape(-1))
+    key = (vals, torch.device(device))
+    t = _NMI_CENTERS.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise DfmirHipError("NMI: bin centers must be uploaded before a graph capture (run one eager step first)")
+        t = _NMI_CENTERS[key] = torch.tensor(vals, dtype=torch.float32, device=device)
+    return t
+
+
+def nmi_loss(y_true, y_pred, centers, sigma_ratio=0.5, max_clip=1.0, mask=None):
+    """-MI of NMI_Loss (util/losses.py:263-348): both inputs clamped to [0, max_clip], the whole tensor (batch and
+    channels) one histogram; `centers`: 2..64 host floats (a list / array; any spacing).  mask (crop_background): any
+    tensor that broadcasts to the inputs' shape; voxels with mask > 1e-4 count.  Returns shape (1,)."""
+    preterm = nmi_preterm(centers, sigma_ratio)
+    _need(y_true, y_pred, mask)
+    c = nmi_centers(centers, y_true.device)
+    if mask is not None:
+        mask = mask.to(device=y_true.device, dtype=torch.float32).expand_as(y_true).contiguous()
+    return NMIFn.apply(y_true, y_pred, c, preterm, float(max_clip), mask)
+
+
 class MeanFn(Function):
     @staticmethod
     def forward(ctx, x):

@@ -5,21 +5,27 @@ models/registration_model.py:97); SURVEY.md section 8 row A13 defines the compos
 reference does ship: `VxmDense(ndims=3, int_steps=7, bidir=True)`
 (models/voxelmorph/torchvoxelmorph/networks.py:1028-1145) + `NCC_Loss(kernel_var=[9,9,9], 'mean')`
 (util/losses.py:132-261) + lambda * `Grad_Loss(dim=3, 'l2')` (util/losses.py:81-130), Adam(2e-4,
-(0.5, 0.999)).  Oracle counterpart: oracle/dfmir_oracle.py::Registration3DStep.
+(0.5, 0.999)).  Oracle counterpart: oracle/dfmir_oracle.py::Registration3DStep.  similarity='nmi' swaps the NCC term for
+`NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity.
 """
+import numpy as np
 import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import Grad_Loss, NCC_Loss
+from .losses import Grad_Loss, NCC_Loss, NMI_Loss
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
 
 class Registration3DModel(object):
     def __init__(self, shape, features=None, lam=1.0, lr=2e-4, betas=(0.5, 0.999), win=9, device="cuda",
-                 capture_step=False, deterministic_wgrad=None):
-        """capture_step (build-defined, as REGISTRATIONModel's opt.capture_step): after two eager steps forward +
+                 capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0):
+        """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window) or 'nmi': NMI_Loss(real_B, warped real_A) with the
+        bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
+        both images to [0, nmi_max_clip] first, as the reference does: data in [-1, 1] loses its negative half (nothing is
+        rescaled here).  The loss key is then 'nmi' instead of 'ncc'.
+        capture_step (build-defined, as REGISTRATIONModel's opt.capture_step): after two eager steps forward +
         losses + backward are captured into ONE hipGraph and replayed; Adam and the gradient all-reduce stay eager.
         Small volumes are host-bound otherwise (128^3: 3.7 ms of Python / autograd / ctypes per 5.2 ms step)."""
         self.device = torch.device(device)
@@ -28,7 +34,15 @@ class Registration3DModel(object):
         self.netR = VxmDense(tuple(shape), features, int_steps=7, bidir=True).to(self.device)
         self.netR.skip_unused_target = True      # the step reads (y_source, flow) only
         self.optimizer_R = FlatAdam(self.netR.parameters(), lr=lr, betas=betas)
-        self.criterionNCC = NCC_Loss(self.device, kernel_var=[win] * len(shape), kernel_type='mean')
+        if similarity not in ('ncc', 'nmi'):
+            raise ValueError("similarity must be 'ncc' or 'nmi', got %r" % (similarity,))
+        self.similarity = similarity
+        if similarity == 'ncc':
+            self.criterionNCC = NCC_Loss(self.device, kernel_var=[win] * len(shape), kernel_type='mean')
+        else:
+            bins = np.linspace(0.0, nmi_max_clip, 32) if nmi_bins is None else nmi_bins
+            self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)
+        self._outputs = ('regA', 'flow', 'loss_' + similarity, 'loss_grad')
         self.criterionGrad = Grad_Loss(dim=len(shape), penalty='l2')
         self.lam = lam
         self._ddp = False
@@ -50,10 +64,13 @@ class Registration3DModel(object):
         y_source, y_target, flow = self.netR(self.real_A, self.real_B)
         self.regA, self.flow = y_source, flow
         self.optimizer_R.zero_grad()
-        self.loss_ncc = self.criterionNCC(y_source, self.real_B)
+        if self.similarity == 'ncc':
+            self.loss_ncc = loss_sim = self.criterionNCC(y_source, self.real_B)
+        else:
+            self.loss_nmi = loss_sim = self.criterionNMI(self.real_B, y_source)
         self.loss_grad = self.criterionGrad(flow)
         with ops.deferred_weight_grads():
-            (self.loss_ncc + self.loss_grad * self.lam).backward()
+            (loss_sim + self.loss_grad * self.lam).backward()
 
     def _apply_updates(self):
         if self._ddp:
@@ -83,7 +100,7 @@ class Registration3DModel(object):
         if st['graph'] is None:
             st['in_A'], st['in_B'] = self.real_A.clone(), self.real_B.clone()
             self.real_A, self.real_B = st['in_A'], st['in_B']
-            for k in ('regA', 'flow', 'loss_ncc', 'loss_grad'):          # drop the previous step's autograd graph
+            for k in self._outputs:                                       # drop the previous step's autograd graph
                 v = getattr(self, k, None)
                 if torch.is_tensor(v) and v.grad_fn is not None:
                     setattr(self, k, v.detach())
@@ -95,7 +112,7 @@ class Registration3DModel(object):
                     self._forward_backward()
             finally:
                 ops.end_graph_capture()
-            st['outputs'] = {k: getattr(self, k) for k in ('regA', 'flow', 'loss_ncc', 'loss_grad')}
+            st['outputs'] = {k: getattr(self, k) for k in self._outputs}
             st.update(graph=graph, shape=shape)
         else:
             if self.real_A is not st['in_A']:
@@ -107,4 +124,5 @@ class Registration3DModel(object):
         self._apply_updates()
 
     def get_current_losses(self):
-        return dict(ncc=float(self.loss_ncc.detach()), grad=float(self.loss_grad.detach()))
+        sim = getattr(self, 'loss_' + self.similarity)
+        return {self.similarity: float(sim.detach()), 'grad': float(self.loss_grad.detach())}

@@ -553,6 +553,21 @@ int dfmir_flow_smooth_fwd_p(const float* flow, float* ws, float* out, int B, int
                             int W, int penalty, void* stream);
 int dfmir_flow_smooth_bwd_p(const float* flow, const float* gout, float* dflow, int B, int C, int D,
                             int H, int W, int penalty, void* stream);
+/* NMI_Loss (util/losses.py:263-348): out[0] = -MI of the soft-binned (Parzen) joint histogram of y_true and y_pred, both
+ * first clamped to [0, max_clip]; all n voxels (batch and channels included) form ONE histogram.  Per voxel
+ * a_k = exp(-preterm (y_true - c_k)^2) normalised over k (b_k the same for y_pred), pab[i][j] = sum_v b[i] a[j] / V,
+ * pa / pb the means of a / b, MI = sum pab log(pab / (pb pa^T + 1e-5) + 1e-5).  centers: nb device floats, 2 <= nb <= 64,
+ * any spacing; preterm = 1 / (2 sigma^2) as the caller computed it.  mask (n floats, may be NULL): only voxels with
+ * mask > 1e-4 count (crop_background), V = their number; V = 0 gives NaN, as the reference.  ws:
+ * dfmir_nmi_ws_floats(n, nb) floats (need not be zeroed): per-workgroup partial histograms, added in index order (the
+ * loss is bit-reproducible), and the gradient terms the backward reads -- keep it between the two calls.
+ * bwd: d_true / d_pred (either may be NULL) = gout[0] * dL/dy, zero where the clamp or the mask cuts; no atomics. */
+long long dfmir_nmi_ws_floats(long long n, int nb);
+int dfmir_nmi_fwd(const float* y_true, const float* y_pred, const float* mask, const float* centers, int nb,
+                  float preterm, float max_clip, long long n, float* ws, float* out, void* stream);
+int dfmir_nmi_bwd(const float* y_true, const float* y_pred, const float* mask, const float* centers, int nb,
+                  float preterm, float max_clip, long long n, const float* ws, const float* gout, float* d_true,
+                  float* d_pred, void* stream);
 /* out = a * b element-wise: `prediction * mask` of Grad_Loss.forward (util/losses.py:120-121). */
 int dfmir_mul(const float* a, const float* b, float* out, long long n, void* stream);
 /* NCC_Loss (util/losses.py:183-261), mean kernel of `win` per axis (odd), zero padding:
