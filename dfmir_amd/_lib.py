@@ -141,6 +141,15 @@ _SIGS = {
     "dfmir_nmi_ws_floats": [c_longlong, c_int],
     "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
     "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],
+    "dfmir_warp_dice_ws_floats": [c_int] * 6,
+    "dfmir_warp_dice_fwd": [c_int, P, P, P, P] + [c_int] * 6 + [P, P, P, P, P],
+    "dfmir_warp_dice_bwd": [c_int, P, P, P, P] + [c_int] * 5 + [P, P, P, P],
+    "dfmir_dice_ws_floats": [c_longlong, c_longlong],
+    "dfmir_dice_fwd": [P, P, c_longlong, c_longlong, P, P, P],
+    "dfmir_dice_bwd": [P, P, c_longlong, c_longlong, P, P, P, P, P],
+    "dfmir_mse_ws_floats": [c_longlong],
+    "dfmir_mse_fwd": [P, P, c_longlong, P, P, P],
+    "dfmir_mse_bwd": [P, P, c_longlong, P, P, P, P],
     "dfmir_ncc_fwd_m": [P, P, P, c_int, P, P, P, P] + [c_int] * 5 + [c_float, P],
     "dfmir_ncc_bwd_m": [P, P, P, c_int, P, P, P, P, P, P] + [c_int] * 5 + [c_float, P],
     "dfmir_ncc_fwd": [P, P, P, P, P, P] + [c_int] * 5 + [c_float, P],
@@ -192,6 +201,9 @@ def lib():
         h.dfmir_conv3d_upwgrad_ws_floats.restype = c_longlong
         h.dfmir_flow_smooth_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
+        h.dfmir_warp_dice_ws_floats.restype = c_longlong
+        h.dfmir_dice_ws_floats.restype = c_longlong
+        h.dfmir_mse_ws_floats.restype = c_longlong
         h.dfmir_warp_bwd_own_ws_floats.restype = c_longlong
         h.dfmir_resize_bwd_ws_floats.restype = c_longlong
         h.dfmir_last_error.argtypes = []

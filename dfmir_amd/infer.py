@@ -3,15 +3,20 @@ warp a label map with nearest-neighbour sampling -- all on the HIP device (the r
 warp to the CPU, test.py:80-81)."""
 import torch
 
+from . import ops
 from .voxelmorph import SpatialTransformer
 
 
 @torch.no_grad()
-def register_pair(model, data, label=None):
-    """Returns dict(fake_B, idt_B, translated_B, warped_A, flow[, warped_label]).
+def register_pair(model, data, label=None, fixed_label=None, labels=None):
+    """Returns dict(fake_B, idt_B, translated_B, warped_A, flow[, warped_label][, dice]).
 
     model: a REGISTRATIONModel (train or test mode); data: {'A','B','A_paths','B_paths'};
-    label: optional [B,1,H,W] tensor warped with mode='nearest' by the same flow (test.py:80-81)."""
+    label: optional [B,1,H,W] tensor warped with mode='nearest' by the same flow (test.py:80-81);
+    fixed_label, labels (with `label`; all three or none take effect): `label` and `fixed_label` are then integer label
+    maps of A and B and `labels` the label values to score -> 'dice', the [B,K] hard-Dice table of A's label warped with
+    nearest-neighbour sampling against B's label, under the same flow that produces 'warped_label'
+    (ops.warp_dice, mode='nearest')."""
     model.set_input(data)
     model.forward()                                        # model.test() without the visuals hook
     translated_B = model.netG(model.real_B)                # test.py:77
@@ -20,4 +25,8 @@ def register_pair(model, data, label=None):
     if label is not None:
         st = SpatialTransformer(tuple(flow.shape[2:]), mode='nearest').to(flow.device)
         out['warped_label'] = st(label.to(flow.device).float(), flow)
+        if fixed_label is not None and labels is not None:
+            mov = ops.as_label_map(label.to(flow.device))
+            fix = ops.as_label_map(fixed_label.to(flow.device))
+            out['dice'] = ops.warp_dice(mov, fix, flow.detach(), labels, mode='nearest')[1]
     return out

@@ -1,7 +1,7 @@
 """Registration losses with the reference's interfaces: `smooothing_loss`
-(models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `Grad`
-(models/voxelmorph/torchvoxelmorph/losses.py:7-67,93-117; also reachable as `dfmir_amd.voxelmorph.losses`), each one
-fused HIP reduction (dfmir_amd.ops)."""
+(models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `MSE` /
+`Dice` / `Grad` (models/voxelmorph/torchvoxelmorph/losses.py:7-117; also reachable as `dfmir_amd.voxelmorph.losses`), each
+one fused HIP reduction (dfmir_amd.ops); `LabelDice` (build-defined) is the Dice of label maps under a flow."""
 import numpy as np
 import torch
 
@@ -129,3 +129,50 @@ class Grad(object):
         if self.loss_mult is not None:
             grad = ops.scale(grad.view(1), self.loss_mult).view(())
         return grad
+
+
+class MSE(object):
+    """vxm `MSE().loss(y_true, y_pred)` = mean((y_true - y_pred)^2) (models/voxelmorph/torchvoxelmorph/losses.py:70-76);
+    gradients to both arguments."""
+
+    def loss(self, y_true, y_pred):
+        return ops.mse_loss(y_true, y_pred)
+
+
+class Dice(object):
+    """vxm `Dice().loss(y_true, y_pred)` = -mean_{b,c} 2 sum(t p) / clamp(sum(t + p), min=1e-5) over float tensors
+    [B,C,*vol] -- soft segmentations or one-hot label maps (models/voxelmorph/torchvoxelmorph/losses.py:79-90); gradients
+    to both arguments.  For integer label maps under a flow use `LabelDice`, which never forms the one-hot tensors."""
+
+    def loss(self, y_true, y_pred):
+        return ops.dice_loss(y_true, y_pred)
+
+
+class LabelDice(object):
+    """Build-defined (the reference ships the pieces, not the composition): the segmentation term of semi-supervised
+    VoxelMorph on integer label maps.  `LabelDice(labels, mode).loss(fixed_label, moving_label, flow)` equals
+
+        Dice().loss(one_hot(fixed_label)[:, labels], SpatialTransformer(size, mode)(one_hot(moving_label)[:, labels], flow))
+
+    with one_hot over the label VALUES as channels (float), i.e. -mean over (batch, listed label) of
+    2 sum(t p) / clamp(sum(t + p), min=1e-5); a listed label present in neither map scores 0 and still counts in the mean,
+    values that are not listed are not scored.  One fused HIP forward and one backward (ops.warp_dice): the one-hot
+    tensors are never formed.  labels: 1..64 distinct integers in [0, 255]; the maps: uint8 [B,1,*vol] (anything else goes
+    through ops.as_label_map, which may sync with the host -- convert once where the inputs are set).  mode 'bilinear'
+    gives a gradient to `flow` only; 'nearest' is the hard Dice of the label warp of test.py:80-81 and has none.
+    `.scores` holds the last [B,K] Dice table (detached)."""
+
+    def __init__(self, labels, mode='bilinear'):
+        self.labels = list(ops._dice_labels(labels))
+        if mode not in ('bilinear', 'nearest'):
+            raise ValueError("LabelDice mode must be 'bilinear' or 'nearest', got %r" % (mode,))
+        self.mode = mode
+        self.scores = None
+
+    def loss(self, fixed_label, moving_label, flow):
+        if fixed_label.dtype != torch.uint8:
+            fixed_label = ops.as_label_map(fixed_label)
+        if moving_label.dtype != torch.uint8:
+            moving_label = ops.as_label_map(moving_label)
+        loss, self.scores = ops.warp_dice(moving_label, fixed_label, flow, self.labels, self.mode)
+        return loss

@@ -2479,6 +2479,205 @@ def nmi_loss(y_true, y_pred, centers, sigma_ratio=0.5, max_clip=1.0, mask=None):
     return NMIFn.apply(y_true, y_pred, c, preterm, float(max_clip), mask)
 
 
+def as_label_map(t):
+    """An integer label map as the contiguous uint8 tensor the Dice kernels read, on the tensor's own device: any integer
+    dtype, bool, or a float tensor with integral values; every value must lie in [0, 255].  The range check reads the
+    extrema back (a host sync), so call it where inputs are set, never inside a captured region."""
+    if not torch.is_tensor(t):
+        raise DfmirHipError("as_label_map: a tensor is required (got %s)" % type(t).__name__)
+    if t.dtype == torch.uint8:
+        return _c(t)
+    if t.dtype == torch.bool:
+        return _c(t.to(torch.uint8))
+    if t.is_complex():
+        raise DfmirHipError("as_label_map: unsupported dtype %s" % t.dtype)
+    if t.numel():
+        lo, hi = t.min().item(), t.max().item()
+        if not (lo >= 0 and hi <= 255):           # (also catches NaN)
+            raise DfmirHipError("as_label_map: label values must lie in [0, 255] (got %s .. %s)" % (lo, hi))
+        if t.is_floating_point() and not bool((t == t.round()).all()):
+            raise DfmirHipError("as_label_map: a float label map must hold integral values")
+    return _c(t.to(torch.uint8))
+
+
+_DICE_STATE = {}
+
+
+def _dice_labels(labels):
+    try:
+        vals = [v for v in (labels.tolist() if hasattr(labels, "tolist") else list(labels))]
+    except TypeError:
+        raise DfmirHipError("warp_dice: labels must be a list of label values")
+    if not 1 <= len(vals) <= 64:
+        raise DfmirHipError("warp_dice scores 1 to 64 labels (got %d)" % len(vals))
+    for v in vals:
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 255:
+            raise DfmirHipError("warp_dice: label values must be integers in [0, 255] (got %r)" % (v,))
+    vals = tuple(int(v) for v in vals)
+    if len(set(vals)) != len(vals):
+        raise DfmirHipError("warp_dice: duplicate label values in %r" % (vals,))
+    return vals
+
+
+def _dice_state(vals, shape, nd, device):
+    """(value -> slot table, workspace) on the device, made once per (labels, shape, device) and reused: a captured step
+    neither uploads nor allocates."""
+    key = (vals, tuple(shape), torch.device(device))
+    st = _DICE_STATE.get(key)
+    if st is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise DfmirHipError("warp_dice: the label table must be uploaded before a graph capture (run one eager step first)")
+        table = [255] * 256
+        for i, v in enumerate(vals):
+            table[v] = i
+        B = shape[0]
+        D, H, W = (shape[2:] if nd == 3 else (1,) + tuple(shape[2:]))
+        n = int(lib().dfmir_warp_dice_ws_floats(nd, B, len(vals), D, H, W))
+        if n <= 0:
+            raise DfmirHipError("warp_dice: unsupported shape %s" % (tuple(shape),))
+        st = _DICE_STATE[key] = (torch.tensor(table, dtype=torch.uint8, device=device),
+                                 torch.empty(n, device=device, dtype=torch.float32))
+    return st
+
+
+class WarpDiceFn(Function):
+    """(loss, dice[B,K]) of a fixed label map against a moving label map warped by `flow` (dfmir_warp_dice_fwd); the
+    gradient goes to `flow` only."""
+
+    @staticmethod
+    def forward(ctx, mov, fix, flow, table, ws, K, mode):
+        nd = flow.dim() - 2
+        B = flow.shape[0]
+        D, H, W = (flow.shape[2:] if nd == 3 else (1,) + tuple(flow.shape[2:]))
+        dev = flow.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        dice = torch.empty(B, K, device=dev, dtype=torch.float32)
+        seeds = torch.empty(2, B, K, device=dev, dtype=torch.float32)
+        check(lib().dfmir_warp_dice_fwd(nd, _p(mov), _p(fix), _p(flow), _p(table), K, B, D, H, W, mode, _p(ws), _p(loss),
+                                        _p(dice), _p(seeds), _st()))
+        ctx.save_for_backward(mov, fix, flow, table, seeds)
+        ctx.meta = (nd, K, B, D, H, W)
+        ctx.mark_non_differentiable(dice)
+        return loss, dice
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gdice):
+        mov, fix, flow, table, seeds = ctx.saved_tensors
+        nd, K, B, D, H, W = ctx.meta
+        if not ctx.needs_input_grad[2]:
+            return (None,) * 7
+        g = _c(g)
+        dflow = torch.empty_like(flow)
+        check(lib().dfmir_warp_dice_bwd(nd, _p(mov), _p(fix), _p(flow), _p(table), K, B, D, H, W, _p(seeds), _p(g),
+                                        _p(dflow), _st()))
+        return None, None, dflow, None, None, None, None
+
+
+def warp_dice(mov, fix, flow, labels, mode='bilinear'):
+    """Dice of the FIXED label map `fix` against the MOVING label map `mov` warped by `flow`, over the label values
+    `labels` (1..64 distinct integers in [0, 255]; values of the maps that are not listed are not scored):
+    Dice().loss(one_hot(fix)[:, labels], SpatialTransformer(one_hot(mov)[:, labels], flow)) of the reference, without the
+    one-hot tensors.  mov / fix: uint8 [B,1,*vol] (ops.as_label_map), flow: fp32 [B,nd,*vol].  Returns (loss, dice[B,K]).
+    mode 'bilinear' (multi-linear weights; gradient to flow) or 'nearest' (the hard Dice of the label warp of
+    test.py:80-81; no gradient).  Never syncs with the host."""
+    vals = _dice_labels(labels)
+    if mode not in ('bilinear', 'nearest'):
+        raise DfmirHipError("warp_dice: mode must be 'bilinear' or 'nearest' (got %r)" % (mode,))
+    nd = flow.dim() - 2
+    if nd not in (2, 3) or flow.shape[1] != nd:
+        raise DfmirHipError("warp_dice: flow must be [B,nd,*vol] with nd = 2 or 3 (got %s)" % (tuple(flow.shape),))
+    want = (flow.shape[0], 1) + tuple(flow.shape[2:])
+    if tuple(mov.shape) != want or tuple(fix.shape) != want:
+        raise DfmirHipError("warp_dice: label maps %s / %s do not match the flow %s (expected %s)"
+                            % (tuple(mov.shape), tuple(fix.shape), tuple(flow.shape), want))
+    if mov.dtype != torch.uint8 or fix.dtype != torch.uint8 or flow.dtype != torch.float32:
+        raise DfmirHipError("warp_dice: uint8 label maps (ops.as_label_map) and an fp32 flow (got %s, %s, %s)"
+                            % (mov.dtype, fix.dtype, flow.dtype))
+    if mode == 'nearest' and flow.requires_grad:
+        raise DfmirHipError("warp_dice: mode='nearest' has no gradient; detach the flow")
+    _need(mov, fix, flow)
+    table, ws = _dice_state(vals, flow.shape, nd, flow.device)
+    return WarpDiceFn.apply(_c(mov), _c(fix), _c(flow), table, ws, len(vals), 1 if mode == 'nearest' else 0)
+
+
+def _dense_pair(y_true, y_pred, what):
+    if y_true.shape != y_pred.shape or y_true.dtype != torch.float32 or y_pred.dtype != torch.float32:
+        raise DfmirHipError("%s: fp32 tensors of one shape (got %s %s, %s %s)"
+                            % (what, tuple(y_true.shape), y_true.dtype, tuple(y_pred.shape), y_pred.dtype))
+    _need(y_true, y_pred)
+    return _c(y_true), _c(y_pred)
+
+
+class DiceFn(Function):
+    """vxm Dice of float tensors [B,C,*vol] (dfmir_dice_fwd / _bwd); gradients to both arguments."""
+
+    @staticmethod
+    def forward(ctx, y_true, y_pred):
+        y_true, y_pred = _dense_pair(y_true, y_pred, "Dice")
+        if y_true.dim() < 3:
+            raise DfmirHipError("Dice: [B,C,*vol] tensors (got %s)" % (tuple(y_true.shape),))
+        planes = y_true.shape[0] * y_true.shape[1]
+        S = y_true.numel() // max(planes, 1)
+        n = int(lib().dfmir_dice_ws_floats(planes, S))
+        if n <= 0:
+            raise DfmirHipError("Dice: unsupported shape %s" % (tuple(y_true.shape),))
+        ws = torch.empty(n, device=y_true.device, dtype=torch.float32)
+        out = torch.empty((), device=y_true.device, dtype=torch.float32)
+        check(lib().dfmir_dice_fwd(_p(y_true), _p(y_pred), planes, S, _p(ws), _p(out), _st()))
+        ctx.save_for_backward(y_true, y_pred, ws)
+        ctx.meta = (planes, S)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        y_true, y_pred, ws = ctx.saved_tensors
+        planes, S = ctx.meta
+        dt = torch.empty_like(y_true) if ctx.needs_input_grad[0] else None
+        dp = torch.empty_like(y_pred) if ctx.needs_input_grad[1] else None
+        if dt is not None or dp is not None:
+            check(lib().dfmir_dice_bwd(_p(y_true), _p(y_pred), planes, S, _p(ws), _p(_c(g)), _p(dt), _p(dp), _st()))
+        return dt, dp
+
+
+def dice_loss(y_true, y_pred):
+    """-mean_{b,c} 2 sum(t p) / max(sum(t + p), 1e-5): vxm `Dice().loss` (torchvoxelmorph/losses.py:79-90)."""
+    return DiceFn.apply(y_true, y_pred)
+
+
+class MSEFn(Function):
+    """mean((t - p)^2) (dfmir_mse_fwd / _bwd); gradients to both arguments."""
+
+    @staticmethod
+    def forward(ctx, y_true, y_pred):
+        y_true, y_pred = _dense_pair(y_true, y_pred, "MSE")
+        n = y_true.numel()
+        nws = int(lib().dfmir_mse_ws_floats(n))
+        if nws <= 0:
+            raise DfmirHipError("MSE: empty tensors")
+        ws = torch.empty(nws, device=y_true.device, dtype=torch.float32)
+        out = torch.empty((), device=y_true.device, dtype=torch.float32)
+        check(lib().dfmir_mse_fwd(_p(y_true), _p(y_pred), n, _p(ws), _p(out), _st()))
+        ctx.save_for_backward(y_true, y_pred)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        y_true, y_pred = ctx.saved_tensors
+        dt = torch.empty_like(y_true) if ctx.needs_input_grad[0] else None
+        dp = torch.empty_like(y_pred) if ctx.needs_input_grad[1] else None
+        if dt is not None or dp is not None:
+            check(lib().dfmir_mse_bwd(_p(y_true), _p(y_pred), y_true.numel(), _p(_c(g)), _p(dt), _p(dp), _st()))
+        return dt, dp
+
+
+def mse_loss(y_true, y_pred):
+    """mean((y_true - y_pred)^2): vxm `MSE().loss` (torchvoxelmorph/losses.py:70-76)."""
+    return MSEFn.apply(y_true, y_pred)
+
+
 class MeanFn(Function):
     @staticmethod
     def forward(ctx, x):

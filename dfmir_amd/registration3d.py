@@ -6,25 +6,31 @@ reference does ship: `VxmDense(ndims=3, int_steps=7, bidir=True)`
 (models/voxelmorph/torchvoxelmorph/networks.py:1028-1145) + `NCC_Loss(kernel_var=[9,9,9], 'mean')`
 (util/losses.py:132-261) + lambda * `Grad_Loss(dim=3, 'l2')` (util/losses.py:81-130), Adam(2e-4,
 (0.5, 0.999)).  Oracle counterpart: oracle/dfmir_oracle.py::Registration3DStep.  similarity='nmi' swaps the NCC term for
-`NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity.
+`NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity.  seg_labels / seg_weight add the segmentation
+term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map against the moving one warped by the flow
+(`losses.LabelDice`).
 """
 import numpy as np
 import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import Grad_Loss, NCC_Loss, NMI_Loss
+from .losses import Grad_Loss, LabelDice, NCC_Loss, NMI_Loss
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
 
 class Registration3DModel(object):
     def __init__(self, shape, features=None, lam=1.0, lr=2e-4, betas=(0.5, 0.999), win=9, device="cuda",
-                 capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0):
+                 capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
+                 seg_labels=None, seg_weight=0.0):
         """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
         both images to [0, nmi_max_clip] first, as the reference does: data in [-1, 1] loses its negative half (nothing is
         rescaled here).  The loss key is then 'nmi' instead of 'ncc'.
+        seg_labels (a list of 1..64 label values in [0, 255]; None = no segmentation term): `set_input` then also takes
+        data['A_seg'] and data['B_seg'], integer label maps [B,1,*shape] of the moving and the fixed image, and the step
+        adds seg_weight * LabelDice(seg_labels).loss(B_seg, A_seg, flow); `get_current_losses()` gains 'dice'.
         capture_step (build-defined, as REGISTRATIONModel's opt.capture_step): after two eager steps forward +
         losses + backward are captured into ONE hipGraph and replayed; Adam and the gradient all-reduce stay eager.
         Small volumes are host-bound otherwise (128^3: 3.7 ms of Python / autograd / ctypes per 5.2 ms step)."""
@@ -43,6 +49,12 @@ class Registration3DModel(object):
             bins = np.linspace(0.0, nmi_max_clip, 32) if nmi_bins is None else nmi_bins
             self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)
         self._outputs = ('regA', 'flow', 'loss_' + similarity, 'loss_grad')
+        self.seg_labels, self.seg_weight = seg_labels, float(seg_weight)
+        self.seg_A = self.seg_B = None
+        if seg_labels is not None:
+            self.criterionDice = LabelDice(seg_labels)
+            self.seg_labels = self.criterionDice.labels
+            self._outputs += ('loss_dice',)
         self.criterionGrad = Grad_Loss(dim=len(shape), penalty='l2')
         self.lam = lam
         self._ddp = False
@@ -59,6 +71,13 @@ class Registration3DModel(object):
     def set_input(self, data):
         self.real_A = data['A'].to(self.device, non_blocking=True)
         self.real_B = data['B'].to(self.device, non_blocking=True)
+        if self.seg_labels is not None:
+            for k in ('A_seg', 'B_seg'):
+                if k not in data:
+                    raise KeyError("Registration3DModel(seg_labels=...) needs data[%r]: an integer label map" % k)
+            # (the range check of as_label_map may sync with the host: here, outside any captured region)
+            self.seg_A = ops.as_label_map(data['A_seg'].to(self.device, non_blocking=True))
+            self.seg_B = ops.as_label_map(data['B_seg'].to(self.device, non_blocking=True))
 
     def _forward_backward(self):
         y_source, y_target, flow = self.netR(self.real_A, self.real_B)
@@ -69,8 +88,12 @@ class Registration3DModel(object):
         else:
             self.loss_nmi = loss_sim = self.criterionNMI(self.real_B, y_source)
         self.loss_grad = self.criterionGrad(flow)
+        total = loss_sim + self.loss_grad * self.lam
+        if self.seg_labels is not None:
+            self.loss_dice = self.criterionDice.loss(self.seg_B, self.seg_A, flow)
+            total = total + self.loss_dice * self.seg_weight
         with ops.deferred_weight_grads():
-            (loss_sim + self.loss_grad * self.lam).backward()
+            total.backward()
 
     def _apply_updates(self):
         if self._ddp:
@@ -88,6 +111,9 @@ class Registration3DModel(object):
         side, cur = st['stream'], torch.cuda.current_stream()
         shape = (tuple(self.real_A.shape), tuple(self.real_B.shape), self.optimizer_R.flat_p.data_ptr(),
                  self.optimizer_R.flat_g.data_ptr())
+        seg = self.seg_labels is not None
+        if seg:
+            shape += (tuple(self.seg_A.shape), tuple(self.seg_B.shape))
         if st['graph'] is not None and st['shape'] != shape:
             st.update(graph=None, eager_steps=0)
         if st['force_eager'] or (st['graph'] is None and st['eager_steps'] < 2):
@@ -100,6 +126,9 @@ class Registration3DModel(object):
         if st['graph'] is None:
             st['in_A'], st['in_B'] = self.real_A.clone(), self.real_B.clone()
             self.real_A, self.real_B = st['in_A'], st['in_B']
+            if seg:
+                st['in_segA'], st['in_segB'] = self.seg_A.clone(), self.seg_B.clone()
+                self.seg_A, self.seg_B = st['in_segA'], st['in_segB']
             for k in self._outputs:                                       # drop the previous step's autograd graph
                 v = getattr(self, k, None)
                 if torch.is_tensor(v) and v.grad_fn is not None:
@@ -118,11 +147,19 @@ class Registration3DModel(object):
             if self.real_A is not st['in_A']:
                 st['in_A'].copy_(self.real_A, non_blocking=True)
                 st['in_B'].copy_(self.real_B, non_blocking=True)
+            if seg and self.seg_A is not st['in_segA']:
+                st['in_segA'].copy_(self.seg_A, non_blocking=True)
+                st['in_segB'].copy_(self.seg_B, non_blocking=True)
             vars(self).update(st['outputs'])
             self.real_A, self.real_B = st['in_A'], st['in_B']
+            if seg:
+                self.seg_A, self.seg_B = st['in_segA'], st['in_segB']
         st['graph'].replay()
         self._apply_updates()
 
     def get_current_losses(self):
         sim = getattr(self, 'loss_' + self.similarity)
-        return {self.similarity: float(sim.detach()), 'grad': float(self.loss_grad.detach())}
+        out = {self.similarity: float(sim.detach()), 'grad': float(self.loss_grad.detach())}
+        if self.seg_labels is not None:
+            out['dice'] = float(self.loss_dice.detach())
+        return out

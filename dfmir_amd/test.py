@@ -10,6 +10,9 @@ CPU -- and writes `<dataroot>/deform_label/<name>` and `<dataroot>/deform_trainA
 `torchvision.utils.save_image` produces for one image (x * 255 + 0.5, clamped, 8-bit, grey replicated to RGB).
 Labels are read from `<dataroot>/trainA_label/<name>` with the names of `<dataroot>/<phase>A` in sorted order, as the
 reference does; a pair without a label file gets no `deform_label` output (the reference raises).
+Build-defined: `--fixed_label_dir DIR` (a sub-folder of dataroot holding B's label maps under the same names) scores each
+pair: its record gains "dice_labels", the label values other than 0 present in either map (the 64 smallest at most), and
+"dice", the hard Dice per such value of A's label warped with nearest-neighbour sampling against B's label.
 """
 import argparse
 import os
@@ -18,6 +21,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import ops
 from .data import create_dataset
 from .infer import register_pair
 from .options import default_options
@@ -34,6 +38,8 @@ def parse(argv=None):
     ap.add_argument('--eval', action='store_true')
     ap.add_argument('--max_dataset_size', type=float, default=float("inf"))
     ap.add_argument('--label_dir', default='trainA_label', help="sub-folder of dataroot with A's label maps (test.py:66)")
+    ap.add_argument('--fixed_label_dir', default=None,
+                    help="sub-folder of dataroot with B's label maps: adds each pair's per-label Dice to its record")
     for k, v in vars(d).items():
         if k in ('gpu_ids', 'isTrain', 'capture_step'):
             continue
@@ -78,6 +84,13 @@ def read_label(path):
     return t[None].contiguous()
 
 
+def read_label_ids(path):
+    """The label image as integer label values [1,1,H,W] (first channel; values above 255 are not supported)."""
+    a = np.asarray(Image.open(path))
+    a = a if a.ndim == 2 else a[..., 0]
+    return torch.from_numpy(np.ascontiguousarray(np.rint(a.astype(np.float64)).astype(np.int64)))[None, None]
+
+
 def main(argv=None):
     opt = parse(argv)
     dataset = create_dataset(opt)
@@ -101,6 +114,8 @@ def main(argv=None):
         print(data["A_paths"][0])
         label_path = os.path.join(str(opt.dataroot), opt.label_dir, str(names[i]))
         label = read_label(label_path) if os.path.exists(label_path) else None
+        fixed_path = (os.path.join(str(opt.dataroot), opt.fixed_label_dir, str(names[i]))
+                      if opt.fixed_label_dir and label is not None else None)
         out = register_pair(model, data, label)
         os.makedirs(out_moved, exist_ok=True)
         save_image(out['warped_A'] / 2 + 0.5, os.path.join(out_moved, str(names[i])))      # test.py:88-90
@@ -110,6 +125,14 @@ def main(argv=None):
             os.makedirs(out_label, exist_ok=True)
             save_image(out['warped_label'], os.path.join(out_label, str(names[i])))        # test.py:83-85
             rec["label"] = os.path.join(out_label, str(names[i]))
+        if fixed_path is not None and os.path.exists(fixed_path):
+            mov, fix = read_label_ids(label_path), read_label_ids(fixed_path)
+            values = sorted((set(torch.unique(mov).tolist()) | set(torch.unique(fix).tolist())) - {0})[:64]
+            if values:
+                dev = out['flow'].device
+                table = ops.warp_dice(ops.as_label_map(mov.to(dev)), ops.as_label_map(fix.to(dev)), out['flow'].detach(),
+                                      values, mode='nearest')[1]
+                rec["dice_labels"], rec["dice"] = values, table[0].tolist()
         written.append(rec)
     return written
 

@@ -227,6 +227,7 @@ def _losses_namespace():
     from . import losses as _l               # (losses imports ops only: no cycle)
     ns = _Namespace()
     ns.NCC, ns.Grad = _l.NCC, _l.Grad        # torchvoxelmorph/losses.py:7-67,93-117
+    ns.MSE, ns.Dice = _l.MSE, _l.Dice        # torchvoxelmorph/losses.py:70-90
     return ns
 
 

@@ -568,6 +568,41 @@ int dfmir_nmi_fwd(const float* y_true, const float* y_pred, const float* mask, c
 int dfmir_nmi_bwd(const float* y_true, const float* y_pred, const float* mask, const float* centers, int nb,
                   float preterm, float max_clip, long long n, const float* ws, const float* gout, float* d_true,
                   float* d_pred, void* stream);
+/* Label-map Dice under a flow: vxm `Dice().loss(one_hot(fix)[:, labels], SpatialTransformer(one_hot(mov)[:, labels], flow))`
+ * (models/voxelmorph/torchvoxelmorph/losses.py:79-90 after layers.py:36-48; mode 1 = the nearest-neighbour label warp of
+ * test.py:80-81, forward only) without the one-hot tensors.  nd = 2 ([B,1,H,W], D = 1) or 3.  mov / fix: 8-bit label maps
+ * [B][D][H][W]; flow: [B][nd][D][H][W] voxel displacements (align_corners=True, zero padding: a corner outside the volume
+ * has weight 0); slot_of: 256 device bytes, label value -> slot 0..K-1 of the scored list (K <= 64), 255 = not scored.
+ * Per (b, l): T = sum_x sum_k w_k [mov(c_k) = l][fix(x) = l], S = sum_x sum_k w_k [mov(c_k) = l], N = #{fix(x) = l};
+ * dice[b][l] = 2 T / max(N + S, 1e-5) (a label in neither map scores 0 and still counts in the mean); loss[0] = -mean.
+ * seeds: 2 B K floats for the backward, gT = -2 / (bottom B K) then gS = 2 T / (bottom^2 B K) (0 under the clamp).
+ * ws: dfmir_warp_dice_ws_floats() floats, 8-byte aligned, need not be zeroed: per-workgroup sums as 64-bit fixed point
+ * (quantum 2^-32), added by a finaliser -- no global atomics, loss / dice / seeds bit-identical from run to run.
+ * bwd: dflow [B][nd][D][H][W] = gout[0] * d loss / d flow, written completely (no zero fill needed), a gather of the seed
+ * table over the corners; gout is read on the device (no host sync).  The label maps get no gradient. */
+long long dfmir_warp_dice_ws_floats(int nd, int B, int K, int D, int H, int W);
+int dfmir_warp_dice_fwd(int nd, const unsigned char* mov, const unsigned char* fix, const float* flow,
+                        const unsigned char* slot_of, int K, int B, int D, int H, int W, int mode, float* ws,
+                        float* loss, float* dice, float* seeds, void* stream);
+int dfmir_warp_dice_bwd(int nd, const unsigned char* mov, const unsigned char* fix, const float* flow,
+                        const unsigned char* slot_of, int K, int B, int D, int H, int W, const float* seeds,
+                        const float* gout, float* dflow, void* stream);
+/* vxm `Dice().loss(y_true, y_pred)` (models/voxelmorph/torchvoxelmorph/losses.py:79-90) of float tensors [planes = B C][S]:
+ * out[0] = -mean over planes of 2 sum(t p) / max(sum(t + p), 1e-5).  ws: dfmir_dice_ws_floats(planes, S) floats (per-chunk
+ * partial sums, added in index order: bit-reproducible; then the per-plane coefficients the backward reads -- keep it
+ * between the two calls).  bwd: d_true / d_pred (either may be NULL) = gout[0] * dL/dy, element-wise. */
+long long dfmir_dice_ws_floats(long long planes, long long S);
+int dfmir_dice_fwd(const float* y_true, const float* y_pred, long long planes, long long S, float* ws, float* out,
+                   void* stream);
+int dfmir_dice_bwd(const float* y_true, const float* y_pred, long long planes, long long S, const float* ws,
+                   const float* gout, float* d_true, float* d_pred, void* stream);
+/* vxm `MSE().loss(y_true, y_pred)` (models/voxelmorph/torchvoxelmorph/losses.py:70-76): out[0] = mean((t - p)^2) over n
+ * elements; ws: dfmir_mse_ws_floats(n) floats (ordered partial sums).  bwd: d_true = gout[0] 2 (t - p) / n, d_pred = -d_true
+ * (either may be NULL). */
+long long dfmir_mse_ws_floats(long long n);
+int dfmir_mse_fwd(const float* y_true, const float* y_pred, long long n, float* ws, float* out, void* stream);
+int dfmir_mse_bwd(const float* y_true, const float* y_pred, long long n, const float* gout, float* d_true, float* d_pred,
+                  void* stream);
 /* out = a * b element-wise: `prediction * mask` of Grad_Loss.forward (util/losses.py:120-121). */
 int dfmir_mul(const float* a, const float* b, float* out, long long n, void* stream);
 /* NCC_Loss (util/losses.py:183-261), mean kernel of `win` per axis (odd), zero padding:
