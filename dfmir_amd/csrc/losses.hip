@@ -954,7 +954,10 @@ extern "C" int dfmir_flow_smooth_bwd(const float* flow, const float* gout, float
 // fwd: final 5 box sums are left in `tmp`.
 extern "C" int dfmir_ncc_fwd_m(const float* I, const float* J, const float* mask, int mode, float* tmp, float* tmp2,
                                float* ws, float* out, int B, int D, int H, int W, int win, float eps, void* stream) {
-  DF_ARG_CHECK(I && J && tmp && tmp2 && ws && out && B > 0 && D > 0 && H > 0 && W > 0 && (win & 1) && (mode == 0 || mode == 1));
+  DF_ARG_CHECK(I && J && tmp && tmp2 && ws && out && B > 0 && D > 0 && H > 0 && W > 0 && (win & 1) && (mode & ~(1 | DFMIR_NCC_VOLUME)) == 0);
+  // a [B,1,1,H,W] VOLUME: the window still spans three axes (win^3 positions, all but win^2 of them zero padding)
+  const bool vol = D > 1 || (mode & DFMIR_NCC_VOLUME);
+  mode &= 1;
   hipStream_t st = (hipStream_t)stream;
   const long long N = (long long)B * D * H * W;
   const int r = win / 2;
@@ -981,7 +984,7 @@ extern "C" int dfmir_ncc_fwd_m(const float* I, const float* J, const float* mask
     DF_LAUNCH_CHECK();
     box_axis_launch(tmp2, tmp, 5, N, W, H, r, st);
     DF_LAUNCH_CHECK();
-    wn = (float)win * win;
+    wn = vol ? (float)win * win * win : (float)win * win;
   }
   // tmp2 is free again after the box passes: its head takes the per-workgroup partials (volumes of >= 2048 / 5 voxels)
   const unsigned ng = df_grid(N, 256, 1024);
@@ -1001,12 +1004,14 @@ extern "C" int dfmir_ncc_bwd_m(const float* I, const float* J, const float* mask
                                float* tmp, float* tmp2, const float* ws, const float* gout, float* dI, int B, int D,
                                int H, int W, int win, float eps, void* stream) {
   DF_ARG_CHECK(I && J && sums && tmp && tmp2 && ws && gout && dI && B > 0 && D > 0 && H > 0 && W > 0 && (win & 1) &&
-               (mode == 0 || mode == 1));
+               (mode & ~(1 | DFMIR_NCC_VOLUME)) == 0);
+  const bool vol = D > 1 || (mode & DFMIR_NCC_VOLUME);
+  mode &= 1;
   hipStream_t st = (hipStream_t)stream;
   const long long N = (long long)B * D * H * W;
   const int r = win / 2;
   const unsigned grid = (unsigned)((N + 255) / 256);
-  const float wn = (D > 1) ? (float)win * win * win : (float)win * win;
+  const float wn = vol ? (float)win * win * win : (float)win * win;
   static DfOptFlag nofuse_o{"DFMIR_NCC_NO_WH_FUSE"};         // A/B: fields, W and H passes as separate launches
   if (r == 4 && D > 1 && !nofuse_o.get()) {
     const int nty = (H + 31) / 32, ntx = (W + 63) / 64;

@@ -23,7 +23,10 @@ class _Loss(object):
 
 class Grad_Loss(_Loss):
     """util/losses.py:81-130: mean over axes of mean(|forward difference|) ('l1', i.e. any penalty other than 'l2' in the
-    reference) or of its square ('l2'); `mask=` multiplies the field first (:119-121); `loss_mult` scales the result."""
+    reference) or of its square ('l2'); `mask=` multiplies the field first (:119-121); `loss_mult` scales the result.
+    Degenerate axes: an axis of extent 1 has no forward differences and the reference's mean over nothing is NaN; here such
+    an axis contributes 0 (value and gradient) and the divisor stays the number of axes -- except a 3-D field of ONE plane
+    ([B,C,1,H,W]), which is taken as the 2-D field it is: mean over H and W only, divided by 2."""
 
     def __init__(self, dim=2, penalty='l2', name=None, loss_mult=None, *args, **kwargs):
         super().__init__(name=name or 'gradient')

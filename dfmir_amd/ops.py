@@ -2347,6 +2347,9 @@ def mul(a, b):
     return MulFn.apply(a, b)
 
 
+NCC_VOLUME = 4            # DFMIR_NCC_VOLUME (include/dfmir_hip.h): mode flag of dfmir_ncc_fwd_m / _bwd_m
+
+
 class NCCFn(Function):
     """Windowed NCC with a win^nd mean window; gradient w.r.t. the prediction I only (J is the fixed target).
     mode 0: -sqrt(mean(cc)) (NCC_Loss, util/losses.py:248-256), with a mask -sqrt(sum(cc * mask) / sum(mask)) and 0 for
@@ -2363,6 +2366,8 @@ class NCCFn(Function):
         nd = I.dim() - 2
         B = I.shape[0]
         D, H, W = I.shape[2:] if nd == 3 else (1,) + tuple(I.shape[2:])
+        if nd == 3 and D == 1:
+            mode = int(mode) | NCC_VOLUME  # a one-plane VOLUME keeps the win^3 window of the reference's conv3d
         N = I.numel()
         sums = torch.empty(5 * N, device=I.device, dtype=torch.float32)
         tmp2 = torch.empty(5 * N, device=I.device, dtype=torch.float32)
@@ -2399,7 +2404,8 @@ class NCCFn(Function):
 
 def ncc_loss(I, J, win=9, eps=1e-5, mask=None, reduction='neg_sqrt_mean'):
     """reduction 'neg_sqrt_mean' (NCC_Loss) or 'neg_mean' (vxm NCC); mask: any tensor that broadcasts to I's shape
-    (bool / byte / float: the reference multiplies cc by it, util/losses.py:261)."""
+    (bool / byte / float: the reference multiplies cc by it, util/losses.py:261).  The window counts win^nd positions by the
+    tensors' RANK: a volume of one plane [B,1,1,H,W] keeps win^3, as the reference's conv3d does."""
     if mask is not None:
         mask = mask.to(device=I.device, dtype=torch.float32).expand_as(I).contiguous()
     return NCCFn.apply(I, J, win, eps, mask, {'neg_sqrt_mean': 0, 'neg_mean': 1}[reduction])

@@ -617,7 +617,10 @@ int dfmir_ncc_bwd(const float* I, const float* J, const float* sums, float* tmp,
 /* The same with a weight per voxel and the reduction chosen.  mask (numel floats, may be NULL): the masked branch of
  * NCC_Loss.forward (util/losses.py:257-261): out = -sqrt(sum(cc * mask) / sum(mask)), 0 when sum(mask) == 0.
  * mode 0 = that form; mode 1 = -sum(cc [* mask]) / n, n = numel (or sum(mask)): vxm NCC(win).loss = -mean(cc)
- * (models/voxelmorph/torchvoxelmorph/losses.py:15-67).  ws[0] = sum(cc * mask), ws[1] = sum(mask) (kept for backward). */
+ * (models/voxelmorph/torchvoxelmorph/losses.py:15-67).  ws[0] = sum(cc * mask), ws[1] = sum(mask) (kept for backward).
+ * mode | DFMIR_NCC_VOLUME: the tensors are VOLUMES [B,1,D,H,W] even if D == 1 -- the reference's conv3d window then still
+ * counts win^3 positions (D == 1 without the flag is a 2-D image: win^2).  Pass the same mode to fwd and bwd. */
+#define DFMIR_NCC_VOLUME 4
 int dfmir_ncc_fwd_m(const float* I, const float* J, const float* mask, int mode, float* tmp, float* tmp2,
                     float* ws, float* out, int B, int D, int H, int W, int win, float eps, void* stream);
 int dfmir_ncc_bwd_m(const float* I, const float* J, const float* mask, int mode, const float* sums,

@@ -1,0 +1,158 @@
+"""Plain float64 references (torch, CPU) of the operations around the convolutions: masked L1, flow smoothness
+(Grad_Loss), windowed NCC, InstanceNorm (+ReLU, +residual), Adam.  TEST infrastructure, written from the formulas in the
+docstrings of oracle/dfmir_oracle.py; tests/test_ref64.py checks each one against the fp32 oracle on small inputs, the GPU
+tests (tests/test_gpu_pointwise_fp64.py) compare the HIP kernels with them.
+
+Every function takes tensors of any float dtype and computes in `dtype` (float64 by default); gradients come from
+autograd on the returned value.  `dtype=torch.float32` turns a function into a plain fp32 restatement (another valid
+summation order), which the GPU tests use as the fp32 yardstick where the fp32 oracle itself is too slow.
+"""
+import torch
+import torch.nn.functional as F
+
+
+def _t(x, dtype):
+    return x if x.dtype == dtype else x.to(dtype)
+
+
+# ------------------------------------------------------------------------------------------------ masked L1
+def threshold_mask(a, b, thr):
+    """(a > thr) | (b > thr) with thr rounded to fp32 first: the images are fp32 and so is the kernel's threshold."""
+    t = float(torch.tensor(thr, dtype=torch.float32))
+    return (a > t) | (b > t)
+
+
+def masked_l1(a, b, mask=None, thr=None, dtype=torch.float64):
+    """sum(|a - b| * m) / sum(m), 0 when sum(m) == 0; m = `mask` (any dtype, non-zero = 1) or the threshold mask
+    (a > thr) | (b > thr); without both: mean |a - b|."""
+    a, b = _t(a, dtype), _t(b, dtype)
+    d = (a - b).abs()
+    if mask is None and thr is None:
+        return d.mean()
+    m = (mask != 0) if mask is not None else threshold_mask(a.detach(), b.detach(), thr)
+    m = m.expand_as(d).to(dtype)
+    n = m.sum()
+    if float(n) == 0.0:
+        return (d * 0).sum()
+    return (d * m).sum() / n
+
+
+# ------------------------------------------------------------------------------------------- flow smoothness
+def grad_loss(flow, penalty='l2', mask=None, loss_mult=None, skip_empty=False, dtype=torch.float64):
+    """mean over the spatial axes of mean(|forward difference|^p), p = 2 ('l2') or 1 ('l1'), of a field [B, C, *spatial]
+    (2-D or 3-D); `mask` multiplies the field first, `loss_mult` the result.  An axis of extent 1 has no differences: the
+    mean over nothing is NaN, as in torch -- unless skip_empty, where such an axis contributes 0 and the divisor stays the
+    number of axes."""
+    f = _t(flow, dtype)
+    if mask is not None:
+        f = f * _t(mask, dtype)
+    nd = f.dim() - 2
+    tot = 0.0
+    for ax in range(2, 2 + nd):
+        n = f.shape[ax]
+        if n == 1 and skip_empty:
+            continue
+        d = f.narrow(ax, 1, n - 1) - f.narrow(ax, 0, n - 1)
+        tot = tot + ((d * d) if penalty == 'l2' else d.abs()).mean()
+    tot = tot / float(nd)
+    return tot if loss_mult is None else tot * loss_mult
+
+
+# ------------------------------------------------------------------------------------------------------ NCC
+def box_sum(x, win, axes, method='cumsum'):
+    """Zero-padded box sums of odd width `win` along `axes`, one axis after the other.  'cumsum': difference of two
+    entries of the running sum (cost independent of win; for float64); 'shift': the plain sum of the win shifted copies."""
+    assert win % 2 == 1
+    r = win // 2
+    for ax in axes:
+        L = x.shape[ax]
+        pad = [0, 0] * (x.dim() - 1 - ax)
+        if method == 'cumsum':
+            c = F.pad(x, pad + [r + 1, r]).cumsum(ax)             # c[k] = sum of x[.. k - r - 1]
+            x = c.narrow(ax, 2 * r + 1, L) - c.narrow(ax, 0, L)   # x[i - r] + ... + x[i + r]
+        else:
+            xp = F.pad(x, pad + [r, r])
+            acc = xp.narrow(ax, 0, L)
+            for d in range(1, win):
+                acc = acc + xp.narrow(ax, d, L)
+            x = acc
+    return x
+
+
+def ncc_map(I, J, win=9, eps=1e-5, dtype=torch.float64, method=None):
+    """cc = cross^2 / (Iv * Jv + eps) over a win^nd box, zero padded: with the box sums Is, Js, I2s, J2s, IJs, n = win^nd,
+    uI = Is / n, uJ = Js / n:  cross = IJs - uJ Is - uI Js + uI uJ n,  Iv = I2s - 2 uI Is + uI^2 n,  Jv likewise."""
+    I, J = _t(I, dtype), _t(J, dtype)
+    method = method or ('cumsum' if dtype == torch.float64 else 'shift')
+    axes = list(range(2, I.dim()))
+    bs = lambda t: box_sum(t, win, axes, method)
+    Is, Js, I2s, J2s, IJs = bs(I), bs(J), bs(I * I), bs(J * J), bs(I * J)
+    n = float(win) ** len(axes)
+    uI, uJ = Is / n, Js / n
+    cross = IJs - uJ * Is - uI * Js + uI * uJ * n
+    Iv = I2s - 2 * uI * Is + uI * uI * n
+    Jv = J2s - 2 * uJ * Js + uJ * uJ * n
+    return cross * cross / (Iv * Jv + eps)
+
+
+def ncc_loss(I, J, win=9, eps=1e-5, mask=None, reduction='neg_sqrt_mean', dtype=torch.float64, method=None):
+    """'neg_sqrt_mean': -sqrt(mean(cc)) (NCC_Loss), 'neg_mean': -mean(cc) (vxm NCC); with a mask the mean is
+    sum(cc * mask) / sum(mask), and the loss is 0 when the mask is empty."""
+    cc = ncc_map(I, J, win, eps, dtype, method)
+    if mask is None:
+        m = cc.mean()
+    else:
+        mk = _t(mask, dtype).expand_as(cc)
+        if float(mk.sum()) == 0.0:
+            return (cc * 0).sum()
+        m = (cc * mk).sum() / mk.sum()
+    return -torch.sqrt(m) if reduction == 'neg_sqrt_mean' else -m
+
+
+def vxm_ncc_loss(y_true, y_pred, win=9, dtype=torch.float64):
+    """-mean(cc), eps 1e-5 (cc is symmetric in its arguments)."""
+    return ncc_loss(y_pred, y_true, win, 1e-5, None, 'neg_mean', dtype)
+
+
+# --------------------------------------------------------------------------------------------- InstanceNorm
+def instance_norm(x, res=None, relu=False, eps=1e-5, dtype=torch.float64):
+    """y = (x - mean) * rstd per (n, c) plane, mean / biased variance over the plane, rstd = 1 / sqrt(var + eps); then
+    ReLU, then + res.  Returns (y, mean, rstd), the statistics as [N * C]."""
+    x = _t(x, dtype)
+    xf = x.reshape(x.shape[0] * x.shape[1], -1)
+    mean = xf.mean(1)
+    var = ((xf - mean[:, None]) ** 2).mean(1)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    y = ((xf - mean[:, None]) * rstd[:, None]).reshape(x.shape)
+    if relu:
+        y = torch.relu(y)
+    if res is not None:
+        y = y + _t(res, dtype)
+    return y, mean, rstd
+
+
+def blur_down(y):
+    """Reflect pad 1, [1 2 1]^2 / 16, stride 2, per channel (the anti-aliased Downsample)."""
+    f = torch.tensor([1.0, 2.0, 1.0], dtype=y.dtype)
+    k = (f[:, None] * f[None, :] / 16.0)[None, None].repeat(y.shape[1], 1, 1, 1)
+    return F.conv2d(F.pad(y, (1, 1, 1, 1), mode="reflect"), k, stride=2, groups=y.shape[1])
+
+
+# ----------------------------------------------------------------------------------------------------- Adam
+class Adam(object):
+    """Adam without weight decay on one tensor, in `dtype`:  m = b1 m + (1 - b1) g,  v = b2 v + (1 - b2) g^2,
+    p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)."""
+
+    def __init__(self, p, lr, betas, eps=1e-8, dtype=torch.float64):
+        self.p = p.detach().to(dtype).clone()
+        self.m, self.v = torch.zeros_like(self.p), torch.zeros_like(self.p)
+        self.lr, self.b1, self.b2, self.eps, self.t, self.dtype = lr, betas[0], betas[1], eps, 0, dtype
+
+    def step(self, g):
+        g = g.to(self.dtype)
+        self.t += 1
+        self.m.mul_(self.b1).add_(g, alpha=1 - self.b1)
+        self.v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
+        bc1, bc2 = 1 - self.b1 ** self.t, 1 - self.b2 ** self.t
+        den = self.v.sqrt().div_(bc2 ** 0.5).add_(self.eps)
+        self.p.addcdiv_(self.m, den, value=-self.lr / bc1)

@@ -1,0 +1,189 @@
+"""CPU: the float64 references of tests/ref64.py against the fp32 oracle (oracle/dfmir_oracle.py, the project's restatement
+of the reference) and plain torch, values and autograd gradients, on small seeded inputs -- this is where the references
+the GPU tests trust are themselves verified.  Agreement is to fp32 round-off of the ORACLE: 2e-5 on scalars, 1e-4 of the
+maximum on gradients, 1e-3 on the NCC gradient (the oracle's conv over win^nd taps in fp32).
+
+The last tests evaluate, with the oracle alone, the ill-conditioned inputs of tests/test_gpu_pointwise_fp64.py: the bound
+`max(bar, 2 x oracle error)` they lead to must stay within 10 x the bar, else the input tests nothing."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import dfmir_oracle as O
+from tests import ref64 as R
+from tests.golden import common as C
+
+
+def rel(got, ref):
+    got, ref = got.detach().double(), ref.detach().double()
+    assert got.shape == ref.shape
+    return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-30)
+
+
+def val_and_grads(fn, *xs, dtype=None):
+    xs = [(x.to(dtype) if dtype else x.clone()).requires_grad_() for x in xs]
+    l = fn(*xs)
+    (l * 3.0).backward()
+    return [l] + [x.grad for x in xs]
+
+
+@pytest.mark.parametrize("n", [1, 37, 1000])
+def test_masked_l1(n):
+    a, b = C.rand(11, n) * 2 - 1, C.rand(12, n) * 2 - 1
+    a[::3] = -1.0
+    mask = (a > -0.95) | (b > -0.95)
+    ref = val_and_grads(lambda x, y: O.masked_l1(x, y, mask.float()), a, b)
+    for got in (val_and_grads(lambda x, y: R.masked_l1(x, y, thr=-0.95), a, b, dtype=torch.float64),
+                val_and_grads(lambda x, y: R.masked_l1(x, y, mask=mask), a, b, dtype=torch.float64)):
+        assert rel(got[0], ref[0]) <= 2e-5
+        assert rel(got[1], ref[1]) <= 1e-4 and rel(got[2], ref[2]) <= 1e-4
+    assert float(R.masked_l1(a, b, mask=torch.zeros(n))) == 0.0 == float(O.masked_l1(a, b, torch.zeros(n)))
+    assert rel(R.masked_l1(a, b), O.masked_l1(a, b, None)) <= 2e-5
+
+
+@pytest.mark.parametrize("shape", [(2, 2, 18, 22), (1, 3, 7, 9, 11)], ids=["2d", "3d"])
+@pytest.mark.parametrize("penalty", ["l2", "l1"])
+def test_grad_loss(shape, penalty):
+    f = C.randn(13, *shape) * 1.5
+    mask = (C.rand(14, shape[0], 1, *shape[2:]) > 0.3).float()
+    for kw in (dict(), dict(mask=mask, loss_mult=2.5)):
+        ref = val_and_grads(lambda x: O.grad_loss(x, penalty, **kw), f)
+        got = val_and_grads(lambda x: R.grad_loss(x, penalty, **kw), f, dtype=torch.float64)
+        assert rel(got[0], ref[0]) <= 2e-5 and rel(got[1], ref[1]) <= 1e-4
+    if len(shape) == 4 and penalty == "l2":
+        assert rel(R.grad_loss(f, "l2"), O.smoothing_loss(f)) <= 2e-5
+    # an axis of extent 1: NaN like torch; skip_empty: the axis contributes 0 and the divisor stays the number of axes
+    g = f[..., :1]
+    assert bool(torch.isnan(R.grad_loss(g, penalty))) and bool(torch.isnan(O.grad_loss(g, penalty)))
+    nd = len(shape) - 2
+    assert rel(R.grad_loss(g, penalty, skip_empty=True) * nd, R.grad_loss(g[..., 0], penalty) * (nd - 1)) <= 1e-12
+
+
+@pytest.mark.parametrize("shape,win", [((2, 1, 24, 28), 9), ((1, 1, 20, 13), 7), ((1, 1, 5, 30), 9), ((1, 1, 12, 14, 16), 9),
+                                       ((2, 1, 7, 10, 11), 5), ((1, 1, 6, 9, 8), 3), ((1, 1, 1, 12, 14), 9)])
+def test_ncc(shape, win):
+    I = C.rand(15, *shape)
+    J = 0.6 * I + 0.4 * C.rand(16, *shape)
+    mask = (C.rand(17, *shape) > 0.35).float()
+    cc = O.ncc_map(I, J, win)
+    for method in ("cumsum", "shift"):
+        assert rel(R.ncc_map(I, J, win, method=method), cc) <= 1e-4
+    assert rel(R.ncc_map(I, J, win, dtype=torch.float32), cc) <= 1e-4          # the plain fp32 restatement
+    assert rel(R.box_sum(I.double(), win, range(2, I.dim()), "cumsum"), R.box_sum(I.double(), win, range(2, I.dim()), "shift")) <= 1e-13
+    for kw, ofn in ((dict(), lambda x: O.ncc_loss(x, J, win)),
+                    (dict(mask=mask), lambda x: O.ncc_loss(x, J, win, mask=mask)),
+                    (dict(reduction="neg_mean"), lambda x: O.vxm_ncc_loss(J, x, win))):
+        ref = val_and_grads(ofn, I)
+        got = val_and_grads(lambda x: R.ncc_loss(x, J, win, **kw), I, dtype=torch.float64)
+        assert rel(got[0], ref[0]) <= 2e-5 and rel(got[1], ref[1]) <= 1e-3, kw
+        g32 = val_and_grads(lambda x: R.ncc_loss(x, J, win, dtype=torch.float32, **kw), I)
+        assert rel(g32[0], ref[0]) <= 2e-5 and rel(g32[1], ref[1]) <= 1e-3, kw
+    assert rel(R.vxm_ncc_loss(J, I, win), O.vxm_ncc_loss(J, I, win)) <= 2e-5
+    assert float(R.ncc_loss(I, J, win, mask=torch.zeros(shape))) == 0.0 == float(O.ncc_loss(I, J, win, mask=torch.zeros(shape)))
+
+
+@pytest.mark.parametrize("shape,relu,res", [((2, 3, 5, 5), False, False), ((2, 3, 9, 11), True, True), ((1, 2, 16, 16), True, False),
+                                            ((1, 2, 16, 16), False, True)])
+def test_instance_norm(shape, relu, res):
+    x, r, cot = C.randn(18, *shape) * 2 + 0.7, (C.randn(19, *shape) if res else None), C.randn(20, *shape)
+
+    def torch_in(x_, r_=None):
+        y = F.instance_norm(x_, eps=1e-5)
+        y = F.relu(y) if relu else y
+        return ((y + r_ if res else y) * cot.to(x_.dtype)).sum()
+
+    def ref_in(x_, r_=None):
+        return (R.instance_norm(x_, r_, relu, 1e-5)[0] * cot.double()).sum()
+    args = (x, r) if res else (x,)
+    ref, got = val_and_grads(torch_in, *args), val_and_grads(ref_in, *args, dtype=torch.float64)
+    for g, o in zip(got[1:], ref[1:]):
+        assert rel(g, o) <= 1e-4
+    y, mean, rstd = R.instance_norm(x, r, relu)
+    yo = F.relu(F.instance_norm(x, eps=1e-5)) if relu else F.instance_norm(x, eps=1e-5)
+    assert rel(y, yo + r if res else yo) <= 2e-5
+    xf = x.double().reshape(mean.numel(), -1)
+    assert rel(mean, xf.mean(1)) <= 1e-12 and rel(rstd, 1 / torch.sqrt(xf.var(1, unbiased=False) + 1e-5)) <= 1e-12
+    # the Downsample of the fused kernel's reference against the oracle's module
+    assert rel(R.blur_down(y), O.BlurDown(shape[1])(y.float())) <= 2e-5 or shape[2] < 3
+
+
+@pytest.mark.parametrize("betas", [(0.5, 0.999), (0.9, 0.999)])
+def test_adam(betas):
+    p0 = C.randn(21, 1001)
+    ref = R.Adam(p0, 2e-4, betas)
+    p64, p32 = p0.double().requires_grad_(), p0.clone().requires_grad_()
+    o64, o32 = torch.optim.Adam([p64], lr=2e-4, betas=betas), torch.optim.Adam([p32], lr=2e-4, betas=betas)
+    for t in range(12):
+        g = C.randn(30 + t, 1001) * (0.1 + t)
+        ref.step(g)
+        p64.grad, p32.grad = g.double(), g.clone()
+        o64.step(); o32.step()
+    assert rel(ref.p - p0.double(), p64 - p0.double()) <= 1e-12          # torch's own Adam in float64: the same rule
+    assert rel(ref.m, o64.state[p64]['exp_avg']) <= 1e-12 and rel(ref.v, o64.state[p64]['exp_avg_sq']) <= 1e-12
+    assert rel(ref.p - p0.double(), p32 - p0) <= 1e-3                    # fp32: p ~ 3 moves by ~2e-3, 1 ulp(p) = 1e-4 of that
+    assert rel(ref.m, o32.state[p32]['exp_avg']) <= 2e-5 and rel(ref.v, o32.state[p32]['exp_avg_sq']) <= 2e-5
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the ill-conditioned inputs of the GPU module, with the oracle alone
+def _gpu_module():
+    from tests import test_gpu_pointwise_fp64 as G
+    return G
+
+
+def _phantom_cases():
+    return [c for c in _gpu_module().NCC_CASES if c[3] != "noise"]
+
+
+@pytest.mark.parametrize("case", _phantom_cases(), ids=[c[0] for c in _phantom_cases()])
+def test_phantom_ncc_inputs_are_testable(case):
+    G = _gpu_module()
+    I, J, mask = G.ncc_inputs(case)
+    fg = float(((I - I.flatten()[0]).abs() > 1e-6).float().mean())
+    if min(case[1][2:]) > 4:
+        assert 0.3 <= fg <= 0.5, "phantom foreground %.2f, wanted about 40 %%" % fg
+    Ir = I.double().requires_grad_()
+    lr = R.ncc_loss(Ir, J, case[2], 1e-5, mask, case[5])
+    (lr * G.NCC_UPSTREAM).backward()
+    lo, dIo = G.ncc_fp32_oracle(case, I, J, mask)
+    assert G.oracle_bound(lr, lo, G.BAR)[0] <= 10 * G.BAR
+    assert G.oracle_bound(Ir.grad, dIo, G.BAR_GRAD)[0] <= 10 * G.BAR_GRAD
+    assert float(lr.detach()) < -0.05                                            # a real similarity, not a vanishing one
+
+
+@pytest.mark.parametrize("family", ["constant", "offset1e3", "one-constant-channel"])
+@pytest.mark.parametrize("plane", [(5, 5), (9, 11), (100, 100), (64, 64), (128, 128), (256, 256)], ids=lambda p: "%dx%d" % p)
+def test_hard_instance_norm_inputs_are_testable(plane, family):
+    G = _gpu_module()
+    H, W = plane
+    x, cot = G.in_input(family, H, W), C.randn(643, 2, 3, H, W)
+    for relu, res in ((False, True), (True, False)):
+        ref = G.in_reference(x, C.randn(642, *x.shape) if res else None, relu, cot)
+        assert G.oracle_bound(ref["y"], ref["y32"], G.BAR, floor=G.in_floor(family))[0] <= 10 * G.BAR
+        where = G.in_dx_where(family, relu, ref)
+        if where is None or bool(where.any()):
+            assert G.oracle_bound(ref["dx"], ref["dx32"], G.BAR_IN_DX, where=where)[0] <= 10 * G.BAR_IN_DX
+    if H in (128, 256):
+        ref = G.in_reference(G.in_input(family, H, H, seed=645), None, True, C.randn(646, 2, 3, H // 2, H // 2), down=True)
+        assert G.oracle_bound(ref["y"], ref["y32"], G.BAR, floor=G.in_floor(family))[0] <= 10 * G.BAR
+        where = G.in_dx_where(family, True, ref)
+        if bool(where.any()):
+            assert G.oracle_bound(ref["dx"], ref["dx32"], G.BAR_IN_DX, where=where)[0] <= 10 * G.BAR_IN_DX
+
+
+def test_full_size_reduction_inputs_are_testable():
+    G = _gpu_module()
+    a, b = C.image_pair(631, 16, 256, 256)
+    m = R.threshold_mask(a, b, -0.95).float()
+    assert G.oracle_bound(R.masked_l1(a, b, thr=-0.95), O.masked_l1(a, b, m), G.BAR)[0] <= 10 * G.BAR
+    x = C.randn(664, (1 << 20) + 3) + 1e3
+    assert G.oracle_bound(x.double().mean(), x.mean(), G.BAR)[0] <= 10 * G.BAR
+
+
+def test_ncc_volume_flag_matches_the_header():
+    """ops.NCC_VOLUME mirrors DFMIR_NCC_VOLUME of include/dfmir_hip.h."""
+    import os
+    import re
+    from dfmir_amd import ops
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dfmir_hip.h")).read()
+    assert int(re.search(r"#define\s+DFMIR_NCC_VOLUME\s+(\d+)", text).group(1)) == ops.NCC_VOLUME
