@@ -34,11 +34,8 @@
 // tap matrix with its dz blocks rotated to match (three pre-rotated copies in LDS, one per phase of the march), and when
 // input plane P has been consumed the lanes of group (P - 1) mod 3 store their plane and clear their columns.  The
 // fp32-FMA kernel this replaces (csrc/conv3dt.hip) ran at the vector rate: 0.32 ms at 160 x 192 x 224 for 0.52 GB.
-#include "conv3x3_common.h"
-#include <type_traits>
+#include "split_f16.h"
 
-typedef _Float16 f16x8_m __attribute__((ext_vector_type(8)));
-typedef float f32x4_m __attribute__((ext_vector_type(4)));
 #ifndef M3_KO
 #define M3_KO 0      // knock-out builds (timing only, scripts/build_ko_march.sh): 1 no MFMAs, 2 no staging loads, 4 no conversion +
 #endif               // LDS stores, 8 no epilogue stores, 16 no epilogue at all, 32 no operand reads after the first plane
@@ -66,45 +63,6 @@ extern "C" void dfmir_m3_trace(unsigned long long* out, int reset) {
 #endif
 
 namespace {
-
-__device__ __forceinline__ int scale_exp_m(float amax) {
-  const int be = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  int e = (amax > 0.f) ? 14 - be : 0;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);
-  return e;
-}
-__device__ __forceinline__ float pow2f_m(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-// (x0, x1) * s -> leading fp16 pair h and residual pair r
-__device__ __forceinline__ void split_pair_m(float x0, float x1, float s, unsigned& h, unsigned& r) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(s), "v"(h));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(s), "v"(h));
-}
-__device__ __forceinline__ void split8_m(const float (&v)[8], float s, u32x4& h, u32x4& r) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    unsigned hh, rr;
-    split_pair_m(v[2 * q], v[2 * q + 1], s, hh, rr);
-    h[q] = hh; r[q] = rr;
-  }
-}
-__device__ __forceinline__ f32x4_m mma16m(u32x4 a, u32x4 b, f32x4_m c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_m, a), __builtin_bit_cast(f16x8_m, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mma32m(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_m, a), __builtin_bit_cast(f16x8_m, b), c, 0, 0, 0);
-}
-
-// compile-time loop: f(std::integral_constant<int, I>) for I = B .. E - 1 (the plane step's schedule is a table over its
-// MFMA groups; `#pragma unroll` left some of these loops peeled instead of unrolled and the register arrays in scratch)
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for_m(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for_m<B + 1, E>(f);
-  }
-}
 
 struct MarchP {
   int N, D, H, W;
@@ -196,7 +154,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
   // ---- prologue: zero the plane slots (pad row / pad units must be finite: they meet zero weights), scales, weights
   for (int u = tid; u < SLOTS * SU; u += 512) Xs[u] = u32x4{0u, 0u, 0u, 0u};
   const float amax = reduce_absmax(x_amax, k.x_n, red);
-  const int ex = scale_exp_m(amax);
+  const int ex = scale_exp(amax);
   float wm = 0.f;
   for (int i = tid; i < 27 * CIN * COUT / 4; i += 512) {
     const float4 v = reinterpret_cast<const float4*>(w_tcc)[i];
@@ -204,8 +162,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
   }
   wm = block_max(wm, red);
   if (!(wm == wm)) wm = __uint_as_float(0x7f800000u);
-  const int ew = scale_exp_m(wm);
-  const float xscale = pow2f_m(ex), wscale = pow2f_m(ew), osc = pow2f_m(-ex) * pow2f_m(-ew);
+  const int ew = scale_exp(wm);
+  const float xscale = pow2f(ex), wscale = pow2f(ew), osc = pow2f(-ex) * pow2f(-ew);
   if (tid == 0) smax = 0u;
   // weight units [(step j, dz)][split][lane]: the lane's 8 reduction values of its k group, for its output channel
   for (int u = tid; u < NSTEP * 3 * 64; u += 512) {
@@ -244,7 +202,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
 #pragma unroll
     for (int c = 0; c < 8; ++c) v[c] = tap >= 0 ? w_tcc[((long long)tap * CIN + c0 + c) * COUT + co] : 0.f;
     u32x4 h, r;
-    split8_m(v, wscale, h, r);
+    split8_scaled(v, wscale, h, r);
     Ws[(jd * 2 + 0) * 64 + ln] = h;
     Ws[(jd * 2 + 1) * 64 + ln] = r;
   }
@@ -316,7 +274,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
           float v_[8];                                                                            \
           _Pragma("unroll") for (int c = 0; c < 8; ++c) v_[c] = __uint_as_float(rq[r + (set_)][c][e]); \
           u32x4 h_, r_;                                                                           \
-          split8_m(v_, xscale, h_, r_);                                                           \
+          split8_scaled(v_, xscale, h_, r_);                                                      \
           if (jpos[r] >= 0 && (jhe[r] < 0 || jhe[r] == e)) {                                      \
             Xd_[jpos[r] + (jhe[r] < 0 ? e : 0)] = h_;                                             \
             Xd_[NO * OP + jpos[r] + (jhe[r] < 0 ? e : 0)] = r_;                                   \
@@ -326,7 +284,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
         float v_[8];                                                                              \
         _Pragma("unroll") for (int c = 0; c < 8; ++c) v_[c] = __uint_as_float(rq[r + (set_)][c][0]); \
         u32x4 h_, r_;                                                                             \
-        split8_m(v_, xscale, h_, r_);                                                             \
+        split8_scaled(v_, xscale, h_, r_);                                                        \
         Xd_[jpos[r]] = h_;                                                                        \
         Xd_[NO * OP + jpos[r]] = r_;                                                              \
       }                                                                                           \
@@ -349,7 +307,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
   }
 
   // accumulators of the three open output planes: [plane slot][tile row][half]
-  using acc_t = typename std::conditional<B32, f32x16, f32x4_m>::type;
+  using acc_t = typename std::conditional<B32, f32x16, f32x4>::type;
   // NSETS = 4 (16 -> 16): the finished plane keeps its set for one more step, during which its epilogue rides between
   // the MFMA groups like the staging atoms (10-13 % of a step was an epilogue with nothing on the matrix pipe); the
   // 32-column form has no registers for a fourth set (96 + 32) and finishes its plane at the end of the step
@@ -418,7 +376,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
   {                                                                                               \
     _Pragma("unroll") for (int q = 2 * (half_); q < 2 * (half_) + 2; ++q) {                       \
       unsigned hh_, rr_;                                                                          \
-      split_pair_m(__uint_as_float(rq[r_][2 * q][e_]), __uint_as_float(rq[r_][2 * q + 1][e_]), xscale, hh_, rr_); \
+      split_pair_scaled(__uint_as_float(rq[r_][2 * q][e_]), __uint_as_float(rq[r_][2 * q + 1][e_]), xscale, hh_, rr_); \
       H_[q] = hh_; R_[q] = rr_;                                                                   \
     }                                                                                             \
   }
@@ -505,8 +463,8 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
     M3_KO_DECL                                                                                    \
     u32x4 av[ACTG ? NE : 1];                                                                      \
     M3_BREAD(0, 0) M3_BREAD(0, 1)                                                                 \
-    static_for_m<0, M3_ADEPTH>([&](auto dc_) __attribute__((always_inline)) { M3_AREAD(decltype(dc_)::value, M3_WU(decltype(dc_)::value, PH_)) }); \
-    static_for_m<0, NSTEP * NDZ * 3>([&](auto tc_) __attribute__((always_inline)) {               \
+    static_for<0, M3_ADEPTH>([&](auto dc_) __attribute__((always_inline)) { M3_AREAD(decltype(dc_)::value, M3_WU(decltype(dc_)::value, PH_)) });   \
+    static_for<0, NSTEP * NDZ * 3>([&](auto tc_) __attribute__((always_inline)) {                 \
       constexpr int t = decltype(tc_)::value, jd = t / 3, p = t % 3, j = jd / NDZ, dz = jd % NDZ, cur = jd % (M3_ADEPTH + 1); \
       constexpr unsigned lmask = step_loads<CIN, COUT>(j);                                        \
       constexpr int qo = step_qoff<CIN, COUT>(j);                                                 \
@@ -515,7 +473,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
         if constexpr (M3_PRIO == 1) { if (wid >= 4) __builtin_amdgcn_s_setprio((jd + 1) & 1); else __builtin_amdgcn_s_setprio(jd & 1); } \
         if constexpr (jd + M3_ADEPTH < NSTEP * NDZ) M3_AREAD((jd + M3_ADEPTH) % (M3_ADEPTH + 1), M3_WU(jd + M3_ADEPTH, PH_)) \
         if constexpr (dz == 0) {                                                                  \
-          static_for_m<0, 12>([&](auto bc_) __attribute__((always_inline)) {                      \
+          static_for<0, 12>([&](auto bc_) __attribute__((always_inline)) {                        \
             constexpr int b = decltype(bc_)::value;                                               \
             if constexpr ((lmask >> b) & 1u) M3_BREAD(b >> 2, b & 3)                              \
           });                                                                                     \
@@ -526,9 +484,9 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
       _Pragma("unroll") for (int r = 0; r < 2; ++r)                                               \
         _Pragma("unroll") for (int h = 0; h < NH; ++h) {                                          \
           if ((M3_KO & 1) && k.D > 0) { M3_SINK(Bu[r + qo][h][sb]); M3_SINK(Aw[cur][sa]); }      \
-          else if constexpr (RC) acc[a][r][h] = mma32m(Aw[cur][sa], Bu[r + qo][h][sb], acc[a][r][h]); \
-          else if constexpr (B32) acc[a][r][h] = mma32m(Bu[r + qo][h][sb], Aw[cur][sa], acc[a][r][h]); \
-          else acc[a][r][h] = mma16m(Bu[r + qo][h][sb], Aw[cur][sa], acc[a][r][h]);              \
+          else if constexpr (RC) acc[a][r][h] = mfma32_f16(Aw[cur][sa], Bu[r + qo][h][sb], acc[a][r][h]); \
+          else if constexpr (B32) acc[a][r][h] = mfma32_f16(Bu[r + qo][h][sb], Aw[cur][sa], acc[a][r][h]); \
+          else acc[a][r][h] = mfma16_f16(Bu[r + qo][h][sb], Aw[cur][sa], acc[a][r][h]);          \
         }                                                                                         \
       __builtin_amdgcn_sched_barrier(0);                                                          \
     });                                                                                           \
@@ -536,7 +494,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
     /* output plane P - 1 is complete; NSETS == 3: its epilogue now, else inside the next step */  \
     if constexpr (NSETS == 3) {                                                                   \
       if (!((M3_KO & 16) && k.D > 0)) {                                                           \
-        static_for_m<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(((PH_) + 2) % 3, decltype(ec_)::value, (P_) - 1) }); \
+        static_for<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(((PH_) + 2) % 3, decltype(ec_)::value, (P_) - 1) });   \
       }                                                                                           \
     }                                                                                             \
     M3_T(3)                                                                                       \
@@ -622,10 +580,10 @@ __global__ __launch_bounds__(512, 1) void conv3d_march_k(const float* __restrict
           av[e] = __builtin_amdgcn_raw_buffer_load_b128(a_src, (pl >= zs && pl < ze && evo[e] != OOB) ? evo[e] + (unsigned)pl * hw4 : OOB, 0, 0);
       }
       switch ((nst + 2) & 3) {                               // set of plane index (nst - 2) relative to P0: (nst - 2 + 4) % 4
-        case 0: static_for_m<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(0, decltype(ec_)::value, pl) }); break;
-        case 1: static_for_m<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(1, decltype(ec_)::value, pl) }); break;
-        case 2: static_for_m<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(2, decltype(ec_)::value, pl) }); break;
-        default: static_for_m<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(NSETS == 4 ? 3 : 0, decltype(ec_)::value, pl) }); break;
+        case 0: static_for<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(0, decltype(ec_)::value, pl) }); break;
+        case 1: static_for<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(1, decltype(ec_)::value, pl) }); break;
+        case 2: static_for<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(2, decltype(ec_)::value, pl) }); break;
+        default: static_for<0, NE>([&](auto ec_) __attribute__((always_inline)) { M3_EPI_ONE(NSETS == 4 ? 3 : 0, decltype(ec_)::value, pl) }); break;
       }
     }
   }

@@ -21,7 +21,7 @@
 // planes 2q-1 .. 2q+2, so K runs over 36 taps' = (dz' in 0..3, dy, dx) and the weight rows of plane p hold
 // W[dz' - p] (zero where dz' - p is outside 0..2): 75 % of the issued products are useful instead of 50 %.  Wave w
 // owns plane pair w & 1 and the y-half w >> 1 of the tile (2 column tiles), 18 k-steps x 6 MFMAs per chunk.
-#include "conv3x3_common.h"
+#include "split_f16.h"
 #ifdef C3S_TRACE      // timing build: per-phase s_memtime sums of every wave 0 -> dfmir_c3s_trace()
 __device__ unsigned long long c3s_trace[16];
 #define C3S_T(i_) { if (tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); atomicAdd(&c3s_trace[i_], t_ - tlast); tlast = t_; } }
@@ -37,27 +37,6 @@ extern "C" void dfmir_c3s_trace(unsigned long long* out, int reset) {
 #ifndef C3S_KO
 #define C3S_KO 0     // knock-out builds for timing: 1 = no MFMAs, 2 = no prefetch loads, 4 = no convert + LDS store
 #endif
-
-typedef _Float16 f16x8_3 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ int scale_exp3(float amax) {
-  const int be = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  int e = (amax > 0.f) ? 14 - be : 0;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);
-  return e;
-}
-__device__ __forceinline__ float pow2f3(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-
-// (x0, x1) * s -> leading fp16 pair h and residual pair r (see split_pair_scaled in conv3x3s.hip)
-__device__ __forceinline__ void split_pair3(float x0, float x1, float s, unsigned& h, unsigned& r) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(s), "v"(h));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(s), "v"(h));
-}
-__device__ __forceinline__ f32x16 mma3(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_3, a), __builtin_bit_cast(f16x8_3, b), c, 0, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Weight split: w_tcc [27][K][M] fp32 (tap-major packing of dfmir_weight_pack, either mode) ->
@@ -94,8 +73,8 @@ __device__ __forceinline__ void conv3d_wsplit_body(const float* __restrict__ w, 
   float m = wslab_absmax(w, K, Ktot, koff, M);
   m = block_max(m, sm);
   if (!(m == m)) m = __uint_as_float(0x7f800000u);
-  const int ew = scale_exp3(m);
-  const float s = pow2f3(ew);
+  const int ew = scale_exp(m);
+  const float s = pow2f(ew);
   if (threadIdx.x == 0 && blockIdx.x == 0) reinterpret_cast<int*>(trailer)[0] = ew;
   const int nchunk = (K + 7) / 8, nmt = pair ? 1 : (M + 31) / 32;
   if (pair == 2) {
@@ -109,12 +88,7 @@ __device__ __forceinline__ void conv3d_wsplit_body(const float* __restrict__ w, 
         v[c] = (tap < 27 && kk < K && co < M) ? w[((long long)tap * Ktot + koff + kk) * M + co] : 0.f;
       }
       u32x4 h, r;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        unsigned hh, rr;
-        split_pair3(v[2 * q], v[2 * q + 1], s, hh, rr);
-        h[q] = hh; r[q] = rr;
-      }
+      split8_scaled(v, s, h, r);
       ws[(long long)ch * 896 + tap * 16 + co] = h;
       ws[(long long)ch * 896 + 448 + tap * 16 + co] = r;
     }
@@ -142,12 +116,7 @@ __device__ __forceinline__ void conv3d_wsplit_body(const float* __restrict__ w, 
       v[c] = (tok && kk < K && mo < M) ? w[((long long)tap * Ktot + koff + kk) * M + mo] : 0.f;
     }
     u32x4 h, r;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      unsigned hh, rr;
-      split_pair3(v[2 * q], v[2 * q + 1], s, hh, rr);
-      h[q] = hh; r[q] = rr;
-    }
+    split8_scaled(v, s, h, r);
     const int tu = (u >> 5) % NT;
     const long long base = (((long long)mt * nchunk + ch) * 2) * (NT * 32);
     ws[base + tu * 32 + co] = h;
@@ -237,9 +206,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
 
   // scales: input scaled by 2^ex when it is split, result rescaled by 2^-ex * 2^-ew
   const float amax = reduce_absmax(x_amax, k.x_n, red);
-  const int ex = scale_exp3(amax);
+  const int ex = scale_exp(amax);
   const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f3(ex), oscale = pow2f3(-ex), oscale2 = pow2f3(-ew);
+  const float xscale = pow2f(ex), oscale = pow2f(-ex), oscale2 = pow2f(-ew);
   if (tid == 0) smax = 0u;
 
   __amdgpu_buffer_rsrc_t x_src = __builtin_amdgcn_make_buffer_rsrc(
@@ -329,12 +298,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
 #define C3S_GLOAD_W(ch_)                                                                          \
   _Pragma("unroll") for (int j = 0; j < NW; ++j)                                                  \
     rw[j] = __builtin_amdgcn_raw_buffer_load_b128(w_src, (unsigned)(((ch_) * WU + tid + 256 * j) * 16), 0, 0);
-#define C3S_SPLIT8(v_, h_, r_)                                                                    \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                 \
-    unsigned hh, rr;                                                                              \
-    split_pair3(v_[2 * q], v_[2 * q + 1], xscale, hh, rr);                                        \
-    h_[q] = hh; r_[q] = rr;                                                                       \
-  }
 #define C3S_LSTORE()                                                                              \
   {                                                                                               \
     if constexpr (VEC) {                                                                          \
@@ -343,14 +306,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
           float v[8];                                                                             \
           _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(rq[c][e]);         \
           u32x4 h, r;                                                                             \
-          C3S_SPLIT8(v, h, r)                                                                     \
+          split8_scaled(v, xscale, h, r);                                                         \
           Xs[posq + e] = h;                                                                       \
           Xs[XP + posq + e] = r;                                                                  \
         }                                                                                         \
       }                                                                                           \
       if (posh >= 0) {                                                                            \
         u32x4 h, r;                                                                               \
-        C3S_SPLIT8(rx[0], h, r)                                                                   \
+        split8_scaled(rx[0], xscale, h, r);                                                       \
         Xs[posh] = h;                                                                             \
         Xs[XP + posh] = r;                                                                        \
       }                                                                                           \
@@ -359,7 +322,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
         const int pos = tid + 256 * s;                                                            \
         if (pos < XP) {                                                                           \
           u32x4 h, r;                                                                             \
-          C3S_SPLIT8(rx[s], h, r)                                                                 \
+          split8_scaled(rx[s], xscale, h, r);                                                     \
           Xs[pos] = h;                                                                            \
           Xs[XP + pos] = r;                                                                       \
         }                                                                                         \
@@ -442,9 +405,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
 #if (C3S_KO & 1)
         acc[tt][j][0] += __uint_as_float(B0[cur][j][0] ^ B1[cur][j][1] ^ A0[cur][0] ^ A1[cur][1]);
 #else
-        acc[tt][j] = mma3(A1[cur], B0[cur][j], acc[tt][j]);
-        acc[tt][j] = mma3(A0[cur], B1[cur][j], acc[tt][j]);
-        acc[tt][j] = mma3(A0[cur], B0[cur][j], acc[tt][j]);
+        acc[tt][j] = mfma32_f16(A1[cur], B0[cur][j], acc[tt][j]);
+        acc[tt][j] = mfma32_f16(A0[cur], B1[cur][j], acc[tt][j]);
+        acc[tt][j] = mfma32_f16(A0[cur], B0[cur][j], acc[tt][j]);
 #endif
       }
 #pragma unroll
@@ -480,7 +443,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
 #undef C3S_LSTORE_W
 #undef C3S_OFFS
 #undef C3S_DECODE
-#undef C3S_SPLIT8
 
   // ---- epilogue: acc[j][r] <-> row = (r>>2)*8 + hi*4 + (r&3) = cout - mt*32 (PAIR: plane * 16 + cout),
   //      voxel (wz [+ plane], wy + 2j + (l31>>4), l31&15)
@@ -573,10 +535,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
 // input planes), this form 28/27 -- on a package that sits on its power cap, fewer issued products is time.
 // Wave w = z-plane w of the tile; column tile j = tile row j (8 per wave); lane = (kg = lane >> 4, x = lane & 15):
 // A = Ws[(4 ks + kg) * 16 + x-as-cout], B = patch position of (plane, row j, x) + offset of tap 4 ks + kg.
-typedef float f32x4_3 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4_3 mma16(u32x4 a, u32x4 b, f32x4_3 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_3, a), __builtin_bit_cast(f16x8_3, b), c, 0, 0, 0);
-}
 template <bool VEC, int TT>
 __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __restrict__ x, const float* __restrict__ x_amax,
                                                           const u32x4* __restrict__ wsp, const float* __restrict__ w_trailer,
@@ -618,9 +576,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
   C3M_DECODE(t_first)
 
   const float amax = reduce_absmax(x_amax, k.x_n, red);
-  const int ex = scale_exp3(amax);
+  const int ex = scale_exp(amax);
   const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f3(ex), osc = pow2f3(-ex) * pow2f3(-ew);
+  const float xscale = pow2f(ex), osc = pow2f(-ex) * pow2f(-ew);
   if (tid == 0) smax = 0u;
 
   __amdgpu_buffer_rsrc_t x_src = __builtin_amdgcn_make_buffer_rsrc(
@@ -685,7 +643,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
   const int moff = 2 * HY * HX + (kg < 3 ? kg : 2) * HX + 2;   // mixed k-step: (dz 2, dy kg, dx 2); group 3 reads any valid unit
   const int mtap = kg < 3 ? 20 + 3 * kg : 27;
 
-  f32x4_3 acc[TT][NJ];
+  f32x4 acc[TT][NJ];
   float rx[NS][8];
   u32x4 rq[8];
   u32x4 rw[NW];
@@ -707,12 +665,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
 #define C3M_GLOAD_W(ch_)                                                                          \
   _Pragma("unroll") for (int j = 0; j < NW; ++j)                                                  \
     rw[j] = __builtin_amdgcn_raw_buffer_load_b128(w_src, (tid + 256 * j) < WU ? (unsigned)(((ch_) * WU + tid + 256 * j) * 16) : OOB, 0, 0);
-#define C3M_SPLIT8(v_, h_, r_)                                                                    \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                 \
-    unsigned hh, rr;                                                                              \
-    split_pair3(v_[2 * q], v_[2 * q + 1], xscale, hh, rr);                                        \
-    h_[q] = hh; r_[q] = rr;                                                                       \
-  }
 #define C3M_LSTORE()                                                                              \
   {                                                                                               \
     if constexpr (VEC) {                                                                          \
@@ -721,14 +673,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
           float v[8];                                                                             \
           _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(rq[c][e]);         \
           u32x4 h, r;                                                                             \
-          C3M_SPLIT8(v, h, r)                                                                     \
+          split8_scaled(v, xscale, h, r);                                                         \
           Xs[posq + e] = h;                                                                       \
           Xs[XP + posq + e] = r;                                                                  \
         }                                                                                         \
       }                                                                                           \
       if (posh >= 0) {                                                                            \
         u32x4 h, r;                                                                               \
-        C3M_SPLIT8(rx[0], h, r)                                                                   \
+        split8_scaled(rx[0], xscale, h, r);                                                       \
         Xs[posh] = h;                                                                             \
         Xs[XP + posh] = r;                                                                        \
       }                                                                                           \
@@ -736,8 +688,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
       _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                            \
         const int pos = tid + 256 * s;                                                            \
         if (pos < XP) {                                                                           \
-          u32x4 h, r;                                                                             \
-          C3M_SPLIT8(rx[s], h, r)                                                                 \
+          u32x4 h, r;   /* spelled out: with split8_scaled here the !VEC instance is register-allocated differently */ \
+          _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                         \
+            unsigned hh, rr;                                                                      \
+            split_pair_scaled(rx[s][2 * q], rx[s][2 * q + 1], xscale, hh, rr);                    \
+            h[q] = hh; r[q] = rr;                                                                 \
+          }                                                                                       \
           Xs[pos] = h;                                                                            \
           Xs[XP + pos] = r;                                                                       \
         }                                                                                         \
@@ -750,7 +706,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
 #endif
 #define C3M_PART(p_) { if ((p_) < NPART && (!(C3M_KO & 1) || k.D < 0)) C3M_GLOAD_X(nch, p_); }
 #define C3M_MMA3(acc_, ah_, al_, bh_, bl_)                                                        \
-  { if (!(C3M_KO & 4) || k.D < 0) { acc_ = mma16(bh_, al_, acc_); acc_ = mma16(bl_, ah_, acc_); acc_ = mma16(bh_, ah_, acc_); } }   /* rows = the 16 voxels of a tile row, columns = output channels */
+  { if (!(C3M_KO & 4) || k.D < 0) { acc_ = mfma16_f16(bh_, al_, acc_); acc_ = mfma16_f16(bl_, ah_, acc_); acc_ = mfma16_f16(bh_, ah_, acc_); } }   /* rows = the 16 voxels of a tile row, columns = output channels */
 #pragma unroll
   for (int s = 0; s < NPART; ++s) C3M_GLOAD_X(0, s);
   C3M_GLOAD_W(0);
@@ -763,7 +719,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
 #pragma unroll
   for (int t = 0; t < TT; ++t)
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[t][j] = f32x4_3{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   int it = 0, ch = 0;
   for (int q = 0; q < niter * k.nchunk; ++q) {
 #pragma unroll
@@ -888,7 +844,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
 #pragma unroll
    for (int t = 0; t < TT; ++t)
 #pragma unroll
-     for (int j = 0; j < NJ; ++j) acc[t][j] = f32x4_3{0.f, 0.f, 0.f, 0.f};
+     for (int j = 0; j < NJ; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
    cn = n; cz0 = z0; cy0 = y0; cx0 = x0;
    ch = 0; ++it;
   }
@@ -896,7 +852,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
 #undef C3M_OFFS
 #undef C3M_GLOAD_X
 #undef C3M_GLOAD_W
-#undef C3M_SPLIT8
 #undef C3M_LSTORE
 #undef C3M_LSTORE_W
 #undef C3M_PART
@@ -1057,8 +1012,8 @@ __device__ __forceinline__ void conv3d_up_wsplit_body(const float* __restrict__ 
   float m = wslab_absmax(w, Ka, Ktot, 0, M);
   m = 8.f * block_max(m, sm);
   if (!(m == m)) m = __uint_as_float(0x7f800000u);
-  const int ew = scale_exp3(m);
-  const float s = pow2f3(ew);
+  const int ew = scale_exp(m);
+  const float s = pow2f(ew);
   if (threadIdx.x == 0 && blockIdx.x == 0) reinterpret_cast<int*>(trailer)[0] = ew;
   const int nchunk = (Ka + 7) / 8, nmt = (M + 31) / 32;
   const int units = 4 * nmt * nchunk * 16 * 32;
@@ -1077,12 +1032,7 @@ __device__ __forceinline__ void conv3d_up_wsplit_body(const float* __restrict__ 
                                  : 0.f;
     }
     u32x4 h, r;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      unsigned hh, rr;
-      split_pair3(v[2 * q], v[2 * q + 1], s, hh, rr);
-      h[q] = hh; r[q] = rr;
-    }
+    split8_scaled(v, s, h, r);
     const long long base = ((((long long)pzy * nmt + mt) * nchunk + ch) * 2) * 512;
     ws[base + slot * 32 + co] = h;
     ws[base + 512 + slot * 32 + co] = r;
@@ -1096,8 +1046,8 @@ __device__ __forceinline__ void conv3d_up_wsplit_body(const float* __restrict__ 
   }
   ms = block_max(ms, sm);
   if (!(ms == ms)) ms = __uint_as_float(0x7f800000u);
-  const int es = scale_exp3(ms);
-  const float ss = pow2f3(es);
+  const int es = scale_exp(ms);
+  const float ss = pow2f(es);
   if (threadIdx.x == 0 && blockIdx.x == 0) reinterpret_cast<int*>(trailer)[1] = es;
   u32x4* wsk = ws + 2LL * units;                          // after the phase units (h and r of every (slot, cout))
   for (int u = blockIdx.x * 1024 + threadIdx.x; u < nmt * 10 * 32; u += gridDim.x * 1024) {
@@ -1110,12 +1060,7 @@ __device__ __forceinline__ void conv3d_up_wsplit_body(const float* __restrict__ 
       v[i] = (t < 9 && dx < 3 && c < Cb && mo < M) ? w[((long long)(t * 3 + dx) * Ktot + Ka + c) * M + mo] : 0.f;
     }
     u32x4 h, r;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      unsigned hh, rr;
-      split_pair3(v[2 * q], v[2 * q + 1], ss, hh, rr);
-      h[q] = hh; r[q] = rr;
-    }
+    split8_scaled(v, ss, h, r);
     wsk[(long long)mt * 640 + t * 32 + co] = h;
     wsk[(long long)mt * 640 + 320 + t * 32 + co] = r;
   }
@@ -1185,9 +1130,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
   const int mt = blockIdx.y, pzy = (int)(rid & 3), pz = pzy >> 1, py = pzy & 1;
 
   const float amax = reduce_absmax(x_amax, k.x_n, red);
-  const int ex = scale_exp3(amax);
+  const int ex = scale_exp(amax);
   const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f3(ex), osc = pow2f3(-ex) * pow2f3(-ew);
+  const float xscale = pow2f(ex), osc = pow2f(-ex) * pow2f(-ew);
 
   const __amdgpu_buffer_rsrc_t x_src = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(x + (long long)n * k.Ca * S), 0, (unsigned)((long long)k.Ca * S * 4), 0x00020000);
@@ -1243,12 +1188,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
 #define C3U_GLOAD_W(ch_)                                                                          \
   _Pragma("unroll") for (int j = 0; j < NW; ++j)                                                  \
     rw[j] = __builtin_amdgcn_raw_buffer_load_b128(w_src, (unsigned)(((ch_) * WU + tid + 256 * j) * 16), 0, 0);
-#define C3U_SPLIT8(v_, h_, r_)                                                                    \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                 \
-    unsigned hh, rr;                                                                              \
-    split_pair3(v_[2 * q], v_[2 * q + 1], xscale, hh, rr);                                        \
-    h_[q] = hh; r_[q] = rr;                                                                       \
-  }
 #define C3U_LSTORE()                                                                              \
   {                                                                                               \
     if (posq >= 0) {                                                                              \
@@ -1256,14 +1195,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
         float v[8];                                                                               \
         _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(rq[c][e]);           \
         u32x4 h, r;                                                                               \
-        C3U_SPLIT8(v, h, r)                                                                       \
+        split8_scaled(v, xscale, h, r);                                                           \
         Xs[posq + e] = h;                                                                         \
         Xs[XP + posq + e] = r;                                                                    \
       }                                                                                           \
     }                                                                                             \
     if (posh >= 0) {                                                                              \
       u32x4 h, r;                                                                                 \
-      C3U_SPLIT8(rh, h, r)                                                                        \
+      split8_scaled(rh, xscale, h, r);                                                            \
       Xs[posh] = h;                                                                               \
       Xs[XP + posh] = r;                                                                          \
     }                                                                                             \
@@ -1347,9 +1286,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         if ((C3U_KO & 8) && k.D > 0) { acc[tp >> 2][j][0] += __uint_as_float(A1[cur][0] ^ B0[cur][j][1] ^ A0[cur][2] ^ B1[cur][j][3]); continue; }
-        acc[tp >> 2][j] = mma3(A1[cur], B0[cur][j], acc[tp >> 2][j]);
-        acc[tp >> 2][j] = mma3(A0[cur], B1[cur][j], acc[tp >> 2][j]);
-        acc[tp >> 2][j] = mma3(A0[cur], B0[cur][j], acc[tp >> 2][j]);
+        acc[tp >> 2][j] = mfma32_f16(A1[cur], B0[cur][j], acc[tp >> 2][j]);
+        acc[tp >> 2][j] = mfma32_f16(A0[cur], B1[cur][j], acc[tp >> 2][j]);
+        acc[tp >> 2][j] = mfma32_f16(A0[cur], B0[cur][j], acc[tp >> 2][j]);
       }
 #pragma unroll
       for (int i = 0; i < 3 * NJ; ++i) {
@@ -1368,7 +1307,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
 #undef C3U_GLOAD_W
 #undef rq
 #undef rw
-#undef C3U_SPLIT8
 #undef C3U_LSTORE
 #undef C3U_OPLOAD
 
@@ -1377,20 +1315,20 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
     // ---- the skip channels: accumulators to the skip products' scale, stage the patch + weights, 2 x 5 k-steps
     __syncthreads();                                       // every wave is done with Xs / Ws
     const float bmax = reduce_absmax(k.b_amax, k.b_n, red);
-    const int eb = scale_exp3(bmax);
+    const int eb = scale_exp(bmax);
     const int es = reinterpret_cast<const int*>(w_trailer)[1];
-    const float bscale = pow2f3(eb);
+    const float bscale = pow2f(eb);
     {
       int d = (eb + es) - (ex + ew);
       d = d > 120 ? 120 : (d < -120 ? -120 : d);
-      const float rs = pow2f3(d);
+      const float rs = pow2f(d);
 #pragma unroll
       for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[p][j][r] *= rs;
-      osc_f = pow2f3(-eb) * pow2f3(-es);
+      osc_f = pow2f(-eb) * pow2f(-es);
     }
     unsigned* Xw = reinterpret_cast<unsigned*>(Xs);
     constexpr int NTASK = SNTASK, NIT = SNIT;
@@ -1409,7 +1347,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           unsigned hh, rr;
-          split_pair3(__uint_as_float(stg[i][e]), __uint_as_float(stg[SNIT + i][e]), bscale, hh, rr);
+          split_pair_scaled(__uint_as_float(stg[i][e]), __uint_as_float(stg[SNIT + i][e]), bscale, hh, rr);
           h[e] = hh; r[e] = rr;
         }
         *reinterpret_cast<u32x4*>(Xw + row * SRS + 4 + 4 * q) = h;
@@ -1418,7 +1356,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
     }
     if (tid < SROWS) {
       unsigned hh, rr;
-      split_pair3(rh[0], rh[1], bscale, hh, rr);
+      split_pair_scaled(rh[0], rh[1], bscale, hh, rr);
       Xw[tid * SRS + 3] = hh;
       Xw[SPW + tid * SRS + 3] = rr;
     }
@@ -1442,9 +1380,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
           const unsigned* p0 = Xw + sbase[j] + toff + px;
           const u32x4 b0{p0[0], p0[1], p0[2], p0[3]};
           const u32x4 b1{p0[SPW], p0[SPW + 1], p0[SPW + 2], p0[SPW + 3]};
-          acc[px][j] = mma3(a1, b0, acc[px][j]);
-          acc[px][j] = mma3(a0, b1, acc[px][j]);
-          acc[px][j] = mma3(a0, b0, acc[px][j]);
+          acc[px][j] = mfma32_f16(a1, b0, acc[px][j]);
+          acc[px][j] = mfma32_f16(a0, b1, acc[px][j]);
+          acc[px][j] = mfma32_f16(a0, b0, acc[px][j]);
         }
       }
     }
@@ -1573,8 +1511,8 @@ __device__ __forceinline__ void conv3d_up_wsplit_t_body(const float* __restrict_
   float m = wslab_absmax(w, Ka, Ktot, 0, M);
   m = 8.f * block_max(m, sm);
   if (!(m == m)) m = __uint_as_float(0x7f800000u);
-  const int ew = scale_exp3(m);
-  const float s = pow2f3(ew);
+  const int ew = scale_exp(m);
+  const float s = pow2f(ew);
   if (threadIdx.x == 0 && blockIdx.x == 0) reinterpret_cast<int*>(trailer)[0] = ew;
   const int nchunk = (M + 7) / 8, nmt = (Ka + 31) / 32;     // reduction = output channels, rows = a's channels
   const int units = 4 * nmt * nchunk * 16 * 32;
@@ -1594,12 +1532,7 @@ __device__ __forceinline__ void conv3d_up_wsplit_t_body(const float* __restrict_
                                  : 0.f;
     }
     u32x4 h, r;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      unsigned hh, rr;
-      split_pair3(v[2 * q], v[2 * q + 1], s, hh, rr);
-      h[q] = hh; r[q] = rr;
-    }
+    split8_scaled(v, s, h, r);
     const long long base = ((((long long)pzy * nmt + mt) * nchunk + ch) * 2) * 512;
     ws[base + slot * 32 + ci_l] = h;
     ws[base + 512 + slot * 32 + ci_l] = r;
@@ -1679,9 +1612,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_dgrad_k(const float* __restr
   }
   const int mt = blockIdx.y;
   const float amax = reduce_absmax(dy_amax, k.dy_n, red);
-  const int ex = scale_exp3(amax);
+  const int ex = scale_exp(amax);
   const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f3(ex), osc = pow2f3(-ex) * pow2f3(-ew);
+  const float xscale = pow2f(ex), osc = pow2f(-ex) * pow2f(-ew);
   if (tid == 0) smax = 0u;
 
   const __amdgpu_buffer_rsrc_t y_src = __builtin_amdgcn_make_buffer_rsrc(
@@ -1737,7 +1670,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_dgrad_k(const float* __restr
             u32x4 h, r;                                                                           \
             _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                       \
               unsigned hh, rr;                                                                    \
-              split_pair3(__uint_as_float(rq[i][2 * q][e]), __uint_as_float(rq[i][2 * q + 1][e]), xscale, hh, rr); \
+              split_pair_scaled(__uint_as_float(rq[i][2 * q][e]), __uint_as_float(rq[i][2 * q + 1][e]), xscale, hh, rr); \
               h[q] = hh; r[q] = rr;                                                               \
             }                                                                                     \
             const int pos = (e & 1) * 2 * XP + trow[i] * HX + hx;                                 \
@@ -1780,9 +1713,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_dgrad_k(const float* __restr
       if (tp + 1 < 8) C3D_OPLOAD(cur ^ 1, tp + 1)
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        acc[j] = mma3(A1[cur], B0[cur][j], acc[j]);
-        acc[j] = mma3(A0[cur], B1[cur][j], acc[j]);
-        acc[j] = mma3(A0[cur], B0[cur][j], acc[j]);
+        acc[j] = mfma32_f16(A1[cur], B0[cur][j], acc[j]);
+        acc[j] = mfma32_f16(A0[cur], B1[cur][j], acc[j]);
+        acc[j] = mfma32_f16(A0[cur], B0[cur][j], acc[j]);
       }
 #pragma unroll
       for (int i = 0; i < 3 * NJ; ++i) {
@@ -1924,10 +1857,10 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_split_k(const float* __restr
   const int l31 = lane & 31, hi = lane >> 5;
   const long long S = (long long)k.D * k.H * k.W;
 
-  const int ex = scale_exp3(reduce_absmax(x_amax, k.x_n, red));
+  const int ex = scale_exp(reduce_absmax(x_amax, k.x_n, red));
   __syncthreads();
-  const int ed = scale_exp3(reduce_absmax(dy_amax, k.dy_n, red));
-  const float xscale = pow2f3(ex), dscale = pow2f3(ed), oscale = pow2f3(-ex), oscale2 = pow2f3(-ed);
+  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
+  const float xscale = pow2f(ex), dscale = pow2f(ed), oscale = pow2f(-ex), oscale2 = pow2f(-ed);
 
   f32x16 acc[NCH][2];
 #pragma unroll
@@ -2003,7 +1936,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_split_k(const float* __restr
     if (xrow) {
       unsigned ph[9], pr[9];
 #pragma unroll
-      for (int j = 0; j < 9; ++j) split_pair3(rx[2 * j], rx[2 * j + 1], xscale, ph[j], pr[j]);
+      for (int j = 0; j < 9; ++j) split_pair_scaled(rx[2 * j], rx[2 * j + 1], xscale, ph[j], pr[j]);
       const int ubase = xci * CIS + (xhz * HY + xhy) * 2;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -2030,9 +1963,9 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_split_k(const float* __restr
           const u32x4 v = ry[2 * u + q];
           if (db_y) bacc += (__uint_as_float(v[0]) + __uint_as_float(v[1])) + (__uint_as_float(v[2]) + __uint_as_float(v[3]));
           unsigned hh, rr;
-          split_pair3(__uint_as_float(v[0]), __uint_as_float(v[1]), dscale, hh, rr);
+          split_pair_scaled(__uint_as_float(v[0]), __uint_as_float(v[1]), dscale, hh, rr);
           h[2 * q] = hh; r[2 * q] = rr;
-          split_pair3(__uint_as_float(v[2]), __uint_as_float(v[3]), dscale, hh, rr);
+          split_pair_scaled(__uint_as_float(v[2]), __uint_as_float(v[3]), dscale, hh, rr);
           h[2 * q + 1] = hh; r[2 * q + 1] = rr;
         }
         Ys[ub + u] = h;
@@ -2067,9 +2000,9 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_split_k(const float* __restr
         for (int s = 0; s < 2; ++s) {
           if (!tok[s]) continue;
           const u32x4 a0 = Xs[aoff[s] + zy], a1 = Xs[XSPL + aoff[s] + zy];
-          acc[c2][s] = mma3(a1, b0, acc[c2][s]);
-          acc[c2][s] = mma3(a0, b1, acc[c2][s]);
-          acc[c2][s] = mma3(a0, b0, acc[c2][s]);
+          acc[c2][s] = mfma32_f16(a1, b0, acc[c2][s]);
+          acc[c2][s] = mfma32_f16(a0, b1, acc[c2][s]);
+          acc[c2][s] = mfma32_f16(a0, b0, acc[c2][s]);
         }
       }
     }
@@ -2127,16 +2060,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_split_k(const float* __restr
 #ifndef W3T_KO
 #define W3T_KO 0     // knock-out builds for timing: 1 = no MFMAs, 2 = no prefetch loads, 4 = no convert + LDS store, 8 = no operand reads
 #endif
-typedef short s16x4_3 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_3* lds_tr_ptr;
-__device__ __forceinline__ uint2 tr_read8(unsigned byte_addr) {
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(uintptr_t)byte_addr));
-}
-#define TR_PAIR(dst_, addr_)                                                                      \
-  {                                                                                               \
-    const uint2 u0_ = tr_read8(addr_), u1_ = tr_read8((addr_) + 64u);                             \
-    dst_ = u32x4{u0_.x, u0_.y, u1_.x, u1_.y};                                                     \
-  }
 
 template <int NCH>
 struct W3T {
@@ -2170,10 +2093,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restr
   const long long S = (long long)k.D * k.H * k.W;
   const unsigned s4 = (unsigned)S * 4u;
 
-  const int ex = scale_exp3(reduce_absmax(x_amax, k.x_n, red));
+  const int ex = scale_exp(reduce_absmax(x_amax, k.x_n, red));
   __syncthreads();
-  const int ed = scale_exp3(reduce_absmax(dy_amax, k.dy_n, red));
-  const float xscale = pow2f3(ex), dscale = pow2f3(ed), oscale = pow2f3(-ex), oscale2 = pow2f3(-ed);
+  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
+  const float xscale = pow2f(ex), dscale = pow2f(ed), oscale = pow2f(-ex), oscale2 = pow2f(-ed);
 
   constexpr int NA = PAIR ? 3 : 2;                         // accumulators (row tiles) per chunk and wave
   constexpr int NKS = PAIR ? 8 : 16;                       // k-steps per phase
@@ -2293,7 +2216,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restr
       u32x4 h, r;                                                                                 \
       _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                             \
         unsigned hh, rr;                                                                          \
-        split_pair3(__uint_as_float(rq[2 * q][e]), __uint_as_float(rq[2 * q + 1][e]), xscale, hh, rr); \
+        split_pair_scaled(__uint_as_float(rq[2 * q][e]), __uint_as_float(rq[2 * q + 1][e]), xscale, hh, rr); \
         h[q] = hh; r[q] = rr;                                                                     \
       }                                                                                           \
       Xs[xpos0 + e] = h;                                                                          \
@@ -2310,7 +2233,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restr
       u32x4 h, r;                                                                                 \
       _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                             \
         unsigned hh, rr;                                                                          \
-        split_pair3(__uint_as_float(ry[2 * q][e]), __uint_as_float(ry[2 * q + 1][e]), dscale, hh, rr); \
+        split_pair_scaled(__uint_as_float(ry[2 * q][e]), __uint_as_float(ry[2 * q + 1][e]), dscale, hh, rr); \
         h[q] = hh; r[q] = rr;                                                                     \
       }                                                                                           \
       Ys[yunit0 + 4 * e] = h;                                                                     \
@@ -2326,17 +2249,21 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restr
   // HALF-step ahead -- tile 1's while tile 0's three MFMAs run and vice versa -- B (shared by both tiles) is
   // double-buffered and fetched one step ahead: 32 operand registers instead of 48 (three chunks of accumulators +
   // both staging sets + 48 did not fit 256 registers).
+  // (the two reads of a pair stay spelled out at this one site: through tr_pair the PAIR instances of this kernel come out
+  // of the compiler with another schedule of their address arithmetic)
+#define W3T_TR_PAIR64(dst_, addr_)                                                                \
+  {                                                                                               \
+    const uint2 u0_ = tr_read(addr_), u1_ = tr_read((addr_) + 64u);                               \
+    dst_ = u32x4{u0_.x, u0_.y, u1_.x, u1_.y};                                                     \
+  }
 #define W3T_READ_A(t_, s_)                                                                        \
   {                                                                                               \
     const unsigned ko = (unsigned)((((s_) >> 3) * SZP + ((s_) & 7) * HXP) * 16);                  \
-    TR_PAIR(A1[t_], aaddr[t_] + ko + XPOS * 16u)                                                  \
-    TR_PAIR(A0[t_], aaddr[t_] + ko)                                                               \
+    W3T_TR_PAIR64(A1[t_], aaddr[t_] + ko + XPOS * 16u)                                            \
+    W3T_TR_PAIR64(A0[t_], aaddr[t_] + ko)                                                         \
   }
 #define W3T_READ_B(B_, b_, s_, off_)                                                              \
-  {                                                                                               \
-    const uint2 u0_ = tr_read8(baddr[0] + (unsigned)(s_) * 1024u + (off_)), u1_ = tr_read8(baddr[1] + (unsigned)(s_) * 1024u + (off_)); \
-    B_[b_] = u32x4{u0_.x, u0_.y, u1_.x, u1_.y};                                                   \
-  }
+  B_[b_] = tr_pair(baddr[0] + (unsigned)(s_) * 1024u + (off_), baddr[1] + (unsigned)(s_) * 1024u + (off_));
   // the 16 k-steps of chunk c_ (LAST_: the next phase starts a new tile, so dY is prefetched too -- a wave-uniform
   // branch around one load per step; two copies of the loop behind one branch cost 32 registers of accumulator copies)
 #define W3T_KLOOP(c_, LAST_)                                                                      \
@@ -2377,17 +2304,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restr
       /* tile 8, k-steps 2 wid and 2 wid + 1 (wave-uniform offsets: one add per address) */        \
       _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                             \
         const unsigned ko = (unsigned)((2 * wid + u) * HXP * 16), kb = (unsigned)(2 * wid + u) * 1024u; \
-        TR_PAIR(A1[u], aaddr[2] + ko + XPOS * 16u)                                                \
-        TR_PAIR(A0[u], aaddr[2] + ko)                                                             \
-        { const uint2 u0_ = tr_read8(baddr[0] + kb), u1_ = tr_read8(baddr[1] + kb);               \
-          B0[u] = u32x4{u0_.x, u0_.y, u1_.x, u1_.y}; }                                            \
-        { const uint2 v0_ = tr_read8(baddr[0] + kb + YU * 16u), v1_ = tr_read8(baddr[1] + kb + YU * 16u); \
-          B1[u] = u32x4{v0_.x, v0_.y, v1_.x, v1_.y}; }                                            \
+        A1[u] = tr_pair(aaddr[2] + ko + XPOS * 16u, aaddr[2] + ko + XPOS * 16u + 64u);            \
+        A0[u] = tr_pair(aaddr[2] + ko, aaddr[2] + ko + 64u);                                      \
+        B0[u] = tr_pair(baddr[0] + kb, baddr[1] + kb);                                            \
+        B1[u] = tr_pair(baddr[0] + kb + YU * 16u, baddr[1] + kb + YU * 16u);                      \
       }                                                                                           \
       _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                             \
-        acc[c_][NA - 1] = mma3(A1[u], B0[u], acc[c_][NA - 1]);                                    \
-        acc[c_][NA - 1] = mma3(A0[u], B1[u], acc[c_][NA - 1]);                                    \
-        acc[c_][NA - 1] = mma3(A0[u], B0[u], acc[c_][NA - 1]);                                    \
+        acc[c_][NA - 1] = mfma32_f16(A1[u], B0[u], acc[c_][NA - 1]);                              \
+        acc[c_][NA - 1] = mfma32_f16(A0[u], B1[u], acc[c_][NA - 1]);                              \
+        acc[c_][NA - 1] = mfma32_f16(A0[u], B0[u], acc[c_][NA - 1]);                              \
       }                                                                                           \
       __builtin_amdgcn_sched_barrier(0);                                                          \
     }                                                                                             \
@@ -2396,9 +2321,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restr
 #define W3T_MMA(c_, t) acc[c_][t][0] += __uint_as_float(A1[t][0] ^ B0[cur][1] ^ A0[t][2] ^ B1[cur][3]);
 #else
 #define W3T_MMA(c_, t)                                                                            \
-  acc[c_][t] = mma3(A1[t], B0[cur], acc[c_][t]);                                                  \
-  acc[c_][t] = mma3(A0[t], B1[cur], acc[c_][t]);                                                  \
-  acc[c_][t] = mma3(A0[t], B0[cur], acc[c_][t]);
+  acc[c_][t] = mfma32_f16(A1[t], B0[cur], acc[c_][t]);                                            \
+  acc[c_][t] = mfma32_f16(A0[t], B1[cur], acc[c_][t]);                                            \
+  acc[c_][t] = mfma32_f16(A0[t], B0[cur], acc[c_][t]);
 #endif
 
   u32x4 A0[2], A1[2], B0[2], B1[2];
@@ -2451,6 +2376,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restr
 #undef W3T_GLOAD_Y1
 #undef W3T_STORE_X
 #undef W3T_STORE_Y
+#undef W3T_TR_PAIR64
 #undef W3T_READ_A
 #undef W3T_READ_B
 #undef W3T_KLOOP

@@ -16,7 +16,7 @@
 // read through wave-uniform addresses from the fp32 tap-major packing [27][Cin][Cout] (scalar loads: an SGPR operand per FMA).
 // Epilogue as the split kernels': bias, activation, optionally the derivative of the LeakyReLU whose output is `act_src`
 // (the data gradient lands in front of that activation), the range probe of the result for the next split conv.
-#include "common.h"
+#include "split_f16.h"
 
 namespace {
 constexpr int T_TZ = 4, T_TX = 32, T_PZ = T_TZ + 2, T_PITCH = 40;
@@ -424,31 +424,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_s2c2_wgrad_k(const float* __res
 // staged once as scaled fp16 pairs, in-plane halo of the 3-channel operand only.  The four waves (two rows each) meet in
 // LDS in wave order, then one set of df_acc adds per workgroup; the bias gradient is summed from the staged dY.
 // ------------------------------------------------------------------------------------------------
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split_pair_t(float x0, float x1, float s, unsigned& h, unsigned& r) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(s), "v"(h));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(s), "v"(h));
-}
-__device__ __forceinline__ void split8_t(const float* v, float s, u32x4_t& h, u32x4_t& r) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    unsigned hh, rr;
-    split_pair_t(v[2 * q], v[2 * q + 1], s, hh, rr);
-    h[q] = hh; r[q] = rr;
-  }
-}
-__device__ __forceinline__ f32x4_t mma16t(u32x4_t a, u32x4_t b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ int scale_exp_t(float amax) {
-  const int be = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  int e = (amax > 0.f) ? 14 - be : 0;
-  return e < -100 ? -100 : (e > 100 ? 100 : e);
-}
 struct FwP {
   int N, D, H, W, Cout;
   int x_n, dy_n;                 // floats of the two range probes
@@ -467,8 +442,8 @@ __global__ __launch_bounds__(256, CO <= 3 ? 3 : 2) void conv3d_flow_wgrad_k(cons
   constexpr int FW_NCOL = 3 * CO;                  // (co, dx) columns held
   constexpr int FW_DSLOT = 2 * FW_NCOL * FW_DCS;   // [split][col]
   // ONE x slot: plane z + 1 is written after the barrier that ends the reads of plane z (16.9 KB + 35.4 KB: three workgroups per CU)
-  __shared__ __attribute__((aligned(16))) u32x4_t Xa[FW_XSLOT];
-  __shared__ __attribute__((aligned(16))) u32x4_t Dsh[3 * FW_DSLOT];     // 35.4 KB for CO = 3 (also the epilogue's reduction buffer)
+  __shared__ __attribute__((aligned(16))) u32x4 Xa[FW_XSLOT];
+  __shared__ __attribute__((aligned(16))) u32x4 Dsh[3 * FW_DSLOT];       // 35.4 KB for CO = 3 (also the epilogue's reduction buffer)
   __shared__ float red[17];
   __shared__ float bsum[160];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l15 = lane & 15, kg = lane >> 4;
@@ -483,11 +458,11 @@ __global__ __launch_bounds__(256, CO <= 3 ? 3 : 2) void conv3d_flow_wgrad_k(cons
   const long long HW = (long long)k.H * k.W, S = HW * k.D;
   const float* xn = x + (long long)n * 16 * S;
   const float* dn = dy + (long long)n * k.Cout * S;
-  const int ex = scale_exp_t(reduce_absmax(x_amax, k.x_n, red));
+  const int ex = scale_exp(reduce_absmax(x_amax, k.x_n, red));
   __syncthreads();
-  const int ed = scale_exp_t(reduce_absmax(dy_amax, k.dy_n, red));
-  const float xscale = __uint_as_float((unsigned)(ex + 127) << 23), dscale = __uint_as_float((unsigned)(ed + 127) << 23);
-  const float osc = __uint_as_float((unsigned)(-ex + 127) << 23) * __uint_as_float((unsigned)(-ed + 127) << 23);
+  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
+  const float xscale = pow2f(ex), dscale = pow2f(ed);
+  const float osc = pow2f(-ex) * pow2f(-ed);
   const int ncol = 3 * k.Cout;
 
   // x staging: two items per thread, item = (ci, row, 8 voxels)
@@ -516,8 +491,8 @@ __global__ __launch_bounds__(256, CO <= 3 ? 3 : 2) void conv3d_flow_wgrad_k(cons
     _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                        \
       const int i_ = tid + 256 * j, ci_ = i_ >> 5, row_ = (i_ >> 2) & 7, g_ = i_ & 3;                      \
       const float v_[8] = {rx[j][0].x, rx[j][0].y, rx[j][0].z, rx[j][0].w, rx[j][1].x, rx[j][1].y, rx[j][1].z, rx[j][1].w}; \
-      u32x4_t h_, r_;                                                                                      \
-      split8_t(v_, xscale, h_, r_);                                                                        \
+      u32x4 h_, r_;                                                                                        \
+      split8_scaled(v_, xscale, h_, r_);                                                                   \
       Xa[ci_ * FW_XCS + row_ * 4 + g_] = h_;                                                               \
       Xa[(16 + ci_) * FW_XCS + row_ * 4 + g_] = r_;                                                        \
     }                                                                                                      \
@@ -541,17 +516,17 @@ __global__ __launch_bounds__(256, CO <= 3 ? 3 : 2) void conv3d_flow_wgrad_k(cons
     if ((own_) && d_row >= 1 && d_row <= 8)                                                                \
       bacc += ((w_[1] + w_[2]) + (w_[3] + w_[4])) + ((w_[5] + w_[6]) + (w_[7] + w_[8]));                   \
     _Pragma("unroll") for (int dx_ = 0; dx_ < 3; ++dx_) {                                                  \
-      u32x4_t h_, r_;                                                                                      \
-      split8_t(&w_[2 - dx_], dscale, h_, r_);                                                              \
+      u32x4 h_, r_;                                                                                        \
+      split8_scaled(&w_[2 - dx_], dscale, h_, r_);                                                         \
       const int u_ = (slot_) * FW_DSLOT + (d_co * 3 + dx_) * FW_DCS + d_row * 4 + d_g;                     \
       Dsh[u_] = h_;                                                                                        \
       Dsh[u_ + FW_NCOL * FW_DCS] = r_;                                                                     \
     }                                                                                                      \
   }
 
-  f32x4_t acc[9];
+  f32x4 acc[9];
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 9; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   // prologue: dY planes zs - 1, zs, zs + 1 -> slots (z + 3) % 3; x plane zs -> buffer 0
   FW_GLOAD_D(zs - 1) FW_LSTORE_D((zs + 2) % 3, false)
@@ -567,19 +542,19 @@ __global__ __launch_bounds__(256, CO <= 3 ? 3 : 2) void conv3d_flow_wgrad_k(cons
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
       const int row = 2 * wid + rr;
-      const u32x4_t ah = Xa[l15 * FW_XCS + row * 4 + kg];
-      const u32x4_t ar = Xa[(16 + l15) * FW_XCS + row * 4 + kg];
+      const u32x4 ah = Xa[l15 * FW_XCS + row * 4 + kg];
+      const u32x4 ar = Xa[(16 + l15) * FW_XCS + row * 4 + kg];
 #pragma unroll
       for (int dz = 0; dz < 3; ++dz) {
         const int slot = (z - dz + 1 + 3) % 3;
 #pragma unroll
         for (int dyy = 0; dyy < 3; ++dyy) {
           const int u = slot * FW_DSLOT + bcol * FW_DCS + (row - dyy + 2) * 4 + kg;
-          const u32x4_t bh = Dsh[u], br = Dsh[u + FW_NCOL * FW_DCS];
-          f32x4_t a_ = acc[dz * 3 + dyy];
-          a_ = mma16t(ah, bh, a_);
-          a_ = mma16t(ah, br, a_);
-          a_ = mma16t(ar, bh, a_);
+          const u32x4 bh = Dsh[u], br = Dsh[u + FW_NCOL * FW_DCS];
+          f32x4 a_ = acc[dz * 3 + dyy];
+          a_ = mfma16_f16(ah, bh, a_);
+          a_ = mfma16_f16(ah, br, a_);
+          a_ = mfma16_f16(ar, bh, a_);
           acc[dz * 3 + dyy] = a_;
         }
       }

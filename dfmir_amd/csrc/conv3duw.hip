@@ -27,12 +27,8 @@
 //                             two waves per SIMD, 8 tiles per wave, never fused.  Same speed on the up-sampled share
 //                             (profiles/r05_bench_upwgrad.txt): these kernels are bound by the sum of their matrix and staging
 //                             work, not by how the waves share it (hardware fact 10).
-#include "conv3x3_common.h"
-#include <type_traits>
+#include "split_f16.h"
 
-typedef _Float16 f16x8_u __attribute__((ext_vector_type(8)));
-typedef short s16x4_u __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_u* lds_tr_ptr_u;
 #ifndef UW_KO
 #define UW_KO 0      // knock-out builds (timing only): 1 no MFMAs, 2 no staging loads, 4 no conversion + LDS stores, 8 no operand reads,
                      // 16 no epilogue atomics (one store per lane instead), 32 dY loads from a cache-resident 4 KB (4-wave kernel)
@@ -40,45 +36,12 @@ typedef __attribute__((address_space(3))) s16x4_u* lds_tr_ptr_u;
 
 namespace {
 
-__device__ __forceinline__ int scale_exp_u(float amax) {
-  const int be = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  int e = (amax > 0.f) ? 14 - be : 0;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);
-  return e;
-}
-__device__ __forceinline__ float pow2f_u(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-// (x0, x1) * s -> leading fp16 pair h and residual pair r
-__device__ __forceinline__ void split_pair_u(float x0, float x1, float s, unsigned& h, unsigned& r) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(s), "v"(h));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(s), "v"(h));
-}
-__device__ __forceinline__ f32x16 mma_u(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_u, a), __builtin_bit_cast(f16x8_u, b), c, 0, 0, 0);
-}
-// the same with the accumulator in VGPRs.  The 16 `a` tiles of conv3d_upwgrad4_k fill the 256 AGPRs; the compiler only
+// mfma32_f16 with the accumulator in VGPRs.  The 16 `a` tiles of conv3d_upwgrad4_k fill the 256 AGPRs; the compiler only
 // emits the AGPR form of an MFMA and would swap whole tiles between the two files around every b product (152 v_accvgpr
 // moves per half-step).  Hazards the compiler cannot see behind the asm: the tile is only ever read by the next product of
 // its own chain (same vDst as SrcC: back-to-back issue is legal) until the epilogue, which waits first.
 __device__ __forceinline__ void mma_v(u32x4 a, u32x4 b, f32x16& c) {
   asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-// 16 lanes x 8 bytes: lane 4 j + q supplies the address of (voxel j, channel quad q); lane 4 q + c receives the c-th
-// channel of quad q at voxels j = 0..3 (scripts/ubench/tr_read_probe.hip)
-__device__ __forceinline__ uint2 tr_read_u(unsigned byte_addr) {
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr_u)(uintptr_t)byte_addr));
-}
-__device__ __forceinline__ u32x4 tr_pair_u(unsigned a0, unsigned a1) {
-  const uint2 u0 = tr_read_u(a0), u1 = tr_read_u(a1);
-  return u32x4{u0.x, u0.y, u1.x, u1.y};
-}
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for_u(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for_u<B + 1, E>(f);
-  }
 }
 
 struct UwP {
@@ -108,10 +71,10 @@ __global__ __launch_bounds__(512, 1) void conv3d_upwgrad_k(const float* __restri
   const int l31 = lane & 31, hi = lane >> 5;
   const int px = wid & 1, py = (wid >> 1) & 1, szi = wid >> 2;
 
-  const int ea = scale_exp_u(reduce_absmax(a_amax, k.a_n, red));
+  const int ea = scale_exp(reduce_absmax(a_amax, k.a_n, red));
   __syncthreads();
-  const int ed = scale_exp_u(reduce_absmax(dy_amax, k.dy_n, red));
-  const float ascale = pow2f_u(ea), dscale = pow2f_u(ed), osc_a = pow2f_u(-ea), osc_d = pow2f_u(-ed);
+  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
+  const float ascale = pow2f(ea), dscale = pow2f(ed), osc_a = pow2f(-ea), osc_d = pow2f(-ed);
 
   const int D = 2 * k.Dl, H = 2 * k.Hl, W = 2 * k.Wl;
   (void)D;
@@ -169,7 +132,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_upwgrad_k(const float* __restri
     u32x4 h_, r_;                                                                                 \
     _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                            \
       unsigned hh_, rr_;                                                                          \
-      split_pair_u(__uint_as_float(V_(2 * q_)), __uint_as_float(V_(2 * q_ + 1)), scale_, hh_, rr_); \
+      split_pair_scaled(__uint_as_float(V_(2 * q_)), __uint_as_float(V_(2 * q_ + 1)), scale_, hh_, rr_); \
       h_[q_] = hh_; r_[q_] = rr_;                                                                 \
     }                                                                                             \
     UW_LDS_ST(addr_, h_) UW_LDS_ST((addr_) + (lo_), r_)                                           \
@@ -193,17 +156,17 @@ __global__ __launch_bounds__(512, 1) void conv3d_upwgrad_k(const float* __restri
     const unsigned bb0_ = bl[0] + (PZ_) * UW_YBUF, bb1_ = bl[1] + (PZ_) * UW_YBUF;                \
     const unsigned yst_ = yst0 + ((PZ_) ^ 1) * UW_YBUF;                                           \
     u32x4 B0[2], B1[2], A0, A1;                                                                   \
-    static_for_u<0, 10>([&](auto jc_) __attribute__((always_inline)) {                            \
+    static_for<0, 10>([&](auto jc_) __attribute__((always_inline)) {                              \
       constexpr int j_ = decltype(jc_)::value, R_ = j_ >> 1, ix_ = j_ & 1;                        \
       if constexpr (ix_ == 0 && R_ < 4) {                                                         \
         if (!(UW_KO & 8) || R_ == 0) {                                                            \
-          B0[R_ & 1] = tr_pair_u(bb0_ + R_ * 1024, bb1_ + R_ * 1024);                             \
-          B1[R_ & 1] = tr_pair_u(bb0_ + R_ * 1024 + UW_YSPLIT, bb1_ + R_ * 1024 + UW_YSPLIT);     \
+          B0[R_ & 1] = tr_pair(bb0_ + R_ * 1024, bb1_ + R_ * 1024);                               \
+          B1[R_ & 1] = tr_pair(bb0_ + R_ * 1024 + UW_YSPLIT, bb1_ + R_ * 1024 + UW_YSPLIT);       \
         }                                                                                         \
       }                                                                                           \
       if (!(UW_KO & 8) || j_ == 0) {                                                              \
-        A0 = tr_pair_u(al[0][ix_] + ab_ + R_ * 1152, al[1][ix_] + ab_ + R_ * 1152);               \
-        A1 = tr_pair_u(al[0][ix_] + ab_ + R_ * 1152 + UW_ASPLIT, al[1][ix_] + ab_ + R_ * 1152 + UW_ASPLIT); \
+        A0 = tr_pair(al[0][ix_] + ab_ + R_ * 1152, al[1][ix_] + ab_ + R_ * 1152);                 \
+        A1 = tr_pair(al[0][ix_] + ab_ + R_ * 1152 + UW_ASPLIT, al[1][ix_] + ab_ + R_ * 1152 + UW_ASPLIT);   \
       }                                                                                           \
       if constexpr (j_ < 4) {                                                                     \
         if constexpr ((PZ_) == 0) { UW_YLOAD(rq0, 2 * j_, yoff_) UW_YLOAD(rq0, 2 * j_ + 1, yoff_) } \
@@ -223,14 +186,14 @@ __global__ __launch_bounds__(512, 1) void conv3d_upwgrad_k(const float* __restri
       if constexpr ((PZ_) == 1 && j_ == 8) { UW_CONV_ST(UW_V_RA, ascale, ast0 + (sn_), UW_ASPLIT) } \
       if (!(UW_KO & 1)) {                                                                         \
         if constexpr (R_ < 4) {       /* iy = 0: dY row R */                                      \
-          acc[PZ_][ix_] = mma_u(A1, B0[R_ & 1], acc[PZ_][ix_]);                                   \
-          acc[PZ_][ix_] = mma_u(A0, B1[R_ & 1], acc[PZ_][ix_]);                                   \
-          acc[PZ_][ix_] = mma_u(A0, B0[R_ & 1], acc[PZ_][ix_]);                                   \
+          acc[PZ_][ix_] = mfma32_f16(A1, B0[R_ & 1], acc[PZ_][ix_]);                              \
+          acc[PZ_][ix_] = mfma32_f16(A0, B1[R_ & 1], acc[PZ_][ix_]);                              \
+          acc[PZ_][ix_] = mfma32_f16(A0, B0[R_ & 1], acc[PZ_][ix_]);                              \
         }                                                                                         \
         if constexpr (R_ >= 1) {      /* iy = 1: dY row R - 1 */                                  \
-          acc[PZ_][2 + ix_] = mma_u(A1, B0[(R_ - 1) & 1], acc[PZ_][2 + ix_]);                     \
-          acc[PZ_][2 + ix_] = mma_u(A0, B1[(R_ - 1) & 1], acc[PZ_][2 + ix_]);                     \
-          acc[PZ_][2 + ix_] = mma_u(A0, B0[(R_ - 1) & 1], acc[PZ_][2 + ix_]);                     \
+          acc[PZ_][2 + ix_] = mfma32_f16(A1, B0[(R_ - 1) & 1], acc[PZ_][2 + ix_]);                \
+          acc[PZ_][2 + ix_] = mfma32_f16(A0, B1[(R_ - 1) & 1], acc[PZ_][2 + ix_]);                \
+          acc[PZ_][2 + ix_] = mfma32_f16(A0, B0[(R_ - 1) & 1], acc[PZ_][2 + ix_]);                \
         }                                                                                         \
       } else {                                                                                    \
         acc[PZ_][ix_][0] += __uint_as_float(A0[0] ^ A1[1] ^ B0[R_ & 1][2] ^ B1[R_ & 1][3]);       \
@@ -369,10 +332,10 @@ __global__ __launch_bounds__(256, 1) void conv3d_upwgrad4_k(const float* __restr
   const int l31 = lane & 31, hi = lane >> 5;
   const int px = wid & 1, py = wid >> 1;
 
-  const int ea = scale_exp_u(reduce_absmax(a_amax, k.a_n, red));
+  const int ea = scale_exp(reduce_absmax(a_amax, k.a_n, red));
   __syncthreads();
-  const int ed = scale_exp_u(reduce_absmax(dy_amax, k.dy_n, red));
-  const float ascale = pow2f_u(ea), dscale = pow2f_u(ed), osc_a = pow2f_u(-ea), osc_d = pow2f_u(-ed);
+  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
+  const float ascale = pow2f(ea), dscale = pow2f(ed), osc_a = pow2f(-ea), osc_d = pow2f(-ed);
 
   const int D = 2 * k.Dl, H = 2 * k.Hl, W = 2 * k.Wl;
   const unsigned HW = (unsigned)(H * W), HWl = (unsigned)(k.Hl * k.Wl);
@@ -475,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_upwgrad4_k(const float* __restr
     u32x4 h_, r_;                                                                                 \
     _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                            \
       unsigned hh_, rr_;                                                                          \
-      split_pair_u(__uint_as_float(V_(2 * q_)), __uint_as_float(V_(2 * q_ + 1)), scale_, hh_, rr_); \
+      split_pair_scaled(__uint_as_float(V_(2 * q_)), __uint_as_float(V_(2 * q_ + 1)), scale_, hh_, rr_); \
       h_[q_] = hh_; r_[q_] = rr_;                                                                 \
     }                                                                                             \
     UW_LDS_ST(addr_, h_) UW_LDS_ST((addr_) + (lo_), r_)                                           \
@@ -503,7 +466,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_upwgrad4_k(const float* __restr
   if (FUSEB && !(UW_KO & 4)) {                                                                    \
     _Pragma("unroll") for (int e_ = 0; e_ < 2; ++e_) {                                            \
       unsigned h_, r_;                                                                            \
-      split_pair_u(__uint_as_float(rb[0][e_]), __uint_as_float(rb[1][e_]), ascale, h_, r_);       \
+      split_pair_scaled(__uint_as_float(rb[0][e_]), __uint_as_float(rb[1][e_]), ascale, h_, r_);  \
       if (bst[e_] != OOB) {                                                                       \
         UW_LDS_ST4(bst[e_] + (slot_), h_) UW_LDS_ST4(bsy[e_] + (slot_), h_)                       \
         UW_LDS_ST4(bst[e_] + (slot_) + UW_BSPLIT, r_) UW_LDS_ST4(bsy[e_] + (slot_) + UW_BSPLIT, r_) \
@@ -531,18 +494,18 @@ __global__ __launch_bounds__(256, 1) void conv3d_upwgrad4_k(const float* __restr
       constexpr int g2_ = decltype(gc2_)::value, R2_ = g2_ < 20 ? g2_ / 5 : 4, k2_ = g2_ < 20 ? g2_ % 5 : g2_ - 19; \
       if constexpr (g2_ < 24) {                                                                   \
         if constexpr (k2_ == 0) {                                                                 \
-          B0[R2_ & 1] = tr_pair_u(bb0_ + R2_ * 1024, bb1_ + R2_ * 1024);                          \
-          B1[R2_ & 1] = tr_pair_u(bb0_ + R2_ * 1024 + UW_YSPLIT, bb1_ + R2_ * 1024 + UW_YSPLIT);  \
+          B0[R2_ & 1] = tr_pair(bb0_ + R2_ * 1024, bb1_ + R2_ * 1024);                            \
+          B1[R2_ & 1] = tr_pair(bb0_ + R2_ * 1024 + UW_YSPLIT, bb1_ + R2_ * 1024 + UW_YSPLIT);    \
         } else {                                                                                  \
           constexpr int ix2_ = (k2_ - 1) >> 1, iz2_ = (k2_ - 1) & 1;                              \
           const unsigned ab_ = iz2_ ? (sa1_) : (sa0_);                                            \
-          A0[g2_ & 1] = tr_pair_u(al[0][ix2_] + ab_ + R2_ * 1152, al[1][ix2_] + ab_ + R2_ * 1152); \
-          A1[g2_ & 1] = tr_pair_u(al[0][ix2_] + ab_ + R2_ * 1152 + UW_ASPLIT, al[1][ix2_] + ab_ + R2_ * 1152 + UW_ASPLIT); \
+          A0[g2_ & 1] = tr_pair(al[0][ix2_] + ab_ + R2_ * 1152, al[1][ix2_] + ab_ + R2_ * 1152);   \
+          A1[g2_ & 1] = tr_pair(al[0][ix2_] + ab_ + R2_ * 1152 + UW_ASPLIT, al[1][ix2_] + ab_ + R2_ * 1152 + UW_ASPLIT);   \
         }                                                                                         \
       }                                                                                           \
     };                                                                                            \
     rd_(std::integral_constant<int, 0>{});                                                        \
-    static_for_u<0, 24>([&](auto gc_) __attribute__((always_inline)) {                            \
+    static_for<0, 24>([&](auto gc_) __attribute__((always_inline)) {                              \
       constexpr int g_ = decltype(gc_)::value, R_ = g_ < 20 ? g_ / 5 : 4, kk_ = g_ < 20 ? g_ % 5 : g_ - 19; \
       constexpr int ix_ = kk_ ? (kk_ - 1) >> 1 : 0, iz_ = kk_ ? (kk_ - 1) & 1 : 0;                \
       constexpr bool nextb_ = g_ + 1 < 20 && (g_ + 1) % 5 == 0;   /* the next group opens a row: its dY operand replaces */ \
@@ -568,8 +531,8 @@ __global__ __launch_bounds__(256, 1) void conv3d_upwgrad4_k(const float* __restr
           if constexpr (FUSEB) {      /* b tiles: their operands are read here (the A buffer of this group is free) */ \
             _Pragma("unroll") for (int T_ = 0; T_ < 2; ++T_) {                                    \
               const unsigned q0_ = qa_[T_] + R_ * qstep[T_], q1_ = q0_ + qd[T_];                  \
-              A0[g_ & 1] = tr_pair_u(q0_, q1_);                                                   \
-              A1[g_ & 1] = tr_pair_u(q0_ + UW_BSPLIT, q1_ + UW_BSPLIT);                           \
+              A0[g_ & 1] = tr_pair(q0_, q1_);                                                     \
+              A1[g_ & 1] = tr_pair(q0_ + UW_BSPLIT, q1_ + UW_BSPLIT);                             \
               mma_v(A1[g_ & 1], B0[R_ & 1], accb[T_]);                                            \
               mma_v(A0[g_ & 1], B1[R_ & 1], accb[T_]);                                            \
               mma_v(A0[g_ & 1], B0[R_ & 1], accb[T_]);                                            \
@@ -577,14 +540,14 @@ __global__ __launch_bounds__(256, 1) void conv3d_upwgrad4_k(const float* __restr
           }                                                                                       \
         } else {                                                                                  \
           if constexpr (R_ < 4) {       /* iy = 0: dY row R */                                    \
-            acc[PZ_][iz_][ix_] = mma_u(A1[g_ & 1], B0[R_ & 1], acc[PZ_][iz_][ix_]);               \
-            acc[PZ_][iz_][ix_] = mma_u(A0[g_ & 1], B1[R_ & 1], acc[PZ_][iz_][ix_]);               \
-            acc[PZ_][iz_][ix_] = mma_u(A0[g_ & 1], B0[R_ & 1], acc[PZ_][iz_][ix_]);               \
+            acc[PZ_][iz_][ix_] = mfma32_f16(A1[g_ & 1], B0[R_ & 1], acc[PZ_][iz_][ix_]);          \
+            acc[PZ_][iz_][ix_] = mfma32_f16(A0[g_ & 1], B1[R_ & 1], acc[PZ_][iz_][ix_]);          \
+            acc[PZ_][iz_][ix_] = mfma32_f16(A0[g_ & 1], B0[R_ & 1], acc[PZ_][iz_][ix_]);          \
           }                                                                                       \
           if constexpr (R_ >= 1) {      /* iy = 1: dY row R - 1 */                                \
-            acc[PZ_][iz_][2 + ix_] = mma_u(A1[g_ & 1], B0[(R_ - 1) & 1], acc[PZ_][iz_][2 + ix_]); \
-            acc[PZ_][iz_][2 + ix_] = mma_u(A0[g_ & 1], B1[(R_ - 1) & 1], acc[PZ_][iz_][2 + ix_]); \
-            acc[PZ_][iz_][2 + ix_] = mma_u(A0[g_ & 1], B0[(R_ - 1) & 1], acc[PZ_][iz_][2 + ix_]); \
+            acc[PZ_][iz_][2 + ix_] = mfma32_f16(A1[g_ & 1], B0[(R_ - 1) & 1], acc[PZ_][iz_][2 + ix_]); \
+            acc[PZ_][iz_][2 + ix_] = mfma32_f16(A0[g_ & 1], B1[(R_ - 1) & 1], acc[PZ_][iz_][2 + ix_]); \
+            acc[PZ_][iz_][2 + ix_] = mfma32_f16(A0[g_ & 1], B0[(R_ - 1) & 1], acc[PZ_][iz_][2 + ix_]); \
           }                                                                                       \
         }                                                                                         \
       } else if constexpr (kk_ != 0) {                                                            \
@@ -657,7 +620,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_upwgrad4_k(const float* __restr
           if (ast[e] != OOB) { UW_CONV_ST(UW_V_PA, ascale, ast[e] + (unsigned)p * UW_ASLOT, UW_ASPLIT) }
           if (FUSEB && !(UW_KO & 4) && bst[e] != OOB) {
             unsigned h_, r_;
-            split_pair_u(__uint_as_float(pb[p][0][e]), __uint_as_float(pb[p][1][e]), ascale, h_, r_);
+            split_pair_scaled(__uint_as_float(pb[p][0][e]), __uint_as_float(pb[p][1][e]), ascale, h_, r_);
             const unsigned so_ = (unsigned)p * UW_BSLOT;
             UW_LDS_ST4(bst[e] + so_, h_) UW_LDS_ST4(bsy[e] + so_, h_)
             UW_LDS_ST4(bst[e] + so_ + UW_BSPLIT, r_) UW_LDS_ST4(bsy[e] + so_ + UW_BSPLIT, r_)
@@ -828,19 +791,8 @@ int df_conv3d_upwgrad_launch(const float* a, const float* a_amax, int a_n, const
   // z segments: a workgroup (one per CU) walks ceil(items / CUs) items of zlen planes, each with a prologue worth ~2 planes
   const long long cols = (long long)N * k.ncy * k.ncx;
   static DfOptInt nseg_o{"DFMIR_UPWGRAD_NSEG", 0};
-  int best = 1;
-  long long best_cost = -1;
-  for (int s = 1; s <= Dl && s <= 64; ++s) {
-    const int zl = (Dl + s - 1) / s;
-    const int ns = (Dl + zl - 1) / zl;
-    const long long rounds = (cols * ns + ncu - 1) / ncu;
-    const long long cost = rounds * (zl + 2);
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = ns; }
-  }
-  const long long forced = nseg_o.get();
-  if (forced > 0 && forced <= Dl) best = (int)forced;
-  k.zlen = (Dl + best - 1) / best;
-  k.nseg = (Dl + k.zlen - 1) / k.zlen;
+  const ZSegments zs = march_z_segments(Dl, cols, ncu, 2, nseg_o.get());
+  k.nseg = zs.nseg; k.zlen = zs.zlen;
   k.nitems = (int)(cols * k.nseg);
   k.fx = df_det_fx();
   const unsigned grid = (unsigned)(k.nitems < ncu ? k.nitems : ncu);

@@ -14,48 +14,13 @@
 // stride = 128 (mod 256) bytes so that the two 128-byte windows of a 32-lane read fall on different banks.  Workgroups end
 // with atomics straight into the tap-major gradient (each accumulator row IS a (tap, co) row).  The bias gradient is summed
 // from the interior dY quads as they are staged.
-#include "conv3x3_common.h"
-#include <type_traits>
+#include "split_f16.h"
 
-typedef _Float16 f16x8_w __attribute__((ext_vector_type(8)));
-typedef short s16x4_w __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4_w* lds_tr_ptr_w;
 #ifndef WM_KO
 #define WM_KO 0      // knock-out builds (timing only): 1 no MFMAs, 2 no staging loads, 4 no conversion + LDS stores, 8 no operand reads
 #endif
 
 namespace {
-
-__device__ __forceinline__ int scale_exp_w(float amax) {
-  const int be = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  int e = (amax > 0.f) ? 14 - be : 0;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);
-  return e;
-}
-__device__ __forceinline__ float pow2f_w(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-__device__ __forceinline__ void split_pair_w(float x0, float x1, float s, unsigned& h, unsigned& r) {
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(s), "v"(h));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(s), "v"(h));
-}
-__device__ __forceinline__ f32x16 mma_w(u32x4 a, u32x4 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_w, a), __builtin_bit_cast(f16x8_w, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ uint2 tr_read_w(unsigned byte_addr) {
-  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr_w)(uintptr_t)byte_addr));
-}
-__device__ __forceinline__ u32x4 tr_pair_w(unsigned a0, unsigned a1) {
-  const uint2 u0 = tr_read_w(a0), u1 = tr_read_w(a1);
-  return u32x4{u0.x, u0.y, u1.x, u1.y};
-}
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for_w(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for_w<B + 1, E>(f);
-  }
-}
 
 struct WmP {
   int N, D, H, W;
@@ -92,10 +57,10 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_march_k(const float* __re
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
 
-  const int ex = scale_exp_w(reduce_absmax(x_amax, k.x_n, red));
+  const int ex = scale_exp(reduce_absmax(x_amax, k.x_n, red));
   __syncthreads();
-  const int ed = scale_exp_w(reduce_absmax(dy_amax, k.dy_n, red));
-  const float xscale = pow2f_w(ex), dscale = pow2f_w(ed), osc_x = pow2f_w(-ex), osc_d = pow2f_w(-ed);
+  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
+  const float xscale = pow2f(ex), dscale = pow2f(ed), osc_x = pow2f(-ex), osc_d = pow2f(-ed);
 
   const unsigned HW = (unsigned)(k.H * k.W), S4 = HW * (unsigned)k.D * 4u;
 
@@ -153,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_march_k(const float* __re
     u32x4 h_, r_;                                                                                 \
     _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                            \
       unsigned hh_, rr_;                                                                          \
-      split_pair_w(__uint_as_float(rq_[2 * q_][e_]), __uint_as_float(rq_[2 * q_ + 1][e_]), scale_, hh_, rr_); \
+      split_pair_scaled(__uint_as_float(rq_[2 * q_][e_]), __uint_as_float(rq_[2 * q_ + 1][e_]), scale_, hh_, rr_); \
       h_[q_] = hh_; r_[q_] = rr_;                                                                 \
     }                                                                                             \
     WM_LDS_ST(addr_, h_) WM_LDS_ST((addr_) + (lo_), r_)                                           \
@@ -182,7 +147,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_march_k(const float* __re
   {                                                                                               \
     const unsigned fb0_ = fl[0] + (PB_) * WM_FBUF, fb1_ = fl[1] + (PB_) * WM_FBUF;                \
     unsigned toff[14];            /* this lane's tap of each tile: slot of its plane + row + column offset */ \
-    static_for_w<0, 14>([&](auto tc_) __attribute__((always_inline)) {                            \
+    static_for<0, 14>([&](auto tc_) __attribute__((always_inline)) {                              \
       constexpr int T_ = decltype(tc_)::value;                                                    \
       constexpr int z0_ = wm_oz(T_, 0), z1_ = wm_oz(T_, T_ == 13 ? 0 : 1);                        \
       constexpr unsigned c0_ = (unsigned)((1 + wm_oy(T_, 0)) * (int)WM_SROW + (1 + wm_ox(T_, 0)) * 32); \
@@ -198,18 +163,18 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_march_k(const float* __re
       if constexpr (g2_ < 56) {                                                                   \
         constexpr int kb2_ = g2_ / 14, T2_ = g2_ % 14;                                            \
         const unsigned a_ = toff[T2_] + (unsigned)((2 * wid + (kb2_ >> 1)) * (int)WM_SROW + (kb2_ & 1) * 512); \
-        S0[g2_ & 1] = tr_pair_w(a_, a_ + 128u);                                                   \
-        S1[g2_ & 1] = tr_pair_w(a_ + WM_SSPLIT, a_ + 128u + WM_SSPLIT);                           \
+        S0[g2_ & 1] = tr_pair(a_, a_ + 128u);                                                     \
+        S1[g2_ & 1] = tr_pair(a_ + WM_SSPLIT, a_ + 128u + WM_SSPLIT);                             \
       }                                                                                           \
     };                                                                                            \
     rds_(std::integral_constant<int, 0>{});                                                       \
-    static_for_w<0, 56>([&](auto gc_) __attribute__((always_inline)) {                            \
+    static_for<0, 56>([&](auto gc_) __attribute__((always_inline)) {                              \
       constexpr int g_ = decltype(gc_)::value, kb_ = g_ / 14, T_ = g_ % 14;                       \
       if constexpr (T_ == 0) {      /* the x operand of this K block */                           \
         const unsigned fo2_ = (unsigned)(((2 * wid + (kb_ >> 1)) * 32 + (kb_ & 1) * 16) * 64);    \
         if (!(WM_KO & 8) || kb_ == 0) {                                                           \
-          F0 = tr_pair_w(fb0_ + fo2_, fb1_ + fo2_);                                               \
-          F1 = tr_pair_w(fb0_ + fo2_ + WM_FSPLIT, fb1_ + fo2_ + WM_FSPLIT);                       \
+          F0 = tr_pair(fb0_ + fo2_, fb1_ + fo2_);                                                 \
+          F1 = tr_pair(fb0_ + fo2_ + WM_FSPLIT, fb1_ + fo2_ + WM_FSPLIT);                         \
         }                                                                                         \
       }                                                                                           \
       if (!(WM_KO & 8) || g_ == 0) rds_(std::integral_constant<int, g_ + 1>{});                   \
@@ -221,9 +186,9 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_march_k(const float* __re
       if constexpr (g_ == 19) so_ = (soff_);                                                      \
       if constexpr (g_ >= 19 && g_ < 27) { WM_SLOAD(g_ - 19, so_) }                               \
       if (!(WM_KO & 1)) {                                                                         \
-        acc[T_] = mma_w(F1, S0[g_ & 1], acc[T_]);                                                 \
-        acc[T_] = mma_w(F0, S1[g_ & 1], acc[T_]);                                                 \
-        acc[T_] = mma_w(F0, S0[g_ & 1], acc[T_]);                                                 \
+        acc[T_] = mfma32_f16(F1, S0[g_ & 1], acc[T_]);                                            \
+        acc[T_] = mfma32_f16(F0, S1[g_ & 1], acc[T_]);                                            \
+        acc[T_] = mfma32_f16(F0, S0[g_ & 1], acc[T_]);                                            \
       } else {                                                                                    \
         acc[T_][0] += __uint_as_float(F0[0] ^ F1[1] ^ S0[g_ & 1][2] ^ S1[g_ & 1][3]);             \
       }                                                                                           \
@@ -305,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_march_k(const float* __re
   {
     const float sc = osc_x * osc_d;
     const int g = l31 >> 4, co = l31 & 15;
-    static_for_w<0, 14>([&](auto tc_) __attribute__((always_inline)) {
+    static_for<0, 14>([&](auto tc_) __attribute__((always_inline)) {
       constexpr int T = decltype(tc_)::value;
       const int oz = g ? wm_oz(T, 1) : wm_oz(T, 0), oy = g ? wm_oy(T, 1) : wm_oy(T, 0), ox = g ? wm_ox(T, 1) : wm_ox(T, 0);
       const int tap = (1 - oz) * 9 + (1 - oy) * 3 + (1 - ox);
@@ -343,19 +308,8 @@ int df_conv3d_wgrad_march_launch(const float* x, const float* x_amax, int x_n, c
   const int ncu = df_cu_count();
   const long long cols = (long long)N * k.ncy * k.ncx;
   static DfOptInt nseg_o{"DFMIR_WGRAD_MARCH_NSEG", 0};
-  int best = 1;
-  long long best_cost = -1;
-  for (int s = 1; s <= D && s <= 64; ++s) {
-    const int zl = (D + s - 1) / s;
-    const int ns = (D + zl - 1) / zl;
-    const long long rounds = (cols * ns + ncu - 1) / ncu;
-    const long long cost = rounds * (zl + 3);
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = ns; }
-  }
-  const long long forced = nseg_o.get();
-  if (forced > 0 && forced <= D) best = (int)forced;
-  k.zlen = (D + best - 1) / best;
-  k.nseg = (D + k.zlen - 1) / k.zlen;
+  const ZSegments zs = march_z_segments(D, cols, ncu, 3, nseg_o.get());
+  k.nseg = zs.nseg; k.zlen = zs.zlen;
   k.nitems = (int)(cols * k.nseg);
   const unsigned grid = (unsigned)(k.nitems < ncu ? k.nitems : ncu);
   conv3d_wgrad_march_k<<<grid, 256, 0, st>>>(x, x_amax, dy, dy_amax, dwt, k);

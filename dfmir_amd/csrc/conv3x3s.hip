@@ -25,7 +25,7 @@
 //     lane's MFMA B operand is one ds_read_b128;
 //   * K = 16 of one MFMA = 2 taps x 8 channels: lanes 0-31 feed tap 2j, lanes 32-63 tap 2j+1 (their B
 //     reads differ by the tap's patch shift).  The ninth tap pairs with a zero operand (10 % idle).
-#include "conv3x3_common.h"
+#include "split_f16.h"
 
 // Wave priorities of the ping-pong kernels (s_setprio): the computing group above the converting one.  With equal
 // priorities the SIMD arbiter favours the lower wave slots, so group A's convert/store instructions displaced group
@@ -41,10 +41,8 @@
 #endif
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32 (RNE), a in the low half
   const f32x2 v = {a, b};
@@ -67,33 +65,10 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned (&p)[NSP
     p[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
   }
 }
-// The scaled fp16x2 split of a pair in 4 instructions: v_fma_mix{lo,hi}_f16 multiply by the (power-of-two) scale,
-// subtract the leading term read straight from its fp16 half, and round to fp16 once -- the same values as
-// cvt(x*s), cvt(x*s - float(h)) (x*s and the difference are exact), without the 2 multiplies, 2 conversions back
-// and 2 subtractions.  Every VALU instruction of the converting wave costs the computing wave matrix-pipe time.
-__device__ __forceinline__ void split_pair_scaled(float x0, float x1, float s, unsigned (&p)[2]) {
-  unsigned h, r;
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x0), "v"(s), "v"(h));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r) : "v"(x1), "v"(s), "v"(h));
-  p[0] = h; p[1] = r;
-}
 template <int NSP>
 __device__ __forceinline__ void split_pair_s(float x0, float x1, float s, unsigned (&p)[NSP]) {
-  if constexpr (NSP == 2) split_pair_scaled(x0, x1, s, p);
+  if constexpr (NSP == 2) split_pair_scaled(x0, x1, s, p[0], p[1]);
   else split_pair<NSP>(x0, x1, p);                               // bf16x3 is unscaled
-}
-// 8 fp32 (times the scale s in the fp16x2 form) -> NSP 16-B vectors of 8 halves
-template <int NSP>
-__device__ __forceinline__ void split8_s(const float v[8], float s, u32x4 (&out)[NSP]) {
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    unsigned p[NSP];
-    split_pair_s<NSP>(v[2 * w], v[2 * w + 1], s, p);
-#pragma unroll
-    for (int q = 0; q < NSP; ++q) out[q][w] = p[q];
-  }
 }
 // 8 fp32 -> NSP 16-B vectors of 8 halves
 template <int NSP>
@@ -106,26 +81,23 @@ __device__ __forceinline__ void split8(const float v[8], u32x4 (&out)[NSP]) {
     for (int s = 0; s < NSP; ++s) out[s][w] = p[s];
   }
 }
+// 8 fp32 (times the scale s in the fp16x2 form) -> NSP 16-B vectors of 8 halves
+template <int NSP>
+__device__ __forceinline__ void split8_s(const float v[8], float s, u32x4 (&out)[NSP]) {
+  if constexpr (NSP == 2) split8_scaled(v, s, out[0], out[1]);
+  else split8<NSP>(v, out);                                      // bf16x3 is unscaled
+}
 template <int NSP>
 __device__ __forceinline__ f32x16 mma16(u32x4 a, u32x4 b, f32x16 c) {
   if constexpr (NSP == 3)
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
   else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    return mfma32_f16(a, b, c);
 }
 // products kept, smallest first: (A term, B term)
 template <int NSP> struct Prod;
 template <> struct Prod<3> { static constexpr int N = 6; static constexpr int A[6] = {2, 0, 1, 1, 0, 0}, B[6] = {0, 2, 1, 0, 1, 0}; };
 template <> struct Prod<2> { static constexpr int N = 3; static constexpr int A[3] = {1, 0, 0}, B[3] = {0, 1, 0}; };
-
-// power-of-two scale exponent of a tensor whose max |.| is amax: |a| * 2^e < 2^15 (fp16 max 65504)
-__device__ __forceinline__ int scale_exp(float amax) {
-  const int be = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  int e = (amax > 0.f) ? 14 - be : 0;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);   // 2^e and 2^-e stay normal fp32 numbers
-  return e;
-}
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
 
 // ---- max |x| of a tensor, folded into a device scalar: out = max(out, max|x|)
 __global__ __launch_bounds__(256) void absmax_k(const float* __restrict__ x, long long n, unsigned* __restrict__ out) {
@@ -1063,7 +1035,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_cs_k(const float* __rest
       }
       float* yp = yb + rowoff + ox;
 #ifdef CS_NT_STORE
-      if (k.vec4) __builtin_nontemporal_store(f32x4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4v*>(yp));
+      if (k.vec4) __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(yp));
 #else
       if (k.vec4) *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
 #endif
@@ -1757,7 +1729,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_split2_k(const float* __
     baccx += xin ? ((r[1] + r[2]) + (r[3] + r[4])) + ((r[5] + r[6]) + (r[7] + r[8])) : 0.f;      \
     unsigned pa[5][NSP], pb[4][NSP];                                                             \
     if (W2_KO & 4) { _Pragma("unroll") for (int i = 0; i < 5; ++i) { pa[i][0] = __float_as_uint(r[2 * i]); pa[i][1] = __float_as_uint(r[2 * i + 1]); } } \
-    else _Pragma("unroll") for (int i = 0; i < 5; ++i) split_pair_scaled(r[2 * i], r[2 * i + 1], xscale, pa[i]); \
+    else _Pragma("unroll") for (int i = 0; i < 5; ++i) split_pair_scaled(r[2 * i], r[2 * i + 1], xscale, pa[i][0], pa[i][1]); \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                \
       _Pragma("unroll") for (int s = 0; s < NSP; ++s) pb[i][s] = __builtin_amdgcn_alignbit(pa[i + 1][s], pa[i][s], 16); \
     if (!(W2_KO & 2) || k.N < 0) _Pragma("unroll") for (int s = 0; s < NSP; ++s) {                 \

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_split_w1_k(const float* __rest
 #define W1_POS(s2_) ((tid + 256 * (s2_)) < NPOS ? (tid + 256 * (s2_)) : NPOS + (tid & 15))
 #define W1_CONVPAIR(s2_, p_)                                                                     \
   { unsigned pr_[2];                                                                             \
-    split_pair_scaled(__uint_as_float(rx[s2_][2 * (p_)]), __uint_as_float(rx[s2_][2 * (p_) + 1]), xscale, pr_); \
+    split_pair_scaled(__uint_as_float(rx[s2_][2 * (p_)]), __uint_as_float(rx[s2_][2 * (p_) + 1]), xscale, pr_[0], pr_[1]); \
     cvh[((p_) >> 2)][(p_) & 3] = pr_[0]; cvl[((p_) >> 2)][(p_) & 3] = pr_[1]; }
 #define W1_CONVSTORE(buf_, s2_, hf_)                                                             \
   { Xs[buf_][(0 * 2 + (hf_)) * XP + W1_POS(s2_)] = cvh[hf_]; Xs[buf_][(1 * 2 + (hf_)) * XP + W1_POS(s2_)] = cvl[hf_]; }
