@@ -21,7 +21,7 @@
 // planes 2q-1 .. 2q+2, so K runs over 36 taps' = (dz' in 0..3, dy, dx) and the weight rows of plane p hold
 // W[dz' - p] (zero where dz' - p is outside 0..2): 75 % of the issued products are useful instead of 50 %.  Wave w
 // owns plane pair w & 1 and the y-half w >> 1 of the tile (2 column tiles), 18 k-steps x 6 MFMAs per chunk.
-#include "split_f16.h"
+#include "conv3d_tile.h"
 #ifdef C3S_TRACE      // timing build: per-phase s_memtime sums of every wave 0 -> dfmir_c3s_trace()
 __device__ unsigned long long c3s_trace[16];
 #define C3S_T(i_) { if (tid == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); atomicAdd(&c3s_trace[i_], t_ - tlast); tlast = t_; } }
@@ -157,14 +157,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
                                                       const u32x4* __restrict__ wsp, const float* __restrict__ w_trailer,
                                                       const float* __restrict__ bias, float* __restrict__ y,
                                                       float* __restrict__ y_amax, C3sP k) {
-  constexpr int TZ = 4, TY = 8, TX = 16, HY = TY + 2, HX = TX + 2;
-  constexpr int XP = (TZ + 2) * HY * HX;                  // 1080 positions
-  constexpr int NS = (XP + 255) / 256;                    // 5 position slots per thread
+  using namespace c3tile;
   constexpr int NT = PAIR ? 36 : 28;                      // taps (taps') per chunk in the weight units
   constexpr int WU = 2 * NT * 32;                         // 1792 / 2304 16-B units of one chunk's weights
   constexpr int NW = WU / 256;                            // 7 / 9
   constexpr int NJ = PAIR ? 2 : 4;                        // column tiles (2 rows x 16 voxels) per wave
-  constexpr unsigned OOB = 0x80000000u;
   __shared__ u32x4 Xs[2 * XP];
   __shared__ u32x4 Ws[WU];
   __shared__ float red[17];
@@ -174,100 +171,33 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
   const int l31 = lane & 31, hi = lane >> 5;
   const long long S = (long long)k.D * k.H * k.W;
   C3S_T0()
-  // workgroup -> tile: the dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (one L2 each), so ids
-  // with the same residue get one contiguous eighth of the tiles; within it x runs fastest, then z, then y: the
-  // z-halo (2 of 6 planes) of a tile is the previous x-row's data, still in that XCD's L2.
-  // PERSISTENT: the J = gridDim.x / 8 workgroups of an XCD walk its eighth together (iteration i: tiles i J .. i J + J - 1),
-  // and the prefetch of a tile's last phase already fetches the first chunk of the workgroup's NEXT tile, so only the
-  // first tile of a workgroup pays the exposed prologue (a per-phase trace had it at 10-23 % of a one-tile workgroup).
-  const long long per_xcd = (k.ntile + 7) / 8;
-  const int J = (int)(gridDim.x >> 3);
-  const long long t_first = (long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  long long t_lim = (long long)((blockIdx.x & 7) + 1) * per_xcd;
-  if (t_lim > k.ntile) t_lim = k.ntile;
-  if (t_first >= t_lim) return;
-  const int niter = (int)((t_lim - t_first + J - 1) / J);
+  C3TILE_XCD_WALK()
   int n, z0, y0, x0;                                        // the tile being LOADED (one phase ahead of the compute)
-#define C3S_DECODE(t_)                                                                            \
-  {                                                                                               \
-    long long pid_ = (t_);                                                                        \
-    const int bx_ = (int)(pid_ % k.nx); pid_ /= k.nx;                                             \
-    const int bz_ = (int)(pid_ % k.nz); pid_ /= k.nz;                                             \
-    const int by_ = (int)(pid_ % k.ny);                                                           \
-    n = (int)(pid_ / k.ny);                                                                       \
-    z0 = bz_ * TZ; y0 = by_ * TY * TT; x0 = bx_ * TX;      /* (k.ny counts groups of TT tiles) */  \
-  }
-  C3S_DECODE(t_first)
+  C3TILE_DECODE(t_first, TZ, TT)
   const int mt = blockIdx.y;
 #ifdef C3S_STAGGER
   // the second workgroup of a CU starts half a phase late, so that the pair does not stage / compute in lockstep
   if ((blockIdx.x >> 3) & 32) { for (int i_ = 0; i_ < C3S_STAGGER; ++i_) __builtin_amdgcn_s_sleep(64); }
 #endif
 
-  // scales: input scaled by 2^ex when it is split, result rescaled by 2^-ex * 2^-ew
-  const float amax = reduce_absmax(x_amax, k.x_n, red);
-  const int ex = scale_exp(amax);
-  const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f(ex), oscale = pow2f(-ex), oscale2 = pow2f(-ew);
+  C3TILE_SCALES(x_amax, k.x_n)
   if (tid == 0) smax = 0u;
 
   __amdgpu_buffer_rsrc_t x_src = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(x + (long long)n * k.Cin * S), 0, (unsigned)((long long)k.Cin * S * 4), 0x00020000);
   const unsigned s4 = (unsigned)S * 4u;
-  // Patch loads.  VEC (W % 4 == 0): thread t < 240 owns the 16-B quad q = t & 3 of halo row t >> 2 (rows = 6 planes x
-  // 10 y; the quad covers patch columns 1 + 4q .. 4 + 4q, i.e. x0 + 4q ..) in all 8 channels of the chunk -- 8
-  // buffer_load_dwordx4, converted to 4 LDS units -- and thread t < 120 additionally the left / right halo column
-  // (t & 1) of row t >> 1 (8 buffer_load_dword -> 1 unit).  Otherwise: 5 patch positions per thread, 8 dword loads each.
   constexpr int NPART = VEC ? 8 : NS;                     // load parts of a chunk (spread over the k-steps)
   unsigned gbyte[NS];
   unsigned gq = OOB, gh = OOB;
   int posq = -1, posh = -1;
-  // global offsets of this thread's patch loads for tile t_ of the group (rows y0 + t_ * TY ..)
-#define C3S_OFFS(t_)                                                                              \
-  {                                                                                               \
-    const int yt0_ = y0 + (t_) * TY;                                                              \
-    if constexpr (VEC) {                                                                          \
-      gq = OOB; gh = OOB;                                                                         \
-      if (tid < 240) {                                                                            \
-        const int row = tid >> 2, q = tid & 3;                                                    \
-        const int hz = row / HY, hy = row % HY;                                                   \
-        const int gz = z0 - 1 + hz, gy = yt0_ - 1 + hy, gx = x0 + 4 * q;                          \
-        posq = row * HX + 1 + 4 * q;                                                              \
-        if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && gx < k.W)             \
-          gq = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;                                       \
-      }                                                                                           \
-      if (tid < 120) {                                                                            \
-        const int row = tid >> 1, side = tid & 1;                                                 \
-        const int hz = row / HY, hy = row % HY;                                                   \
-        const int gz = z0 - 1 + hz, gy = yt0_ - 1 + hy, gx = side ? x0 + TX : x0 - 1;             \
-        posh = row * HX + (side ? HX - 1 : 0);                                                    \
-        if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && (unsigned)gx < (unsigned)k.W) \
-          gh = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;                                       \
-      }                                                                                           \
-    } else {                                                                                      \
-      _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                            \
-        const int pos = tid + 256 * s;                                                            \
-        unsigned off = OOB;                                                                       \
-        if (pos < XP) {                                                                           \
-          const int hx = pos % HX, t = pos / HX, hy = t % HY, hz = t / HY;                        \
-          const int gz = z0 - 1 + hz, gy = yt0_ - 1 + hy, gx = x0 - 1 + hx;                       \
-          if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && (unsigned)gx < (unsigned)k.W) \
-            off = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;                                    \
-        }                                                                                         \
-        gbyte[s] = off;                                                                           \
-      }                                                                                           \
-    }                                                                                             \
-  }
-  C3S_OFFS(0)
+  C3TILE_OFFS(VEC, y0)
   const u32x4* wchunk = wsp + (long long)mt * k.nchunk * WU;
 
-  // this lane's B positions: column tile j = rows 2j, 2j+1 of plane wid; voxel (row, x) = (2j + (l31 >> 4), lx) with
-  // lx = l31 & 15 in the even row and (l31 - 2) & 15 in the odd one: with the row stride of 18 units that rotation
-  // puts the 16 lanes a ds_read_b128 serves together ({0-3,12-15,20-27}, {4-11,16-19,28-31}) on 16 distinct bank quads
+  // this lane's B positions: column tile j = rows 2j, 2j+1 of plane wid; voxel (row, x) = (2j + (l31 >> 4), lx)
   // (PAIR: planes 2 (wid & 1) + p, rows 4 (wid >> 1) + 2j, 2j+1)
   const int wz = PAIR ? 2 * (wid & 1) : wid, wy = PAIR ? 4 * (wid >> 1) : 0;
   int pbase[NJ];
-  const int lx = (l31 - 2 * (l31 >> 4)) & 15;
+  const int lx = C3TILE_LANE_X(l31);
 #pragma unroll
   for (int j = 0; j < NJ; ++j) pbase[j] = (wz * HY + wy + 2 * j + (l31 >> 4)) * HX + lx;
 
@@ -277,58 +207,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
   u32x4 rq[8];                                             // VEC: the quad of channel c
   u32x4 rw[NW];
 
-  // Global loads of a chunk, in NS + 1 parts that the compute loop spreads over its first k-steps.  No branches: a
-  // channel past Cin (padding of the last chunk, or the chunk after the last) is past the descriptor's range and
-  // reads as zero without touching memory; the same holds for the weight units past the last chunk.
+  // the weight units past the last chunk are past the descriptor's range and read as zero, like the patch's channels
   const __amdgpu_buffer_rsrc_t w_src = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<u32x4*>(wsp + (long long)mt * k.nchunk * WU), 0, (unsigned)(k.nchunk * WU * 16), 0x00020000);
-#define C3S_GLOAD_X(ch_, s_)                                                                      \
-  {                                                                                               \
-    const unsigned cbase = (unsigned)((ch_) * 8) * s4;                                            \
-    if constexpr (VEC) {                                                                          \
-      const unsigned co_ = cbase + (unsigned)(s_) * s4;                                           \
-      rq[s_] = __builtin_amdgcn_raw_buffer_load_b128(x_src, gq == OOB ? OOB : gq + co_, 0, 0);    \
-      rx[0][s_] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_src, gh == OOB ? OOB : gh + co_, 0, 0)); \
-    } else {                                                                                      \
-      _Pragma("unroll") for (int c = 0; c < 8; ++c)                                               \
-        rx[s_][c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(                         \
-            x_src, gbyte[s_] == OOB ? OOB : gbyte[s_] + cbase + (unsigned)c * s4, 0, 0));         \
-    }                                                                                             \
-  }
 #define C3S_GLOAD_W(ch_)                                                                          \
   _Pragma("unroll") for (int j = 0; j < NW; ++j)                                                  \
     rw[j] = __builtin_amdgcn_raw_buffer_load_b128(w_src, (unsigned)(((ch_) * WU + tid + 256 * j) * 16), 0, 0);
-#define C3S_LSTORE()                                                                              \
-  {                                                                                               \
-    if constexpr (VEC) {                                                                          \
-      if (posq >= 0) {                                                                            \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                           \
-          float v[8];                                                                             \
-          _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(rq[c][e]);         \
-          u32x4 h, r;                                                                             \
-          split8_scaled(v, xscale, h, r);                                                         \
-          Xs[posq + e] = h;                                                                       \
-          Xs[XP + posq + e] = r;                                                                  \
-        }                                                                                         \
-      }                                                                                           \
-      if (posh >= 0) {                                                                            \
-        u32x4 h, r;                                                                               \
-        split8_scaled(rx[0], xscale, h, r);                                                       \
-        Xs[posh] = h;                                                                             \
-        Xs[XP + posh] = r;                                                                        \
-      }                                                                                           \
-    } else {                                                                                      \
-      _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                            \
-        const int pos = tid + 256 * s;                                                            \
-        if (pos < XP) {                                                                           \
-          u32x4 h, r;                                                                             \
-          split8_scaled(rx[s], xscale, h, r);                                                     \
-          Xs[pos] = h;                                                                            \
-          Xs[XP + pos] = r;                                                                       \
-        }                                                                                         \
-      }                                                                                           \
-    }                                                                                             \
-  }
 #define C3S_LSTORE_W() _Pragma("unroll") for (int j = 0; j < NW; ++j) Ws[tid + 256 * j] = rw[j];
   // operands of k-step tp_ (taps 2tp, 2tp+1; tap 27 of the 28-tap form has zero weights, any valid offset) -> set b_
 #define C3S_OPLOAD(b_, tp_)                                                                       \
@@ -348,10 +232,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
 
   u32x4 A0[2], A1[2], B0[2][NJ], B1[2][NJ];
 #pragma unroll
-  for (int s = 0; s < NPART; ++s) C3S_GLOAD_X(0, s);
+  for (int s = 0; s < NPART; ++s) C3TILE_GLOAD(VEC, 0, s);
   C3S_GLOAD_W(0);
   C3S_T(0)
-  C3S_LSTORE();
+  C3TILE_LSTORE(VEC)
   C3S_LSTORE_W();
   C3S_T(1)
   __syncthreads();
@@ -378,11 +262,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
     const int nch = tile_end ? 0 : ((tt + 1 < TT) ? ch : ch + 1);
     const int wch = tile_end ? 0 : ch + 1;
     if (tile_end && more) {
-      C3S_DECODE(t_first + (long long)(it + 1) * J)
+      C3TILE_DECODE(t_first + (long long)(it + 1) * J, TZ, TT)
       x_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (long long)n * k.Cin * S), 0,
                                                 (unsigned)((long long)k.Cin * S * 4), 0x00020000);
     }
-    if (TT > 1 || tile_end) C3S_OFFS((tt + 1) % TT)
+    if (TT > 1 || tile_end) C3TILE_OFFS(VEC, y0 + ((tt + 1) % TT) * TY)
     C3S_OPLOAD(0, 0);
     // one k-step: the next step's 2 + 2 NJ operand reads and one part of the next chunk's global loads are pinned
     // between this step's 3 NJ MFMAs (one MFMA, one LDS read, one buffer load, ...), so the wave never waits on
@@ -392,10 +276,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
       const int cur = tp & 1;
       if (!(C3S_KO & 2)) {
 #ifdef C3S_EARLY
-        if (2 * tp < NPART) { C3S_GLOAD_X(nch, 2 * tp); if (2 * tp + 1 < NPART) C3S_GLOAD_X(nch, 2 * tp + 1); }
+        if (2 * tp < NPART) { C3TILE_GLOAD(VEC, nch, 2 * tp); if (2 * tp + 1 < NPART) C3TILE_GLOAD(VEC, nch, 2 * tp + 1); }
         if (2 * tp == NPART && tt + 1 == TT) C3S_GLOAD_W(wch);
 #else
-        if (tp < NPART) C3S_GLOAD_X(nch, tp);
+        if (tp < NPART) C3TILE_GLOAD(VEC, nch, tp);
         if (tp == NPART && tt + 1 == TT) C3S_GLOAD_W(wch);
 #endif
       }
@@ -425,7 +309,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
       __syncthreads();
       C3S_T(4)
       if (!(C3S_KO & 4)) {
-        C3S_LSTORE();
+        C3TILE_LSTORE(VEC)
         if (tt + 1 == TT) { C3S_LSTORE_W(); }
       }
       C3S_T(5)
@@ -436,13 +320,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
   }
   const bool tile_done = (ch + 1 == k.nchunk);
   if (!tile_done) { ++ch; continue; }
-#undef C3S_GLOAD_X
 #undef C3S_GLOAD_W
 #undef C3S_OPLOAD
-#undef C3S_LSTORE
 #undef C3S_LSTORE_W
-#undef C3S_OFFS
-#undef C3S_DECODE
 
   // ---- epilogue: acc[j][r] <-> row = (r>>2)*8 + hi*4 + (r&3) = cout - mt*32 (PAIR: plane * 16 + cout),
   //      voxel (wz [+ plane], wy + 2j + (l31>>4), l31&15)
@@ -460,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_k(const float* __restrict
   const __amdgpu_buffer_rsrc_t y_dst = __builtin_amdgcn_make_buffer_rsrc(
       y + (long long)cn * k.Cout * S, 0, (unsigned)((long long)k.Cout * S * 4), 0x00020000);
   const unsigned plane4 = (unsigned)(k.H * k.W) * 4u;
-  const float osc = oscale * oscale2;
+  const float osc = oscale * oscale2;   // formed here: formed in the prologue, every instance is register-allocated differently
 #pragma unroll
   for (int tt = 0; tt < TT; ++tt) {
   const int yt0 = cy0 + tt * TY;
@@ -540,14 +420,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
                                                           const u32x4* __restrict__ wsp, const float* __restrict__ w_trailer,
                                                           const float* __restrict__ bias, float* __restrict__ y,
                                                           float* __restrict__ y_amax, C3sP k) {
-  constexpr int TZ = 4, TY = 8, TX = 16, HY = TY + 2, HX = TX + 2;
-  constexpr int XP = (TZ + 2) * HY * HX;                  // 1080 positions
-  constexpr int NS = (XP + 255) / 256;
+  using namespace c3tile;
   constexpr int WU = 2 * 28 * 16;                         // 896 16-B units of one chunk's weights
   constexpr int NW = (WU + 255) / 256;                    // 4 (the last partly)
   constexpr int NJ = 8;                                   // column tiles (tile rows) per wave
   constexpr int NKS = 7;
-  constexpr unsigned OOB = 0x80000000u;
   __shared__ u32x4 Xs[2 * XP];
   __shared__ u32x4 Ws[WU];
   __shared__ float red[17];
@@ -556,29 +433,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l15 = lane & 15, kg = lane >> 4;
   const long long S = (long long)k.D * k.H * k.W;
-  const long long per_xcd = (k.ntile + 7) / 8;
-  const int J = (int)(gridDim.x >> 3);
-  const long long t_first = (long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  long long t_lim = (long long)((blockIdx.x & 7) + 1) * per_xcd;
-  if (t_lim > k.ntile) t_lim = k.ntile;
-  if (t_first >= t_lim) return;
-  const int niter = (int)((t_lim - t_first + J - 1) / J);
+  C3TILE_XCD_WALK()
   int n, z0, y0, x0;
-#define C3M_DECODE(t_)                                                                            \
-  {                                                                                               \
-    long long pid_ = (t_);                                                                        \
-    const int bx_ = (int)(pid_ % k.nx); pid_ /= k.nx;                                             \
-    const int bz_ = (int)(pid_ % k.nz); pid_ /= k.nz;                                             \
-    const int by_ = (int)(pid_ % k.ny);                                                           \
-    n = (int)(pid_ / k.ny);                                                                       \
-    z0 = bz_ * TZ; y0 = by_ * TY * TT; x0 = bx_ * TX;                                             \
-  }
-  C3M_DECODE(t_first)
+  C3TILE_DECODE(t_first, TZ, TT)
 
-  const float amax = reduce_absmax(x_amax, k.x_n, red);
-  const int ex = scale_exp(amax);
-  const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f(ex), osc = pow2f(-ex) * pow2f(-ew);
+  C3TILE_SCALES(x_amax, k.x_n)
+  const float osc = oscale * oscale2;
   if (tid == 0) smax = 0u;
 
   __amdgpu_buffer_rsrc_t x_src = __builtin_amdgcn_make_buffer_rsrc(
@@ -588,42 +448,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
   unsigned gbyte[NS];
   unsigned gq = OOB, gh = OOB;
   int posq = -1, posh = -1;
-#define C3M_OFFS(t_)                                                                              \
-  {                                                                                               \
-    const int yt0_ = y0 + (t_) * TY;                                                              \
-    if constexpr (VEC) {                                                                          \
-      gq = OOB; gh = OOB;                                                                         \
-      if (tid < 240) {                                                                            \
-        const int row = tid >> 2, q = tid & 3;                                                    \
-        const int hz = row / HY, hy = row % HY;                                                   \
-        const int gz = z0 - 1 + hz, gy = yt0_ - 1 + hy, gx = x0 + 4 * q;                          \
-        posq = row * HX + 1 + 4 * q;                                                              \
-        if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && gx < k.W)             \
-          gq = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;                                       \
-      }                                                                                           \
-      if (tid < 120) {                                                                            \
-        const int row = tid >> 1, side = tid & 1;                                                 \
-        const int hz = row / HY, hy = row % HY;                                                   \
-        const int gz = z0 - 1 + hz, gy = yt0_ - 1 + hy, gx = side ? x0 + TX : x0 - 1;             \
-        posh = row * HX + (side ? HX - 1 : 0);                                                    \
-        if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && (unsigned)gx < (unsigned)k.W) \
-          gh = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;                                       \
-      }                                                                                           \
-    } else {                                                                                      \
-      _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                            \
-        const int pos = tid + 256 * s;                                                            \
-        unsigned off = OOB;                                                                       \
-        if (pos < XP) {                                                                           \
-          const int hx = pos % HX, t = pos / HX, hy = t % HY, hz = t / HY;                        \
-          const int gz = z0 - 1 + hz, gy = yt0_ - 1 + hy, gx = x0 - 1 + hx;                       \
-          if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && (unsigned)gx < (unsigned)k.W) \
-            off = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;                                    \
-        }                                                                                         \
-        gbyte[s] = off;                                                                           \
-      }                                                                                           \
-    }                                                                                             \
-  }
-  C3M_OFFS(0)
+  C3TILE_OFFS(VEC, y0)
 
   // this lane's B positions (plane wid, row j, column l15) and the patch offsets of its taps 4 ks + kg
   // ROW-REUSE k-steps (round 4).  The 27 taps are walked as two sets of four (dz, dx) pairs -- S0 = pairs 0-3, S1 = pairs 4-7,
@@ -649,42 +474,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
   u32x4 rw[NW];
   const __amdgpu_buffer_rsrc_t w_src = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<u32x4*>(wsp), 0, (unsigned)(k.nchunk * WU * 16), 0x00020000);
-#define C3M_GLOAD_X(ch_, s_)                                                                      \
-  {                                                                                               \
-    const unsigned cbase = (unsigned)((ch_) * 8) * s4;                                            \
-    if constexpr (VEC) {                                                                          \
-      const unsigned co_ = cbase + (unsigned)(s_) * s4;                                           \
-      rq[s_] = __builtin_amdgcn_raw_buffer_load_b128(x_src, gq == OOB ? OOB : gq + co_, 0, 0);    \
-      rx[0][s_] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_src, gh == OOB ? OOB : gh + co_, 0, 0)); \
-    } else {                                                                                      \
-      _Pragma("unroll") for (int c = 0; c < 8; ++c)                                               \
-        rx[s_][c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(                         \
-            x_src, gbyte[s_] == OOB ? OOB : gbyte[s_] + cbase + (unsigned)c * s4, 0, 0));         \
-    }                                                                                             \
-  }
 #define C3M_GLOAD_W(ch_)                                                                          \
   _Pragma("unroll") for (int j = 0; j < NW; ++j)                                                  \
     rw[j] = __builtin_amdgcn_raw_buffer_load_b128(w_src, (tid + 256 * j) < WU ? (unsigned)(((ch_) * WU + tid + 256 * j) * 16) : OOB, 0, 0);
 #define C3M_LSTORE()                                                                              \
   {                                                                                               \
-    if constexpr (VEC) {                                                                          \
-      if (posq >= 0) {                                                                            \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                           \
-          float v[8];                                                                             \
-          _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(rq[c][e]);         \
-          u32x4 h, r;                                                                             \
-          split8_scaled(v, xscale, h, r);                                                         \
-          Xs[posq + e] = h;                                                                       \
-          Xs[XP + posq + e] = r;                                                                  \
-        }                                                                                         \
-      }                                                                                           \
-      if (posh >= 0) {                                                                            \
-        u32x4 h, r;                                                                               \
-        split8_scaled(rx[0], xscale, h, r);                                                       \
-        Xs[posh] = h;                                                                             \
-        Xs[XP + posh] = r;                                                                        \
-      }                                                                                           \
-    } else {                                                                                      \
+    if constexpr (VEC) C3TILE_LSTORE_VEC(rx[0]) else {                                            \
       _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                            \
         const int pos = tid + 256 * s;                                                            \
         if (pos < XP) {                                                                           \
@@ -704,11 +499,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
 #ifndef C3M_KO
 #define C3M_KO 0          // knock-out builds (timing only): 1 no global X loads, 2 no conversion + LDS stores, 4 no MFMAs, 8 no epilogue stores
 #endif
-#define C3M_PART(p_) { if ((p_) < NPART && (!(C3M_KO & 1) || k.D < 0)) C3M_GLOAD_X(nch, p_); }
+#define C3M_PART(p_) { if ((p_) < NPART && (!(C3M_KO & 1) || k.D < 0)) C3TILE_GLOAD(VEC, nch, p_); }
 #define C3M_MMA3(acc_, ah_, al_, bh_, bl_)                                                        \
   { if (!(C3M_KO & 4) || k.D < 0) { acc_ = mfma16_f16(bh_, al_, acc_); acc_ = mfma16_f16(bl_, ah_, acc_); acc_ = mfma16_f16(bh_, ah_, acc_); } }   /* rows = the 16 voxels of a tile row, columns = output channels */
 #pragma unroll
-  for (int s = 0; s < NPART; ++s) C3M_GLOAD_X(0, s);
+  for (int s = 0; s < NPART; ++s) C3TILE_GLOAD(VEC, 0, s);
   C3M_GLOAD_W(0);
   C3M_LSTORE();
   C3M_LSTORE_W();
@@ -729,11 +524,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
     const int nch = tile_end ? 0 : ((tt + 1 < TT) ? ch : ch + 1);
     const int wch = tile_end ? 0 : ch + 1;
     if (tile_end && more) {
-      C3M_DECODE(t_first + (long long)(it + 1) * J)
+      C3TILE_DECODE(t_first + (long long)(it + 1) * J, TZ, TT)
       x_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (long long)n * k.Cin * S), 0,
                                                 (unsigned)((long long)k.Cin * S * 4), 0x00020000);
     }
-    if (TT > 1 || tile_end) C3M_OFFS((tt + 1) % TT)
+    if (TT > 1 || tile_end) C3TILE_OFFS(VEC, y0 + ((tt + 1) % TT) * TY)
 #pragma unroll
     for (int S = 0; S < 2; ++S) {
       u32x4 Ah[3], Al[3], Bh[2], Bl[2];
@@ -848,9 +643,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
    cn = n; cz0 = z0; cy0 = y0; cx0 = x0;
    ch = 0; ++it;
   }
-#undef C3M_DECODE
-#undef C3M_OFFS
-#undef C3M_GLOAD_X
 #undef C3M_GLOAD_W
 #undef C3M_LSTORE
 #undef C3M_LSTORE_W
@@ -863,10 +655,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_split_m16_k(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-static bool split3d_off() {
-  static DfOptFlag a{"DFMIR_CONV3D_FP32"}, b{"DFMIR_CONV_FP32"};
-  return a.get() || b.get();
-}
 static bool pair3d_off() {
   static DfOptFlag o{"DFMIR_CONV3D_NO_PAIR"};
   return o.get();
@@ -1094,12 +882,10 @@ template <bool SKIP2>
 __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restrict__ x, const float* __restrict__ x_amax,
                                                          const u32x4* __restrict__ wsp, const float* __restrict__ w_trailer,
                                                          float* __restrict__ y, C3uP k) {
-  constexpr int TZ = 4, TY = 8, TX = 16, HY = TY + 2, HX = TX + 2;
-  constexpr int XP = (TZ + 2) * HY * HX;                  // 1080 positions
+  using namespace c3tile;
   constexpr int WU = 2 * 16 * 32;                         // 1024 16-B units of one chunk's weights (2 px x 8 slots)
   constexpr int NW = WU / 256;                            // 4
   constexpr int NJ = 4;
-  constexpr unsigned OOB = 0x80000000u;
   constexpr int SRS = 40, SROWS = 9 * 17, SPW = SROWS * SRS;       // skip patch: row stride (words), rows, words per split
   constexpr int XSU = SKIP2 ? ((2 * SPW + 3) / 4 > 2 * XP ? (2 * SPW + 3) / 4 : 2 * XP) : 2 * XP;
   __shared__ u32x4 Xs[XSU];
@@ -1110,59 +896,30 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const long long S = (long long)k.D * k.H * k.W;
-  // tiles: XCD-contiguous eighths, x fastest, then z, then y (as conv3d_split_k); one tile per workgroup
-  // The four (pz, py) instances of a tile sit in neighbouring workgroup ids of the SAME XCD (round 5): as the outermost grid
+  // One tile per workgroup.  The four (pz, py) instances of a tile sit in neighbouring workgroup ids of the SAME XCD (round 5): as the outermost grid
   // dimension they were four passes over the volume, each re-reading the patch of `a` from memory (fetch 887 MB for 165 MB
   // of inputs).
-  const long long per_xcd = (k.ntile + 7) / 8;
   const unsigned rid = blockIdx.x >> 3;
-  const long long tile = (long long)(blockIdx.x & 7) * per_xcd + (rid >> 2);
-  if ((long long)(rid >> 2) >= per_xcd || tile >= k.ntile) return;
+  C3TILE_XCD_TILE(rid >> 2)
   int n, z0, y0, x0;
-  {
-    long long pid = tile;
-    const int bx = (int)(pid % k.nx); pid /= k.nx;
-    const int bz = (int)(pid % k.nz); pid /= k.nz;
-    const int by = (int)(pid % k.ny);
-    n = (int)(pid / k.ny);
-    z0 = bz * TZ; y0 = by * TY; x0 = bx * TX;
-  }
+  C3TILE_DECODE(tile, TZ, 1)
   const int mt = blockIdx.y, pzy = (int)(rid & 3), pz = pzy >> 1, py = pzy & 1;
 
-  const float amax = reduce_absmax(x_amax, k.x_n, red);
-  const int ex = scale_exp(amax);
-  const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f(ex), osc = pow2f(-ex) * pow2f(-ew);
+  C3TILE_SCALES(x_amax, k.x_n)
+  const float osc = oscale * oscale2;
 
   const __amdgpu_buffer_rsrc_t x_src = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(x + (long long)n * k.Ca * S), 0, (unsigned)((long long)k.Ca * S * 4), 0x00020000);
   const unsigned s4 = (unsigned)S * 4u;
-  // patch loads (the VEC form of conv3d_split_k): thread t < 240 owns quad q = t & 3 of halo row t >> 2 in all 8 channels
-  // of the chunk, thread t < 120 additionally the left / right halo column of row t >> 1
   unsigned gq = OOB, gh = OOB;
   int posq = -1, posh = -1;
-  if (tid < 240) {
-    const int row = tid >> 2, q = tid & 3;
-    const int hz = row / HY, hy = row % HY;
-    const int gz = z0 - 1 + hz, gy = y0 - 1 + hy, gx = x0 + 4 * q;
-    posq = row * HX + 1 + 4 * q;
-    if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && gx < k.W)
-      gq = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;
-  }
-  if (tid < 120) {
-    const int row = tid >> 1, side = tid & 1;
-    const int hz = row / HY, hy = row % HY;
-    const int gz = z0 - 1 + hz, gy = y0 - 1 + hy, gx = side ? x0 + TX : x0 - 1;
-    posh = row * HX + (side ? HX - 1 : 0);
-    if ((unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H && (unsigned)gx < (unsigned)k.W)
-      gh = (unsigned)((gz * k.H + gy) * k.W + gx) * 4u;
-  }
+  C3TILE_OFFS_VEC(y0)
   const __amdgpu_buffer_rsrc_t w_src = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<u32x4*>(wsp + ((long long)pzy * gridDim.y + mt) * k.nchunk * WU), 0, (unsigned)(k.nchunk * WU * 16), 0x00020000);
 
-  // B positions of this lane: column tile j = rows 2j, 2j + 1 of plane wid (see conv3d_split_k for the lane rotation);
+  // B positions of this lane: column tile j = rows 2j, 2j + 1 of plane wid;
   // tap slot (tz, ty, tx) of parity (pz, py, px) sits at patch offset ((pz + tz) HY + (py + ty)) HX + (px + tx)
-  const int lx = (l31 - 2 * (l31 >> 4)) & 15;
+  const int lx = C3TILE_LANE_X(l31);
   int pbase[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) pbase[j] = ((wid + pz) * HY + 2 * j + (l31 >> 4) + py) * HX + lx + hi;   // + tx = hi
@@ -1179,33 +936,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
   u32x4 stg[8 + NW];                                       // rq = stg[0..7] (the patch quads), rw = stg[8..]; the skip phase reuses them
 #define rq stg
 #define rw (stg + 8)
-#define C3U_GLOAD_X(ch_, s_)                                                                      \
-  {                                                                                               \
-    const unsigned co_ = (unsigned)((ch_) * 8 + (s_)) * s4;                                       \
-    rq[s_] = __builtin_amdgcn_raw_buffer_load_b128(x_src, gq == OOB ? OOB : gq + co_, 0, 0);      \
-    rh[s_] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_src, gh == OOB ? OOB : gh + co_, 0, 0)); \
-  }
 #define C3U_GLOAD_W(ch_)                                                                          \
   _Pragma("unroll") for (int j = 0; j < NW; ++j)                                                  \
     rw[j] = __builtin_amdgcn_raw_buffer_load_b128(w_src, (unsigned)(((ch_) * WU + tid + 256 * j) * 16), 0, 0);
 #define C3U_LSTORE()                                                                              \
   {                                                                                               \
-    if (posq >= 0) {                                                                              \
-      _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                             \
-        float v[8];                                                                               \
-        _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(rq[c][e]);           \
-        u32x4 h, r;                                                                               \
-        split8_scaled(v, xscale, h, r);                                                           \
-        Xs[posq + e] = h;                                                                         \
-        Xs[XP + posq + e] = r;                                                                    \
-      }                                                                                           \
-    }                                                                                             \
-    if (posh >= 0) {                                                                              \
-      u32x4 h, r;                                                                                 \
-      split8_scaled(rh, xscale, h, r);                                                            \
-      Xs[posh] = h;                                                                               \
-      Xs[XP + posh] = r;                                                                          \
-    }                                                                                             \
+    C3TILE_LSTORE_VEC(rh)                                                                         \
     _Pragma("unroll") for (int j = 0; j < NW; ++j) Ws[tid + 256 * j] = rw[j];                     \
   }
   // operands of k-step tp_ = px * 4 + tz * 2 + ty (tx = this half-wave): unit u = 2 tp_ + hi
@@ -1264,7 +1000,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
 #endif               //    wave of the SIMD covers the LDS latency); 0: one step ahead (31 spilled registers)
   u32x4 A0[2], A1[2], B0[2][NJ], B1[2][NJ];
 #pragma unroll
-  for (int s = 0; s < 8; ++s) C3U_GLOAD_X(0, s);
+  for (int s = 0; s < 8; ++s) C3TILE_GLOAD_VEC(0, s, rh)
   C3U_GLOAD_W(0);
   C3U_LSTORE();
   __syncthreads();
@@ -1277,7 +1013,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
       const int cur = C3U_SB ? 0 : (tp & 1);
       if (C3U_SB) C3U_OPLOAD(0, tp);
       if (more) {                                             // next chunk's loads, one channel per k-step (uniform branch)
-        C3U_GLOAD_X(ch + 1, tp);
+        C3TILE_GLOAD_VEC(ch + 1, tp, rh)
         if (tp == 7) C3U_GLOAD_W(ch + 1);
       } else if (C3U_SKIP_PREFETCH) {
         C3U_SKIP_GLOAD(tp)                                    // (SNIT = 6 task slots, then the halo column)
@@ -1303,7 +1039,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_phase_k(const float* __restr
       __syncthreads();
     }
   }
-#undef C3U_GLOAD_X
 #undef C3U_GLOAD_W
 #undef rq
 #undef rw
@@ -1587,7 +1322,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_dgrad_k(const float* __restr
   constexpr int WU = 2 * 16 * 32;                         // 1024 units of one (pzy, chunk)'s weights
   constexpr int NJ = 2;
   constexpr int NTASK = HZ * HY * 10, NIT = (NTASK + 255) / 256;   // (row, aligned quad) tasks: 400 -> 2 per thread
-  constexpr unsigned OOB = 0x80000000u;
+  constexpr unsigned OOB = c3tile::OOB;
   __shared__ u32x4 Xs[2 * 2 * XP];                        // [px][split][position]
   __shared__ u32x4 Ws[WU];
   __shared__ float red[17];
@@ -1598,23 +1333,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_dgrad_k(const float* __restr
   const long long S = (long long)k.D * k.H * k.W;
   const int Df = 2 * k.D, Hf = 2 * k.H, Wf = 2 * k.W;
   const long long Sf = (long long)Df * Hf * Wf;
-  const long long per_xcd = (k.ntile + 7) / 8;
-  const long long tile = (long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  if ((long long)(blockIdx.x >> 3) >= per_xcd || tile >= k.ntile) return;
+  C3TILE_XCD_TILE(blockIdx.x >> 3)
   int n, z0, y0, x0;
-  {
-    long long pid = tile;
-    const int bx = (int)(pid % k.nx); pid /= k.nx;
-    const int bz = (int)(pid % k.nz); pid /= k.nz;
-    const int by = (int)(pid % k.ny);
-    n = (int)(pid / k.ny);
-    z0 = bz * TZ; y0 = by * TY; x0 = bx * TX;
-  }
+  C3TILE_DECODE(tile, TZ, 1)
   const int mt = blockIdx.y;
-  const float amax = reduce_absmax(dy_amax, k.dy_n, red);
-  const int ex = scale_exp(amax);
-  const int ew = reinterpret_cast<const int*>(w_trailer)[0];
-  const float xscale = pow2f(ex), osc = pow2f(-ex) * pow2f(-ew);
+  C3TILE_SCALES(dy_amax, k.dy_n)
+  const float osc = oscale * oscale2;
   if (tid == 0) smax = 0u;
 
   const __amdgpu_buffer_rsrc_t y_src = __builtin_amdgcn_make_buffer_rsrc(
@@ -1628,9 +1352,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_up_dgrad_k(const float* __restr
     trow[i] = task < NTASK ? task / 10 : -1;
     tq[i] = task - 10 * (task / 10);
   }
-  // this lane's output voxels: plane wz, rows wy + 2 j + (l31 >> 4), column lx (lane rotation as conv3d_split_k)
+  // this lane's output voxels: plane wz, rows wy + 2 j + (l31 >> 4), column lx
   const int wz = wid & 1, wy = 4 * (wid >> 1);
-  const int lx = (l31 - 2 * (l31 >> 4)) & 15;
+  const int lx = C3TILE_LANE_X(l31);
   int pbase[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) pbase[j] = (wz * HY + wy + 2 * j + (l31 >> 4)) * HX + lx + hi;      // + sx = hi
@@ -1808,789 +1532,4 @@ extern "C" int dfmir_conv3d_split_fwd_add(const DfConvGeom* g, const float* b, c
                                           float* y_amax, void* stream) {
   DF_ARG_CHECK(g && y && (!w_tcc || (Ktot >= koff + g->Cin && koff >= 0)));
   return conv3d_split_fwd_impl(g, b, b_amax, b_amax_n, w_tcc, ws, bias, y, y_amax, g->Cout, stream, y, 0.f, 2, Ktot, koff);
-}
-
-// ================================================================================================
-// wgrad:  dWt[tap][ci][co] += sum_v X[ci][v + tap] * dY[co][v]   with the VOXEL as the MFMA K (16 consecutive x).
-//
-// Workgroup = 4 waves, persistent over 2 x 4 x 16-voxel patches of its share of the volume, ALL input channels
-// (<= 48, in chunks of 8) and all output channels (<= 32).  MFMA rows = (tap, ci) of a chunk (27 x 8 = 216 -> 7 row
-// tiles of 32), columns = co.  Wave w keeps the accumulators of row tiles {(w+c) mod 4, (w+c) mod 4 + 4} of every
-// chunk c (the padding tile 7 rotates over the waves) and runs all 8 k-steps (x-rows) of a patch for them, so no
-// cross-wave reduction is needed; one atomicAdd per accumulator at the very end (split-K over workgroups).
-// LDS per patch: dY split once, [split][co][row][unit] (unit = 8 voxels x fp16 = 16 B); per chunk: X split into three
-// x-aligned copies [split][dx][ci][hz][hy][unit] (copy dx holds x + dx - 1), so every tap reads 16-B aligned units
-// (an unaligned ds_read_b128 runs at quarter rate).  A thread converts one 18-voxel row: 9 packed pairs serve the
-// copies dx = 0 and dx = 2 (same pairing, one dword apart), v_alignbit makes the dx = 1 pairing.
-// ================================================================================================
-struct W3sP {
-  int N, Cin, Cout, D, H, W;
-  int nz, ny, nx;
-  long long npatch, per_block;
-  long long nslot;               // tr kernel: workgroups per XCD along grid.x (per_block = tiles per XCD)
-  int x_n, dy_n;
-  int nchunk;                    // chunks of 8 input channels in the layer; blockIdx.y * NCH = this workgroup's first
-  long long s_tap, s_row, s_col; // output index = tap' * s_tap + ci * s_row + co * s_col, tap' = flip ? 26 - tap : tap
-  int flip;
-  float* db;                     // optional bias gradient: db[.] += sum over voxels of the layer's output gradient
-  int db_from_x;                 // 0: db indexed by co, summed from the dY operand;  1: by ci, from the X operand (swapped roles)
-  // X = cat(nearest_up2(xa), x) never materialised (tr kernel): channels 0 .. Ca - 1 are read from the HALF-resolution
-  // tensor xa [N, Ca, D/2, H/2, W/2] at (z >> 1, y >> 1, x >> 1), the remaining Cin - Ca from x [N, Cin - Ca, D, H, W]
-  const float* xa;
-  int Ca;
-  const float* fx;               // deterministic mode (common.h df_acc): dwt holds 64-bit fixed-point sums, db is NULL
-};
-
-template <int NCH>
-__global__ __launch_bounds__(256) void conv3d_wgrad_split_k(const float* __restrict__ x, const float* __restrict__ x_amax,
-                                                            const float* __restrict__ dy, const float* __restrict__ dy_amax,
-                                                            float* __restrict__ dwt, W3sP k) {
-  constexpr int PZ = 2, PY = 4, HZ = PZ + 2, HY = PY + 2;
-  constexpr int CIS = HZ * HY * 2 + 1;                    // 49 units: ci stride == 16 B (mod 256 B)
-  constexpr int XSPL = 3 * 8 * CIS;                       // 1176 units per split
-  constexpr int COS = 17, YSPL = 32 * COS;                // dY: co stride 17 units, 544 per split
-  __shared__ u32x4 Xs[2 * XSPL];
-  __shared__ u32x4 Ys[2 * YSPL];
-  __shared__ float red[17];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int l31 = lane & 31, hi = lane >> 5;
-  const long long S = (long long)k.D * k.H * k.W;
-
-  const int ex = scale_exp(reduce_absmax(x_amax, k.x_n, red));
-  __syncthreads();
-  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
-  const float xscale = pow2f(ex), dscale = pow2f(ed), oscale = pow2f(-ex), oscale2 = pow2f(-ed);
-
-  f32x16 acc[NCH][2];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[c][s][r] = 0.f;
-
-  // staging roles
-  const bool xrow = tid < 8 * HZ * HY;                    // 192 threads: one (ci, hz, hy) row of 18 voxels each
-  const int xci = tid / (HZ * HY), xrem = tid % (HZ * HY), xhz = xrem / HY, xhy = xrem % HY;
-  const int yco = tid >> 3, yr = tid & 7;                 // dY: (co, row) -> 16 voxels
-  constexpr unsigned OOB = 0x80000000u;
-
-  const int c_base = blockIdx.y * NCH;
-  const long long p_begin = (long long)blockIdx.x * k.per_block;
-  long long p_end = p_begin + k.per_block;
-  if (p_end > k.npatch) p_end = k.npatch;
-  if (p_begin >= p_end) return;
-  const int niter = (int)(p_end - p_begin) * NCH;
-
-  float rx[18];
-  u32x4 ry[4];
-  __amdgpu_buffer_rsrc_t x_src, y_src;
-  int pz0 = 0, py0 = 0, px0 = 0;
-  float bacc = 0.f;                                       // this thread's share of the bias gradient
-  const bool db_y = k.db && !k.db_from_x && blockIdx.y == 0;
-  const bool db_x = k.db && k.db_from_x && xrow && xhz >= 1 && xhz <= PZ && xhy >= 1 && xhy <= PY;   // the patch's own rows
-
-#define W3S_GLOAD(it_)                                                                            \
-  {                                                                                               \
-    const long long p_ = p_begin + (it_) / NCH;                                                   \
-    const int c_ = (it_) % NCH;                                                                   \
-    const int ca_ = c_base + c_;                                                                  \
-    long long q_ = p_;                                                                            \
-    const int bx_ = (int)(q_ % k.nx); q_ /= k.nx;                                                 \
-    const int by_ = (int)(q_ % k.ny); q_ /= k.ny;                                                 \
-    const int bz_ = (int)(q_ % k.nz);                                                             \
-    const int n_ = (int)(q_ / k.nz);                                                              \
-    pz0 = bz_ * PZ; py0 = by_ * PY; px0 = bx_ * 16;                                               \
-    x_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (long long)n_ * k.Cin * S), 0,   \
-                                              (unsigned)((long long)k.Cin * S * 4), 0x00020000);  \
-    {                                                                                             \
-      const int gz = pz0 - 1 + xhz, gy = py0 - 1 + xhy, ci = ca_ * 8 + xci;                       \
-      const bool rowok = xrow && ci < k.Cin && (unsigned)gz < (unsigned)k.D && (unsigned)gy < (unsigned)k.H;  \
-      const unsigned base = (unsigned)(((long long)ci * S + ((long long)gz * k.H + gy) * k.W + px0 - 1) * 4);  \
-      _Pragma("unroll") for (int j = 0; j < 18; ++j) {                                            \
-        const int gx = px0 - 1 + j;                                                               \
-        rx[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(                             \
-            x_src, (rowok && (unsigned)gx < (unsigned)k.W) ? base + 4u * j : OOB, 0, 0));         \
-      }                                                                                           \
-    }                                                                                             \
-    if (c_ == 0) {                                                                                \
-      y_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy + (long long)n_ * k.Cout * S), 0,   \
-                                                (unsigned)((long long)k.Cout * S * 4), 0x00020000);   \
-      const int gz = pz0 + (yr >> 2), gy = py0 + (yr & 3);                                        \
-      const bool rowok = yco < k.Cout && gz < k.D && gy < k.H;                                    \
-      const unsigned base = (unsigned)(((long long)yco * S + ((long long)gz * k.H + gy) * k.W + px0) * 4);  \
-      _Pragma("unroll") for (int q = 0; q < 4; ++q)                                               \
-        ry[q] = __builtin_amdgcn_raw_buffer_load_b128(y_src, (rowok && px0 + 4 * q < k.W) ? base + 16u * q : OOB, 0, 0);  \
-    }                                                                                             \
-  }
-
-  W3S_GLOAD(0);
-  for (int it = 0; it < niter; ++it) {
-    const int c = it % NCH;
-    __syncthreads();                                       // previous compute is done with the LDS buffers
-    if (db_x) {
-#pragma unroll
-      for (int j = 1; j <= 16; ++j) bacc += rx[j];          // loads outside the frame returned 0
-    }
-    if (xrow) {
-      unsigned ph[9], pr[9];
-#pragma unroll
-      for (int j = 0; j < 9; ++j) split_pair_scaled(rx[2 * j], rx[2 * j + 1], xscale, ph[j], pr[j]);
-      const int ubase = xci * CIS + (xhz * HY + xhy) * 2;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        u32x4 h0, h1, h2, r0, r1, r2;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          h0[q] = ph[4 * u + q]; r0[q] = pr[4 * u + q];                               // voxels x-1 .. (copy dx = 0)
-          h2[q] = ph[4 * u + q + 1]; r2[q] = pr[4 * u + q + 1];                       // voxels x+1 .. (copy dx = 2)
-          h1[q] = __builtin_amdgcn_alignbit(ph[4 * u + q + 1], ph[4 * u + q], 16);    // voxels x ..   (copy dx = 1)
-          r1[q] = __builtin_amdgcn_alignbit(pr[4 * u + q + 1], pr[4 * u + q], 16);
-        }
-        Xs[0 * 8 * CIS + ubase + u] = h0; Xs[XSPL + 0 * 8 * CIS + ubase + u] = r0;
-        Xs[1 * 8 * CIS + ubase + u] = h1; Xs[XSPL + 1 * 8 * CIS + ubase + u] = r1;
-        Xs[2 * 8 * CIS + ubase + u] = h2; Xs[XSPL + 2 * 8 * CIS + ubase + u] = r2;
-      }
-    }
-    if (c == 0) {
-      const int ub = yco * COS + yr * 2;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        u32x4 h, r;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const u32x4 v = ry[2 * u + q];
-          if (db_y) bacc += (__uint_as_float(v[0]) + __uint_as_float(v[1])) + (__uint_as_float(v[2]) + __uint_as_float(v[3]));
-          unsigned hh, rr;
-          split_pair_scaled(__uint_as_float(v[0]), __uint_as_float(v[1]), dscale, hh, rr);
-          h[2 * q] = hh; r[2 * q] = rr;
-          split_pair_scaled(__uint_as_float(v[2]), __uint_as_float(v[3]), dscale, hh, rr);
-          h[2 * q + 1] = hh; r[2 * q + 1] = rr;
-        }
-        Ys[ub + u] = h;
-        Ys[YSPL + ub + u] = r;
-      }
-    }
-    __syncthreads();
-    if (it + 1 < niter) W3S_GLOAD(it + 1);
-
-    // this wave's two row tiles of chunk c
-    int aoff[2];
-    bool tok[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int tile = ((wid + c) & 3) + 4 * s;
-      tok[s] = tile < 7;
-      int rho = tile * 32 + l31;
-      if (rho > 215) rho = 215;                            // padding rows: any valid address (results discarded)
-      const int tap = rho >> 3, ci = rho & 7;
-      const int dz = tap / 9, dyy = (tap / 3) % 3, dx = tap % 3;
-      aoff[s] = (dx * 8 + ci) * CIS + (dz * HY + dyy) * 2 + hi;
-    }
-    const int boff = l31 * COS + hi;
-#pragma unroll
-    for (int c2 = 0; c2 < NCH; ++c2) {
-      if (c2 != c || c_base + c >= k.nchunk) continue;     // static accumulator index; a padding chunk has no work
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int zy = ((r >> 2) * HY + (r & 3)) * 2;
-        const u32x4 b0 = Ys[boff + r * 2], b1 = Ys[YSPL + boff + r * 2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          if (!tok[s]) continue;
-          const u32x4 a0 = Xs[aoff[s] + zy], a1 = Xs[XSPL + aoff[s] + zy];
-          acc[c2][s] = mfma32_f16(a1, b0, acc[c2][s]);
-          acc[c2][s] = mfma32_f16(a0, b1, acc[c2][s]);
-          acc[c2][s] = mfma32_f16(a0, b0, acc[c2][s]);
-        }
-      }
-    }
-  }
-#undef W3S_GLOAD
-
-  // ---- epilogue: acc[c][s][r] <-> row (r>>2)*8 + hi*4 + (r&3) of tile ((wid+c)&3) + 4s, column co = l31
-  const float sc = oscale * oscale2;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int tile = ((wid + c) & 3) + 4 * s;
-      if (tile >= 7 || l31 >= k.Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rho = tile * 32 + (r >> 2) * 8 + hi * 4 + (r & 3);
-        const int tap = rho >> 3, ci = (c_base + c) * 8 + (rho & 7);
-        const int to = k.flip ? 26 - tap : tap;
-        if (rho < 216 && ci < k.Cin) df_acc(dwt, to * k.s_tap + ci * k.s_row + l31 * k.s_col, acc[c][s][r] * sc, k.fx);
-      }
-    }
-  if (db_y && yco < k.Cout) atomicAdd(&k.db[yco], bacc);
-  if (db_x) {
-    // the X rows of chunk c were summed while c was staged; bacc mixes the chunks of this workgroup row only when
-    // NCH > 1, which the swapped-role launch (one chunk) never has
-    const int ci = c_base * 8 + xci;
-    if (ci < k.Cin) atomicAdd(&k.db[ci], bacc);
-  }
-}
-
-// ================================================================================================
-// wgrad, transpose-read form (default):  the same GEMM -- rows (tap, ci), columns co, K = voxels -- but the operands
-// are read from the FORWARD kernel's LDS images with ds_read_b64_tr_b16 (gfx950): X as [position][8 channels x fp16]
-// (16 B per position and split), dY as [voxel][32 output channels x fp16] (64 B).  In a 16-lane group the hardware
-// hands lane 4q + c, element j the c-th fp16 at the address supplied by lane 4j + q: with lane (j, q) pointing at
-// (voxel j, channel quad q) every lane receives 4 consecutive voxels of its own row -- a K-major MFMA operand out of a
-// channel-major image.  A tap is then nothing but a position offset (16-B granular, so dx shifts stay aligned): ONE
-// copy of the patch instead of three, the patch is staged exactly like the forward kernel's (8 x buffer_load_dwordx4
-// per thread, 4 v_fma_mix per value pair), and a tile can be four times larger for the same LDS.
-//
-// Workgroup = 4 waves, persistent over 2 x 8 x 16-voxel tiles (16 k-steps = x-rows of 16 voxels); per tile the dY
-// image is staged once and the X patch (4 x 10 x 18 positions) once per 8-channel chunk.  Row tile T of a chunk =
-// taps 4T .. 4T+3 x 8 channels (7 tiles, tap 27 is padding); wave w owns tiles (w + c) & 3 and that + 4 of chunk c
-// (accumulators of <= 3 chunks resident: 96 AGPRs, two workgroups per CU so that one stages while the other computes).
-// Bank behaviour of the reads: the 32 lanes served together cover 4 taps x 4 x-positions x 16 B; taps of one
-// (dz, dy) are contiguous, the next (dz, dy) must start 112..192 B further (mod 256): row stride 25 positions, plane
-// stride 250 -- odd, so that the staging stores of 4 consecutive rows x 2 quads (one ds_write_b128 lane group) fall on
-// 8 different 16-B bank slots (measured: all of the kernel's bank conflicts were these stores at stride 24).  dY: 4 voxels x 64 B contiguous; the channel group is XORed with (voxel >> 2) & 3 so that the staging
-// stores of a wave (one channel group, 4 voxel quads) spread over the banks.
-// ================================================================================================
-#ifndef W3T_NOSKIP
-#define W3T_NOSKIP 0
-#endif
-#ifndef W3T_KO
-#define W3T_KO 0     // knock-out builds for timing: 1 = no MFMAs, 2 = no prefetch loads, 4 = no convert + LDS store, 8 = no operand reads
-#endif
-
-template <int NCH>
-struct W3T {
-  static constexpr int TZ = 2, TY = 8, TX = 16, HZ = 4, HY = 10, HXP = 25, SZP = HY * HXP;
-  static constexpr int XPOS = HZ * SZP;                  // 1000 units per split
-  static constexpr int YU = TZ * TY * TX * 4;            // 1024 units per split
-};
-
-// PAIR form (<= 16 output channels: half of the 32 MFMA columns would be padding): the columns are (plane p, co) --
-// columns 0-15 take dY of the tile's z-plane 0, columns 16-31 the SAME voxel (y, x) of plane 1 -- and K runs over
-// plane 0 only (8 k-steps).  Rows then are (tap', ci) with tap' = (dz' in 0..3, dy, dx) over the patch's four planes:
-// row (dz', .) x column (p, .) is a term of dW[dz' - p] (dropped where dz' - p is outside 0..2): 9 row tiles x 8
-// k-steps instead of 7 x 16.  A wave owns tiles w and w + 4 and k-steps 2w, 2w + 1 of tile 8 (the partial sums meet
-// in the atomics of the epilogue): 18 tile-steps per wave and phase instead of 32.
-// UPCAT: X = cat(nearest_up2(xa), x) read in place (see W3sP::xa).  A compile-time variant: a branch around the operand
-// prefetch splits the k-loop's basic block and with it the MFMA / LDS / VMEM interleave (measured: +35 % on every shape),
-// so both sources are loaded branch-free -- the inactive one with an out-of-range offset (returns 0, no memory access).
-template <int NCH, bool PAIR, bool UPCAT>
-__global__ __launch_bounds__(256, 2) void conv3d_wgrad_tr_k(const float* __restrict__ x, const float* __restrict__ x_amax,
-                                                         const float* __restrict__ dy, const float* __restrict__ dy_amax,
-                                                         float* __restrict__ dwt, W3sP k) {
-  using G = W3T<NCH>;
-  constexpr int TZ = G::TZ, TY = G::TY, HY = G::HY, HXP = G::HXP, SZP = G::SZP, XPOS = G::XPOS, YU = G::YU;
-  constexpr unsigned OOB = 0x80000000u;
-  __shared__ u32x4 Xs[2 * XPOS];
-  __shared__ u32x4 Ys[2 * YU];
-  __shared__ float red[17];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int l31 = lane & 31, hi = lane >> 5;
-  const long long S = (long long)k.D * k.H * k.W;
-  const unsigned s4 = (unsigned)S * 4u;
-
-  const int ex = scale_exp(reduce_absmax(x_amax, k.x_n, red));
-  __syncthreads();
-  const int ed = scale_exp(reduce_absmax(dy_amax, k.dy_n, red));
-  const float xscale = pow2f(ex), dscale = pow2f(ed), oscale = pow2f(-ex), oscale2 = pow2f(-ed);
-
-  constexpr int NA = PAIR ? 3 : 2;                         // accumulators (row tiles) per chunk and wave
-  constexpr int NKS = PAIR ? 8 : 16;                       // k-steps per phase
-  f32x16 acc[NCH][NA];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int s = 0; s < NA; ++s)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[c][s][r] = 0.f;
-
-  const int c_base = blockIdx.y * NCH;
-  int nc = k.nchunk - c_base;                              // chunks of this workgroup row
-  if (nc > NCH) nc = NCH;
-  // Tiles: workgroup ids go round-robin to the 8 XCDs (one L2 each), so XCD e = id & 7 owns the e-th eighth of the
-  // tile list and its J workgroups (slot j = id >> 3) walk it together: in iteration i they hold the J consecutive
-  // tiles i J .. i J + J - 1 of the eighth.  The list runs x fastest, then over 2 x 2 blocks of (z, y): a window of J
-  // tiles is a few full x-rows of neighbouring (z, y), so the halos (3.75x the tile in the patch) are mostly L2 hits.
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const long long t_first = (long long)xcd * k.per_block + slot;       // per_block = tiles per XCD
-  long long t_lim = (long long)(xcd + 1) * k.per_block;
-  if (t_lim > k.npatch) t_lim = k.npatch;
-  const int J = (int)k.nslot;
-  if (t_first >= t_lim || nc <= 0) return;
-  const int niter = (int)((t_lim - t_first + J - 1) / J);
-
-  // ---- staging roles.  X: thread t < 240 owns the aligned quad qq (x0 - 4 + 4 qq ..) of halo row t / 6 (40 rows of
-  // 6 quads; quads 0 and 5 contribute one position each) in the 8 channels of the chunk.  dY: wave w owns channel
-  // group w, thread = (row 0..15, quad 0..3) of the tile.
-  const bool xt = tid < 240;
-  const int xm = tid / 80, xr80 = tid - 80 * xm;           // quad pair m = 0..2; 8 consecutive lanes = 4 rows x 2 quads
-  const int xrow = xr80 >> 1, xqq = 2 * xm + (xr80 & 1);
-  const int xhz = xrow / HY, xhy = xrow - HY * xhz;
-  const int xpos0 = xhz * SZP + xhy * HXP + 4 * xqq - 3;   // unit of element e: xpos0 + e
-  const int xe0 = xqq == 0 ? 3 : 0, xe1 = xqq == 5 ? 1 : 4;
-  const int yq = tid & 3, yrow = (tid >> 2) & 15;
-  const bool yt = wid * 8 < k.Cout;
-  // unit of element e: yunit0 + 4 e  (PAIR: plane 1 takes the other 32-B half of the voxel's 64 B, so that the columns
-  // of both planes, read together, fall on different banks)
-  const int yunit0 = (yrow * 16 + 4 * yq) * 4 + (wid ^ yq ^ (PAIR ? (yrow >> 3) * 2 : 0));
-  const bool db_y = k.db && !k.db_from_x && blockIdx.y == 0 && yt;
-  const bool db_x = k.db && k.db_from_x && xt && xhz >= 1 && xhz <= TZ && xhy >= 1 && xhy <= TY && xqq >= 1 && xqq <= 4;
-  float bacc[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) bacc[c] = 0.f;
-
-  // ---- operand addresses (bytes in LDS).  Source role of this lane in its 16-lane group: j = voxel, q = channel quad.
-  const int sj = (lane & 15) >> 2, sq = lane & 3, sg = (lane >> 4) & 1;
-  const unsigned xs_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)Xs;
-  const unsigned ys_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)Ys;
-  // B (dY): voxel = s * 16 + 8 hi + 4 i + j, channel quad = 4 sg + sq -> unit (2 sg + (sq >> 1)) ^ ((2 hi + i) & 3)
-  // PAIR: column group sg = plane, voxel + 128 sg, channel quad sq -> unit (sq >> 1) ^ ((2 hi + i) & 3) ^ 2 sg
-  unsigned baddr[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-    baddr[i] = PAIR ? ys_base + (unsigned)(((128 * sg + 8 * hi + 4 * i + sj) * 4 + ((sq >> 1) ^ ((2 * hi + i) & 3) ^ (2 * sg))) * 16 + (sq & 1) * 8)
-                    : ys_base + (unsigned)(((8 * hi + 4 * i + sj) * 4 + ((2 * sg + (sq >> 1)) ^ ((2 * hi + i) & 3))) * 16 + (sq & 1) * 8);
-
-  u32x4 rq[8], ry[8];
-  int tn, tz, ty, tx;                                      // tile being LOADED (runs one phase ahead of the compute)
-  const int nzb = (k.nz + 1) >> 1;
-  const int cells = 4 * nzb * ((k.ny + 1) >> 1);           // (z, y) cells per image incl. the phantom ones of odd counts
-#define W3T_DECODE(t_)                                                                            \
-  {                                                                                               \
-    long long q_ = (t_);                                                                          \
-    tx = (int)(q_ % k.nx); q_ /= k.nx;                                                            \
-    const int u_ = (int)(q_ % cells);                                                             \
-    tn = (int)(q_ / cells);                                                                       \
-    const int b_ = u_ >> 2;                                                                       \
-    tz = 2 * (b_ % nzb) + (u_ & 1);                                                               \
-    ty = 2 * (b_ / nzb) + ((u_ >> 1) & 1);                                                        \
-  }
-  W3T_DECODE(t_first)
-  unsigned gq = OOB, gy_ = OOB, gqa = OOB;
-  __amdgpu_buffer_rsrc_t x_src, y_src, xa_src;
-  const int Cup = UPCAT ? k.Ca : 0;                         // channels taken from the half-resolution tensor
-  const int Dh = k.D >> 1, Hh = k.H >> 1, Wh = k.W >> 1;
-  const unsigned sa4 = (unsigned)((long long)Dh * Hh * Wh) * 4u;
-#define W3T_TILE_ADDR()                                                                           \
-  {                                                                                               \
-    const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * 16;                                           \
-    x_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (long long)tn * (k.Cin - Cup) * S), 0,   \
-                                              (unsigned)((long long)(k.Cin - Cup) * S * 4), 0x00020000);  \
-    if (UPCAT) xa_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(k.xa + (long long)tn * Cup * (sa4 >> 2)), 0,   \
-                                                        (unsigned)((long long)Cup * sa4), 0x00020000);  \
-    y_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy + (long long)tn * k.Cout * S), 0, \
-                                              (unsigned)((long long)k.Cout * S * 4), 0x00020000); \
-    {                                                                                             \
-      const int gz = z0 - 1 + xhz, gyy = y0 - 1 + xhy, gx = x0 - 4 + 4 * xqq;                     \
-      gq = (xt && tz < k.nz && ty < k.ny && (unsigned)gz < (unsigned)k.D && (unsigned)gyy < (unsigned)k.H && (unsigned)gx < (unsigned)k.W) \
-               ? (unsigned)((gz * k.H + gyy) * k.W + gx) * 4u : OOB;                              \
-      gqa = (UPCAT && gq != OOB) ? (unsigned)(((gz >> 1) * Hh + (gyy >> 1)) * Wh + (gx >> 1)) * 4u : OOB;   \
-    }                                                                                             \
-    {                                                                                             \
-      const int gz = z0 + (yrow >> 3), gyy = y0 + (yrow & 7), gx = x0 + 4 * yq;                   \
-      gy_ = (yt && tz < k.nz && ty < k.ny && gz < k.D && gyy < k.H && gx < k.W) ? (unsigned)((gz * k.H + gyy) * k.W + gx) * 4u : OOB; \
-    }                                                                                             \
-  }
-#define W3T_GLOAD_X1(ca_, c_)                                                                     \
-  if constexpr (UPCAT) {     /* a chunk lies entirely in one of the two tensors (Ca % 8 == 0): wave-uniform selects */ \
-    typedef unsigned u32x2w_ __attribute__((ext_vector_type(2)));                                 \
-    const bool up_ = (ca_) * 8 < Cup;                                                             \
-    const u32x2w_ v2_ = __builtin_amdgcn_raw_buffer_load_b64(                                     \
-        xa_src, (up_ && gqa != OOB) ? gqa + (unsigned)((ca_) * 8 + (c_)) * sa4 : OOB, 0, 0);      \
-    const u32x4 v4_ = __builtin_amdgcn_raw_buffer_load_b128(                                      \
-        x_src, (!up_ && gq != OOB) ? gq + (unsigned)((ca_) * 8 + (c_) - Cup) * s4 : OOB, 0, 0);   \
-    rq[c_] = u32x4{v2_[0] | v4_[0], v2_[0] | v4_[1], v2_[1] | v4_[2], v2_[1] | v4_[3]};           \
-  } else {                                                                                        \
-    rq[c_] = __builtin_amdgcn_raw_buffer_load_b128(x_src, gq == OOB ? OOB : gq + (unsigned)((ca_) * 8 + (c_)) * s4, 0, 0); \
-  }
-#define W3T_GLOAD_Y1(c_)                                                                          \
-  ry[c_] = __builtin_amdgcn_raw_buffer_load_b128(y_src, gy_ == OOB ? OOB : gy_ + (unsigned)(wid * 8 + (c_)) * s4, 0, 0);
-#define W3T_STORE_X()                                                                             \
-  if (xt) {                                                                                       \
-    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                               \
-      if (e < xe0 || e >= xe1) continue;                                                          \
-      u32x4 h, r;                                                                                 \
-      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                             \
-        unsigned hh, rr;                                                                          \
-        split_pair_scaled(__uint_as_float(rq[2 * q][e]), __uint_as_float(rq[2 * q + 1][e]), xscale, hh, rr); \
-        h[q] = hh; r[q] = rr;                                                                     \
-      }                                                                                           \
-      Xs[xpos0 + e] = h;                                                                          \
-      Xs[XPOS + xpos0 + e] = r;                                                                   \
-    }                                                                                             \
-    if (db_x) {                                                                                   \
-      _Pragma("unroll") for (int c = 0; c < 8; ++c)                                               \
-        bacc[c] += (__uint_as_float(rq[c][0]) + __uint_as_float(rq[c][1])) + (__uint_as_float(rq[c][2]) + __uint_as_float(rq[c][3])); \
-    }                                                                                             \
-  }
-#define W3T_STORE_Y()                                                                             \
-  if (yt) {                                                                                       \
-    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                               \
-      u32x4 h, r;                                                                                 \
-      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                             \
-        unsigned hh, rr;                                                                          \
-        split_pair_scaled(__uint_as_float(ry[2 * q][e]), __uint_as_float(ry[2 * q + 1][e]), dscale, hh, rr); \
-        h[q] = hh; r[q] = rr;                                                                     \
-      }                                                                                           \
-      Ys[yunit0 + 4 * e] = h;                                                                     \
-      Ys[YU + yunit0 + 4 * e] = r;                                                                \
-    }                                                                                             \
-    if (db_y) {                                                                                   \
-      _Pragma("unroll") for (int c = 0; c < 8; ++c)                                               \
-        bacc[c] += (__uint_as_float(ry[c][0]) + __uint_as_float(ry[c][1])) + (__uint_as_float(ry[c][2]) + __uint_as_float(ry[c][3])); \
-    }                                                                                             \
-  }
-  // operands of k-step s_ (x-row (z, y) = (s_ >> 3, s_ & 7)) into register set b_
-  // Operand reads of k-step s_ (x-row (z, y) = (s_ >> 3, s_ & 7)).  A (one row tile) is single-buffered and fetched one
-  // HALF-step ahead -- tile 1's while tile 0's three MFMAs run and vice versa -- B (shared by both tiles) is
-  // double-buffered and fetched one step ahead: 32 operand registers instead of 48 (three chunks of accumulators +
-  // both staging sets + 48 did not fit 256 registers).
-  // (the two reads of a pair stay spelled out at this one site: through tr_pair the PAIR instances of this kernel come out
-  // of the compiler with another schedule of their address arithmetic)
-#define W3T_TR_PAIR64(dst_, addr_)                                                                \
-  {                                                                                               \
-    const uint2 u0_ = tr_read(addr_), u1_ = tr_read((addr_) + 64u);                               \
-    dst_ = u32x4{u0_.x, u0_.y, u1_.x, u1_.y};                                                     \
-  }
-#define W3T_READ_A(t_, s_)                                                                        \
-  {                                                                                               \
-    const unsigned ko = (unsigned)((((s_) >> 3) * SZP + ((s_) & 7) * HXP) * 16);                  \
-    W3T_TR_PAIR64(A1[t_], aaddr[t_] + ko + XPOS * 16u)                                            \
-    W3T_TR_PAIR64(A0[t_], aaddr[t_] + ko)                                                         \
-  }
-#define W3T_READ_B(B_, b_, s_, off_)                                                              \
-  B_[b_] = tr_pair(baddr[0] + (unsigned)(s_) * 1024u + (off_), baddr[1] + (unsigned)(s_) * 1024u + (off_));
-  // the 16 k-steps of chunk c_ (LAST_: the next phase starts a new tile, so dY is prefetched too -- a wave-uniform
-  // branch around one load per step; two copies of the loop behind one branch cost 32 registers of accumulator copies)
-#define W3T_KLOOP(c_, LAST_)                                                                      \
-  {                                                                                               \
-    W3T_READ_B(B0, 0, 0, 0u) W3T_READ_B(B1, 0, 0, YU * 16u) W3T_READ_A(0, 0)                      \
-    __builtin_amdgcn_sched_barrier(0);                                                            \
-    _Pragma("unroll") for (int s = 0; s < NKS; ++s) {                                             \
-      const int cur = s & 1;                                                                      \
-      if (!(W3T_KO & 8)) {                                                                        \
-        if (tok1) { W3T_READ_A(1, s) }                                                            \
-        if (s + 1 < NKS) W3T_READ_B(B0, cur ^ 1, s + 1, 0u)                                       \
-      }                                                                                           \
-      if (!(W3T_KO & 2)) {                                                                        \
-        if (s < 8) { W3T_GLOAD_X1(ca_next, s); }                                                  \
-        else if (LAST_) { W3T_GLOAD_Y1(s - 8); }                                                  \
-      }                                                                                           \
-      W3T_MMA(c_, 0)                                                                              \
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                          \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                          \
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                          \
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                          \
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                          \
-      __builtin_amdgcn_sched_barrier(0);                                                          \
-      if (s + 1 < NKS && !(W3T_KO & 8)) {                                                         \
-        W3T_READ_A(0, s + 1)                                                                      \
-        W3T_READ_B(B1, cur ^ 1, s + 1, YU * 16u)                                                  \
-      }                                                                                           \
-      if (PAIR && (LAST_) && !(W3T_KO & 2)) { W3T_GLOAD_Y1(s); }   /* 8 k-steps: dY rides in the second half-steps */ \
-      if (tok1) { W3T_MMA(c_, 1) }                                                                \
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                          \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                          \
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                          \
-      if (PAIR) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                \
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                          \
-      __builtin_amdgcn_sched_barrier(0);                                                          \
-    }                                                                                             \
-    if constexpr (PAIR) {                                                                         \
-      /* tile 8, k-steps 2 wid and 2 wid + 1 (wave-uniform offsets: one add per address) */        \
-      _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                             \
-        const unsigned ko = (unsigned)((2 * wid + u) * HXP * 16), kb = (unsigned)(2 * wid + u) * 1024u; \
-        A1[u] = tr_pair(aaddr[2] + ko + XPOS * 16u, aaddr[2] + ko + XPOS * 16u + 64u);            \
-        A0[u] = tr_pair(aaddr[2] + ko, aaddr[2] + ko + 64u);                                      \
-        B0[u] = tr_pair(baddr[0] + kb, baddr[1] + kb);                                            \
-        B1[u] = tr_pair(baddr[0] + kb + YU * 16u, baddr[1] + kb + YU * 16u);                      \
-      }                                                                                           \
-      _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                             \
-        acc[c_][NA - 1] = mfma32_f16(A1[u], B0[u], acc[c_][NA - 1]);                              \
-        acc[c_][NA - 1] = mfma32_f16(A0[u], B1[u], acc[c_][NA - 1]);                              \
-        acc[c_][NA - 1] = mfma32_f16(A0[u], B0[u], acc[c_][NA - 1]);                              \
-      }                                                                                           \
-      __builtin_amdgcn_sched_barrier(0);                                                          \
-    }                                                                                             \
-  }
-#if (W3T_KO & 1)
-#define W3T_MMA(c_, t) acc[c_][t][0] += __uint_as_float(A1[t][0] ^ B0[cur][1] ^ A0[t][2] ^ B1[cur][3]);
-#else
-#define W3T_MMA(c_, t)                                                                            \
-  acc[c_][t] = mfma32_f16(A1[t], B0[cur], acc[c_][t]);                                            \
-  acc[c_][t] = mfma32_f16(A0[t], B1[cur], acc[c_][t]);                                            \
-  acc[c_][t] = mfma32_f16(A0[t], B0[cur], acc[c_][t]);
-#endif
-
-  u32x4 A0[2], A1[2], B0[2], B1[2];
-  unsigned aaddr[NA];
-
-  // prologue: first tile's dY and chunk 0
-  W3T_TILE_ADDR();
-#pragma unroll
-  for (int c = 0; c < 8; ++c) { W3T_GLOAD_X1(c_base, c); W3T_GLOAD_Y1(c); }
-  W3T_STORE_X();
-  W3T_STORE_Y();
-  __syncthreads();
-
-  for (int it = 0; it < niter; ++it) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      if (c >= nc) continue;
-      const bool last = (c + 1 == nc);                     // the next phase starts a new tile (or nothing)
-      const bool more = !last || (it + 1 < niter);
-      if (last) {                                          // advance the load cursor to the next tile
-        if (more) { W3T_DECODE(t_first + (long long)(it + 1) * J) W3T_TILE_ADDR(); } else { gq = OOB; gy_ = OOB; }
-      }
-      const int ca_next = last ? c_base : c_base + c + 1;
-      // this wave's two row tiles of chunk c: lane (j, q, g) of tile T supplies tap 4T + 2g + (q >> 1), channel quad q & 1
-#pragma unroll
-      for (int t = 0; t < NA; ++t) {
-        const int tile = PAIR ? (t < 2 ? wid + 4 * t : 8) : ((wid + c) & 3) + 4 * t;
-        int tap = tile * 4 + 2 * sg + (sq >> 1);           // PAIR: tap' of 36 (dz' = tap' / 9 in 0..3)
-        if (!PAIR && tap > 26) tap = 26;                   // padding rows: any valid address (results discarded)
-        const int dz = tap / 9, dyy = (tap / 3) % 3, dx = tap % 3;
-        aaddr[t] = xs_base + (unsigned)((dz * SZP + dyy * HXP + dx + 8 * hi + sj) * 16 + (sq & 1) * 8);
-      }
-      // the wave whose second row tile is the padding tile 7 skips its reads and MFMAs (wave-uniform): no time gained
-      // (the phase ends at the barrier) but 1/8 of the matrix and LDS energy of a kernel that sits on the power cap
-      const bool tok1 = PAIR || (((wid + c) & 3) != 3) || W3T_NOSKIP;
-      W3T_KLOOP(c, last)
-      if (more) {
-        __syncthreads();
-        if (!(W3T_KO & 4)) {
-          W3T_STORE_X();
-          if (last) W3T_STORE_Y();
-        }
-        __syncthreads();
-      }
-    }
-  }
-#undef W3T_TILE_ADDR
-#undef W3T_DECODE
-#undef W3T_GLOAD_X1
-#undef W3T_GLOAD_Y1
-#undef W3T_STORE_X
-#undef W3T_STORE_Y
-#undef W3T_TR_PAIR64
-#undef W3T_READ_A
-#undef W3T_READ_B
-#undef W3T_KLOOP
-#undef W3T_MMA
-
-  // ---- epilogue: acc[c][s][r] <-> row (r>>2)*8 + hi*4 + (r&3) of tile ((wid+c)&3) + 4s, column co = l31
-  const float sc = oscale * oscale2;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int s = 0; s < NA; ++s) {
-      const int tile = PAIR ? (s < 2 ? wid + 4 * s : 8) : ((wid + c) & 3) + 4 * s;
-      const int co = PAIR ? (l31 & 15) : l31, pl = PAIR ? (l31 >> 4) : 0;
-      if (c >= nc || (!PAIR && tile >= 7) || co >= k.Cout) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rho = tile * 32 + (r >> 2) * 8 + hi * 4 + (r & 3);
-        int tap = rho >> 3;
-        const int ci = (c_base + c) * 8 + (rho & 7);
-        bool ok = ci < k.Cin;
-        if constexpr (PAIR) {
-          const int dz = tap / 9 - pl;                     // row plane dz' against column plane p
-          ok = ok && (unsigned)dz < 3u;
-          tap = dz * 9 + tap % 9;
-        } else {
-          ok = ok && rho < 216;
-        }
-        const int to = k.flip ? 26 - tap : tap;
-        if (ok) df_acc(dwt, to * k.s_tap + ci * k.s_row + co * k.s_col, acc[c][s][r] * sc, k.fx);
-      }
-    }
-  if (k.db) {                                              // wave-uniform: every lane of a wave holds the same 8 channels
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float t = wave_sum((db_y || db_x) ? bacc[c] : 0.f);
-      const int ch = k.db_from_x ? c_base * 8 + c : wid * 8 + c;
-      const int lim = k.db_from_x ? k.Cin : k.Cout;
-      if (lane == 0 && ch < lim && t != 0.f) atomicAdd(&k.db[ch], t);
-    }
-  }
-}
-
-static bool split3d_wgrad_common_ok(const DfConvGeom* g) {
-  return g->KD == 3 && g->KH == 3 && g->KW == 3 && g->stride == 1 && g->dil == 1 && g->pd == 1 && g->ph == 1 &&
-         g->pw == 1 && g->pad_mode == 0 && g->Do == g->Di && g->Ho == g->Hi && g->Wo == g->Wi && g->Di > 1 &&
-         (g->Wi & 3) == 0 && (long long)g->Cin * g->Di * g->Hi * g->Wi * 4 < 0x7FFFFFFFLL &&
-         (long long)g->Cout * g->Di * g->Hi * g->Wi * 4 < 0x7FFFFFFFLL;
-}
-// normal roles: rows = (tap, ci), columns = co.  Few output channels (the 16 -> 3 flow conv): SWAPPED roles -- rows =
-// (tap, co) gathered from shifted dY, columns = ci: dW[t][ci][co] = sum_u X[ci][u] * dY[co][u - t], i.e. the same kernel
-// on (x := dY, dy := X) with the taps flipped and the output transposed (one 8-channel chunk instead of Cin / 8).
-static bool split3d_wgrad_geom_ok(const DfConvGeom* g) {
-  return split3d_wgrad_common_ok(g) && g->Cin >= 8 && g->Cin <= 128 && g->Cout >= 8 && g->Cout <= 32;
-}
-static bool split3d_wgrad_swapped_ok(const DfConvGeom* g) {
-  return split3d_wgrad_common_ok(g) && g->Cout >= 1 && g->Cout < 8 && g->Cin >= 8 && g->Cin <= 32;
-}
-extern "C" int dfmir_conv3d_split_wgrad_ok(const DfConvGeom* g) {
-  return (g && !split3d_off() && (split3d_wgrad_geom_ok(g) || split3d_wgrad_swapped_ok(g))) ? 1 : 0;
-}
-static int conv3d_split_wgrad_impl(const DfConvGeom* g, const float* x, const float* x_amax, int x_amax_n,
-                                   const float* dy, const float* dy_amax, int dy_amax_n, float* dw_tcc, float* db,
-                                   void* stream, const float* xa = nullptr, int Ca = 0, long long s_tap_full = 0);
-// The weight gradient of conv3x3x3 over X = cat(nearest_up2(a), b) without building X: a [N, Ca, D/2, H/2, W/2] is read
-// at (z >> 1, y >> 1, x >> 1) while the operand patch is staged.  g: the full layer (Cin = Ca + Cb); Ca % 8 == 0; even
-// D, H, W; x_amax: a range probe valid for both parts.
-extern "C" int dfmir_conv3d_split_wgrad_upcat(const DfConvGeom* g, const float* a, const float* b, int Ca,
-                                              const float* x_amax, int x_amax_n, const float* dy, const float* dy_amax,
-                                              int dy_amax_n, float* dw_tcc, float* db, void* stream) {
-  DF_ARG_CHECK(g && a && b && Ca > 0 && (Ca & 7) == 0 && Ca < g->Cin && !(g->Di & 1) && !(g->Hi & 1) && !(g->Wi & 7));
-  static DfOptFlag copies_o{"DFMIR_CONV3D_WGRAD_COPIES"};
-  DF_ARG_CHECK(split3d_wgrad_geom_ok(g) && !copies_o.get() && (reinterpret_cast<uintptr_t>(a) & 7) == 0);
-  return conv3d_split_wgrad_impl(g, b, x_amax, x_amax_n, dy, dy_amax, dy_amax_n, dw_tcc, db, stream, a, Ca);
-}
-// The same gradient with the up-sampled channels in PARITY CLASSES (conv3duw.hip: 8 / 27 of their products, one pass over
-// dY at 1.0 x) and the skip channels b on the direct kernel, which also carries the bias gradient.  Ca == 32 (every
-// decoder level of the VoxelMorph U-Net), Cout a multiple of 8 up to 32.  ws: dfmir_conv3d_upwgrad_ws_floats() floats,
-// private to the stream while the call is in flight.
-int df_conv3d_upwgrad_launch(const float* a, const float* a_amax, int a_n, const float* b, const float* dy, const float* dy_amax,
-                             int dy_n, float* dwt, long long s_tap, float* db, float* ws, int N, int Dl, int Hl, int Wl,
-                             int Cout, hipStream_t st);
-int df_conv3d_wgrad_march_launch(const float* x, const float* x_amax, int x_n, const float* dy, const float* dy_amax, int dy_n,
-                                 float* dwt, float* db, int N, int D, int H, int W, hipStream_t st);
-int df_conv3d_flow_wgrad_ok(const DfConvGeom* g, const float* x, const float* dy);
-int df_conv3d_flow_wgrad_launch(const float* x, const float* x_amax, int x_n, const float* dy, const float* dy_amax, int dy_n,
-                                float* dwt, float* db, int N, int D, int H, int W, int Cout, hipStream_t st);
-static bool wgrad_march_geom_ok(const DfConvGeom* g) {
-  static DfOptFlag nomarch_o{"DFMIR_CONV3D_NO_WGRAD_MARCH"};
-  return g->Cin == 32 && g->Cout == 16 && !split3d_off() && split3d_wgrad_geom_ok(g) && !nomarch_o.get() &&
-         (long long)g->Di * g->Hi * g->Wi >= 4096;
-}
-// what the launcher decides: the geometry AND 16-byte aligned operands (x, dy are read as quads)
-static bool wgrad_march_takes(const DfConvGeom* g, const float* x, const float* dy) {
-  return wgrad_march_geom_ok(g) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0;
-}
-// 1 when dfmir_conv3d_split_wgrad / _db take the marching kernel for this layer (csrc/conv3dwm.hip): _is_march answers
-// for 16-byte aligned operands, _is_march_at for the operands given (the SAME predicate the launcher applies)
-extern "C" int dfmir_conv3d_wgrad_is_march(const DfConvGeom* g) { return (g && wgrad_march_geom_ok(g)) ? 1 : 0; }
-extern "C" int dfmir_conv3d_wgrad_is_march_at(const DfConvGeom* g, const float* x, const float* dy) {
-  return (g && wgrad_march_takes(g, x, dy)) ? 1 : 0;
-}
-static bool upwgrad_geom_ok(const DfConvGeom* g, int Ca) {
-  static DfOptFlag off_o{"DFMIR_UPWGRAD_DIRECT"};
-  return !off_o.get() && !split3d_off() && split3d_wgrad_common_ok(g) && Ca == 32 && g->Cin > Ca && g->Cin - Ca <= 128 &&
-         g->Cout >= 8 && g->Cout <= 32 && (g->Cout & 7) == 0 && !(g->Di & 1) && !(g->Hi & 1) && !(g->Wi & 7);
-}
-extern "C" int dfmir_conv3d_upwgrad_ok(const DfConvGeom* g, int Ca) { return (g && upwgrad_geom_ok(g, Ca)) ? 1 : 0; }
-extern "C" long long dfmir_conv3d_upwgrad_ws_floats(void) { return 2 * 72LL * 1024; }   // (64-bit slots in deterministic mode)
-extern "C" int dfmir_conv3d_upwgrad(const DfConvGeom* g, const float* a, const float* b, int Ca, const float* x_amax,
-                                    int x_amax_n, const float* dy, const float* dy_amax, int dy_amax_n, float* dw_tcc,
-                                    float* db, float* ws, void* stream) {
-  DF_ARG_CHECK(g && a && b && ws && x_amax && x_amax_n > 0 && dy && dy_amax && dy_amax_n > 0 && dw_tcc);
-  DF_ARG_CHECK(upwgrad_geom_ok(g, Ca) && (reinterpret_cast<uintptr_t>(a) & 15) == 0 && (reinterpret_cast<uintptr_t>(b) & 7) == 0 &&
-               (reinterpret_cast<uintptr_t>(dy) & 15) == 0);   // 8-byte pair loads of a and b, 16-byte quads of dY
-  const long long s_tap = (long long)g->Cin * g->Cout;
-  // two skip channels (the network's input images at the top level): fused into the same launch, with the bias gradient
-  static DfOptFlag nofuse_o{"DFMIR_UPWGRAD_NO_FUSEB"};
-  const bool fuse = g->Cin - Ca == 2 && !nofuse_o.get();
-  const int rc = df_conv3d_upwgrad_launch(a, x_amax, x_amax_n, fuse ? b : nullptr, dy, dy_amax, dy_amax_n, dw_tcc, s_tap,
-                                          fuse ? db : nullptr, ws, g->N, g->Di / 2, g->Hi / 2, g->Wi / 2, g->Cout,
-                                          (hipStream_t)stream);
-  if (rc || fuse) return rc;
-  DfConvGeom gb = *g;
-  gb.Cin = g->Cin - Ca;
-  return conv3d_split_wgrad_impl(&gb, b, x_amax, x_amax_n, dy, dy_amax, dy_amax_n, dw_tcc + (df_det_fx() ? 2LL : 1LL) * Ca * g->Cout, db,   // (deterministic mode: 8-byte slots)
-                                 stream, nullptr, 0, s_tap);
-}
-extern "C" int dfmir_conv3d_split_wgrad(const DfConvGeom* g, const float* x, const float* x_amax, int x_amax_n,
-                                        const float* dy, const float* dy_amax, int dy_amax_n, float* dw_tcc,
-                                        void* stream) {
-  return conv3d_split_wgrad_impl(g, x, x_amax, x_amax_n, dy, dy_amax, dy_amax_n, dw_tcc, nullptr, stream);
-}
-extern "C" int dfmir_conv3d_split_wgrad_db(const DfConvGeom* g, const float* x, const float* x_amax, int x_amax_n,
-                                           const float* dy, const float* dy_amax, int dy_amax_n, float* dw_tcc,
-                                           float* db, void* stream) {
-  return conv3d_split_wgrad_impl(g, x, x_amax, x_amax_n, dy, dy_amax, dy_amax_n, dw_tcc, db, stream);
-}
-static int conv3d_split_wgrad_impl(const DfConvGeom* g, const float* x, const float* x_amax, int x_amax_n,
-                                   const float* dy, const float* dy_amax, int dy_amax_n, float* dw_tcc, float* db,
-                                   void* stream, const float* xa, int Ca, long long s_tap_full) {
-  DF_ARG_CHECK(g && x && x_amax && x_amax_n > 0 && dy && dy_amax && dy_amax_n > 0 && dw_tcc);
-  // s_tap_full: the rows of a wider gradient [27][Ctot][Cout] (dw_tcc points at this operand's first row): the skip
-  // channels of dfmir_conv3d_upwgrad, any Cin >= 1 (a partial 8-channel chunk reads zeros beyond Cin)
-  const bool rows = s_tap_full > 0 && split3d_wgrad_common_ok(g) && g->Cin >= 1 && g->Cin <= 128 && g->Cout >= 8 && g->Cout <= 32;
-  DF_ARG_CHECK(!split3d_off() && (rows || split3d_wgrad_geom_ok(g) || split3d_wgrad_swapped_ok(g)));
-  hipStream_t st = (hipStream_t)stream;
-  // the full-resolution 32 -> 16 layer: all 27 tap matrices resident, z-marching (conv3dwm.hip)
-  if (!rows && !xa && wgrad_march_takes(g, x, dy))
-    return df_conv3d_wgrad_march_launch(x, x_amax, x_amax_n, dy, dy_amax, dy_amax_n, dw_tcc, db, g->N, g->Di, g->Hi, g->Wi, st);
-  const bool swapped = !rows && !split3d_wgrad_geom_ok(g);
-  // the flow head 16 -> 3: (co, dx) pairs as MFMA columns, z-marching (conv3dt.hip)
-  if (swapped && !xa && df_conv3d_flow_wgrad_ok(g, x, dy))
-    return df_conv3d_flow_wgrad_launch(x, x_amax, x_amax_n, dy, dy_amax, dy_amax_n, dw_tcc, db, g->N, g->Di, g->Hi, g->Wi, g->Cout, st);
-  W3sP k{};
-  k.fx = df_det_fx();
-  k.N = g->N; k.D = g->Di; k.H = g->Hi; k.W = g->Wi;
-  k.xa = xa; k.Ca = xa ? Ca : 0;
-  if (swapped) {
-    k.Cin = g->Cout; k.Cout = g->Cin;                        // kernel roles
-    k.s_tap = (long long)g->Cin * g->Cout; k.s_row = 1; k.s_col = g->Cout; k.flip = 1;
-    k.x_n = dy_amax_n; k.dy_n = x_amax_n;
-    k.db = db; k.db_from_x = 1;
-  } else {
-    k.Cin = g->Cin; k.Cout = g->Cout;
-    k.s_tap = rows ? s_tap_full : (long long)g->Cin * g->Cout; k.s_row = g->Cout; k.s_col = 1; k.flip = 0;
-    k.x_n = x_amax_n; k.dy_n = dy_amax_n;
-    k.db = db; k.db_from_x = 0;
-  }
-  static DfOptFlag tr_o{"DFMIR_CONV3D_WGRAD_COPIES"};
-  const bool tr_off = tr_o.get();   // A/B: the three-copy kernel
-  k.nz = (g->Di + 1) / 2; k.ny = tr_off ? (g->Hi + 3) / 4 : (g->Hi + 7) / 8; k.nx = (g->Wi + 15) / 16;
-  k.npatch = (long long)g->N * k.nz * k.ny * k.nx;
-  long long want = 512;
-  if (want > k.npatch) want = k.npatch;
-  k.per_block = (k.npatch + want - 1) / want;
-  // <= 3 chunks of accumulators per workgroup (96 AGPRs + staging registers: two workgroups per CU, so that one
-  // converts while the other computes); more input channels = a second workgroup row, which stages dY again
-  k.nchunk = (k.Cin + 7) / 8;
-  static DfOptFlag pair_o{"DFMIR_CONV3D_WGRAD_NO_PAIR"};
-  const bool pair_off = pair_o.get();
-  const bool pairw = !tr_off && !pair_off && !swapped && k.Cout <= 16;   // (swapped flow head: measured slower, 0.44 vs 0.31 ms)         // (kernel roles) plane-pair columns: 3 accumulators per chunk
-  const int per_wg = pairw ? (k.nchunk < 2 ? k.nchunk : 2) : (k.nchunk <= 3 ? k.nchunk : (k.nchunk == 4 ? 2 : 3));
-  const unsigned gy = (unsigned)((k.nchunk + per_wg - 1) / per_wg);
-  if (gy > 1) {                                             // keep the number of workgroups
-    want = 512 / gy;
-    if (want > k.npatch) want = k.npatch;
-    k.per_block = (k.npatch + want - 1) / want;
-  }
-  unsigned nbx = (unsigned)((k.npatch + k.per_block - 1) / k.per_block);
-  if (!tr_off) {
-    // tr kernel: the tile list includes the phantom (z, y) cells of odd tile counts (they load nothing); 8 XCD shares,
-    // nslot workgroups each (see the kernel)
-    k.npatch = (long long)g->N * k.nx * 4 * ((k.nz + 1) / 2) * ((k.ny + 1) / 2);
-    k.per_block = (k.npatch + 7) / 8;
-    k.nslot = (long long)(512 / gy / 8);
-    if (k.nslot > k.per_block) k.nslot = k.per_block;
-    if (k.nslot < 1) k.nslot = 1;
-    nbx = (unsigned)(8 * k.nslot);
-  }
-  const float *kx = swapped ? dy : x, *kxa = swapped ? dy_amax : x_amax, *kdy = swapped ? x : dy, *kda = swapped ? x_amax : dy_amax;
-#define W3S_LAUNCH(N_)                                                                            \
-  {                                                                                               \
-    if (tr_off) conv3d_wgrad_split_k<N_><<<dim3(nbx, gy), 256, 0, st>>>(kx, kxa, kdy, kda, dw_tcc, k);   \
-    else if (xa) conv3d_wgrad_tr_k<N_, false, true><<<dim3(nbx, gy), 256, 0, st>>>(kx, kxa, kdy, kda, dw_tcc, k);   \
-    else conv3d_wgrad_tr_k<N_, false, false><<<dim3(nbx, gy), 256, 0, st>>>(kx, kxa, kdy, kda, dw_tcc, k);   \
-  }
-  if (pairw && per_wg == 1 && xa) conv3d_wgrad_tr_k<1, true, true><<<dim3(nbx, gy), 256, 0, st>>>(kx, kxa, kdy, kda, dw_tcc, k);
-  else if (pairw && xa) conv3d_wgrad_tr_k<2, true, true><<<dim3(nbx, gy), 256, 0, st>>>(kx, kxa, kdy, kda, dw_tcc, k);
-  else if (pairw && per_wg == 1) conv3d_wgrad_tr_k<1, true, false><<<dim3(nbx, gy), 256, 0, st>>>(kx, kxa, kdy, kda, dw_tcc, k);
-  else if (pairw) conv3d_wgrad_tr_k<2, true, false><<<dim3(nbx, gy), 256, 0, st>>>(kx, kxa, kdy, kda, dw_tcc, k);
-  else if (per_wg == 1) W3S_LAUNCH(1)
-  else if (per_wg == 2) W3S_LAUNCH(2)
-  else W3S_LAUNCH(3)
-#undef W3S_LAUNCH
-  DF_LAUNCH_CHECK();
-  return 0;
 }

@@ -601,7 +601,7 @@ __global__ __launch_bounds__(256, CO <= 3 ? 3 : 2) void conv3d_flow_wgrad_k(cons
 }
 }  // namespace
 
-// Host side (conv3ds.hip::conv3d_split_wgrad_impl calls this for the 16 -> Cout <= 4 flow head).  dwt: tap-major [27][16][Cout].
+// Host side (conv3dsw.hip::conv3d_split_wgrad_impl calls this for the 16 -> Cout <= 4 flow head).  dwt: tap-major [27][16][Cout].
 int df_conv3d_flow_wgrad_ok(const DfConvGeom* g, const float* x, const float* dy) {
   static DfOptFlag off_o{"DFMIR_CONV3D_NO_FLOW_WGRAD"};     // A/B: the swapped-role tiled kernel
   return !off_o.get() && g->Cin == 16 && g->Cout >= 1 && g->Cout <= 4 && (g->Wi & 3) == 0 && g->Di >= 2 &&

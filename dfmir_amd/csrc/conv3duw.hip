@@ -22,7 +22,7 @@
 //   conv3d_upwgrad4_k<FUSEB>  THE PRODUCT PATH: 256 threads = 4 waves = the (py, px) classes, one wave per SIMD with 512
 //                             registers per lane (16 tiles = the 256 AGPRs); FUSEB: the two skip channels of the top level
 //                             and the bias gradient in the same launch (described at the kernel).  Without FUSEB the skip
-//                             channels keep the direct kernel (conv3ds.hip::dfmir_conv3d_upwgrad).
+//                             channels keep the direct kernel (conv3dsw.hip::dfmir_conv3d_upwgrad).
 //   conv3d_upwgrad_k          the first form, kept as an A/B (DFMIR_UPWGRAD_8WAVE): 512 threads = 8 waves = (py, px) x (iz),
 //                             two waves per SIMD, 8 tiles per wave, never fused.  Same speed on the up-sampled share
 //                             (profiles/r05_bench_upwgrad.txt): these kernels are bound by the sum of their matrix and staging
@@ -778,7 +778,7 @@ __global__ __launch_bounds__(256) void conv3d_upwgrad_fold_k(const float* __rest
 }  // namespace
 
 // Host side.  b != NULL (two skip channels): everything in one launch, rows 0 .. 33 of the tap-major gradient
-// [27][Ctot][Cout] (s_tap = Ctot * Cout) and db; b == NULL: rows 0 .. 31 (conv3ds.hip::dfmir_conv3d_upwgrad runs the
+// [27][Ctot][Cout] (s_tap = Ctot * Cout) and db; b == NULL: rows 0 .. 31 (conv3dsw.hip::dfmir_conv3d_upwgrad runs the
 // direct kernel on the skip channels).  ws: 72 * 1024 floats.
 int df_conv3d_upwgrad_launch(const float* a, const float* a_amax, int a_n, const float* b, const float* dy, const float* dy_amax,
                              int dy_n, float* dwt, long long s_tap, float* db, float* ws, int N, int Dl, int Hl, int Wl,

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_march_k(const float* __re
 
 }  // namespace
 
-// Host side (conv3ds.hip::conv3d_split_wgrad_impl calls this for the 32 -> 16 layer).  dwt: tap-major [27][32][16].
+// Host side (conv3dsw.hip::conv3d_split_wgrad_impl calls this for the 32 -> 16 layer).  dwt: tap-major [27][32][16].
 int df_conv3d_wgrad_march_launch(const float* x, const float* x_amax, int x_n, const float* dy, const float* dy_amax, int dy_n,
                                  float* dwt, float* db, int N, int D, int H, int W, hipStream_t st) {
   WmP k{};

@@ -1,5 +1,5 @@
 // The device primitives of the fp16-pair split kernels ("fp16x2": conv3x3s.hip has the scheme and its error budget), shared by
-// conv3x3s.hip, conv3ds.hip, conv3dm.hip, conv3duw.hip, conv3dwm.hip and conv3dt.hip, and the z-segment choice of the two
+// conv3x3s.hip, conv3ds.hip, conv3dsw.hip, conv3dm.hip, conv3duw.hip, conv3dwm.hip and conv3dt.hip, and the z-segment choice of the two
 // weight-gradient marchers.
 #pragma once
 #include "conv3x3_common.h"

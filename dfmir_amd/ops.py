@@ -206,7 +206,7 @@ def _audit_probe(t, probe, what, plane_max=None):
 
 def _wants_amax(K, stride, dil, Di, Cin, Cout):
     """Shapes the split kernels take (the C side decides; this only avoids useless probes): 2-D 3x3 with more than
-    32 output channels (csrc/conv3x3s.hip), 3-D 3x3x3 with at least 8 channels on both sides (csrc/conv3ds.hip)."""
+    32 output channels (csrc/conv3x3s.hip), 3-D 3x3x3 with at least 8 channels on both sides (csrc/conv3ds.hip; their weight gradient: csrc/conv3dsw.hip)."""
     if tuple(K) == (3, 3, 3):   # Cout < 8 (the flow conv): only its weight gradient is split (swapped operand roles)
         return stride == 1 and dil == 1 and Di > 1 and Cin >= 8 and Cout >= 1 and not _NO_SPLIT3D
     return tuple(K) == (1, 3, 3) and stride == 1 and dil == 1 and Di == 1 and Cout > 32 and Cin >= 16

@@ -120,7 +120,7 @@ int dfmir_conv3d_split_fwd(const DfConvGeom* g, const float* x, const float* x_a
  * cout_used, left by an earlier call -- weights only change at the optimizer step.) */
 int dfmir_conv3d_split_fwd_sub(const DfConvGeom* g, const float* x, const float* x_amax, int x_amax_n, const float* w_tcc,
                                float* ws, const float* bias, float* y, float* y_amax, int cout_used, void* stream);
-/* The weight gradient of the same layers in the same split form (8 <= Cin <= 48, 8 <= Cout <= 32, or Cout < 8 with Cin <= 32; W % 4 == 0), voxels as the
+/* The weight gradient of the same layers in the same split form (csrc/conv3dsw.hip; 8 <= Cin <= 48, 8 <= Cout <= 32, or Cout < 8 with Cin <= 32; W % 4 == 0), voxels as the
  * matrix K: dw_tcc[tap][Cin][Cout] += ...   (accumulates, like dfmir_conv_wgrad). */
 /* As dfmir_conv3d_split_fwd_sub for a dgrad (g->act == 0) whose result is the gradient w.r.t. the OUTPUT of a
  * LeakyReLU: act_src = that output (shape of y); the epilogue multiplies by the activation's derivative

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Knock-out builds of one source file for timing experiments: scripts/build_ko.sh conv3ds W3T_KO 1 2 4 8 ...
+# Knock-out builds of one source file for timing experiments: scripts/build_ko.sh conv3dsw W3T_KO 1 2 4 8 ...
 # -> build/ko/libdfmir_hip_<macro><n>.so (same C ABI; select with DFMIR_HIP_LIB=...).  build/ is git-ignored but travels
 # to the GPU box.
 set -e

@@ -58,7 +58,7 @@ md += row(k1, d[k1], c[k1], 154.6, "non-MFMA VALU per wave and 16-channel chunk:
 md += row(k2, d[k2], c[k2], 154.6, "non-MFMA VALU per wave and run: %.0f; FETCH of its 16-B/lane streams under-counts by 2 (guide's correction)" % ((c[k2]['SQ_INSTS_VALU'] - c[k2]['SQ_VALU_MFMA_BUSY_CYCLES'] / 32) / (2048 * 128))) + "\n"
 md += "\nBoth kernels sit on the 1 400 W package cap (`r01_power_clock.md`); the busy fraction moves with the clock the box sustains (round 1: 68.0 % / 56.8 % at 1.72 / 1.84 GHz).  `bench.py` prices the same kernels over the step's shape mix as `roofline.issued_frac` / `wgrad_issued_frac` (3 products per MAC over the 2.5 PFLOP/s dense fp16 peak; `frac` is the algorithmic third of it) -- see the committed `{TAG}_bench_b16.json`.\n"
 open(P + TAG + '_conv3x3s_pmc.md', 'w').write(md.replace('{TAG}', TAG))
-md3 = ("# PMC counters of the 3-D split kernels (`csrc/conv3ds.hip`, `csrc/conv3dm.hip`), this round's final binary\n\n"
+md3 = ("# PMC counters of the 3-D split kernels (`csrc/conv3ds.hip`, `csrc/conv3dsw.hip`, `csrc/conv3dm.hip`), this round's final binary\n\n"
        "Command: `scripts/prof_conv3d.sh 34-32` and `… 32-16` (`scripts/bench_conv3d.py` under `rocprofv3 --kernel-trace --pmc <group>`, one group per pass): 160×192×224, 404.3 GFLOP (34→32) / 190.3 GFLOP (32→16) per launch.  Raw: `{TAG}_conv3d_pmc_raw.txt`.  The clock column is what the counters give for the profiler's serialised single launches between other work; the sustained figures are below.\n\n" + hdr)
 def gf_of(k, gf):
     m = re.match(r'conv3d_march_k<(\d+), (\d+)', k)
@@ -75,7 +75,7 @@ open(P + TAG + '_conv3d_pmc.md', 'w').write(md3.replace('{TAG}', TAG))
 if os.path.exists(C + 'pmc_upconv3d.txt'):
     su = clean(open(C + 'pmc_upconv3d.txt').read())
     d, c = parse(su)
-    mdu = ("# PMC counters of the parity-class kernels of the nearest_up2 + cat layers (`csrc/conv3ds.hip`, `csrc/conv3duw.hip`)\n\n"
+    mdu = ("# PMC counters of the parity-class kernels of the nearest_up2 + cat layers (`csrc/conv3ds.hip`, `csrc/conv3dsw.hip`, `csrc/conv3duw.hip`)\n\n"
            "Command: `scripts/prof_upconv3d.sh` (`scripts/bench_upconv3d.py`: a [1,32,80,96,112], b [1,2,160,192,224], 34 -> 32 channels, "
            "404.3 GFLOP reference-equivalent per pass; the kernels execute 8/27 of the products of the 32 up-sampled channels).  Raw: `"
            + TAG + "_conv3dup_pmc_raw.txt`.  Rates in the table are REFERENCE-EQUIVALENT FLOP/s.\n\n" + hdr)
