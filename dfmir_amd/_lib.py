@@ -152,6 +152,8 @@ _SIGS = {
     "dfmir_mse_bwd": [P, P, c_longlong, P, P, P, P],
     "dfmir_ncc_fwd_m": [P, P, P, c_int, P, P, P, P] + [c_int] * 5 + [c_float, P],
     "dfmir_ncc_bwd_m": [P, P, P, c_int, P, P, P, P, P, P] + [c_int] * 5 + [c_float, P],
+    "dfmir_ncc_gauss_fwd": [P, P, P, c_int, P, P, P, P] + [c_int] * 4 + [P, c_int, c_float, c_float, P],
+    "dfmir_ncc_gauss_bwd": [P, P, P, c_int, P, P, P, P, P, P] + [c_int] * 4 + [P, c_int, c_float, c_float, P],
     "dfmir_ncc_fwd": [P, P, P, P, P, P] + [c_int] * 5 + [c_float, P],
     "dfmir_ncc_bwd": [P, P, P, P, P, P, P, P] + [c_int] * 5 + [c_float, P],
     "dfmir_patch_gather_fwd_multi": [P, c_int, P, P, c_int, c_int, c_longlong, c_int, P],

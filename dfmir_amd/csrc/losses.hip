@@ -4,6 +4,7 @@
 // so the host never synchronises.
 #include "common.h"
 #include <atomic>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <string>
@@ -326,6 +327,11 @@ __global__ __launch_bounds__(256) void flow_smooth_bwd_k(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------- NCC
+// The taps of a weighted (Gaussian) window along one axis, at most 31 of them.  They travel BY VALUE as a kernel argument:
+// no device-side table and no copy, so a launch sequence is captured into a hipGraph like the box passes'.  The kernels
+// templated on WT run the box sums (WT = false: the taps are not read) or the weighted ones with the same staging.
+#define DFMIR_NCC_MAX_TAPS 31
+struct NccTaps { float w[DFMIR_NCC_MAX_TAPS]; };
 // box sums are separable: W pass fused with the 5 products, then H, then D.
 __global__ __launch_bounds__(256) void ncc_prod_boxw_k(const float* __restrict__ I, const float* __restrict__ J,
                                                        float* __restrict__ o, long long N, int W, int r) {
@@ -390,8 +396,11 @@ __global__ __launch_bounds__(256) void ncc_prod_boxw_x4_k(const float* __restric
 // forms the W-window sums of the 5 products for the 40 rows in LDS and sums 9 rows of them per output: the five
 // intermediate fields of the W pass never travel (137 MB out + 137 MB back in at 160x192x224).  Plain 9-term sums, as in the
 // separate passes (no running differences).
+// WT: the 9 taps tw along W and th along H in place of the ones.
+template <bool WT>
 __global__ __launch_bounds__(256) void ncc_prod_boxwh_k(const float* __restrict__ I, const float* __restrict__ J,
-                                                        float* __restrict__ o, long long N, int H, int W, int nty, int ntx) {
+                                                        float* __restrict__ o, long long N, int H, int W, int nty, int ntx,
+                                                        NccTaps tw, NccTaps th) {
   constexpr int TY = 32, TX = 64, R = 4, PY = TY + 2 * R, PX = TX + 2 * R;
   // 75 KB of static LDS: above the 64 KB most parts allow, within gfx950's 160 KB per CU (this library builds for gfx950 only)
   static_assert((2 * PY * (PX + 1) + 5 * PY * (TX + 1)) * sizeof(float) <= 160 * 1024, "LDS tile exceeds gfx950's 160 KB");
@@ -435,7 +444,12 @@ __global__ __launch_bounds__(256) void ncc_prod_boxwh_k(const float* __restrict_
 #pragma unroll
       for (int d = 0; d < 9; ++d) {
         const float u = a[j + d], v = b[j + d];
-        s0 += u; s1 += v; s2 += u * u; s3 += v * v; s4 += u * v;
+        if constexpr (WT) {
+          const float wu = tw.w[d] * u, wv = tw.w[d] * v;
+          s0 += wu; s1 += wv; s2 += wu * u; s3 += wv * v; s4 += wu * v;
+        } else {
+          s0 += u; s1 += v; s2 += u * u; s3 += v * v; s4 += u * v;
+        }
       }
       sS[0][r][c0 + j] = s0; sS[1][r][c0 + j] = s1; sS[2][r][c0 + j] = s2; sS[3][r][c0 + j] = s3; sS[4][r][c0 + j] = s4;
     }
@@ -455,7 +469,7 @@ __global__ __launch_bounds__(256) void ncc_prod_boxwh_k(const float* __restrict_
       if (y < H) {
         float s = 0.f;
 #pragma unroll
-        for (int d = 0; d < 9; ++d) s += v[j + d];
+        for (int d = 0; d < 9; ++d) s += WT ? th.w[d] * v[j + d] : v[j + d];
         o[(long long)f * N + plane * H * W + (long long)y * W + x0 + x] = s;
       }
     }
@@ -483,9 +497,10 @@ __global__ __launch_bounds__(256) void box_axis_k(const float* __restrict__ in, 
 // keeps the 2R + 1 window values in a register ring -- every input is loaded once (box_axis_k: 2R + 1 times, from
 // L1 / L2), consecutive threads hold consecutive lines, so every load / store instruction is contiguous.  Each output
 // is the plain sum of its window (no running difference: the variance terms cancel to 1e-3 of the sums).
-template <int R, int SEG>
+// WT: ring slot w holds the input at tap (w - j + WN) % WN when output j of a turn is formed.
+template <int R, int SEG, bool WT>
 __global__ __launch_bounds__(256) void box_axis_march_k(const float* __restrict__ in, float* __restrict__ out, int nf,
-                                                        long long N, long long stride, int len) {
+                                                        long long N, long long stride, int len, NccTaps tp) {
   constexpr int WN = 2 * R + 1;
   static_assert(SEG % WN == 0, "segment = whole turns of the ring");
   const long long nline = N / len;
@@ -516,7 +531,7 @@ __global__ __launch_bounds__(256) void box_axis_march_k(const float* __restrict_
         ring[(WN - 1 + j) % WN] = (cc < len) ? p[(long long)cc * stride] : 0.f;
         float sacc = 0.f;
 #pragma unroll
-        for (int w = 0; w < WN; ++w) sacc += ring[w];
+        for (int w = 0; w < WN; ++w) sacc += WT ? tp.w[(w - j + WN) % WN] * ring[w] : ring[w];
         q[(long long)c * stride] = sacc;
       }
     }
@@ -561,7 +576,7 @@ static void box_axis_launch(const float* in, float* out, int nf, long long N, lo
   if (r == 4 && stride > 1 && N % len == 0) {
     constexpr int SEG = 36;
     const long long thr = (N / len) * ((len + SEG - 1) / SEG) * nf;
-    box_axis_march_k<4, SEG><<<(unsigned)((thr + 255) / 256), 256, 0, st>>>(in, out, nf, N, stride, len);
+    box_axis_march_k<4, SEG, false><<<(unsigned)((thr + 255) / 256), 256, 0, st>>>(in, out, nf, N, stride, len, NccTaps{});
   } else if (r == 4 && stride == 1 && (len & 3) == 0 && len >= 8 && N % len == 0 &&
              ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && (N & 3) == 0) {
     box_axis_x4_k<<<(unsigned)(((N >> 2) + 255) / 256), 256, 0, st>>>(in, out, nf, N, len);
@@ -661,10 +676,11 @@ __global__ __launch_bounds__(256) void ncc_fields_k(const float* __restrict__ s,
 // The three gradient fields AND their W and H box passes in one launch (r = 4), tiled like ncc_prod_boxwh_k: the fields are
 // evaluated from the 5 saved box sums over (32 + 8) x (64 + 8) positions of a (b, z) plane (zero outside the image), summed
 // over 9 columns, then over 9 rows -- the field tensor and its W-summed copy never travel.
+template <bool WT>
 __global__ __launch_bounds__(256) void ncc_fields_boxwh_k(const float* __restrict__ s, const float* __restrict__ ws,
                                                           const float* __restrict__ gout, float* __restrict__ o, long long N,
                                                           int H, int W, int nty, int ntx, float wn, float eps,
-                                                          const float* __restrict__ mask, int mode) {
+                                                          const float* __restrict__ mask, int mode, NccTaps tw, NccTaps th) {
   constexpr int TY = 32, TX = 64, R = 4, PY = TY + 2 * R, PX = TX + 2 * R;
   // 66 KB of static LDS (gfx950: 160 KB per CU; see ncc_prod_boxwh_k)
   static_assert((3 * PY * (PX + 1) + 3 * PY * (TX + 1)) * sizeof(float) <= 160 * 1024, "LDS tile exceeds gfx950's 160 KB");
@@ -723,7 +739,7 @@ __global__ __launch_bounds__(256) void ncc_fields_boxwh_k(const float* __restric
       for (int j = 0; j < 16; ++j) {
         float t = 0.f;
 #pragma unroll
-        for (int d = 0; d < 9; ++d) t += a[j + d];
+        for (int d = 0; d < 9; ++d) t += WT ? tw.w[d] * a[j + d] : a[j + d];
         sS[f][r][c0 + j] = t;
       }
     }
@@ -742,7 +758,7 @@ __global__ __launch_bounds__(256) void ncc_fields_boxwh_k(const float* __restric
       if (y < H) {
         float t = 0.f;
 #pragma unroll
-        for (int d = 0; d < 9; ++d) t += v[j + d];
+        for (int d = 0; d < 9; ++d) t += WT ? th.w[d] * v[j + d] : v[j + d];
         o[(long long)f * N + plane * H * W + (long long)y * W + x0 + x] = t;
       }
     }
@@ -751,10 +767,10 @@ __global__ __launch_bounds__(256) void ncc_fields_boxwh_k(const float* __restric
 // The backward's last two passes in one: the box sums of the three gradient fields along the strided axis (D) as
 // box_axis_march_k forms them -- same ring, same order of additions -- and, per output, the combination of ncc_combine_k.
 // The three summed fields (82 MB written and read back at 160x192x224) are never stored; results are bit-identical.
-template <int R, int SEG>
+template <int R, int SEG, bool WT>
 __global__ __launch_bounds__(256) void ncc_boxd_combine_k(const float* __restrict__ in, const float* __restrict__ I,
                                                           const float* __restrict__ J, float* __restrict__ dI,
-                                                          long long N, long long stride, int len) {
+                                                          long long N, long long stride, int len, NccTaps tp) {
   constexpr int WN = 2 * R + 1;
   static_assert(SEG % WN == 0, "segment = whole turns of the ring");
   const long long nline = N / len;
@@ -787,7 +803,7 @@ __global__ __launch_bounds__(256) void ncc_boxd_combine_k(const float* __restric
           ring[f][(WN - 1 + j) % WN] = (cc < len) ? p[(long long)f * N + (long long)cc * stride] : 0.f;
           float a = 0.f;
 #pragma unroll
-          for (int w = 0; w < WN; ++w) a += ring[f][w];
+          for (int w = 0; w < WN; ++w) a += WT ? tp.w[(w - j + WN) % WN] * ring[f][w] : ring[f][w];
           sacc[f] = a;
         }
         const long long i = base + (long long)c * stride;
@@ -969,7 +985,7 @@ extern "C" int dfmir_ncc_fwd_m(const float* I, const float* J, const float* mask
   if (D > 1) {
     if (r == 4 && !nofuse_o.get()) {
       const int nty = (H + 31) / 32, ntx = (W + 63) / 64;
-      ncc_prod_boxwh_k<<<(unsigned)((long long)B * D * nty * ntx), 256, 0, st>>>(I, J, tmp2, N, H, W, nty, ntx);
+      ncc_prod_boxwh_k<false><<<(unsigned)((long long)B * D * nty * ntx), 256, 0, st>>>(I, J, tmp2, N, H, W, nty, ntx, NccTaps{}, NccTaps{});
     } else {
       ncc_prod_boxw_launch(I, J, tmp, N, W, r, st);
       DF_LAUNCH_CHECK();
@@ -1015,7 +1031,7 @@ extern "C" int dfmir_ncc_bwd_m(const float* I, const float* J, const float* mask
   static DfOptFlag nofuse_o{"DFMIR_NCC_NO_WH_FUSE"};         // A/B: fields, W and H passes as separate launches
   if (r == 4 && D > 1 && !nofuse_o.get()) {
     const int nty = (H + 31) / 32, ntx = (W + 63) / 64;
-    ncc_fields_boxwh_k<<<(unsigned)((long long)B * D * nty * ntx), 256, 0, st>>>(sums, ws, gout, tmp, N, H, W, nty, ntx, wn, eps, mask, mode);
+    ncc_fields_boxwh_k<false><<<(unsigned)((long long)B * D * nty * ntx), 256, 0, st>>>(sums, ws, gout, tmp, N, H, W, nty, ntx, wn, eps, mask, mode, NccTaps{}, NccTaps{});
     DF_LAUNCH_CHECK();
   } else {
     ncc_fields_k<<<grid, 256, 0, st>>>(sums, ws, gout, tmp, N, wn, eps, mask, mode);
@@ -1030,7 +1046,7 @@ extern "C" int dfmir_ncc_bwd_m(const float* I, const float* J, const float* mask
   if (D > 1 && r == 4 && (long long)H * W > 1 && !nofuse_d.get()) {
     constexpr int SEG = 36;
     const long long thr = ((long long)B * H * W) * ((D + SEG - 1) / SEG);
-    ncc_boxd_combine_k<4, SEG><<<(unsigned)((thr + 255) / 256), 256, 0, st>>>(tmp, I, J, dI, N, (long long)H * W, D);
+    ncc_boxd_combine_k<4, SEG, false><<<(unsigned)((thr + 255) / 256), 256, 0, st>>>(tmp, I, J, dI, N, (long long)H * W, D, NccTaps{});
     DF_LAUNCH_CHECK();
     return 0;
   }
@@ -1047,6 +1063,179 @@ extern "C" int dfmir_ncc_bwd(const float* I, const float* J, const float* sums, 
                              const float* ws, const float* gout, float* dI, int B, int D, int H, int W,
                              int win, float eps, void* stream) {
   return dfmir_ncc_bwd_m(I, J, nullptr, 0, sums, tmp, tmp2, ws, gout, dI, B, D, H, W, win, eps, stream);
+}
+// ------------------------------------------------------------------- NCC, Gaussian window
+// NCC_Loss(kernel_type='gaussian') (util/losses.py:153-181): the window w = c * g (x) g [(x) g], separable, so the passes
+// are the box passes with taps.  K = 9 (sigma = 3, the default) runs the WT forms of the tiled kernels above; any other odd
+// K <= 31 runs one launch per axis through the two kernels below.  A weighted window has no running sum: every output is K
+// multiply-adds, read from an LDS tile into which each input is staged once per workgroup.
+//
+// Along W (stride 1): a workgroup owns 256 consecutive elements of the flattened tensor and stages them with K/2 more on
+// either side; a tap that leaves the output's own row is skipped (the zero padding), so rows, planes and batch items never
+// mix.  PROD: the inputs are I and J and the five products are formed from the tile (blockIdx.y unused); else field
+// blockIdx.y of `a` is filtered.
+template <bool PROD>
+__global__ __launch_bounds__(256) void ncc_gauss_w_k(const float* __restrict__ a, const float* __restrict__ b,
+                                                     float* __restrict__ o, long long N, int W, int K, NccTaps tp) {
+  __shared__ float sA[256 + DFMIR_NCC_MAX_TAPS - 1], sB[PROD ? 256 + DFMIR_NCC_MAX_TAPS - 1 : 1];
+  const int tid = threadIdx.x, R = K >> 1;
+  const long long i0 = (long long)blockIdx.x * 256;
+  if (!PROD) { a += (long long)blockIdx.y * N; o += (long long)blockIdx.y * N; }
+  for (int e = tid; e < 256 + 2 * R; e += 256) {
+    const long long g = i0 - R + e;
+    const bool in = g >= 0 && g < N;
+    sA[e] = in ? a[g] : 0.f;
+    if (PROD) sB[e] = in ? b[g] : 0.f;
+  }
+  __syncthreads();
+  const long long i = i0 + tid;
+  if (i >= N) return;
+  const int x = N < 0x7FFFFFFFLL ? (int)((unsigned)i % (unsigned)W) : (int)(i % W);
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+  for (int d = 0; d < K; ++d) {
+    if ((unsigned)(x + d - R) >= (unsigned)W) continue;
+    const float w = tp.w[d], u = sA[tid + d];
+    if (PROD) {
+      const float v = sB[tid + d], wu = w * u, wv = w * v;
+      s0 += wu; s1 += wv; s2 += wu * u; s3 += wv * v; s4 += wu * v;
+    } else {
+      s0 += w * u;
+    }
+  }
+  o[i] = s0;
+  if (PROD) { o[N + i] = s1; o[2 * N + i] = s2; o[3 * N + i] = s3; o[4 * N + i] = s4; }
+}
+// Along an axis of stride > 1 (H: stride W; D: stride H * W) and length `len`: a workgroup owns 64 consecutive inner
+// positions x 32 positions of the axis of one field (blockIdx.y) and stages them with K/2 more rows on either side (zero
+// outside the axis); a thread forms 8 outputs of one column.
+__global__ __launch_bounds__(256) void ncc_gauss_axis_k(const float* __restrict__ in, float* __restrict__ out, long long N,
+                                                        long long stride, int len, int K, int nti, int ntl, NccTaps tp) {
+  constexpr int TI = 64, TL = 32;
+  __shared__ float sm[TL + DFMIR_NCC_MAX_TAPS - 1][TI];
+  const int tid = threadIdx.x, R = K >> 1;
+  long long q = blockIdx.x;
+  const long long i0 = (q % nti) * TI; q /= nti;
+  const int l0 = (int)(q % ntl) * TL;
+  const long long base = (long long)blockIdx.y * N + (q / ntl) * len * stride + i0 + (tid & 63);
+  const int c = tid & 63, rq = tid >> 6;
+  const bool cin = i0 + c < stride;
+  for (int r = rq; r < TL + 2 * R; r += 4) {
+    const int l = l0 - R + r;
+    sm[r][c] = (cin && (unsigned)l < (unsigned)len) ? in[base + (long long)l * stride] : 0.f;
+  }
+  __syncthreads();
+  if (!cin) return;
+  for (int j = 0; j < TL / 4; ++j) {
+    const int r = rq * (TL / 4) + j, l = l0 + r;
+    if (l >= len) return;
+    float acc = 0.f;
+    for (int d = 0; d < K; ++d) acc += tp.w[d] * sm[r + d][c];
+    out[base + (long long)l * stride] = acc;
+  }
+}
+static void ncc_gauss_axis_launch(const float* in, float* out, int nf, long long N, long long stride, int len, int K,
+                                  const NccTaps& tp, hipStream_t st) {
+  const int nti = (int)((stride + 63) / 64), ntl = (len + 31) / 32;
+  ncc_gauss_axis_k<<<dim3((unsigned)(N / (stride * len) * ntl * nti), nf), 256, 0, st>>>(in, out, N, stride, len, K, nti, ntl, tp);
+}
+// tw = c * g (applied along W, so that the constant enters once), tg = g (H and D); *wn = the sum of the whole window
+// under the taps as the kernels apply them, = c * (sum g)^nd to their fp32 rounding, in double.
+static bool ncc_gauss_taps(const float* taps, int K, float c, bool vol, NccTaps* tw, NccTaps* tg, float* wn) {
+  if (!taps || K < 3 || K > DFMIR_NCC_MAX_TAPS || !(K & 1) || !(c > 0.f)) return false;
+  double sw = 0.0, sg = 0.0;
+  *tw = NccTaps{}; *tg = NccTaps{};
+  for (int d = 0; d < K; ++d) {
+    if (!(taps[d] > 0.f) || taps[d] != taps[K - 1 - d]) return false;
+    tg->w[d] = taps[d];
+    tw->w[d] = (float)((double)c * taps[d]);
+    sg += tg->w[d]; sw += tw->w[d];
+  }
+  *wn = (float)(sw * sg * (vol ? sg : 1.0));
+  return std::isfinite(*wn);
+}
+// fwd: the final 5 window sums are left in `tmp`, as dfmir_ncc_fwd_m leaves its box sums.
+extern "C" int dfmir_ncc_gauss_fwd(const float* I, const float* J, const float* mask, int mode, float* tmp, float* tmp2,
+                                   float* ws, float* out, int B, int D, int H, int W, const float* taps, int K, float c,
+                                   float eps, void* stream) {
+  NccTaps tw, tg;
+  float wn = 0.f;
+  DF_ARG_CHECK(I && J && tmp && tmp2 && ws && out && B > 0 && D > 0 && H > 0 && W > 0 && (mode & ~(1 | DFMIR_NCC_VOLUME)) == 0 &&
+               ncc_gauss_taps(taps, K, c, D > 1 || (mode & DFMIR_NCC_VOLUME), &tw, &tg, &wn));
+  mode &= 1;
+  hipStream_t st = (hipStream_t)stream;
+  const long long N = (long long)B * D * H * W;
+  hipError_t e = df_zero_async(ws, 8, st);
+  if (e != hipSuccess) return df_set_error((int)e, __FILE__, __LINE__);
+  float* wh = D > 1 ? tmp2 : tmp;                          // the in-plane sums; the D pass moves them to tmp
+  if (K == 9) {
+    const int nty = (H + 31) / 32, ntx = (W + 63) / 64;
+    ncc_prod_boxwh_k<true><<<(unsigned)((long long)B * D * nty * ntx), 256, 0, st>>>(I, J, wh, N, H, W, nty, ntx, tw, tg);
+  } else {
+    float* wo = D > 1 ? tmp : tmp2;
+    ncc_gauss_w_k<true><<<(unsigned)((N + 255) / 256), 256, 0, st>>>(I, J, wo, N, W, K, tw);
+    DF_LAUNCH_CHECK();
+    ncc_gauss_axis_launch(wo, wh, 5, N, W, H, K, tg, st);
+  }
+  DF_LAUNCH_CHECK();
+  if (D > 1) {
+    if (K == 9 && (long long)H * W > 1) {                  // (the march wants a strided axis, as box_axis_launch)
+      constexpr int SEG = 36;
+      const long long thr = (N / D) * ((D + SEG - 1) / SEG) * 5;
+      box_axis_march_k<4, SEG, true><<<(unsigned)((thr + 255) / 256), 256, 0, st>>>(tmp2, tmp, 5, N, (long long)H * W, D, tg);
+    } else {
+      ncc_gauss_axis_launch(tmp2, tmp, 5, N, (long long)H * W, D, K, tg, st);
+    }
+    DF_LAUNCH_CHECK();
+  }
+  const unsigned ng = df_grid(N, 256, 1024);
+  float* part = (5 * N >= 2LL * ng) ? tmp2 : nullptr;      // as dfmir_ncc_fwd_m: tmp2 is free after the passes
+  ncc_cc_reduce_k<<<ng, 256, 0, st>>>(tmp, mask, ws, N, wn, eps, part);
+  DF_LAUNCH_CHECK();
+  ncc_fin_k<<<1, 256, 0, st>>>(ws, out, (float)N, mode, mask != nullptr, part, (int)ng);
+  DF_LAUNCH_CHECK();
+  return 0;
+}
+// bwd: the window is symmetric, so the three gradient fields are filtered with the same taps.
+extern "C" int dfmir_ncc_gauss_bwd(const float* I, const float* J, const float* mask, int mode, const float* sums,
+                                   float* tmp, float* tmp2, const float* ws, const float* gout, float* dI, int B, int D,
+                                   int H, int W, const float* taps, int K, float c, float eps, void* stream) {
+  NccTaps tw, tg;
+  float wn = 0.f;
+  DF_ARG_CHECK(I && J && sums && tmp && tmp2 && ws && gout && dI && B > 0 && D > 0 && H > 0 && W > 0 &&
+               (mode & ~(1 | DFMIR_NCC_VOLUME)) == 0 &&
+               ncc_gauss_taps(taps, K, c, D > 1 || (mode & DFMIR_NCC_VOLUME), &tw, &tg, &wn));
+  mode &= 1;
+  hipStream_t st = (hipStream_t)stream;
+  const long long N = (long long)B * D * H * W;
+  const unsigned grid = (unsigned)((N + 255) / 256);
+  if (K == 9) {
+    const int nty = (H + 31) / 32, ntx = (W + 63) / 64;
+    ncc_fields_boxwh_k<true><<<(unsigned)((long long)B * D * nty * ntx), 256, 0, st>>>(sums, ws, gout, tmp, N, H, W, nty, ntx, wn, eps, mask, mode, tw, tg);
+    DF_LAUNCH_CHECK();
+    if (D > 1 && (long long)H * W > 1) {
+      constexpr int SEG = 36;
+      const long long thr = ((long long)B * H * W) * ((D + SEG - 1) / SEG);
+      ncc_boxd_combine_k<4, SEG, true><<<(unsigned)((thr + 255) / 256), 256, 0, st>>>(tmp, I, J, dI, N, (long long)H * W, D, tg);
+      DF_LAUNCH_CHECK();
+      return 0;
+    }
+  } else {
+    ncc_fields_k<<<grid, 256, 0, st>>>(sums, ws, gout, tmp, N, wn, eps, mask, mode);
+    DF_LAUNCH_CHECK();
+    ncc_gauss_w_k<false><<<dim3(grid, 3), 256, 0, st>>>(tmp, nullptr, tmp2, N, W, K, tw);
+    DF_LAUNCH_CHECK();
+    ncc_gauss_axis_launch(tmp2, tmp, 3, N, W, H, K, tg, st);
+    DF_LAUNCH_CHECK();
+  }
+  const float* fin = tmp;
+  if (D > 1) {
+    ncc_gauss_axis_launch(tmp, tmp2, 3, N, (long long)H * W, D, K, tg, st);
+    DF_LAUNCH_CHECK();
+    fin = tmp2;
+  }
+  ncc_combine_k<<<grid, 256, 0, st>>>(I, J, fin, dI, N);
+  DF_LAUNCH_CHECK();
+  return 0;
 }
 // out = a * b, element-wise (the `prediction * mask` of Grad_Loss.forward, util/losses.py:120-121, and its gradient)
 __global__ __launch_bounds__(256) void mul_k(const float* __restrict__ a, const float* __restrict__ b,

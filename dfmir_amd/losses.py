@@ -46,18 +46,29 @@ class Grad_Loss(_Loss):
 
 
 class NCC_Loss(_Loss):
-    """util/losses.py:132-261 with the 'mean' kernel: -sqrt(mean(cc)) over a win^nd window; with `mask`
-    -sqrt(sum(cc * mask) / sum(mask)) (:257-261; an empty mask gives 0 -- as a device scalar, the reference returns
-    `torch.tensor(0)` after a host sync).  'gaussian' / 'linear' kernels are not on the path."""
+    """util/losses.py:132-261: -sqrt(mean(cc)) of the windowed correlation; with `mask` -sqrt(sum(cc * mask) / sum(mask))
+    (:257-261; an empty mask gives 0 -- as a device scalar, the reference returns `torch.tensor(0)` after a host sync).
+    kernel_type 'mean': a win^nd box, win = kernel_var (default [9] * nd).  'gaussian' (:153-181): sigma = kernel_var[0]
+    (default 3, a positive integer <= 10; the other entries are ignored, as in the reference), K = 3 sigma + ((3 sigma + 1)
+    mod 2) taps per axis, weights c * g(dy) * g(dx) with g(d) = exp(-(d - (K-1)/2)^2 / (2 sigma^2)) and c = 1 /
+    (2.506628274631 sigma), NOT normalised: win_size = sum of the weights.  The reference builds that 2-D window only and
+    its conv3d call fails on a 5-D tensor; the 3-D form here is build-defined: c * g(dz) * g(dy) * g(dx), same c and K,
+    zero padding on all three axes, win_size = c * (sum g)^3 -- also for a one-plane volume [B,1,1,H,W], where only the
+    centre z-tap meets data.  'linear' raises NotImplementedError, as in the reference."""
 
     def __init__(self, device, kernel_var=None, name=None, kernel_type='mean', eps=1e-5, *args, **kwargs):
         super().__init__(name=name or 'ncc')
         assert kernel_type in ['mean', 'gaussian', 'linear']
-        if kernel_type != 'mean':
-            raise NotImplementedError("only the 'mean' NCC kernel is on the path")
+        if kernel_type == 'linear':
+            raise NotImplementedError("Linear kernel for NCC still not implemented")
+        if kernel_type == 'gaussian':
+            ops.ncc_gauss_window(3 if kernel_var is None else kernel_var[0])      # (a bad sigma raises here)
         self.device, self.kernel_var, self.kernel_type, self.eps = device, kernel_var, kernel_type, eps
 
     def forward(self, prediction, target, mask=None, *args, **kwargs):
+        if self.kernel_type == 'gaussian':
+            sigma = 3 if self.kernel_var is None else self.kernel_var[0]
+            return ops.ncc_loss(prediction, target, eps=self.eps, mask=mask, kernel='gaussian', sigma=sigma)
         nd = prediction.dim() - 2
         kv = self.kernel_var if self.kernel_var is not None else [9] * nd
         if len(set(kv)) != 1 or len(kv) != nd:

@@ -7,6 +7,7 @@ eager-PyTorch fallback: a non-CUDA tensor raises.
 import ctypes
 import os
 
+import numpy as np
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -2350,8 +2351,21 @@ def mul(a, b):
 NCC_VOLUME = 4            # DFMIR_NCC_VOLUME (include/dfmir_hip.h): mode flag of dfmir_ncc_fwd_m / _bwd_m
 
 
+def ncc_gauss_window(sigma):
+    """(taps, K, c) of NCC_Loss's Gaussian window (util/losses.py:153-181): K = 3 sigma + ((3 sigma + 1) mod 2) taps
+    g(d) = exp(-(d - (K-1)/2)^2 / (2 sigma^2)), formed in float64 and rounded to fp32, and c = 1 / (2.506628274631 sigma).
+    The window is c * g (x) g [(x) g], not normalised.  sigma: a positive integer <= 10 (K <= 31)."""
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, np.integer)) or not 1 <= sigma <= 10:
+        raise ValueError("NCC Gaussian window: sigma must be a positive integer <= 10, got %r" % (sigma,))
+    sigma = int(sigma)
+    K = 3 * sigma + (3 * sigma + 1) % 2
+    d = np.arange(K, dtype=np.float64) - (K - 1) / 2.0
+    return np.exp(-d * d / (2.0 * sigma * sigma)).astype(np.float32), K, 1.0 / (2.506628274631 * sigma)
+
+
 class NCCFn(Function):
-    """Windowed NCC with a win^nd mean window; gradient w.r.t. the prediction I only (J is the fixed target).
+    """Windowed NCC; gradient w.r.t. the prediction I only (J is the fixed target).  `win`: an odd int = the win^nd mean
+    window, or the (taps, K, c) of ncc_gauss_window = the Gaussian one (dfmir_ncc_gauss_fwd / _bwd).
     mode 0: -sqrt(mean(cc)) (NCC_Loss, util/losses.py:248-256), with a mask -sqrt(sum(cc * mask) / sum(mask)) and 0 for
     an empty mask (:257-261); mode 1: -mean(cc) (vxm NCC.loss, torchvoxelmorph/losses.py:67)."""
 
@@ -2373,14 +2387,19 @@ class NCCFn(Function):
         tmp2 = torch.empty(5 * N, device=I.device, dtype=torch.float32)
         ws = torch.empty(8, device=I.device, dtype=torch.float32)
         out = torch.empty((), device=I.device, dtype=torch.float32)
-        if mask is None and mode == 0:
+        if isinstance(win, tuple):
+            taps, K, c = win
+            win = (np.ascontiguousarray(taps, dtype=np.float32), int(K), float(c))
+            check(lib().dfmir_ncc_gauss_fwd(_p(I), _p(J), _p(mask), int(mode), _p(sums), _p(tmp2), _p(ws), _p(out), B, D, H, W,
+                                            win[0].ctypes.data, win[1], win[2], float(eps), _st()))
+        elif mask is None and mode == 0:
             check(lib().dfmir_ncc_fwd(_p(I), _p(J), _p(sums), _p(tmp2), _p(ws), _p(out), B, D, H, W, int(win),
                                       float(eps), _st()))
         else:
             check(lib().dfmir_ncc_fwd_m(_p(I), _p(J), _p(mask), int(mode), _p(sums), _p(tmp2), _p(ws), _p(out), B, D, H, W,
                                         int(win), float(eps), _st()))
         ctx.save_for_backward(I, J, sums, ws, mask)
-        ctx.meta = (B, D, H, W, int(win), float(eps), int(mode))
+        ctx.meta = (B, D, H, W, win if isinstance(win, tuple) else int(win), float(eps), int(mode))
         return out
 
     @staticmethod
@@ -2393,7 +2412,10 @@ class NCCFn(Function):
         t1 = torch.empty(3 * N, device=I.device, dtype=torch.float32)
         t2 = torch.empty(3 * N, device=I.device, dtype=torch.float32)
         dI = torch.empty_like(I)
-        if mask is None and mode == 0:
+        if isinstance(win, tuple):
+            check(lib().dfmir_ncc_gauss_bwd(_p(I), _p(J), _p(mask), mode, _p(sums), _p(t1), _p(t2), _p(ws), _p(g), _p(dI),
+                                            B, D, H, W, win[0].ctypes.data, win[1], win[2], eps, _st()))
+        elif mask is None and mode == 0:
             check(lib().dfmir_ncc_bwd(_p(I), _p(J), _p(sums), _p(t1), _p(t2), _p(ws), _p(g), _p(dI), B, D, H, W,
                                       win, eps, _st()))
         else:
@@ -2402,13 +2424,25 @@ class NCCFn(Function):
         return dI, None, None, None, None, None
 
 
-def ncc_loss(I, J, win=9, eps=1e-5, mask=None, reduction='neg_sqrt_mean'):
+def ncc_loss(I, J, win=9, eps=1e-5, mask=None, reduction='neg_sqrt_mean', kernel='mean', sigma=None):
     """reduction 'neg_sqrt_mean' (NCC_Loss) or 'neg_mean' (vxm NCC); mask: any tensor that broadcasts to I's shape
     (bool / byte / float: the reference multiplies cc by it, util/losses.py:261).  The window counts win^nd positions by the
-    tensors' RANK: a volume of one plane [B,1,1,H,W] keeps win^3, as the reference's conv3d does."""
+    tensors' RANK: a volume of one plane [B,1,1,H,W] keeps win^3, as the reference's conv3d does.
+    kernel 'mean': the win^nd box; 'gaussian': the window of ncc_gauss_window(sigma) (sigma None = 3; `win` is not read),
+    whose 3-D form c * g (x) g (x) g is build-defined.  There a mask that is broadcast r-fold normalises by
+    its own sum, as the reference's `1 / torch.sum(mask)` does (util/losses.py:260): the loss is sqrt(r) (neg_mean: r) times
+    the one over the expanded mask, which is what the 'mean' kernel keeps returning."""
+    if kernel == 'gaussian':
+        win = ncc_gauss_window(3 if sigma is None else sigma)
+    elif kernel != 'mean':
+        raise ValueError("NCC kernel must be 'mean' or 'gaussian', got %r" % (kernel,))
+    mode = {'neg_sqrt_mean': 0, 'neg_mean': 1}[reduction]
+    r = 1
     if mask is not None:
+        r = I.numel() // mask.numel() if kernel == 'gaussian' else 1
         mask = mask.to(device=I.device, dtype=torch.float32).expand_as(I).contiguous()
-    return NCCFn.apply(I, J, win, eps, mask, {'neg_sqrt_mean': 0, 'neg_mean': 1}[reduction])
+    loss = NCCFn.apply(I, J, win, eps, mask, mode)
+    return loss if r == 1 else scale(loss.view(1), float(r) if mode else float(r) ** 0.5).view(())
 
 
 class NMIFn(Function):

@@ -28,7 +28,9 @@ def default_options(**overrides):
         overlap_registration=True,  # build-defined: netR's forward / backward on a second HIP stream beside the generator's
         deterministic_wgrad=False,  # build-defined: weight / bias gradients by 64-bit fixed-point accumulation (bit-reproducible)
         staged_step=True,          # build-defined: the two-stream step as single-stream pieces (one linear hipGraph each when captured)
-        capture_step=False)        # build-defined: replay the steady-state step as one hipGraph (REGISTRATIONModel)
+        capture_step=False,        # build-defined: replay the steady-state step as one hipGraph (REGISTRATIONModel)
+        ncc_kernel_type='mean',    # build-defined: 'gaussian' = criterionNCC with NCC_Loss's Gaussian window (constructed, not called)
+        ncc_sigma=3)               # build-defined: sigma of that window (a positive integer <= 10)
     for k, v in overrides.items():
         setattr(opt, k, v)
     return opt

@@ -4,7 +4,7 @@ The reference has no 3-D entry point (`vol_shape = (crop_size, crop_size)` is ha
 models/registration_model.py:97); SURVEY.md section 8 row A13 defines the composition from the pieces the
 reference does ship: `VxmDense(ndims=3, int_steps=7, bidir=True)`
 (models/voxelmorph/torchvoxelmorph/networks.py:1028-1145) + `NCC_Loss(kernel_var=[9,9,9], 'mean')`
-(util/losses.py:132-261) + lambda * `Grad_Loss(dim=3, 'l2')` (util/losses.py:81-130), Adam(2e-4,
+(util/losses.py:132-261; ncc_kernel='gaussian' swaps in its Gaussian window) + lambda * `Grad_Loss(dim=3, 'l2')` (util/losses.py:81-130), Adam(2e-4,
 (0.5, 0.999)).  Oracle counterpart: oracle/dfmir_oracle.py::Registration3DStep.  similarity='nmi' swaps the NCC term for
 `NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity.  seg_labels / seg_weight add the segmentation
 term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map against the moving one warped by the flow
@@ -23,8 +23,9 @@ from .voxelmorph import VxmDense
 class Registration3DModel(object):
     def __init__(self, shape, features=None, lam=1.0, lr=2e-4, betas=(0.5, 0.999), win=9, device="cuda",
                  capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
-                 seg_labels=None, seg_weight=0.0):
-        """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window) or 'nmi': NMI_Loss(real_B, warped real_A) with the
+                 seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3):
+        """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window, or with ncc_kernel='gaussian' the Gaussian window of
+        sigma = ncc_sigma, whose 3-D form is build-defined: see NCC_Loss; `win` is then unused) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
         both images to [0, nmi_max_clip] first, as the reference does: data in [-1, 1] loses its negative half (nothing is
         rescaled here).  The loss key is then 'nmi' instead of 'ncc'.
@@ -42,9 +43,12 @@ class Registration3DModel(object):
         self.optimizer_R = FlatAdam(self.netR.parameters(), lr=lr, betas=betas)
         if similarity not in ('ncc', 'nmi'):
             raise ValueError("similarity must be 'ncc' or 'nmi', got %r" % (similarity,))
+        if ncc_kernel not in ('mean', 'gaussian'):
+            raise ValueError("ncc_kernel must be 'mean' or 'gaussian', got %r" % (ncc_kernel,))
         self.similarity = similarity
         if similarity == 'ncc':
-            self.criterionNCC = NCC_Loss(self.device, kernel_var=[win] * len(shape), kernel_type='mean')
+            kernel_var = [win if ncc_kernel == 'mean' else ncc_sigma] * len(shape)
+            self.criterionNCC = NCC_Loss(self.device, kernel_var=kernel_var, kernel_type=ncc_kernel)
         else:
             bins = np.linspace(0.0, nmi_max_clip, 32) if nmi_bins is None else nmi_bins
             self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)

@@ -114,7 +114,12 @@ class REGISTRATIONModel(BaseModel):
             self.criterionGAN = networks.GANLoss(opt.gan_mode).to(self.device)
             self.criterionNCE = [PatchNCELoss(opt).to(self.device) for _ in self.nce_layers]
             self.criterionIdt = None  # torch.nn.L1Loss in the reference; constructed, never called
-            self.criterionNCC = NCC_Loss(self.device, name='ncc', kernel_var=[9, 9], kernel_type='mean')
+            # build-defined options; the criterion is constructed and, as in the reference, never called by the step
+            ncc_kernel = getattr(opt, 'ncc_kernel_type', 'mean')
+            if ncc_kernel not in ('mean', 'gaussian'):
+                raise ValueError("opt.ncc_kernel_type must be 'mean' or 'gaussian', got %r" % (ncc_kernel,))
+            kernel_var = [9, 9] if ncc_kernel == 'mean' else [getattr(opt, 'ncc_sigma', 3)] * 2
+            self.criterionNCC = NCC_Loss(self.device, name='ncc', kernel_var=kernel_var, kernel_type=ncc_kernel)
             self.optimizer_G = FlatAdam(self.netG.parameters(), lr=opt.lr, betas=(opt.beta1, opt.beta2))
             self.optimizer_R = FlatAdam(self.netR.parameters(), lr=opt.lr, betas=(opt.beta1, opt.beta2))
             self.optimizers.append(self.optimizer_G)

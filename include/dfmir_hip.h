@@ -626,6 +626,21 @@ int dfmir_ncc_fwd_m(const float* I, const float* J, const float* mask, int mode,
 int dfmir_ncc_bwd_m(const float* I, const float* J, const float* mask, int mode, const float* sums,
                     float* tmp, float* tmp2, const float* ws, const float* gout, float* dI, int B, int D,
                     int H, int W, int win, float eps, void* stream);
+/* NCC_Loss(kernel_type='gaussian') (util/losses.py:153-181 the window, :183-261 the loss): the argument lists of
+ * dfmir_ncc_fwd_m / _bwd_m with `win` replaced by the window.  taps (HOST memory, K floats, symmetric, > 0): g(d) =
+ * exp(-(d - (K-1)/2)^2 / (2 sigma^2)); K odd, 3..31; c > 0: the window is w = c * g(dy) * g(dx), NOT normalised, zero
+ * padding K/2, and win_size = sum(w) = c * (sum g)^nd is formed here in double.  The reference builds the 2-D window only
+ * (its conv3d call fails on a 5-D tensor); the 3-D form is build-defined: w = c * g(dz) * g(dy) * g(dx) with the same c and
+ * K, which D > 1 or mode | DFMIR_NCC_VOLUME selects (a one-plane volume meets data with its centre z-tap only and keeps
+ * the 3-D win_size).  The taps travel to the kernels by value: nothing is copied to the device and the launches are
+ * capturable.  mask, mode, tmp (5 * numel, the window sums, kept for backward), tmp2, ws: as above; K = 9 runs the tiled
+ * W+H forms of the mean window with taps, any other K one launch per axis. */
+int dfmir_ncc_gauss_fwd(const float* I, const float* J, const float* mask, int mode, float* tmp, float* tmp2,
+                        float* ws, float* out, int B, int D, int H, int W, const float* taps, int K, float c,
+                        float eps, void* stream);
+int dfmir_ncc_gauss_bwd(const float* I, const float* J, const float* mask, int mode, const float* sums,
+                        float* tmp, float* tmp2, const float* ws, const float* gout, float* dI, int B, int D,
+                        int H, int W, const float* taps, int K, float c, float eps, void* stream);
 /* out[t] = scale * sum_l mean(rows[l][t*seg..(t+1)*seg)), rows [L][T*seg]: the per-term
  * `total_nce_loss += loss.mean() * lambda_NCE` ... `/ n_layers` of calculate_NCE_loss (registration_model.py:247-253)
  * for T terms and L layers at once (scale = lambda_NCE / n_layers); bwd fills drows from gout[T]. */
