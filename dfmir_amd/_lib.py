@@ -144,6 +144,9 @@ _SIGS = {
     "dfmir_warp_dice_ws_floats": [c_int] * 6,
     "dfmir_warp_dice_fwd": [c_int, P, P, P, P] + [c_int] * 6 + [P, P, P, P, P],
     "dfmir_warp_dice_bwd": [c_int, P, P, P, P] + [c_int] * 5 + [P, P, P, P],
+    "dfmir_label_hausdorff_ws_bytes": [c_int] * 6,
+    "dfmir_label_edt_sq": [c_int, P, c_int, c_int] + [c_int] * 4 + [P, P],
+    "dfmir_label_hausdorff": [c_int, P, P, P] + [c_int] * 7 + [P, P, P, P, P, P],
     "dfmir_dice_ws_floats": [c_longlong, c_longlong],
     "dfmir_dice_fwd": [P, P, c_longlong, c_longlong, P, P, P],
     "dfmir_dice_bwd": [P, P, c_longlong, c_longlong, P, P, P, P, P],
@@ -204,6 +207,7 @@ def lib():
         h.dfmir_flow_smooth_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_warp_dice_ws_floats.restype = c_longlong
+        h.dfmir_label_hausdorff_ws_bytes.restype = c_longlong
         h.dfmir_dice_ws_floats.restype = c_longlong
         h.dfmir_mse_ws_floats.restype = c_longlong
         h.dfmir_warp_bwd_own_ws_floats.restype = c_longlong

@@ -30,3 +30,16 @@ def register_pair(model, data, label=None, fixed_label=None, labels=None):
             fix = ops.as_label_map(fixed_label.to(flow.device))
             out['dice'] = ops.warp_dice(mov, fix, flow.detach(), labels, mode='nearest')[1]
     return out
+
+
+@torch.no_grad()
+def score_labels(warped_label, fixed_label, labels, percentile=100.0, surface=False):
+    """Hausdorff scores of a warped label map (register_pair's 'warped_label', label ids warped with mode='nearest')
+    against the fixed one: dict(hd[B,K], directed[2,B,K], mean[2,B,K]) in voxels per listed label value
+    (ops.label_hausdorff; direction 0 is warped -> fixed).  Maps that are not uint8 go through ops.as_label_map."""
+    dev = warped_label.device
+    a = warped_label if warped_label.dtype == torch.uint8 else ops.as_label_map(warped_label)
+    fixed_label = fixed_label.to(dev)
+    b = fixed_label if fixed_label.dtype == torch.uint8 else ops.as_label_map(fixed_label)
+    hd, directed, mean, _ = ops.label_hausdorff(a, b, labels, percentile, surface)
+    return dict(hd=hd, directed=directed, mean=mean)

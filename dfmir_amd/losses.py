@@ -1,7 +1,8 @@
 """Registration losses with the reference's interfaces: `smooothing_loss`
 (models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `MSE` /
 `Dice` / `Grad` (models/voxelmorph/torchvoxelmorph/losses.py:7-117; also reachable as `dfmir_amd.voxelmorph.losses`), each
-one fused HIP reduction (dfmir_amd.ops); `LabelDice` (build-defined) is the Dice of label maps under a flow."""
+one fused HIP reduction (dfmir_amd.ops); `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
+(util/loss_metrics.py:105-132) and `LabelHausdorff` (build-defined) are evaluation metrics on the HIP distance transform."""
 import numpy as np
 import torch
 
@@ -190,3 +191,46 @@ class LabelDice(object):
             moving_label = ops.as_label_map(moving_label)
         loss, self.scores = ops.warp_dice(moving_label, fixed_label, flow, self.labels, self.mode)
         return loss
+
+
+class HausdorffDistance(object):
+    """util/loss_metrics.py:105-132: `HausdorffDistance().compute(pred, target)`, the Hausdorff distance in voxels of the
+    two binary masks `pred > 0.5` and `target > 0.5` ([B,1,*vol], 2-D or 3-D): the largest distance from a voxel of one
+    mask to the nearest voxel of the other, +inf when either mask is empty.  The reference copies both tensors to the host
+    and runs scipy's distance transform; here the exact integer transform and the reduction are HIP kernels
+    (ops.label_hausdorff) and nothing leaves the device.  Returns a [B] tensor.  For B = 1 that is the reference's value.
+    Build-defined divergence for B > 1: the reference hands the whole [B,1,*vol] array to scipy, so the batch axis counts
+    as a spatial axis and masks of different samples are measured against each other (a batch whose sample 0 holds only
+    `pred` and whose sample 1 holds only `target` gives a finite distance there); here every sample is scored on its own."""
+
+    def compute(self, pred, target):
+        assert (
+            pred.shape[1] == 1 and target.shape[1] == 1
+        ), "Only binary channel supported"
+        a = (pred > 0.5).to(torch.uint8)
+        b = (target > 0.5).to(torch.uint8)
+        return ops.label_hausdorff(a, b, [1], mean=False)[0][:, 0]
+
+
+class LabelHausdorff(object):
+    """Build-defined: the Hausdorff distance of two integer label maps per label value, the evaluation-side companion of
+    `LabelDice`.  `LabelHausdorff(labels, percentile, surface).compute(a_label, b_label)` returns hd[B,K] in voxels: per
+    listed label the larger of the two directed distances, each the `percentile` (nearest rank; 100 = the maximum, 95 =
+    HD95) of the distances from the voxels of one map's label to the nearest voxel of the other's; surface=True measures
+    between the border voxels instead.  A label that either map lacks scores +inf.  labels: 1..64 distinct integers in
+    [0, 255]; the maps: uint8 [B,1,*vol] (anything else goes through ops.as_label_map, which may sync with the host).
+    `.directed` and `.mean` hold the last call's [2,B,K] tables (direction 0: a -> b).  No gradients."""
+
+    def __init__(self, labels, percentile=100.0, surface=False):
+        self.labels = list(ops._dice_labels(labels))
+        ops._hd_percentile(percentile)
+        self.percentile, self.surface = float(percentile), bool(surface)
+        self.directed = self.mean = None
+
+    def compute(self, a_label, b_label):
+        if a_label.dtype != torch.uint8:
+            a_label = ops.as_label_map(a_label)
+        if b_label.dtype != torch.uint8:
+            b_label = ops.as_label_map(b_label)
+        hd, self.directed, self.mean, _ = ops.label_hausdorff(a_label, b_label, self.labels, self.percentile, self.surface)
+        return hd

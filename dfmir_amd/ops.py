@@ -2641,6 +2641,102 @@ def warp_dice(mov, fix, flow, labels, mode='bilinear'):
     return WarpDiceFn.apply(_c(mov), _c(fix), _c(flow), table, ws, len(vals), 1 if mode == 'nearest' else 0)
 
 
+EDT_SQ_INF = 1 << 29          # DFMIR_EDT_SQ_INF: "no voxel of the set in this batch element"
+HD_SURFACE = 1                # DFMIR_HD_SURFACE
+_HD_WS = {}
+
+
+def _label_vol(t, what):
+    """(nd, B, D, H, W) of a uint8 label map [B,1,*vol]."""
+    if not torch.is_tensor(t) or t.dim() not in (4, 5) or t.shape[1] != 1:
+        raise DfmirHipError("%s: label maps are [B,1,*vol] tensors with 2 or 3 spatial axes (got %s)"
+                            % (what, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if t.dtype != torch.uint8:
+        raise DfmirHipError("%s: uint8 label maps (ops.as_label_map) (got %s)" % (what, t.dtype))
+    nd = t.dim() - 2
+    D, H, W = (t.shape[2:] if nd == 3 else (1,) + tuple(t.shape[2:]))
+    return nd, int(t.shape[0]), int(D), int(H), int(W)
+
+
+def _hd_ws(nd, B, K, D, H, W, device, what):
+    """The scratch of the distance passes, made once per (label count, shape, device) and reused; an unsupported shape
+    raises here, before anything is launched."""
+    n = int(lib().dfmir_label_hausdorff_ws_bytes(nd, B, K, D, H, W))
+    if n <= 0:
+        raise DfmirHipError("%s: unsupported shape %s (every axis must lie in 1..256)" % (what, (B, D, H, W)))
+    if device is None:
+        return None
+    key = (nd, B, min(K, 4), D, H, W, torch.device(device))
+    ws = _HD_WS.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise DfmirHipError("%s: the scratch must be allocated before a graph capture (run one eager call first)" % what)
+        ws = _HD_WS[key] = torch.empty(n // 4, device=device, dtype=torch.int32)
+    return ws
+
+
+def label_edt_sq(label_map, value, surface=False):
+    """Exact squared Euclidean distance transform: int32 [B,*vol], min over voxels y of the same batch element with
+    label_map(y) == value of |x - y|^2, EDT_SQ_INF where there is none.  surface=True: distances to the BORDER voxels of
+    that set (set voxels with a face neighbour outside the set or outside the volume; a volume of one plane counts the
+    in-plane neighbours only).  label_map: uint8 [B,1,*vol], every axis <= 256.  Never syncs with the host."""
+    if isinstance(value, bool) or int(value) != value or not 0 <= int(value) <= 255:
+        raise DfmirHipError("label_edt_sq: the label value must be an integer in [0, 255] (got %r)" % (value,))
+    nd, B, D, H, W = _label_vol(label_map, "label_edt_sq")
+    _hd_ws(nd, B, 1, D, H, W, None, "label_edt_sq")
+    _need(label_map)
+    m = _c(label_map)
+    out = torch.empty((B,) + tuple(m.shape[2:]), device=m.device, dtype=torch.int32)
+    check(lib().dfmir_label_edt_sq(nd, _p(m), int(value), 1 if surface else 0, B, D, H, W, _p(out), _st()))
+    return out
+
+
+def _hd_percentile(percentile):
+    """percentile in (0, 100], a multiple of 0.001 -> thousandths as an integer."""
+    try:
+        q = float(percentile)
+    except (TypeError, ValueError):
+        raise DfmirHipError("label_hausdorff: percentile must be a number (got %r)" % (percentile,))
+    qm = int(round(1000.0 * q)) if q == q and abs(q) < 1e9 else 0
+    if not (0.0 < q <= 100.0) or qm < 1 or abs(1000.0 * q - qm) > 1e-6:
+        raise DfmirHipError("label_hausdorff: percentile must lie in (0, 100] and be a multiple of 0.001 (got %r)"
+                            % (percentile,))
+    return qm
+
+
+def label_hausdorff(a, b, labels, percentile=100.0, surface=False, mean=True):
+    """Hausdorff distance of two label maps per batch element and label value, in voxels, on the exact distance
+    transform (dfmir_label_hausdorff) -- the reference's HausdorffDistance (util/loss_metrics.py:105-132) without the host.
+    a / b: uint8 [B,1,*vol] (ops.as_label_map) of equal shape, every axis <= 256; labels: 1..64 distinct integers in
+    [0, 255].  Returns (hd[B,K] fp32, directed[2,B,K] fp32, mean[2,B,K] fp32, d2[2,B,K] int32): direction 0 is a -> b (over
+    the voxels of a's set, the distance to b's set), 1 the converse; d2 is the `percentile` of the squared distances by
+    nearest rank (100: the maximum), directed its square root, mean the mean distance, hd the larger directed value.
+    A label that either map lacks gives +inf (d2: EDT_SQ_INF).  surface=True measures between the border voxels of the
+    sets.  mean=False skips the mean (and, at percentile 100, the histogram it needs) and returns None in its place.
+    Never syncs with the host."""
+    vals = _dice_labels(labels)
+    qm = _hd_percentile(percentile)
+    nd, B, D, H, W = _label_vol(a, "label_hausdorff")
+    _label_vol(b, "label_hausdorff")
+    if tuple(a.shape) != tuple(b.shape):
+        raise DfmirHipError("label_hausdorff: label maps %s / %s do not match" % (tuple(a.shape), tuple(b.shape)))
+    K = len(vals)
+    _hd_ws(nd, B, K, D, H, W, None, "label_hausdorff")
+    _need(a, b)
+    a, b = _c(a), _c(b)
+    ws = _hd_ws(nd, B, K, D, H, W, a.device, "label_hausdorff")
+    dev = a.device
+    hd = torch.empty(B, K, device=dev, dtype=torch.float32)
+    directed = torch.empty(2, B, K, device=dev, dtype=torch.float32)
+    mean_t = torch.empty(2, B, K, device=dev, dtype=torch.float32) if mean else None
+    d2 = torch.empty(2, B, K, device=dev, dtype=torch.int32)
+    host_vals = (ctypes.c_ubyte * K)(*vals)
+    check(lib().dfmir_label_hausdorff(nd, _p(a), _p(b), ctypes.cast(host_vals, ctypes.c_void_p), K, B, D, H, W, qm,
+                                      HD_SURFACE if surface else 0, _p(ws), _p(hd), _p(directed), _p(mean_t), _p(d2),
+                                      _st()))
+    return hd, directed, mean_t, d2
+
+
 def _dense_pair(y_true, y_pred, what):
     if y_true.shape != y_pred.shape or y_true.dtype != torch.float32 or y_pred.dtype != torch.float32:
         raise DfmirHipError("%s: fp32 tensors of one shape (got %s %s, %s %s)"

@@ -13,6 +13,9 @@ reference does; a pair without a label file gets no `deform_label` output (the r
 Build-defined: `--fixed_label_dir DIR` (a sub-folder of dataroot holding B's label maps under the same names) scores each
 pair: its record gains "dice_labels", the label values other than 0 present in either map (the 64 smallest at most), and
 "dice", the hard Dice per such value of A's label warped with nearest-neighbour sampling against B's label.
+`--hausdorff Q` (with `--fixed_label_dir`): the record also gains "hd", the Hausdorff distance in voxels at percentile Q
+(100 = the maximum, 95 = HD95) per value of "dice_labels", of A's label ids warped with nearest-neighbour sampling by the
+pair's flow against B's label (inf for a value that either map lacks).
 """
 import argparse
 import os
@@ -23,7 +26,8 @@ from PIL import Image
 
 from . import ops
 from .data import create_dataset
-from .infer import register_pair
+from .infer import register_pair, score_labels
+from .voxelmorph import SpatialTransformer
 from .options import default_options
 from .registration_model import REGISTRATIONModel
 
@@ -40,6 +44,8 @@ def parse(argv=None):
     ap.add_argument('--label_dir', default='trainA_label', help="sub-folder of dataroot with A's label maps (test.py:66)")
     ap.add_argument('--fixed_label_dir', default=None,
                     help="sub-folder of dataroot with B's label maps: adds each pair's per-label Dice to its record")
+    ap.add_argument('--hausdorff', type=float, default=None,
+                    help="percentile Q in (0, 100]: with --fixed_label_dir, adds each pair's per-label Hausdorff distance")
     for k, v in vars(d).items():
         if k in ('gpu_ids', 'isTrain', 'capture_step'):
             continue
@@ -133,6 +139,10 @@ def main(argv=None):
                 table = ops.warp_dice(ops.as_label_map(mov.to(dev)), ops.as_label_map(fix.to(dev)), out['flow'].detach(),
                                       values, mode='nearest')[1]
                 rec["dice_labels"], rec["dice"] = values, table[0].tolist()
+                if opt.hausdorff is not None:
+                    st = SpatialTransformer(tuple(out['flow'].shape[2:]), mode='nearest').to(dev)
+                    warped_ids = st(mov.to(dev).float(), out['flow'].detach())
+                    rec["hd"] = score_labels(warped_ids, fix.to(dev), values, percentile=opt.hausdorff)['hd'][0].tolist()
         written.append(rec)
     return written
 

@@ -587,6 +587,33 @@ int dfmir_warp_dice_fwd(int nd, const unsigned char* mov, const unsigned char* f
 int dfmir_warp_dice_bwd(int nd, const unsigned char* mov, const unsigned char* fix, const float* flow,
                         const unsigned char* slot_of, int K, int B, int D, int H, int W, const float* seeds,
                         const float* gout, float* dflow, void* stream);
+/* Exact squared Euclidean distance transform of a label map, and the Hausdorff distance of two label maps on it: the
+ * reference's `HausdorffDistance` (util/loss_metrics.py:105-132; scipy's distance_transform_edt on the host there) per batch
+ * element and per label.  nd = 2 ([B,1,H,W], D = 1) or 3; maps: 8-bit [B][D][H][W]; every axis <= 256, B <= 65535.
+ * dfmir_label_edt_sq: out[B][D][H][W] int32 = min over voxels y with map(y) == value of |x - y|^2, DFMIR_EDT_SQ_INF where
+ * the batch element holds no such voxel.  surface != 0: the set is replaced by its border voxels -- set voxels with a face
+ * neighbour outside the set or outside the volume (4 neighbours in 2-D, 6 in 3-D; a volume of one plane, D == 1, counts the
+ * in-plane ones only).  One launch per axis, `out` is the only scratch.
+ * dfmir_label_hausdorff: labels = K <= 64 label values in HOST memory (they travel to the kernels by value: nothing is copied
+ * to the device, the launches are capturable).  Direction 0 is a -> b (over the voxels of a's set, the distance to b's set),
+ * direction 1 the converse; flags & DFMIR_HD_SURFACE replaces both sets by their borders.  qm = percentile in thousandths,
+ * 1 .. 100000.  Per (direction, b, k), n = size of the source set:
+ *   d2[dir][b][k]       the smallest d2 whose cumulative count reaches r = max(1, ceil(qm n / 100000)) (nearest rank;
+ *                       qm = 100000: the maximum), int32
+ *   directed[dir][b][k] sqrt(d2) (formed in double, rounded once)
+ *   mean[dir][b][k]     mean of sqrt(d2) over the source set, summed in double over the histogram; mean may be NULL
+ *   hd[b][k]            max of directed over the two directions
+ * If either set is empty for (b, k): hd = directed = mean = +inf, d2 = DFMIR_EDT_SQ_INF (the reference's rule).
+ * ws: dfmir_label_hausdorff_ws_bytes() bytes, 4-byte aligned, need not be zeroed; labels run in chunks of 4, so it does not
+ * grow with K beyond that (-1: unsupported shape; nothing is launched).  Integer atomics only: bit-identical from run to run. */
+#define DFMIR_EDT_SQ_INF (1 << 29)
+#define DFMIR_HD_SURFACE 1
+long long dfmir_label_hausdorff_ws_bytes(int nd, int B, int K, int D, int H, int W);
+int dfmir_label_edt_sq(int nd, const unsigned char* map, int value, int surface, int B, int D, int H, int W, int* out,
+                       void* stream);
+int dfmir_label_hausdorff(int nd, const unsigned char* a, const unsigned char* b, const unsigned char* labels, int K, int B,
+                          int D, int H, int W, int qm, int flags, void* ws, float* hd, float* directed, float* mean,
+                          int* d2, void* stream);
 /* vxm `Dice().loss(y_true, y_pred)` (models/voxelmorph/torchvoxelmorph/losses.py:79-90) of float tensors [planes = B C][S]:
  * out[0] = -mean over planes of 2 sum(t p) / max(sum(t + p), 1e-5).  ws: dfmir_dice_ws_floats(planes, S) floats (per-chunk
  * partial sums, added in index order: bit-reproducible; then the per-plane coefficients the backward reads -- keep it
