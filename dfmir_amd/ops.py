@@ -4,7 +4,9 @@ Every op here launches hand-written gfx950 kernels on torch's *current* HIP stre
 pointers; torch is used only for memory, streams and the autograd tape.  There is no CPU or
 eager-PyTorch fallback: a non-CUDA tensor raises.
 """
+import collections
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -70,6 +72,8 @@ def _env_on(name):
 # ------------------------------------------------------------------------------------------------
 # raw launches
 # ------------------------------------------------------------------------------------------------
+# conv_raw / conv_wgrad_raw go in three steps: _plan_conv_* picks the kernel (the one place that asks the library's *_ok
+# queries and reads the A/B switches), _launch_conv_* issues it, _conv_*_label names it for the profiler below.
 # Optional launch profiler (bench.py): called as prof(kind, flops, launch) where launch() issues
 # the kernel; lets the bench bracket the dominant kernel with HIP events on the launch stream.
 _CONV_PROFILER = [None]
@@ -206,11 +210,149 @@ def _audit_probe(t, probe, what, plane_max=None):
 
 
 def _wants_amax(K, stride, dil, Di, Cin, Cout):
-    """Shapes the split kernels take (the C side decides; this only avoids useless probes): 2-D 3x3 with more than
-    32 output channels (csrc/conv3x3s.hip), 3-D 3x3x3 with at least 8 channels on both sides (csrc/conv3ds.hip; their weight gradient: csrc/conv3dsw.hip)."""
+    """Shapes the split kernels take (the C side decides, asked by _plan_conv_fwd / _plan_conv_wgrad; this only avoids useless
+    probes): 2-D 3x3 with more than 32 output channels (csrc/conv3x3s.hip), 3-D 3x3x3 with at least 8 channels on both sides
+    (csrc/conv3ds.hip; their weight gradient: csrc/conv3dsw.hip)."""
     if tuple(K) == (3, 3, 3):   # Cout < 8 (the flow conv): only its weight gradient is split (swapped operand roles)
         return stride == 1 and dil == 1 and Di > 1 and Cin >= 8 and Cout >= 1 and not _NO_SPLIT3D
     return tuple(K) == (1, 3, 3) and stride == 1 and dil == 1 and Di == 1 and Cout > 32 and Cin >= 16
+
+
+# A/B switches of the conv paths, from the environment at import; tests assign to them later: read them at call time
+_NO_TINY3D = _env_on("DFMIR_CONV3D_NO_TINY")  # A/B switch: the flow head on the split kernels
+_NO_TINYVOL = _env_on("DFMIR_NO_TINYVOL")     # A/B switch (also read by the library): no conv_tinyvol_k
+_NO_S2 = _env_on("DFMIR_CONV3D_NO_S2")        # A/B switch: the stride-2 encoder levels on the generic gather kernels
+_NO_FLOW_MARCH = _env_on("DFMIR_CONV3D_NO_FLOW_MARCH")  # A/B switch: the flow head's forward on the fp32-FMA kernel
+_NO_ACTGRAD = _env_on("DFMIR_NO_ACTGRAD")     # A/B switch: LeakyReLU backward always as its own pass
+_NO_RES = _env_on("DFMIR_NO_RES")       # A/B switch: residual added by a separate kernel
+_NO_DEAD_TAIL = _env_on("DFMIR_NO_DEAD_TAIL")   # A/B switch: dgrad also for skip channels that need none
+_NO_CH_SCALE = _env_on("DFMIR_NO_CH_SCALE")   # A/B switch: one dY scale per tensor in the split wgrad
+_NO_RING = _env_on("DFMIR_NO_RING")     # A/B switch: reflect dgrad as padded-frame conv + fold
+_LAST_ACTGRAD = [False]     # did the last conv_raw() apply an activation derivative in its epilogue?
+
+
+def _size_label(c, small=True):     # channel class in the bench profiler's kinds (the weight gradient has no "small")
+    return "L" if c > 64 else ("M" if c > 32 else ("S" if c > 4 or not small else "small"))
+
+
+def _call_profiler(prof, launch, kind, flops, issued):
+    if issued is not None and getattr(prof, "accepts_issued", False):
+        prof(kind, flops, launch, issued)
+    else:
+        prof(kind, flops, launch)
+
+
+_ConvFwdPlan = collections.namedtuple("_ConvFwdPlan", "kernel cout_used act_src fuse_res tiling")
+
+
+def _plan_conv_fwd(g, K, probe, res, ring, cout_used, no_bias, act_src):
+    """Which forward kernel takes the layer g: flow_march | tiny3d | s2c2 | s2m | s2d | march3d | split3d | res2d | generic.
+    Pure: no launch, no allocation; asks the library's *_ok queries in a fixed order, each only while its answer matters.
+    cout_used, act_src: what the caller asked for where that kernel does it, else None; fuse_res: the residual goes into the
+    epilogue; tiling: the split tiling ("split" / "march") that took the layer, or None -- the label counts its issued products
+    even under a stride-2 kernel, which launches ahead of it (the real library never accepts a layer for both)."""
+    L, gp = lib(), ctypes.byref(g)
+    N, Cin, Cout, Wi, stride, dil, act = g.N, g.Cin, g.Cout, g.Wi, g.stride, g.dil, g.act
+    yshape, vol = (N, Cout, g.Do, g.Ho, g.Wo), g.Do * g.Ho * g.Wo
+    if res is not None or ring is not None:       # only the 2-D 3x3 epilogue folds them in; otherwise a separate add
+        fuse_res = bool(res is not None and not _NO_RES and probe and res.is_contiguous() and tuple(res.shape) == yshape
+                        and L.dfmir_conv3x3_res_ok(gp))
+        return _ConvFwdPlan("res2d" if (fuse_res or ring is not None) else "generic", None, None, fuse_res, None)
+    if tuple(K) != (3, 3, 3):
+        return _ConvFwdPlan("generic", None, None, False, None)
+    # the flow head / its data gradient (16 -> 3, 3 -> 16): plain fp32 FMAs (csrc/conv3dt.hip)
+    tiny = not _NO_TINY3D and (cout_used is None or cout_used == Cout) and bool(L.dfmir_conv3d_tiny_ok(gp))
+    # ... the head itself on the z-marching kernel's FLOW form when the volume is large enough for it (csrc/conv3dm.hip)
+    flow = (tiny and Cin == 16 and Cout == 3 and act == 0 and act_src is None and probe and not _NO_FLOW_MARCH
+            and Wi % 4 == 0 and bool(L.dfmir_conv3d_march_ok(gp)))
+    # the first encoder level (2 -> 16, stride 2) from an LDS-staged patch (csrc/conv3dt.hip)
+    s2c2 = not tiny and stride == 2 and Cin == 2 and not _NO_TINY3D and cout_used is None and bool(L.dfmir_conv3d_s2c2_ok(gp))
+    # the deeper stride-2 encoder levels and their data gradients (fp32 MFMA from LDS-staged patches: csrc/conv3ds2.hip)
+    plain = cout_used is None and act_src is None and not _NO_S2
+    s2m = plain and not s2c2 and stride == 2 and dil == 1 and bool(L.dfmir_conv3d_s2_ok(gp))
+    s2d = plain and stride == 1 and dil == 2 and no_bias and act == 0 and bool(L.dfmir_conv3d_s2_dgrad_ok(gp))
+    split = not tiny and not s2c2 and probe and bool(L.dfmir_conv3d_split_ok(gp))
+    # <= 512 output voxels per image (the deepest levels of the 6-level U-Net: 8^3, 4^3, 2^3): a split launch costs its
+    # 45-80 us of prologue whatever the volume; conv_tinyvol_k (behind dfmir_conv_fwd_scaled) takes 20-30
+    if split and cout_used is None and not _NO_TINYVOL and Cout <= 64 and vol <= 512 and N * vol <= 8192:
+        split = False
+    if not split:
+        cout_used = None                                     # only the split 3-D kernel computes a channel subset
+    # the full-resolution layers with Cin x Cout <= 512: the z-marching kernel (csrc/conv3dm.hip)
+    march = split and (cout_used is None or cout_used == Cout) and Wi % 4 == 0 and bool(L.dfmir_conv3d_march_ok(gp))
+    if act_src is not None and not ((split or tiny) and act == 0 and tuple(act_src.shape) == yshape and act_src.is_contiguous()):
+        act_src = None                                       # ... and only these epilogues apply an activation derivative
+    kernel = ("flow_march" if flow else "tiny3d" if tiny else "s2c2" if s2c2 else "s2m" if s2m else "s2d" if s2d
+              else "march3d" if march else "split3d" if split else "generic")
+    return _ConvFwdPlan(kernel, cout_used, act_src, False, "march" if march else "split" if split else None)
+
+
+def _launch_probed(y, call):
+    """Issue a kernel that leaves the range probe of y for the next layer: call(pointer to a fresh probe)."""
+    slot = amax_slot(y.device, PROBE_SLOTS)
+    check(call(_p(slot)))
+    tag_amax(y, slot)              # survives as is when y is a backward result (dgrad) ...
+    _LAST_CONV_AMAX[0] = slot      # ... and is re-attached by conv() to the tensor Function.apply returns
+
+
+def _launch_conv_fwd(plan, g, x5, x_amax, w_tcc, bias, y, res, ring, act_slope):
+    L, gp, k = lib(), ctypes.byref(g), plan.kernel
+    x, w, b, yp, src, slope = _p(x5), _p(w_tcc), _p(bias), _p(y), _p(plan.act_src), float(act_slope)
+    xa, xa_n = _p(x_amax), 0 if x_amax is None else x_amax.numel()
+    if k in ("flow_march", "march3d"):                        # (the FLOW form has no activation derivative: src is None)
+        slope = slope if k == "march3d" else 0.0
+        _launch_probed(y, lambda slot: L.dfmir_conv3d_march_fwd(gp, x, xa, xa_n, w, b, yp, slot, src, slope, _st()))
+    elif k == "tiny3d":
+        _launch_probed(y, lambda slot: L.dfmir_conv3d_tiny_fwd(gp, x, w, b, yp, slot, src, slope, _st()))
+    elif k in ("s2c2", "s2m"):
+        fn = L.dfmir_conv3d_s2c2_fwd if k == "s2c2" else L.dfmir_conv3d_s2_fwd
+        _launch_probed(y, lambda slot: fn(gp, x, w, b, yp, slot, _st()))
+    elif k == "s2d":
+        check(L.dfmir_conv3d_s2_dgrad(gp, x, w, yp, _st()))
+    elif k == "split3d":
+        # fp16x2 split form on the 16-bit matrix pipe.  The split weights are kept per packed-weight buffer and re-made only when
+        # it was re-packed (generation and cache live ON the persistent buffer's tensor object: a temporary packing has neither)
+        Cin, Cout = g.Cin, g.Cout
+        cu = Cout if plan.cout_used is None else plan.cout_used
+        pair_ = L.dfmir_conv3d_split_is_pair(cu)
+        ws, need_ = _ws_cached(w_tcc, (Cin, Cout, cu), L.dfmir_conv3d_split_ws_floats(Cin, Cout), x5.device,
+                               job=(0, Cin, cu if pair_ else Cout, pair_, Cin, 0, 0))
+        w, ws = (w if need_ else None), _p(ws)
+        if plan.act_src is not None:   # dgrad into the output of a LeakyReLU: the epilogue applies its derivative (csrc/conv3ds.hip)
+            _launch_probed(y, lambda slot: L.dfmir_conv3d_split_fwd_actgrad(gp, x, xa, xa_n, w, ws, b, yp, slot, cu, src, slope, _st()))
+        else:
+            _launch_probed(y, lambda slot: L.dfmir_conv3d_split_fwd_sub(gp, x, xa, xa_n, w, ws, b, yp, slot, cu, _st()))
+    elif k == "res2d":
+        check(L.dfmir_conv3x3_fwd_scaled_res(gp, x, xa, xa_n, w, b, _p(res) if plan.fuse_res else None,
+                                             *((_p(ring[0]), ring[1]) if ring is not None else (None, 0)), yp, _st()))
+    else:
+        check(L.dfmir_conv_fwd_scaled(gp, x, xa, xa_n, w, b, yp, _st()))
+    if res is not None and not plan.fuse_res:
+        y.add_(res.reshape(y.shape))
+
+
+def _conv_fwd_label(plan, g):
+    """(kind, flops, issued or None) of the launch for the bench profiler (bench.py keys on the kind strings)."""
+    N, Cin, Cout, dil = g.N, g.Cin, g.Cout, g.dil
+    K, pad = (g.KD, g.KH, g.KW), (g.pd, g.ph, g.pw)
+    flops = 2.0 * N * Cout * g.Do * g.Ho * g.Wo * Cin * K[0] * K[1] * K[2] / (dil ** 3 if K[0] > 1 else dil ** 2)
+    size = _size_label(Cout)
+    is3x3 = K == (1, 3, 3) and g.stride == 1 and dil == 1 and g.Di == 1 and pad[1] == pad[2] and pad[1] in (1, 2) and Cout > 4
+    is3d = (K == (3, 3, 3) and g.stride == 1 and dil == 1 and pad == (1, 1, 1) and g.pad_mode == 0
+            and not (Cout <= 4 and Cin < 8))              # what csrc/conv3d.hip::df_conv3d_fwd_try takes
+    kind = ("conv3dt_" if plan.kernel in ("flow_march", "tiny3d", "s2c2", "s2m", "s2d") else "conv3x3_" if is3x3
+            else ("conv3ds_" if plan.tiling else "conv3d_") if is3d else "conv_mfma_") + size
+    if not plan.tiling:
+        return kind, flops, None
+    # 16-bit products the kernel ISSUES per algorithmic MAC: 3 (a0b0 + a0b1 + a1b0) x the padding of its tiling --
+    # taps 27 -> 28 (plane-pair rows: 27 -> 36 taps'), input channels to whole chunks of 8, output channels to 32 rows
+    cu = Cout if plan.cout_used is None else plan.cout_used
+    form_ = lib().dfmir_conv3d_split_is_pair(cu)      # 0: 32 rows, 1: plane pairs (36 taps'), 2: 16 rows
+    pad_k = (36.0 if form_ == 1 else 28.0) / 27.0 * (8.0 * ((Cin + 7) // 8)) / Cin
+    pad_m = (16.0 / cu) if form_ else (32.0 * ((cu + 31) // 32)) / cu
+    if plan.tiling == "march":                        # no padded rows; 16 -> 16 walks 10 tap slots per 9 taps
+        pad_k, pad_m = ((10.0 / 9.0) if (Cin == 16 and Cout == 16) else 1.0), 1.0
+    return kind, flops * cu / Cout, 3.0 * pad_k * pad_m * flops * cu / Cout
 
 
 def conv_raw(x5, w_tcc, bias, Cout, K, stride, pad, dil, pad_mode, act, slope, out_sp, x_amax=None, res=None, ring=None,
@@ -222,143 +364,17 @@ def conv_raw(x5, w_tcc, bias, Cout, K, stride, pad, dil, pad_mode, act, slope, o
     y = torch.empty((N, Cout) + tuple(out_sp), device=x5.device, dtype=torch.float32)
     g = DfConvGeom(N, Cin, Cout, Di, Hi, Wi, out_sp[0], out_sp[1], out_sp[2], K[0], K[1], K[2],
                    stride, dil, pad[0], pad[1], pad[2], pad_mode, act, float(slope))
-    fuse_res = (res is not None and not _NO_RES and x_amax is not None and res.is_contiguous() and tuple(res.shape) == tuple(y.shape)
-                and lib().dfmir_conv3x3_res_ok(ctypes.byref(g)))
-    # the flow head / its data gradient (16 -> 3, 3 -> 16): plain fp32 FMAs (csrc/conv3dt.hip)
-    tiny3d = (tuple(K) == (3, 3, 3) and res is None and ring is None and not _NO_TINY3D
-              and (cout_used is None or cout_used == Cout) and bool(lib().dfmir_conv3d_tiny_ok(ctypes.byref(g))))
-    # ... the head itself on the z-marching kernel's FLOW form when the volume is large enough for it (csrc/conv3dm.hip)
-    flow_march = (tiny3d and Cin == 16 and Cout == 3 and act == 0 and act_src is None and x_amax is not None
-                  and not _NO_FLOW_MARCH and Wi % 4 == 0 and bool(lib().dfmir_conv3d_march_ok(ctypes.byref(g))))
-    # the first encoder level (2 -> 16, stride 2) from an LDS-staged patch (csrc/conv3dt.hip)
-    s2c2 = (not tiny3d and tuple(K) == (3, 3, 3) and stride == 2 and Cin == 2 and res is None and ring is None and not _NO_TINY3D
-            and cout_used is None and bool(lib().dfmir_conv3d_s2c2_ok(ctypes.byref(g))))
-    # the deeper stride-2 encoder levels and their data gradients (fp32 MFMA from LDS-staged patches: csrc/conv3ds2.hip)
-    plain = res is None and ring is None and cout_used is None and act_src is None and tuple(K) == (3, 3, 3) and not _NO_S2
-    s2m = plain and not s2c2 and stride == 2 and dil == 1 and bool(lib().dfmir_conv3d_s2_ok(ctypes.byref(g)))
-    s2d = (plain and stride == 1 and dil == 2 and bias is None and act == 0
-           and bool(lib().dfmir_conv3d_s2_dgrad_ok(ctypes.byref(g))))
-    split3d = (not tiny3d and not s2c2 and x_amax is not None and tuple(K) == (3, 3, 3) and res is None and ring is None
-               and bool(lib().dfmir_conv3d_split_ok(ctypes.byref(g))))
-    # <= 512 output voxels per image (the deepest levels of the 6-level U-Net: 8^3, 4^3, 2^3): a split launch costs its
-    # 45-80 us of prologue whatever the volume; conv_tinyvol_k (behind dfmir_conv_fwd_scaled) takes 20-30
-    if (split3d and cout_used is None and not _NO_TINYVOL and Cout <= 64
-            and out_sp[0] * out_sp[1] * out_sp[2] <= 512 and N * out_sp[0] * out_sp[1] * out_sp[2] <= 8192):
-        split3d = False
-    if cout_used is not None and not split3d:
-        cout_used = None                                     # only the split 3-D kernel computes a channel subset
-    # the full-resolution layers with Cin x Cout <= 512: the z-marching kernel (csrc/conv3dm.hip)
-    march3d = (split3d and (cout_used is None or cout_used == Cout) and Wi % 4 == 0
-               and bool(lib().dfmir_conv3d_march_ok(ctypes.byref(g))))
-    if act_src is not None and not ((split3d or tiny3d) and act == 0 and tuple(act_src.shape) == tuple(y.shape)
-                                    and act_src.is_contiguous()):
-        act_src = None                                       # ... and only these epilogues apply an activation derivative
-    _LAST_ACTGRAD[0] = act_src is not None
+    plan = _plan_conv_fwd(g, K, x_amax is not None, res, ring, cout_used, bias is None, act_src)
+    _LAST_ACTGRAD[0] = plan.act_src is not None
     if _PROBE_AUDIT["on"] and x_amax is not None:
         _audit_probe(x5, x_amax, "conv input %s -> %d ch, k=%s" % (tuple(x5.shape), Cout, tuple(K)))
-
-    def launch():
-        if flow_march:
-            slot = amax_slot(x5.device, PROBE_SLOTS)
-            check(lib().dfmir_conv3d_march_fwd(ctypes.byref(g), _p(x5), _p(x_amax), x_amax.numel(), _p(w_tcc), _p(bias),
-                                               _p(y), _p(slot), None, 0.0, _st()))
-            tag_amax(y, slot)
-            _LAST_CONV_AMAX[0] = slot
-        elif tiny3d:
-            slot = amax_slot(x5.device, PROBE_SLOTS)
-            check(lib().dfmir_conv3d_tiny_fwd(ctypes.byref(g), _p(x5), _p(w_tcc), _p(bias), _p(y), _p(slot), _p(act_src),
-                                              float(act_slope), _st()))
-            tag_amax(y, slot)
-            _LAST_CONV_AMAX[0] = slot
-        elif s2c2:
-            slot = amax_slot(x5.device, PROBE_SLOTS)
-            check(lib().dfmir_conv3d_s2c2_fwd(ctypes.byref(g), _p(x5), _p(w_tcc), _p(bias), _p(y), _p(slot), _st()))
-            tag_amax(y, slot)
-            _LAST_CONV_AMAX[0] = slot
-        elif s2m:
-            slot = amax_slot(x5.device, PROBE_SLOTS)
-            check(lib().dfmir_conv3d_s2_fwd(ctypes.byref(g), _p(x5), _p(w_tcc), _p(bias), _p(y), _p(slot), _st()))
-            tag_amax(y, slot)
-            _LAST_CONV_AMAX[0] = slot
-        elif s2d:
-            check(lib().dfmir_conv3d_s2_dgrad(ctypes.byref(g), _p(x5), _p(w_tcc), _p(y), _st()))
-        elif march3d:
-            slot = amax_slot(x5.device, PROBE_SLOTS)
-            check(lib().dfmir_conv3d_march_fwd(ctypes.byref(g), _p(x5), _p(x_amax), x_amax.numel(), _p(w_tcc), _p(bias),
-                                               _p(y), _p(slot), _p(act_src), float(act_slope), _st()))
-            tag_amax(y, slot)
-            _LAST_CONV_AMAX[0] = slot
-        elif split3d:
-            # fp16x2 split form on the 16-bit matrix pipe; the kernel leaves the range probe of y for the next layer.
-            # The split weights are kept per packed-weight buffer and re-made only when that buffer was re-packed.
-            cu = Cout if cout_used is None else cout_used
-            # (the generation and the cache live ON the persistent packed buffer's tensor object: a temporary packing
-            # has neither, and an address recycled by the allocator cannot alias a stale entry)
-            pair_ = lib().dfmir_conv3d_split_is_pair(cu)
-            ws, need_ = _ws_cached(w_tcc, (Cin, Cout, cu), lib().dfmir_conv3d_split_ws_floats(Cin, Cout), x5.device,
-                                   job=(0, Cin, cu if pair_ else Cout, pair_, Cin, 0, 0))
-            w_arg = w_tcc if need_ else None
-            slot = amax_slot(x5.device, PROBE_SLOTS)
-            if act_src is not None:
-                # dgrad into the output of a LeakyReLU: the epilogue applies the activation's derivative (csrc/conv3ds.hip)
-                check(lib().dfmir_conv3d_split_fwd_actgrad(ctypes.byref(g), _p(x5), _p(x_amax), x_amax.numel(), _p(w_arg),
-                                                           _p(ws), _p(bias), _p(y), _p(slot), cu, _p(act_src),
-                                                           float(act_slope), _st()))
-            else:
-                check(lib().dfmir_conv3d_split_fwd_sub(ctypes.byref(g), _p(x5), _p(x_amax), x_amax.numel(), _p(w_arg), _p(ws),
-                                                       _p(bias), _p(y), _p(slot), cu, _st()))
-            tag_amax(y, slot)              # survives as is when y is a backward result (dgrad) ...
-            _LAST_CONV_AMAX[0] = slot      # ... and is re-attached by conv() to the tensor Function.apply returns
-        elif fuse_res or ring is not None:
-            check(lib().dfmir_conv3x3_fwd_scaled_res(ctypes.byref(g), _p(x5), _p(x_amax), x_amax.numel(), _p(w_tcc),
-                                                     _p(bias), _p(res) if fuse_res else None,
-                                                     _p(ring[0]) if ring is not None else None,
-                                                     ring[1] if ring is not None else 0, _p(y), _st()))
-            if res is not None and not fuse_res:
-                y.add_(res.reshape(y.shape))
-        else:
-            check(lib().dfmir_conv_fwd_scaled(ctypes.byref(g), _p(x5), _p(x_amax),
-                                              0 if x_amax is None else x_amax.numel(), _p(w_tcc), _p(bias), _p(y), _st()))
-            if res is not None:
-                y.add_(res.reshape(y.shape))
-
+    launch = functools.partial(_launch_conv_fwd, plan, g, x5, x_amax, w_tcc, bias, y, res, ring, act_slope)
     prof = _CONV_PROFILER[0]
     if prof is None:
         launch()
     else:
-        flops = 2.0 * N * Cout * out_sp[0] * out_sp[1] * out_sp[2] * Cin * K[0] * K[1] * K[2] / (dil ** 3 if K[0] > 1 else dil ** 2)
-        size = "L" if Cout > 64 else ("M" if Cout > 32 else ("S" if Cout > 4 else "small"))
-        is3x3 = (tuple(K) == (1, 3, 3) and stride == 1 and dil == 1 and Di == 1 and pad[1] == pad[2]
-                 and pad[1] in (1, 2) and Cout > 4)
-        is3d = (tuple(K) == (3, 3, 3) and stride == 1 and dil == 1 and tuple(pad) == (1, 1, 1) and pad_mode == 0
-                and not (Cout <= 4 and Cin < 8))          # what csrc/conv3d.hip::df_conv3d_fwd_try takes
-        kind = ("conv3x3_" if is3x3 else (("conv3ds_" if split3d else "conv3d_") if is3d else "conv_mfma_")) + size
-        if tiny3d or s2c2 or s2m or s2d:
-            kind = "conv3dt_" + size
-        if split3d:
-            # 16-bit products the kernel ISSUES per algorithmic MAC: 3 (a0b0 + a0b1 + a1b0) x the padding of its tiling --
-            # taps 27 -> 28 (plane-pair rows: 27 -> 36 taps'), input channels to whole chunks of 8, output channels to 32 rows
-            cu = Cout if cout_used is None else cout_used
-            form_ = lib().dfmir_conv3d_split_is_pair(cu)      # 0: 32 rows, 1: plane pairs (36 taps'), 2: 16 rows
-            pad_k = (36.0 if form_ == 1 else 28.0) / 27.0 * (8.0 * ((Cin + 7) // 8)) / Cin
-            pad_m = (16.0 / cu) if form_ else (32.0 * ((cu + 31) // 32)) / cu
-            if march3d:                                       # no padded rows; 16 -> 16 walks 10 tap slots per 9 taps
-                pad_k, pad_m = ((10.0 / 9.0) if (Cin == 16 and Cout == 16) else 1.0), 1.0
-            if getattr(prof, "accepts_issued", False):
-                prof(kind, flops * cu / Cout, launch, 3.0 * pad_k * pad_m * flops * cu / Cout)
-            else:
-                prof(kind, flops * cu / Cout, launch)
-        else:
-            prof(kind, flops, launch)
+        _call_profiler(prof, launch, *_conv_fwd_label(plan, g))
     return y
-
-
-_LAST_ACTGRAD = [False]     # did the last conv_raw() apply an activation derivative in its epilogue?
-_NO_TINY3D = _env_on("DFMIR_CONV3D_NO_TINY")  # A/B switch: the flow head on the split kernels
-_NO_TINYVOL = _env_on("DFMIR_NO_TINYVOL")     # A/B switch (also read by the library): no conv_tinyvol_k
-_NO_S2 = _env_on("DFMIR_CONV3D_NO_S2")        # A/B switch: the stride-2 encoder levels on the generic gather kernels
-_NO_FLOW_MARCH = _env_on("DFMIR_CONV3D_NO_FLOW_MARCH")  # A/B switch: the flow head's forward on the fp32-FMA kernel
-_NO_ACTGRAD = _env_on("DFMIR_NO_ACTGRAD")     # A/B switch: LeakyReLU backward always as its own pass
 
 
 def _tag_ok(t, tag):
@@ -435,117 +451,126 @@ def bias_grad(dy5, db):
     acc.end(None, db)
 
 
+_WGRAD_SPLIT = ("upwgrad", "split_upcat", "split3d")      # the kernels behind dfmir_conv3d_split_wgrad_ok
+
+
+def _plan_conv_wgrad(g, K, probed, parts):
+    """Which weight-gradient kernel takes the layer g: s2c2 | s2m | upwgrad | split_upcat | split3d | generic.  Pure, like
+    _plan_conv_fwd; probed = the caller has the range probes of both operands."""
+    L, gp = lib(), ctypes.byref(g)
+    k3 = tuple(K) == (3, 3, 3)
+    split = probed and k3 and bool(L.dfmir_conv3d_split_wgrad_ok(gp))
+    if parts is not None:
+        if not split:
+            raise DfmirHipError("conv_wgrad_raw(parts=...) needs the split 3-D weight-gradient kernel")
+        # the up-sampled channels in parity classes (csrc/conv3duw.hip) where the volume fills the chip
+        min_vox = min(_UPWGRAD_MIN_VOX, _UPWGRAD_MIN_VOX_FUSED) if parts[1].shape[1] == 2 else _UPWGRAD_MIN_VOX
+        upw = parts[0][0, 0].numel() >= min_vox and L.dfmir_conv3d_upwgrad_ok(gp, parts[0].shape[1])
+        return "upwgrad" if upw else "split_upcat"
+    if k3 and g.stride == 2:
+        if g.Cin == 2 and not _NO_TINY3D and L.dfmir_conv3d_s2c2_ok(gp):
+            return "s2c2"
+        if not _NO_S2 and L.dfmir_conv3d_s2_ok(gp):
+            return "s2m"
+    return "split3d" if split else "generic"
+
+
+def _launch_conv_wgrad(kernel, g, x5, dy5, x_amax, dy_amax, dy_pmax, parts, dw, db):
+    L, gp = lib(), ctypes.byref(g)
+    x, dy, dwp, dbp = _p(x5), _p(dy5), _p(dw), _p(db)
+    xa, xa_n = _p(x_amax), 0 if x_amax is None else x_amax.numel()
+    ya, ya_n = _p(dy_amax), 0 if dy_amax is None else dy_amax.numel()
+    if kernel == "s2c2":
+        if db is not None:
+            check(L.dfmir_bias_grad(dy, dbp, dy5.shape[0], g.Cout, g.Do * g.Ho * g.Wo, _st()))   # accumulates
+        check(L.dfmir_conv3d_s2c2_wgrad(gp, x, dy, dwp, _st()))
+    elif kernel == "s2m":
+        check(L.dfmir_conv3d_s2_wgrad(gp, x, dy, dwp, dbp, _st()))   # db fused
+    elif kernel in ("upwgrad", "split_upcat"):
+        args = (gp, _p(parts[0]), _p(parts[1]), parts[0].shape[1], xa, xa_n, dy, ya, ya_n, dwp, dbp)
+        check(L.dfmir_conv3d_upwgrad(*args, _p(_upwgrad_ws(dy5.device)), _st()) if kernel == "upwgrad"
+              else L.dfmir_conv3d_split_wgrad_upcat(*args, _st()))
+    elif kernel == "split3d":
+        check(L.dfmir_conv3d_split_wgrad_db(gp, x, xa, xa_n, dy, ya, ya_n, dwp, dbp, _st()))   # db fused
+    else:
+        pm = dy_pmax if (dy_pmax is not None and dy_pmax.numel() == g.N * g.Cout and dy_amax is not None) else None
+        check(L.dfmir_conv_wgrad_scaled_ch(gp, x, xa, xa_n, dy, ya, ya_n, _p(pm), dwp, dbp, _st()))
+
+
+def _conv_wgrad_label(kernel, g, x5, dy5, parts, want_issued):
+    """(kind, flops, issued or None) of the launch for the bench profiler; want_issued: the profiler takes the issued
+    products (the parity-class kernel has a kind of its own only then)."""
+    Cin, Cout, Wi = g.Cin, g.Cout, g.Wi
+    K, pad = (g.KD, g.KH, g.KW), (g.pd, g.ph, g.pw)
+    size = _size_label(Cout, small=False)
+    flops = 2.0 * g.N * Cout * g.Do * g.Ho * g.Wo * Cin * (K[0] * K[1] * K[2])
+    split = kernel in _WGRAD_SPLIT
+    is3x3 = (K == (1, 3, 3) and g.stride == 1 and g.Di == 1 and pad[1] == 1 and pad[2] == 1 and Cout >= 64 and Cin >= 32
+             and (g.Hi * Wi) % 32 == 0 and Wi % 32 == 0)
+    is3d = (K == (3, 3, 3) and g.stride == 1 and pad == (1, 1, 1) and g.pad_mode == 0 and Cout <= 32
+            and Wi % 4 == 0)                              # csrc/conv3d.hip::df_conv3d_wgrad_try
+    kind = ("wgrad3dt_S" if kernel in ("s2c2", "s2m") else
+            ("wgrad3x3_" if is3x3 else (("wgrad3ds_" if split else "wgrad3d_") if is3d else "conv_wgrad_")) + size)
+    if not (split and is3d and want_issued):
+        return kind, flops, None
+    # 16-bit products the kernel ISSUES per algorithmic MAC (cf. _conv_fwd_label): 3 x the padding of its tiling
+    if kernel == "upwgrad":     # parity classes: 8 / 27 of the up-sampled share, 32 columns; fused skip pair: 54 -> 64 rows
+        Ca_, Cb_ = parts[0].shape[1], parts[1].shape[1]
+        skip_ = (64.0 / 54.0) if Cb_ == 2 else (28.0 / 27.0) * (8.0 * ((Cb_ + 7) // 8)) / Cb_
+        pad_ = ((8.0 / 27.0) * Ca_ + skip_ * Cb_) / Cin * (32.0 / Cout)
+        kind = "wgrad3dup_" + size
+    elif Cout < 8:          # the flow head: roles swapped, rows = (tap, co of a chunk of 8), columns = ci of 32
+        pad_ = (28.0 / 27.0) * (8.0 / Cout) * (32.0 / Cin)
+    elif parts is None and lib().dfmir_conv3d_wgrad_is_march_at(ctypes.byref(g), _p(x5), _p(dy5)):   # 14 tiles of two taps for 27
+        pad_ = 28.0 / 27.0
+    elif Cout <= 16:        # plane-pair columns: 36 taps' of 27, 16 columns per plane
+        pad_ = (36.0 / 27.0) * (8.0 * ((Cin + 7) // 8)) / Cin * (16.0 / Cout)
+    else:
+        pad_ = (28.0 / 27.0) * (8.0 * ((Cin + 7) // 8)) / Cin * (32.0 / Cout)
+    return kind, flops, 3.0 * pad_ * flops
+
+
 def conv_wgrad_raw(x5, dy5, K, stride, pad, pad_mode, out=None, x_amax=None, dy_amax=None, db=None, dy_pmax=None,
                    parts=None):
     """dW in the tap-major packing; `out` (same packing) is accumulated into when given.  parts = (a, b): the operand is
     cat(nearest_up2(a), b), never built (x5 is None; the caller checked upcat_wgrad_ok)."""
     if parts is not None:
-        a_, b_ = parts
-        N, Cin = b_.shape[0], a_.shape[1] + b_.shape[1]
-        Di, Hi, Wi = b_.shape[2:]
-        x5 = b_
-    else:
-        N, Cin, Di, Hi, Wi = x5.shape
+        x5 = parts[1]
+    N, Cin, Di, Hi, Wi = x5.shape
+    if parts is not None:
+        Cin += parts[0].shape[1]
     _, Cout, Do, Ho, Wo = dy5.shape
-    T = K[0] * K[1] * K[2]
-    dw = zeros((T, Cin, Cout), x5.device) if out is None else out
+    dw = zeros((K[0] * K[1] * K[2], Cin, Cout), x5.device) if out is None else out
     g = DfConvGeom(N, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, K[0], K[1], K[2], stride, 1, pad[0], pad[1],
                    pad[2], pad_mode, 0, 0.0)
-    split3d = (x_amax is not None and dy_amax is not None and tuple(K) == (3, 3, 3)
-               and bool(lib().dfmir_conv3d_split_wgrad_ok(ctypes.byref(g))))
-    if parts is not None and not split3d:
-        raise DfmirHipError("conv_wgrad_raw(parts=...) needs the split 3-D weight-gradient kernel")
+    kernel = _plan_conv_wgrad(g, K, x_amax is not None and dy_amax is not None, parts)
     if _PROBE_AUDIT["on"]:
         if x_amax is not None:
             for t_ in (parts if parts is not None else (x5,)):
                 _audit_probe(t_, x_amax, "wgrad x %s" % (tuple(t_.shape),))
         if dy_amax is not None:
-            pm_ = dy_pmax if (dy_pmax is not None and dy_pmax.numel() == N * Cout and not split3d) else None
+            pm_ = dy_pmax if (dy_pmax is not None and dy_pmax.numel() == N * Cout and kernel not in _WGRAD_SPLIT) else None
             _audit_probe(dy5, dy_amax, "wgrad dY %s" % (tuple(dy5.shape),), plane_max=pm_)
-
-    # the up-sampled channels in parity classes (csrc/conv3duw.hip) where the volume fills the chip
-    upw = (parts is not None
-           and parts[0][0, 0].numel() >= (min(_UPWGRAD_MIN_VOX, _UPWGRAD_MIN_VOX_FUSED) if parts[1].shape[1] == 2 else _UPWGRAD_MIN_VOX)
-           and bool(lib().dfmir_conv3d_upwgrad_ok(ctypes.byref(g), parts[0].shape[1])))
-    s2c2 = (parts is None and tuple(K) == (3, 3, 3) and stride == 2 and Cin == 2 and not _NO_TINY3D
-            and bool(lib().dfmir_conv3d_s2c2_ok(ctypes.byref(g))))
-    s2m = (parts is None and not s2c2 and tuple(K) == (3, 3, 3) and stride == 2 and not _NO_S2
-           and bool(lib().dfmir_conv3d_s2_ok(ctypes.byref(g))))
     # deterministic mode: the kernels add 64-bit fixed-point sums into a scratch, never a bias gradient (its own pass below)
     det = _DetAcc(dw.numel(), Cout if db is not None else 0, N * Do * Ho * Wo, x5 if parts is None else None, x_amax,
                   dy5, dy_amax) if _DET["on"] else None
-    dw_real, db_real = dw, db
-    if det is not None:
-        dw, db = det.dw, None
-
-    def launch():
-        if s2c2:
-            if db is not None:
-                check(lib().dfmir_bias_grad(_p(dy5), _p(db), dy5.shape[0], Cout, Do * Ho * Wo, _st()))   # accumulates
-            check(lib().dfmir_conv3d_s2c2_wgrad(ctypes.byref(g), _p(x5), _p(dy5), _p(dw), _st()))
-            return
-        if s2m:
-            check(lib().dfmir_conv3d_s2_wgrad(ctypes.byref(g), _p(x5), _p(dy5), _p(dw), _p(db), _st()))   # db fused
-            return
-        if parts is not None:
-            if upw:
-                check(lib().dfmir_conv3d_upwgrad(ctypes.byref(g), _p(parts[0]), _p(parts[1]), parts[0].shape[1],
-                                                 _p(x_amax), x_amax.numel(), _p(dy5), _p(dy_amax), dy_amax.numel(),
-                                                 _p(dw), _p(db), _p(_upwgrad_ws(dy5.device)), _st()))
-                return
-            check(lib().dfmir_conv3d_split_wgrad_upcat(ctypes.byref(g), _p(parts[0]), _p(parts[1]), parts[0].shape[1],
-                                                       _p(x_amax), x_amax.numel(), _p(dy5), _p(dy_amax), dy_amax.numel(),
-                                                       _p(dw), _p(db), _st()))
-            return
-        if split3d:
-            check(lib().dfmir_conv3d_split_wgrad_db(ctypes.byref(g), _p(x5), _p(x_amax), x_amax.numel(), _p(dy5),
-                                                    _p(dy_amax), dy_amax.numel(), _p(dw), _p(db), _st()))   # db fused
-            return
-        pm = dy_pmax if (dy_pmax is not None and dy_pmax.numel() == N * Cout and dy_amax is not None) else None
-        check(lib().dfmir_conv_wgrad_scaled_ch(ctypes.byref(g), _p(x5), _p(x_amax),
-                                               0 if x_amax is None else x_amax.numel(), _p(dy5), _p(dy_amax),
-                                               0 if dy_amax is None else dy_amax.numel(), _p(pm), _p(dw), _p(db), _st()))
-
+    launch = functools.partial(_launch_conv_wgrad, kernel, g, x5, dy5, x_amax, dy_amax, dy_pmax, parts,
+                               *((dw, db) if det is None else (det.dw, None)))
     if det is not None:
         try:
             launch()
-            if db_real is not None:
+            if db is not None:
                 check(lib().dfmir_bias_grad(_p(dy5), _p(det.db), dy5.shape[0], Cout, Do * Ho * Wo, _st()))
         except BaseException:
             det.abort()
             raise
-        det.end(dw_real, db_real)
-        return dw_real
+        det.end(dw, db)
+        return dw
     prof = _CONV_PROFILER[0]
     if prof is None:
         launch()
     else:
-        is3x3 = (tuple(K) == (1, 3, 3) and stride == 1 and Di == 1 and pad[1] == 1 and pad[2] == 1
-                 and Cout >= 64 and Cin >= 32 and (Hi * Wi) % 32 == 0 and Wi % 32 == 0)
-        size = "L" if Cout > 64 else ("M" if Cout > 32 else "S")
-        is3d = (tuple(K) == (3, 3, 3) and stride == 1 and tuple(pad) == (1, 1, 1) and pad_mode == 0 and Cout <= 32
-                and Wi % 4 == 0)                          # csrc/conv3d.hip::df_conv3d_wgrad_try
-        flops = 2.0 * N * Cout * Do * Ho * Wo * Cin * T
-        kind = ("wgrad3dt_S" if (s2c2 or s2m) else
-                ("wgrad3x3_" if is3x3 else (("wgrad3ds_" if split3d else "wgrad3d_") if is3d else "conv_wgrad_")) + size)
-        if split3d and is3d and not s2c2 and getattr(prof, "accepts_issued", False):
-            # 16-bit products the kernel ISSUES per algorithmic MAC (cf. conv_raw): 3 x the padding of its tiling
-            if upw:     # parity classes: 8 / 27 of the up-sampled share, 32 columns; fused skip pair: 54 -> 64 rows
-                Ca_, Cb_ = parts[0].shape[1], parts[1].shape[1]
-                skip_ = (64.0 / 54.0) if Cb_ == 2 else (28.0 / 27.0) * (8.0 * ((Cb_ + 7) // 8)) / Cb_
-                pad_ = ((8.0 / 27.0) * Ca_ + skip_ * Cb_) / Cin * (32.0 / Cout)
-                kind = "wgrad3dup_" + size
-            elif Cout < 8:          # the flow head: roles swapped, rows = (tap, co of a chunk of 8), columns = ci of 32
-                pad_ = (28.0 / 27.0) * (8.0 / Cout) * (32.0 / Cin)
-            elif parts is None and lib().dfmir_conv3d_wgrad_is_march_at(ctypes.byref(g), _p(x5), _p(dy5)):   # 14 tiles of two taps for 27
-                pad_ = 28.0 / 27.0
-            elif Cout <= 16:        # plane-pair columns: 36 taps' of 27, 16 columns per plane
-                pad_ = (36.0 / 27.0) * (8.0 * ((Cin + 7) // 8)) / Cin * (16.0 / Cout)
-            else:
-                pad_ = (28.0 / 27.0) * (8.0 * ((Cin + 7) // 8)) / Cin * (32.0 / Cout)
-            prof(kind, flops, launch, 3.0 * pad_ * flops)
-        else:
-            prof(kind, flops, launch)
+        _call_profiler(prof, launch, *_conv_wgrad_label(kernel, g, x5, dy5, parts, getattr(prof, "accepts_issued", False)))
     return dw
 
 
@@ -659,10 +684,6 @@ def bump_weights_epoch():
 # wgrad kernels of all those passes accumulate into ONE persistent tap-major buffer per module and the
 # bias gradients straight into `bias.grad`; the buffers are unpacked into `weight.grad` once, on exit.
 # Without it every pass pays a zero-fill, an unpack and an autograd `add` per parameter (~900 tiny launches).
-_NO_RES = _env_on("DFMIR_NO_RES")       # A/B switch: residual added by a separate kernel
-_NO_DEAD_TAIL = _env_on("DFMIR_NO_DEAD_TAIL")   # A/B switch: dgrad also for skip channels that need none
-_NO_CH_SCALE = _env_on("DFMIR_NO_CH_SCALE")   # A/B switch: one dY scale per tensor in the split wgrad
-_NO_RING = _env_on("DFMIR_NO_RING")     # A/B switch: reflect dgrad as padded-frame conv + fold
 _DEFER = {"on": False, "pending": {}}
 
 
@@ -808,110 +829,109 @@ class ConvFn(Function):
 def _conv_backward_impl(ctx, dy, dskip, x5, weight, y5):
     """Backward of y = act(conv(x5, weight) + bias) for a ctx-like object carrying cfg, x_amax, dead_tail, in_act,
     has_bias, needs_input_grad (x, weight, bias); returns (dx, dw, db).  Shared by ConvFn and UpCatConv3dFn."""
-    if True:
-        nd, K, stride, p3, pad_mode, act, slope, owner = ctx.cfg
-        dy5 = _c(dy) if nd == 3 else _c(dy).unsqueeze(2)
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        want_probe = _wants_amax(K, stride, 1, dy5.shape[2], Cout, Cin) or ctx.x_amax is not None
-        dy_amax = None
-        if act and _tag_ok(dy, getattr(dy, "_df_premasked", None)) and dy.is_contiguous():
-            pass      # the producing dgrad already multiplied by this activation's derivative (and left the range probe)
-        elif act:
-            dpre = torch.empty_like(dy5)
-            if want_probe and nd == 3 and not ((dy5.data_ptr() | y5.data_ptr() | dpre.data_ptr()) & 15):
-                # the activation's backward leaves the range probe of what it writes (3-D tensors are 0.1-1 GB: a
-                # separate absmax pass would cost 10 % of the dgrad it serves)
-                dy_amax = amax_slot(dy5.device, PROBE_SLOTS)
-                check(lib().dfmir_act_bwd_amax(_p(dy5), _p(y5), _p(dpre), dy5.numel(), act, float(slope), _p(dy_amax), _st()))
+    nd, K, stride, p3, pad_mode, act, slope, owner = ctx.cfg
+    dy5 = _c(dy) if nd == 3 else _c(dy).unsqueeze(2)
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    want_probe = _wants_amax(K, stride, 1, dy5.shape[2], Cout, Cin) or ctx.x_amax is not None
+    dy_amax = None
+    if act and _tag_ok(dy, getattr(dy, "_df_premasked", None)) and dy.is_contiguous():
+        pass      # the producing dgrad already multiplied by this activation's derivative (and left the range probe)
+    elif act:
+        dpre = torch.empty_like(dy5)
+        if want_probe and nd == 3 and not ((dy5.data_ptr() | y5.data_ptr() | dpre.data_ptr()) & 15):
+            # the activation's backward leaves the range probe of what it writes (3-D tensors are 0.1-1 GB: a
+            # separate absmax pass would cost 10 % of the dgrad it serves)
+            dy_amax = amax_slot(dy5.device, PROBE_SLOTS)
+            check(lib().dfmir_act_bwd_amax(_p(dy5), _p(y5), _p(dpre), dy5.numel(), act, float(slope), _p(dy_amax), _st()))
+        else:
+            check(lib().dfmir_act_bwd(_p(dy5), _p(y5), _p(dpre), dy5.numel(), act, float(slope), _st()))
+        dy5 = dpre
+    dx = dw = db = None
+    # dY feeds the dgrad conv (as its input) and the wgrad: one range probe for both
+    if want_probe and dy_amax is None:
+        dy_amax = amax_of(dy) if (dy.is_contiguous() and (not act or dy5.data_ptr() == dy.data_ptr())) else absmax(dy5)
+    if ctx.needs_input_grad[0]:
+        wd = owner.packed(1) if owner is not None else weight_pack(weight, 1)
+        in_sp = tuple(x5.shape[2:])
+        gf = None
+        if stride == 1 and pad_mode == 1 and dy_amax is not None and not _NO_RING:
+            gf = DfConvGeom(x5.shape[0], Cin, Cout, 1, in_sp[1], in_sp[2], 1, in_sp[1], in_sp[2], K[0], K[1], K[2],
+                            1, 1, p3[0], p3[1], p3[2], 1, 0, 0.0)
+            gd = DfConvGeom(x5.shape[0], Cout, Cin, 1, in_sp[1], in_sp[2], 1, in_sp[1], in_sp[2], K[0], K[1], K[2],
+                            1, 1, p3[0], p3[1], p3[2], 0, 0, 0.0)      # the zero-padded dgrad as a conv
+            if not (lib().dfmir_conv3x3_reflect_ring_ok(ctypes.byref(gf))
+                    and lib().dfmir_conv3x3_res_ok(ctypes.byref(gd))):
+                gf = None
+        if gf is not None:
+            # the one-pixel ring of the padded frame first (four 1-D convolutions of dY's border lines, into a
+            # compact buffer), then the frame's interior = the zero-padded "same" dgrad on full tiles, whose
+            # epilogue folds the ring (and the skip branch's gradient) in   (csrc/conv3x3s.hip)
+            rl = lib().dfmir_conv3x3_reflect_ring_len(ctypes.byref(gf))
+            ringbuf = torch.empty(x5.shape[0] * 4 * Cin * rl, device=dy5.device, dtype=torch.float32)
+            ctag = getattr(dy, "_df_cols", None)
+            cols = ctag[0] if (ctag is not None and ctag[1] == dy._version and ctag[2] == dy.data_ptr()
+                               and dy.is_contiguous() and not act) else None
+            check(lib().dfmir_conv3x3_reflect_ring(ctypes.byref(gf), _p(dy5), _p(cols), _p(dy_amax), dy_amax.numel(),
+                                                   _p(wd), _p(ringbuf), _st()))
+            res5 = None
+            if dskip is not None:
+                res5 = _c(dskip) if nd == 3 else _c(dskip).unsqueeze(2)
+                dskip = None
+            dx5 = conv_raw(dy5, wd, None, Cin, K, 1, p3, 1, 0, 0, 0.0, in_sp, dy_amax, res=res5, ring=(ringbuf, rl))
+        elif stride == 1 and pad_mode == 1:
+            # full correlation onto the reflect-padded frame, then fold the halo back
+            padp = tuple(K[i] - 1 for i in range(3))
+            out_sp = tuple(in_sp[i] + 2 * p3[i] for i in range(3))
+            dxp = conv_raw(dy5, wd, None, Cin, K, 1, padp, 1, 0, 0, 0.0, out_sp, dy_amax)
+            if p3[0] != 0 or p3[1] != p3[2]:
+                raise DfmirHipError("reflect padding is 2-D, symmetric only")
+            dx5 = torch.empty_like(x5)
+            if dskip is not None:
+                check(lib().dfmir_reflect_pad2d_bwd_add(_p(dxp), _p(_c(dskip)), _p(dx5), x5.shape[0] * Cin,
+                                                        in_sp[1], in_sp[2], p3[1], _st()))
+                dskip = None
             else:
-                check(lib().dfmir_act_bwd(_p(dy5), _p(y5), _p(dpre), dy5.numel(), act, float(slope), _st()))
-            dy5 = dpre
-        dx = dw = db = None
-        # dY feeds the dgrad conv (as its input) and the wgrad: one range probe for both
-        if want_probe and dy_amax is None:
-            dy_amax = amax_of(dy) if (dy.is_contiguous() and (not act or dy5.data_ptr() == dy.data_ptr())) else absmax(dy5)
-        if ctx.needs_input_grad[0]:
-            wd = owner.packed(1) if owner is not None else weight_pack(weight, 1)
-            in_sp = tuple(x5.shape[2:])
-            gf = None
-            if stride == 1 and pad_mode == 1 and dy_amax is not None and not _NO_RING:
-                gf = DfConvGeom(x5.shape[0], Cin, Cout, 1, in_sp[1], in_sp[2], 1, in_sp[1], in_sp[2], K[0], K[1], K[2],
-                                1, 1, p3[0], p3[1], p3[2], 1, 0, 0.0)
-                gd = DfConvGeom(x5.shape[0], Cout, Cin, 1, in_sp[1], in_sp[2], 1, in_sp[1], in_sp[2], K[0], K[1], K[2],
-                                1, 1, p3[0], p3[1], p3[2], 0, 0, 0.0)      # the zero-padded dgrad as a conv
-                if not (lib().dfmir_conv3x3_reflect_ring_ok(ctypes.byref(gf))
-                        and lib().dfmir_conv3x3_res_ok(ctypes.byref(gd))):
-                    gf = None
-            if gf is not None:
-                # the one-pixel ring of the padded frame first (four 1-D convolutions of dY's border lines, into a
-                # compact buffer), then the frame's interior = the zero-padded "same" dgrad on full tiles, whose
-                # epilogue folds the ring (and the skip branch's gradient) in   (csrc/conv3x3s.hip)
-                rl = lib().dfmir_conv3x3_reflect_ring_len(ctypes.byref(gf))
-                ringbuf = torch.empty(x5.shape[0] * 4 * Cin * rl, device=dy5.device, dtype=torch.float32)
-                ctag = getattr(dy, "_df_cols", None)
-                cols = ctag[0] if (ctag is not None and ctag[1] == dy._version and ctag[2] == dy.data_ptr()
-                                   and dy.is_contiguous() and not act) else None
-                check(lib().dfmir_conv3x3_reflect_ring(ctypes.byref(gf), _p(dy5), _p(cols), _p(dy_amax), dy_amax.numel(),
-                                                       _p(wd), _p(ringbuf), _st()))
-                res5 = None
-                if dskip is not None:
-                    res5 = _c(dskip) if nd == 3 else _c(dskip).unsqueeze(2)
-                    dskip = None
-                dx5 = conv_raw(dy5, wd, None, Cin, K, 1, p3, 1, 0, 0, 0.0, in_sp, dy_amax, res=res5, ring=(ringbuf, rl))
-            elif stride == 1 and pad_mode == 1:
-                # full correlation onto the reflect-padded frame, then fold the halo back
-                padp = tuple(K[i] - 1 for i in range(3))
-                out_sp = tuple(in_sp[i] + 2 * p3[i] for i in range(3))
-                dxp = conv_raw(dy5, wd, None, Cin, K, 1, padp, 1, 0, 0, 0.0, out_sp, dy_amax)
-                if p3[0] != 0 or p3[1] != p3[2]:
-                    raise DfmirHipError("reflect padding is 2-D, symmetric only")
-                dx5 = torch.empty_like(x5)
-                if dskip is not None:
-                    check(lib().dfmir_reflect_pad2d_bwd_add(_p(dxp), _p(_c(dskip)), _p(dx5), x5.shape[0] * Cin,
-                                                            in_sp[1], in_sp[2], p3[1], _st()))
-                    dskip = None
-                else:
-                    check(lib().dfmir_reflect_pad2d_bwd(_p(dxp), _p(dx5), x5.shape[0] * Cin, in_sp[1], in_sp[2],
-                                                        p3[1], _st()))
-            else:
-                padp = tuple(K[i] - 1 - p3[i] for i in range(3))
-                used = Cin - ctx.dead_tail if (ctx.dead_tail and stride == 1 and not _NO_DEAD_TAIL) else None
-                ia = ctx.in_act if (stride == 1 and nd == 3) else None
-                dx5 = conv_raw(dy5, wd, None, Cin, K, 1, padp, stride, 0, 0, 0.0, in_sp, dy_amax, cout_used=used,
-                               act_src=x5 if ia else None, act_slope=ia[1] if ia else 0.0)
-                if ia and _LAST_ACTGRAD[0]:
-                    dx5._df_premasked = (dx5._version, dx5.data_ptr())
-            dx = dx5 if nd == 3 else dx5.squeeze(2)
-        if dskip is not None:       # not folded in above (x needs no conv-path gradient, or non-reflect dgrad)
-            dx = dskip if dx is None else dx + dskip
-        defer = (_DEFER["on"] and owner is not None and getattr(owner, "weight", None) is not None
-                 and owner.weight.grad is not None and owner.weight.grad.is_contiguous())
-        # bias gradient target: straight into bias.grad when deferring, else a fresh buffer (returned to autograd);
-        # it rides along with the wgrad call (which reads dY anyway) when there is one
-        db_buf = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            bg = getattr(owner, "bias", None).grad if defer and getattr(owner, "bias", None) is not None else None
-            if bg is not None and bg.is_contiguous():
-                db_buf = bg
-            else:
-                db = db_buf = zeros(Cout, dy5.device)
-        if ctx.needs_input_grad[1]:
-            ptag = getattr(dy, "_df_pmax", None) if not act else None     # per-plane maxima of dY (InstanceNorm backward)
-            dy_pmax = ptag[0] if (ptag is not None and ptag[1] == dy._version and ptag[2] == dy.data_ptr()
-                                  and dy.is_contiguous() and not _NO_CH_SCALE) else None
-            parts = getattr(ctx, "x_parts", None)
-            if defer:
-                T = K[0] * K[1] * K[2]
-                conv_wgrad_raw(x5, dy5, K, stride, p3, pad_mode,
-                               out=_deferred_buffer(owner, T, Cin, Cout, tuple(weight.shape), dy5.device),
-                               x_amax=ctx.x_amax, dy_amax=dy_amax, db=db_buf, dy_pmax=dy_pmax, parts=parts)
-            else:
-                dwt = conv_wgrad_raw(x5, dy5, K, stride, p3, pad_mode, x_amax=ctx.x_amax, dy_amax=dy_amax, db=db_buf,
-                                     dy_pmax=dy_pmax, parts=parts)
-                dw = weight_unpack(dwt, tuple(weight.shape))
-        elif db_buf is not None:
-            bias_grad(dy5, db_buf)                                                           # accumulates
-        return dx, dw, db
+                check(lib().dfmir_reflect_pad2d_bwd(_p(dxp), _p(dx5), x5.shape[0] * Cin, in_sp[1], in_sp[2],
+                                                    p3[1], _st()))
+        else:
+            padp = tuple(K[i] - 1 - p3[i] for i in range(3))
+            used = Cin - ctx.dead_tail if (ctx.dead_tail and stride == 1 and not _NO_DEAD_TAIL) else None
+            ia = ctx.in_act if (stride == 1 and nd == 3) else None
+            dx5 = conv_raw(dy5, wd, None, Cin, K, 1, padp, stride, 0, 0, 0.0, in_sp, dy_amax, cout_used=used,
+                           act_src=x5 if ia else None, act_slope=ia[1] if ia else 0.0)
+            if ia and _LAST_ACTGRAD[0]:
+                dx5._df_premasked = (dx5._version, dx5.data_ptr())
+        dx = dx5 if nd == 3 else dx5.squeeze(2)
+    if dskip is not None:       # not folded in above (x needs no conv-path gradient, or non-reflect dgrad)
+        dx = dskip if dx is None else dx + dskip
+    defer = (_DEFER["on"] and owner is not None and getattr(owner, "weight", None) is not None
+             and owner.weight.grad is not None and owner.weight.grad.is_contiguous())
+    # bias gradient target: straight into bias.grad when deferring, else a fresh buffer (returned to autograd);
+    # it rides along with the wgrad call (which reads dY anyway) when there is one
+    db_buf = None
+    if ctx.has_bias and ctx.needs_input_grad[2]:
+        bg = getattr(owner, "bias", None).grad if defer and getattr(owner, "bias", None) is not None else None
+        if bg is not None and bg.is_contiguous():
+            db_buf = bg
+        else:
+            db = db_buf = zeros(Cout, dy5.device)
+    if ctx.needs_input_grad[1]:
+        ptag = getattr(dy, "_df_pmax", None) if not act else None     # per-plane maxima of dY (InstanceNorm backward)
+        dy_pmax = ptag[0] if (ptag is not None and ptag[1] == dy._version and ptag[2] == dy.data_ptr()
+                              and dy.is_contiguous() and not _NO_CH_SCALE) else None
+        parts = getattr(ctx, "x_parts", None)
+        if defer:
+            T = K[0] * K[1] * K[2]
+            conv_wgrad_raw(x5, dy5, K, stride, p3, pad_mode,
+                           out=_deferred_buffer(owner, T, Cin, Cout, tuple(weight.shape), dy5.device),
+                           x_amax=ctx.x_amax, dy_amax=dy_amax, db=db_buf, dy_pmax=dy_pmax, parts=parts)
+        else:
+            dwt = conv_wgrad_raw(x5, dy5, K, stride, p3, pad_mode, x_amax=ctx.x_amax, dy_amax=dy_amax, db=db_buf,
+                                 dy_pmax=dy_pmax, parts=parts)
+            dw = weight_unpack(dwt, tuple(weight.shape))
+    elif db_buf is not None:
+        bias_grad(dy5, db_buf)                                                           # accumulates
+    return dx, dw, db
 
 
 _LAST_CONV_AMAX = [None]
@@ -1391,18 +1411,16 @@ class UpCatConv3dFn(Function):
         pb = _probe64(b) if pb is None else pb
         y = torch.empty((N, Cout, 2 * D, 2 * H, 2 * W), device=a.device, dtype=torch.float32)
         g = DfConvGeom(N, Cb, Cout, 2 * D, 2 * H, 2 * W, 2 * D, 2 * H, 2 * W, 3, 3, 3, 1, 1, 1, 1, 1, 0, act, float(slope))
-        fused_ = Cb <= 2 and act in (0, 1) and not _NO_UPSKIP2
-        ws_up, split_up = _ws_cached(w_tcc, ("up", Ca, Cout, Cb if fused_ else 0), lib().dfmir_conv3d_up_ws_floats(Ca, Cout),
-                                     a.device, job=(1, Ca, Cout, 0, Ca + Cb, 0, Cb if fused_ else 0))
-        ws_sk, split_sk = (None, False) if (Cb <= 2 and act in (0, 1) and not _NO_UPSKIP2) else \
+        fused = Cb <= 2 and act in (0, 1) and not _NO_UPSKIP2
+        ws_up, split_up = _ws_cached(w_tcc, ("up", Ca, Cout, Cb if fused else 0), lib().dfmir_conv3d_up_ws_floats(Ca, Cout),
+                                     a.device, job=(1, Ca, Cout, 0, Ca + Cb, 0, Cb if fused else 0))
+        ws_sk, split_sk = (None, False) if fused else \
             _ws_cached(w_tcc, ("skip", Ca, Cb, Cout), lib().dfmir_conv3d_split_ws_floats(Cb, Cout), a.device,
                        job=(0, Cb, Cout, lib().dfmir_conv3d_split_is_pair(Cout), Ca + Cb, Ca, 0))
         slot = amax_slot(a.device, PROBE_SLOTS)
         if _PROBE_AUDIT["on"]:
             _audit_probe(a, pa, "upcat conv a %s" % (tuple(a.shape),))
             _audit_probe(b, pb, "upcat conv b %s" % (tuple(b.shape),))
-
-        fused = Cb <= 2 and act in (0, 1) and not _NO_UPSKIP2
 
         def launch_fused():
             check(lib().dfmir_conv3d_up_skip2_fwd(_p(a), _p(pa), pa.numel(), _p(b), _p(pb), pb.numel(), Cb,
@@ -1419,7 +1437,7 @@ class UpCatConv3dFn(Function):
 
         prof = _CONV_PROFILER[0]
         vox = 8.0 * N * D * H * W
-        size = "L" if Cout > 64 else ("M" if Cout > 32 else ("S" if Cout > 4 else "small"))
+        size = _size_label(Cout)
         if fused:
             if prof is None:
                 launch_fused()
@@ -1502,7 +1520,7 @@ class UpCatConv3dFn(Function):
             if prof is None:
                 launch()
             else:
-                size = "L" if Ca > 64 else ("M" if Ca > 32 else ("S" if Ca > 4 else "small"))
+                size = _size_label(Ca)
                 prof("conv3dup_" + size, 2.0 * 8.0 * N * D * H * W * Cout * Ca * 27, launch)     # reference-equivalent FLOPs
             tag_amax(da, slot)
             if ia:
