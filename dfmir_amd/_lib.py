@@ -141,6 +141,10 @@ _SIGS = {
     "dfmir_nmi_ws_floats": [c_longlong, c_int],
     "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
     "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],
+    "dfmir_mind_ws_floats": [c_int] * 8,
+    "dfmir_mind_desc": [P] + [c_int] * 7 + [P, P, P],
+    "dfmir_mind_fwd": [P, P, P] + [c_int] * 7 + [P, P, P],
+    "dfmir_mind_bwd": [P, P, P] + [c_int] * 7 + [P, P, P, P, P, P],
     "dfmir_warp_dice_ws_floats": [c_int] * 6,
     "dfmir_warp_dice_fwd": [c_int, P, P, P, P] + [c_int] * 6 + [P, P, P, P, P],
     "dfmir_warp_dice_bwd": [c_int, P, P, P, P] + [c_int] * 5 + [P, P, P, P],
@@ -206,6 +210,7 @@ def lib():
         h.dfmir_conv3d_upwgrad_ws_floats.restype = c_longlong
         h.dfmir_flow_smooth_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
+        h.dfmir_mind_ws_floats.restype = c_longlong
         h.dfmir_warp_dice_ws_floats.restype = c_longlong
         h.dfmir_label_hausdorff_ws_bytes.restype = c_longlong
         h.dfmir_dice_ws_floats.restype = c_longlong

@@ -1,7 +1,7 @@
 """Registration losses with the reference's interfaces: `smooothing_loss`
 (models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `MSE` /
 `Dice` / `Grad` (models/voxelmorph/torchvoxelmorph/losses.py:7-117; also reachable as `dfmir_amd.voxelmorph.losses`), each
-one fused HIP reduction (dfmir_amd.ops); `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
+one fused HIP reduction (dfmir_amd.ops); `MIND_Loss` (build-defined) is the MIND-SSC multi-modal similarity; `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
 (util/loss_metrics.py:105-132) and `LabelHausdorff` (build-defined) are evaluation metrics on the HIP distance transform."""
 import numpy as np
 import torch
@@ -111,6 +111,40 @@ class NMI_Loss(_Loss):
                             mask=mask if self.crop_background else None)
 
     forward = __call__
+
+
+class MIND_Loss(_Loss):
+    """Build-defined (the reference ships no MIND): the MIND-SSC similarity of Heinrich et al. (MICCAI 2013), a local,
+    contrast-invariant self-similarity descriptor compared voxel-wise with an L2 loss -- the multi-modal companion of the
+    mono-modal NCC_Loss and the global NMI_Loss.  `MIND_Loss(radius, dilation)(prediction, target, mask=None)`.
+
+    Inputs [B,1,*vol], fp32, 2-D or 3-D (nd axes); radius r and dilation d in 1..4; clamp = replicate the border per axis
+    and per sample.  Neighbours n = 2 * axis + (0: -d, 1: +d) over the axes in the order (z,) y, x; channels = the pairs
+    p < q of neighbours on different axes, in lexicographic order: C = 12 in 3-D -- (0,2) (0,3) (0,4) (0,5) (1,2) (1,3)
+    (1,4) (1,5) (2,4) (2,5) (3,4) (3,5) -- and C = 4 in 2-D -- (0,2) (0,3) (1,2) (1,3) of -y, +y, -x, +x.  Per sample:
+
+        s_k(y) = (I(clamp(y + p_k)) - I(clamp(y + q_k)))^2
+        D_k(x) = (2r+1)^-nd * sum over t in [-r,r]^nd of s_k(clamp(x + t))    (x + t is clamped first, the shifts clamp again)
+        m_k = D_k - min_j D_j,   V = mean_k m_k,   mu = mean of V over the whole tensor (batch included)
+        Vc = min(max(V, 0.001 mu), 1000 mu),   M_k = exp(-m_k / Vc)  in (0, 1]
+
+    A volume of one plane [B,1,1,H,W] keeps the 3-D definition with 12 channels (the z shifts clamp onto the plane).
+    Loss: the mean over (B, C, voxels) of (M_pred - M_target)^2; with `mask` (anything that broadcasts to [B,1,*vol], float
+    weights) sum mask * mean_k (.)^2 / sum mask, and 0 (a device scalar, no host sync) for an empty mask.  Gradients go to
+    both images.  Three build-defined points: mu is a constant in the backward (both clamp bounds are detached); min sends
+    its gradient to the FIRST minimal channel in the order above; a constant image has mu = 0, the formula is 0 / 0 there
+    and the loss is NaN (no epsilon is added).  Where V is clamped nothing flows through V; everything else is the exact
+    chain rule.  Bit-identical from run to run; capturable (ops.mind_loss; dfmir_amd/csrc/mind.hip)."""
+
+    def __init__(self, radius=2, dilation=2, name='mind', *args, **kwargs):
+        super().__init__(name=name)
+        for what, v in (("radius", radius), ("dilation", dilation)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 4:
+                raise ValueError("MIND_Loss: %s must be an integer in 1..4, got %r" % (what, v))
+        self.radius, self.dilation = int(radius), int(dilation)
+
+    def forward(self, prediction, target, mask=None, *args, **kwargs):
+        return ops.mind_loss(prediction, target, self.radius, self.dilation, mask=mask)
 
 
 class NCC(object):

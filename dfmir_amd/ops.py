@@ -2537,6 +2537,94 @@ def nmi_loss(y_true, y_pred, centers, sigma_ratio=0.5, max_clip=1.0, mask=None):
     return NMIFn.apply(y_true, y_pred, c, preterm, float(max_clip), mask)
 
 
+def _mind_geom(I, radius, dilation, what):
+    """(nd, B, D, H, W, C) of a MIND input after the argument checks (ValueError: nothing is launched)."""
+    for name, v in (("radius", radius), ("dilation", dilation)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 4:
+            raise ValueError("%s: %s must be an integer in 1..4, got %r" % (what, name, v))
+    if I.dim() not in (4, 5):
+        raise ValueError("%s: expects [B,1,H,W] or [B,1,D,H,W] tensors, got %d dims" % (what, I.dim()))
+    if I.shape[1] != 1:
+        raise ValueError("%s: expects single-channel images, got %d channels" % (what, I.shape[1]))
+    if I.numel() == 0:
+        raise ValueError("%s: empty tensor %s" % (what, tuple(I.shape)))
+    nd = I.dim() - 2
+    D, H, W = I.shape[2:] if nd == 3 else (1,) + tuple(I.shape[2:])
+    return nd, int(I.shape[0]), int(D), int(H), int(W), 12 if nd == 3 else 4
+
+
+def _mind_ws(geom, r, d, which, device):
+    nd, B, D, H, W, _ = geom
+    n = int(lib().dfmir_mind_ws_floats(nd, B, D, H, W, r, d, which))
+    if n < 0:
+        raise DfmirHipError("MIND: unsupported shape %s" % ((B, D, H, W),))
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def mind_descriptor(I, radius=2, dilation=2):
+    """The MIND-SSC descriptor M [B,C,*vol] of I [B,1,*vol] (C = 12 in 3-D, 4 in 2-D; the definition and the channel order:
+    losses.MIND_Loss).  No gradient: for inspection and tests."""
+    geom = _mind_geom(I, radius, dilation, "mind_descriptor")
+    _need(I)
+    if I.dtype != torch.float32:
+        raise DfmirHipError("MIND: fp32 tensors only (got %s)" % I.dtype)
+    I = _c(I.detach())
+    nd, B, D, H, W, C = geom
+    ws = _mind_ws(geom, int(radius), int(dilation), 0, I.device)
+    out = torch.empty((B, C) + tuple(I.shape[2:]), device=I.device, dtype=torch.float32)
+    check(lib().dfmir_mind_desc(_p(I), nd, B, D, H, W, int(radius), int(dilation), _p(ws), _p(out), _st()))
+    return out
+
+
+class MINDFn(Function):
+    """L2 loss of the MIND-SSC descriptors of two images (dfmir_mind_fwd / _bwd); gradients to both.  The workspace that
+    lives until the backward holds m = D - min D of both images (C floats per voxel and image)."""
+
+    @staticmethod
+    def forward(ctx, a, b, radius, dilation, mask=None):
+        a, b = _c(a), _c(b)
+        geom = _mind_geom(a, radius, dilation, "mind_loss")
+        nd, B, D, H, W, _ = geom
+        ws = _mind_ws(geom, radius, dilation, 0, a.device)
+        out = torch.empty((), device=a.device, dtype=torch.float32)
+        check(lib().dfmir_mind_fwd(_p(a), _p(b), _p(mask), nd, B, D, H, W, radius, dilation, _p(ws), _p(out), _st()))
+        ctx.save_for_backward(a, b, mask, ws)
+        ctx.meta = (geom, radius, dilation)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, b, mask, ws = ctx.saved_tensors
+        geom, radius, dilation = ctx.meta
+        nd, B, D, H, W, _ = geom
+        g = _c(g)
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            tmp = _mind_ws(geom, radius, dilation, 1, a.device)
+            check(lib().dfmir_mind_bwd(_p(a), _p(b), _p(mask), nd, B, D, H, W, radius, dilation, _p(ws), _p(tmp), _p(g),
+                                       _p(da), _p(db), _st()))
+        return da, db, None, None, None
+
+
+def mind_loss(a, b, radius=2, dilation=2, mask=None):
+    """MIND-SSC loss of two single-channel images [B,1,*vol] (2-D or 3-D; the definition: losses.MIND_Loss): the mean over
+    (B, C, voxels) of (M_a - M_b)^2, or with `mask` (anything that broadcasts to [B,1,*vol], used as float weights)
+    sum mask * mean_k (M_a - M_b)^2 / sum mask -- 0 for an empty mask, as a device scalar without a host sync.  Gradients go
+    to both images.  ValueError on a bad radius / dilation (1..4 each), rank or channel count; a CPU tensor raises the
+    usual "no CPU fallback" error."""
+    _mind_geom(a, radius, dilation, "mind_loss")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("mind_loss: the two images differ in shape (%s, %s)" % (tuple(a.shape), tuple(b.shape)))
+    _need(a, b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise DfmirHipError("MIND: fp32 tensors only (got %s, %s)" % (a.dtype, b.dtype))
+    if mask is not None:
+        mask = mask.to(device=a.device, dtype=torch.float32).expand_as(a).contiguous()
+    return MINDFn.apply(a, b, int(radius), int(dilation), mask)
+
+
 def as_label_map(t):
     """An integer label map as the contiguous uint8 tensor the Dice kernels read, on the tensor's own device: any integer
     dtype, bool, or a float tensor with integral values; every value must lie in [0, 255].  The range check reads the

@@ -6,7 +6,7 @@ reference does ship: `VxmDense(ndims=3, int_steps=7, bidir=True)`
 (models/voxelmorph/torchvoxelmorph/networks.py:1028-1145) + `NCC_Loss(kernel_var=[9,9,9], 'mean')`
 (util/losses.py:132-261; ncc_kernel='gaussian' swaps in its Gaussian window) + lambda * `Grad_Loss(dim=3, 'l2')` (util/losses.py:81-130), Adam(2e-4,
 (0.5, 0.999)).  Oracle counterpart: oracle/dfmir_oracle.py::Registration3DStep.  similarity='nmi' swaps the NCC term for
-`NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity.  seg_labels / seg_weight add the segmentation
+`NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity; similarity='mind' for the build-defined MIND-SSC loss (`MIND_Loss`).  seg_labels / seg_weight add the segmentation
 term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map against the moving one warped by the flow
 (`losses.LabelDice`).
 """
@@ -15,7 +15,7 @@ import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import Grad_Loss, LabelDice, NCC_Loss, NMI_Loss
+from .losses import Grad_Loss, LabelDice, MIND_Loss, NCC_Loss, NMI_Loss
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
@@ -23,12 +23,14 @@ from .voxelmorph import VxmDense
 class Registration3DModel(object):
     def __init__(self, shape, features=None, lam=1.0, lr=2e-4, betas=(0.5, 0.999), win=9, device="cuda",
                  capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
-                 seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3):
+                 seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3, mind_radius=2, mind_dilation=2):
         """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window, or with ncc_kernel='gaussian' the Gaussian window of
         sigma = ncc_sigma, whose 3-D form is build-defined: see NCC_Loss; `win` is then unused) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
         both images to [0, nmi_max_clip] first, as the reference does: data in [-1, 1] loses its negative half (nothing is
-        rescaled here).  The loss key is then 'nmi' instead of 'ncc'.
+        rescaled here).  The loss key is then 'nmi' instead of 'ncc'.  similarity='mind': MIND_Loss(mind_radius,
+        mind_dilation)(warped real_A, real_B), the local multi-modal similarity (build-defined: see MIND_Loss), for 2-D and
+        3-D shapes; the loss key is 'mind'.
         seg_labels (a list of 1..64 label values in [0, 255]; None = no segmentation term): `set_input` then also takes
         data['A_seg'] and data['B_seg'], integer label maps [B,1,*shape] of the moving and the fixed image, and the step
         adds seg_weight * LabelDice(seg_labels).loss(B_seg, A_seg, flow); `get_current_losses()` gains 'dice'.
@@ -41,14 +43,16 @@ class Registration3DModel(object):
         self.netR = VxmDense(tuple(shape), features, int_steps=7, bidir=True).to(self.device)
         self.netR.skip_unused_target = True      # the step reads (y_source, flow) only
         self.optimizer_R = FlatAdam(self.netR.parameters(), lr=lr, betas=betas)
-        if similarity not in ('ncc', 'nmi'):
-            raise ValueError("similarity must be 'ncc' or 'nmi', got %r" % (similarity,))
+        if similarity not in ('ncc', 'nmi', 'mind'):
+            raise ValueError("similarity must be 'ncc', 'nmi' or 'mind', got %r" % (similarity,))
         if ncc_kernel not in ('mean', 'gaussian'):
             raise ValueError("ncc_kernel must be 'mean' or 'gaussian', got %r" % (ncc_kernel,))
         self.similarity = similarity
         if similarity == 'ncc':
             kernel_var = [win if ncc_kernel == 'mean' else ncc_sigma] * len(shape)
             self.criterionNCC = NCC_Loss(self.device, kernel_var=kernel_var, kernel_type=ncc_kernel)
+        elif similarity == 'mind':
+            self.criterionMIND = MIND_Loss(radius=mind_radius, dilation=mind_dilation)
         else:
             bins = np.linspace(0.0, nmi_max_clip, 32) if nmi_bins is None else nmi_bins
             self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)
@@ -89,6 +93,8 @@ class Registration3DModel(object):
         self.optimizer_R.zero_grad()
         if self.similarity == 'ncc':
             self.loss_ncc = loss_sim = self.criterionNCC(y_source, self.real_B)
+        elif self.similarity == 'mind':
+            self.loss_mind = loss_sim = self.criterionMIND(y_source, self.real_B)
         else:
             self.loss_nmi = loss_sim = self.criterionNMI(self.real_B, y_source)
         self.loss_grad = self.criterionGrad(flow)

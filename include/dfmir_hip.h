@@ -568,6 +568,32 @@ int dfmir_nmi_fwd(const float* y_true, const float* y_pred, const float* mask, c
 int dfmir_nmi_bwd(const float* y_true, const float* y_pred, const float* mask, const float* centers, int nb,
                   float preterm, float max_clip, long long n, const float* ws, const float* gout, float* d_true,
                   float* d_pred, void* stream);
+/* MIND-SSC (Heinrich et al., MICCAI 2013), build-defined: a local, contrast-invariant self-similarity descriptor of a
+ * single-channel image and the L2 loss of two descriptors.  I: [B][D][H][W] fp32, nd = 2 (D = 1) or 3; radius r and
+ * dilation d in 1..4; every axis >= 1 (also shorter than r + d); clamp = replicate the border per axis and sample.
+ * Neighbours n = 2 * axis + (0: -d, 1: +d) over the nd axes in the order (z,) y, x; channels = the pairs p < q of neighbours
+ * on different axes in lexicographic order: C = 12 in 3-D ((0,2) (0,3) (0,4) (0,5) (1,2) (1,3) (1,4) (1,5) (2,4) (2,5)
+ * (3,4) (3,5)), C = 4 in 2-D ((0,2) (0,3) (1,2) (1,3) of -y, +y, -x, +x).  nd = 3 with D = 1 keeps the 12 channels.
+ *   s_k(y) = (I(clamp(y + p_k)) - I(clamp(y + q_k)))^2
+ *   D_k(x) = (2r+1)^-nd sum_{t in [-r,r]^nd} s_k(clamp(x + t))        m_k = D_k - min_j D_j        V = mean_k m_k
+ *   mu = mean of V over the whole tensor (batch included)             Vc = min(max(V, 0.001 mu), 1000 mu)
+ *   M_k = exp(-m_k / Vc)     (a constant image has mu = 0 and gives NaN: no epsilon is added)
+ * dfmir_mind_desc: out[B][C][D][H][W] = M.  dfmir_mind_fwd: out[0] = mean over (B, C, voxels) of (Ma - Mb)^2, or with
+ * mask ([B][D][H][W] float weights) sum mask * mean_k (Ma_k - Mb_k)^2 / sum mask; an empty mask gives 0.
+ * dfmir_mind_bwd: da / db (either may be NULL) = gout[0] * dL/d(a / b): mu is a constant (both clamp bounds detached),
+ * min sends its gradient to the FIRST minimal channel, nothing flows through V where it is clamped; otherwise the exact
+ * chain rule, in gather form.  No atomics: every sum goes through per-workgroup slots added in index order, so loss and
+ * gradients are bit-identical from run to run.  Nothing syncs, allocates or keeps state; mu stays on the device.
+ * ws: dfmir_mind_ws_floats(..., 0) floats, 8-byte aligned, need not be zeroed; it holds m of both images (C floats per
+ * voxel and image) -- keep it between fwd and bwd.  tmp: dfmir_mind_ws_floats(..., 1) floats of backward scratch.
+ * The size query returns -1 for arguments the other entry points refuse. */
+long long dfmir_mind_ws_floats(int nd, int B, int D, int H, int W, int radius, int dilation, int which);
+int dfmir_mind_desc(const float* I, int nd, int B, int D, int H, int W, int radius, int dilation, float* ws, float* out,
+                    void* stream);
+int dfmir_mind_fwd(const float* a, const float* b, const float* mask, int nd, int B, int D, int H, int W, int radius,
+                   int dilation, float* ws, float* out, void* stream);
+int dfmir_mind_bwd(const float* a, const float* b, const float* mask, int nd, int B, int D, int H, int W, int radius,
+                   int dilation, const float* ws, float* tmp, const float* gout, float* da, float* db, void* stream);
 /* Label-map Dice under a flow: vxm `Dice().loss(one_hot(fix)[:, labels], SpatialTransformer(one_hot(mov)[:, labels], flow))`
  * (models/voxelmorph/torchvoxelmorph/losses.py:79-90 after layers.py:36-48; mode 1 = the nearest-neighbour label warp of
  * test.py:80-81, forward only) without the one-hot tensors.  nd = 2 ([B,1,H,W], D = 1) or 3.  mov / fix: 8-bit label maps
