@@ -36,6 +36,8 @@ _SIGS = {
     "dfmir_conv3x3_reflect_ring_ok": [_GP],
     "dfmir_conv3x3_reflect_ring_len": [_GP],
     "dfmir_conv3x3_reflect_ring": [_GP, P, P, P, c_int, P, P, P],
+    "dfmir_conv3x3_bwd_pair_ok": [_GP, _GP],
+    "dfmir_conv3x3_bwd_pair": [_GP, _GP, P, P, c_int, P, P, P, P, c_int, P, P, P, c_int, P, P, POINTER(c_int), P],
     "dfmir_conv_fwd_scaled": [_GP, P, P, c_int, P, P, P, P],
     "dfmir_conv_wgrad_scaled": [_GP, P, P, c_int, P, P, c_int, P, P, P],
     "dfmir_conv_wgrad_scaled_ch": [_GP, P, P, c_int, P, P, c_int, P, P, P, P],

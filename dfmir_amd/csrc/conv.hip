@@ -1047,6 +1047,34 @@ extern "C" int dfmir_conv3x3_reflect_ring(const DfConvGeom* g, const float* dy, 
   if (rc) return df_set_error(rc, __FILE__, __LINE__);
   return 0;
 }
+int df_conv3x3_bwd_pair_ok(const DfConvGeom* gd, const DfConvGeom* gw);
+bool df_conv3x3_bwd_pair_try(const DfConvGeom* gd, const DfConvGeom* gw, const float* dy, const float* dy_amax, int dy_n,
+                             const float* dy_pmax, const float* wd_packed, const float* res, const float* ring, int ring_rl,
+                             float* dx, const float* x, const float* x_amax, int x_n, float* dw_tcc, float* db,
+                             hipStream_t st, int* rc);
+extern "C" int dfmir_conv3x3_bwd_pair_ok(const DfConvGeom* gd, const DfConvGeom* gw) {
+  return (gd && gw && check_geom(gd) == 0 && check_geom(gw) == 0 && !use_generic_only()) ? df_conv3x3_bwd_pair_ok(gd, gw) : 0;
+}
+extern "C" int dfmir_conv3x3_bwd_pair(const DfConvGeom* gd, const DfConvGeom* gw, const float* dy, const float* dy_amax,
+                                      int dy_amax_n, const float* dy_pmax, const float* wd_packed, const float* res,
+                                      const float* ring, int ring_len, float* dx, const float* x, const float* x_amax,
+                                      int x_amax_n, float* dw_tcc, float* db, int* paired, void* stream) {
+  DF_ARG_CHECK(gd && gw && check_geom(gd) == 0 && check_geom(gw) == 0 && dy && wd_packed && dx && x && dw_tcc && paired);
+  DF_ARG_CHECK(gd->N == gw->N && gd->Cin == gw->Cout && gd->Cout == gw->Cin && gw->dil == 1 && gw->Cin < (1 << 19));
+  DF_ARG_CHECK(!ring || (ring_len >= (gd->Ho > gd->Wo ? gd->Ho : gd->Wo) + 2 && gd->Ho >= 4 && gd->Wo >= 4));
+  *paired = 0;
+  int rc = 0;
+  if (!use_generic_only() && df_conv3x3_bwd_pair_try(gd, gw, dy, dy_amax, dy_amax_n, dy_pmax, wd_packed, res, ring, ring_len,
+                                                     dx, x, x_amax, x_amax_n, dw_tcc, db, (hipStream_t)stream, &rc)) {
+    *paired = rc == 0 ? 1 : 0;
+    return rc;
+  }
+  // either side would not have chosen the pair's kernels: the two launches as they are issued one by one
+  rc = (res || ring) ? dfmir_conv3x3_fwd_scaled_res(gd, dy, dy_amax, dy_amax_n, wd_packed, nullptr, res, ring, ring_len, dx, stream)
+                     : conv_fwd_impl(gd, dy, dy_amax, dy_amax_n, wd_packed, nullptr, dx, stream);
+  if (rc) return rc;
+  return conv_wgrad_impl(gw, x, x_amax, x_amax_n, dy, dy_amax, dy_amax_n, dw_tcc, db, stream, dy_pmax);
+}
 extern "C" int dfmir_weight_pack_batch(const DfPackJob* jobs_host, int njobs, void* table_dev, int upload,
                                        void* stream) {
   DF_ARG_CHECK(jobs_host && table_dev && njobs > 0 && njobs <= 65535);

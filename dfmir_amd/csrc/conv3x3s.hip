@@ -740,7 +740,7 @@ __device__ unsigned g_cs_wg[2048 * 6];
 extern "C" int dfmir_cs_wg_dump(unsigned* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cs_wg), sizeof(unsigned) * 2048 * 6);
 }
-#define WGT(slot_) { if (threadIdx.x == 0 && blockIdx.x < 2048 && blockIdx.y == 0) g_cs_wg[blockIdx.x * 6 + (slot_)] = (unsigned)wall_clock64(); }
+#define WGT(slot_) { if (threadIdx.x == 0 && bix < 2048 && biy == 0) g_cs_wg[bix * 6 + (slot_)] = (unsigned)wall_clock64(); }
 #else
 #define WGT(slot_)
 #define TRC(slot_)
@@ -748,309 +748,27 @@ extern "C" int dfmir_cs_wg_dump(unsigned* out) {
 // <RR, CPG, TH>: <*, 64, 8> = 128 output channels per workgroup on an 8 x 32 tile (RR: row-reuse compute phase);
 // <true, 32, 16> = 64 output channels on a 16 x 32 tile (the 128->64 / 64<-128 layers at 256^2): a wave still owns
 // 32 couts x 4 tile rows, a group its 32 couts over all 16 rows.
+// LDS of the kernel: Wg[2][WUG] | Xs[2][NSP * 2 * XP] | bs[2 * CPG].  The kernel body (conv3x3s_cs_body.inc) only names the three
+// arrays: the stand-alone kernel declares them as static __shared__ arrays, conv3x3_bwd_pair_k -- which includes this body next
+// to the weight gradient's -- carves them out of ONE raw arena by these offsets (two sets of static arrays reachable from one
+// kernel would be allocated side by side: 120 KB + 131 KB).
+template <int CPG, int TH>
+struct CsLds {
+  static constexpr int XP = (TH == 8 ? CS_XP : 640);
+  static constexpr int WUG = 2 * 9 * 2 * CPG;             // 16-B units of one group's weight chunk (16 channels)
+  static constexpr int XSU = 2 * 2 * XP;                  // 16-B units of one patch buffer
+  static constexpr int XS_OFF = 2 * WUG * 16, BS_OFF = XS_OFF + 2 * XSU * 16, BYTES = BS_OFF + 2 * CPG * 4;
+};
 template <bool RR, int CPG, int TH>
 __global__ __launch_bounds__(512, 1) void conv3x3_split_cs_k(const float* __restrict__ x, const u32x4* __restrict__ ws,
                                                              const float* __restrict__ bias, float* __restrict__ y,
                                                              ConvCsP k, SplitScale sc) {
-  static_assert((CPG == 64 && TH == 8) || (RR && CPG == 32 && TH == 16), "tile forms");
-  constexpr int CS_TH = TH;
-  constexpr int NSP = 2, XP = (TH == 8 ? CS_XP : 640), NPOS = (CS_TH + 2) * CS_PW;
-  constexpr int WUG = NSP * 9 * 2 * CPG;                  // 16-B units of one group's weight chunk (16 channels)
-  constexpr int NW = (WUG + 255) / 256;                   // 9 (CPG 64) / 5 (CPG 32, the last one half used) per thread
-  constexpr int NS = (NPOS + 255) / 256;                  // 2 / 3 patch positions per thread
-  __shared__ __attribute__((aligned(16))) u32x4 Wg[2][WUG];
-  __shared__ __attribute__((aligned(16))) u32x4 Xs[2][NSP * 2 * XP];
+  using L = CsLds<CPG, TH>;
+  __shared__ __attribute__((aligned(16))) u32x4 Wg[2][L::WUG];
+  __shared__ __attribute__((aligned(16))) u32x4 Xs[2][L::XSU];
   __shared__ float bs[2 * CPG];
-#ifdef CS_TRACE
-  __shared__ unsigned trc[8 * 32 * 8];
-  const bool trace_blk = blockIdx.x == 300 && blockIdx.y == 0;
-  const unsigned long long trc_t0 = __builtin_readcyclecounter(), trc_r0 = wall_clock64();
-#endif
-
-  // wave-uniform by construction; readfirstlane tells the compiler so (otherwise every buffer load whose
-  // descriptor depends on the group is wrapped in a waterfall loop)
-  const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-  const int tid = threadIdx.x & 255, lane = tid & 63, wid = tid >> 6;
-  const int l31 = lane & 31, lhi = lane >> 5;
-  const int HWo = k.Ho * k.Wo, HWi = k.Hi * k.Wi;
-  if (k.dephase > 0 && blockIdx.y == 0 && blockIdx.x < 256) {
-    const unsigned long long t0 = wall_clock64();
-    const unsigned wait = blockIdx.x * (unsigned)k.dephase >> 8;
-    while ((unsigned)(wall_clock64() - t0) < wait) __builtin_amdgcn_s_sleep(4);
-  }
-  WGT(0)
-#ifdef CS_TRACE
-  if (threadIdx.x == 0 && blockIdx.x < 2048 && blockIdx.y == 0) {
-    g_cs_wg[blockIdx.x * 6 + 4] = __builtin_amdgcn_s_getreg(63492);       // HW_REG_HW_ID
-    g_cs_wg[blockIdx.x * 6 + 5] = __builtin_amdgcn_s_getreg(63508);       // HW_REG_XCC_ID
-  }
-#endif
-  int bt = blockIdx.x, bm = blockIdx.y;
-  if (k.xcd_pair == 1) { bm = (bt >> 3) & 1; bt = ((bt >> 4) << 3) + (bt & 7); }
-  else if (k.xcd_pair >= 2) {   // XCD e = id & 7 walks a contiguous eighth of the tiles; xcd_pair - 1 cout slices of a tile back to back
-    const int ny = k.xcd_pair - 1, per = (int)(gridDim.x >> 3) / ny, j = bt >> 3;
-    bm = j % ny;
-    bt = (bt & 7) * per + j / ny;
-  }
-  const int tx = bt % k.tiles_x; bt /= k.tiles_x;
-  const int ty = bt % k.tiles_y;
-  const int n = bt / k.tiles_y;
-  const int oy0 = ty * CS_TH, ox0 = tx * CS_TW;
-  const int m0 = bm * (2 * CPG), m0g = m0 + CPG * grp;
-
-  const int ex = scale_exp(reduce_absmax(sc.x_amax, sc.x_n, bs));     // bs: scratch here, bias below
-  __syncthreads();
-  const int ew = (int)sc.w_trailer[1];
-  const float xscale = pow2f(ex), oscale = pow2f(-ex), oscale2 = pow2f(-ew);
-
-  constexpr unsigned OOB = 0x80000000u;
-  // this thread's patch positions: byte offset of channel ch of its 8-channel half, within a 16-channel slab
-  unsigned gvo[NS][8];
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const int pos = tid + 256 * s;
-    int off = -1;
-    if (pos < NPOS) {
-      const int r = pos / CS_PW, c = pos - r * CS_PW;
-      off = halo_offset(oy0 - k.pad + r, ox0 - k.pad + c, k.Hi, k.Wi, k.pad_mode);
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) gvo[s][c] = off < 0 ? OOB : (unsigned)(off + (8 * grp + c) * HWi) * 4u;
-  }
-  if (threadIdx.x < 2 * CPG) bs[threadIdx.x] = (bias && (m0 + (int)threadIdx.x) < k.Cout) ? bias[m0 + threadIdx.x] : 0.f;
-
-  // MFMA operand indices.  Plain form: wave w of a group owns 64 couts x tile rows 2w, 2w+1 (32 pixels each);
-  // row-reuse form: 32 couts (w & 1) x tile rows 4(w >> 1) .. +3
-  int pb[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) pb[j] = lhi * XP + (2 * wid + j) * CS_PW + l31;
-  const int rowgrp = CPG == 64 ? (wid >> 1) : wid;        // this wave's 4 tile rows
-  const int xb = lhi * XP + 4 * rowgrp * CS_PW + l31;
-  const int abase = lhi * CPG + l31 + ((RR && CPG == 64) ? 32 * (wid & 1) : 0);
-
-  f32x16 acc[4];                                          // plain: [cout block i][row j] at 2i + j; row-reuse: [row]
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-  const float* xn = x + (long long)n * k.Cin * HWi;
-  const int chunks8 = (k.Cin + 7) / 8, chunks = (k.Cin + 15) / 16;
-  // weight unit idx = r*64 + co with r = (split*9 + tap)*2 + half; global unit ((2c + half)*NSP*9 + split*9 + tap)*Cout + cout
-  unsigned wb[NW];
-#pragma unroll
-  for (int j = 0; j < NW; ++j) {
-    const int idx = tid + 256 * j;
-    const int co = m0g + (idx % CPG), r = idx / CPG;
-    const int half = r & 1, st = r >> 1;
-    wb[j] = (idx < WUG && co < k.Cout) ? (unsigned)((half * NSP * 9 + st) * k.Cout + co) * 16u : OOB;
-  }
-  const int wunits8 = NSP * 9 * k.Cout;                   // units of one 8-channel chunk in the packed weights
-
-  u32x4 rw[NW];
-  unsigned rx[NS][8];
-#define CS_GLOADW(c_)                                                                            \
-  {                                                                                              \
-    const int q_ = 2 * (c_);                                                                     \
-    const int left_ = chunks8 - q_;                                                              \
-    const __amdgpu_buffer_rsrc_t rw_ = __builtin_amdgcn_make_buffer_rsrc(                        \
-        const_cast<u32x4*>(ws + (long long)q_ * wunits8), 0,                                     \
-        left_ > 0 ? (unsigned)((left_ < 2 ? left_ : 2) * wunits8) * 16u : 0u, 0x00020000);       \
-    _Pragma("unroll") for (int j = 0; j < NW; ++j) rw[j] = __builtin_amdgcn_raw_buffer_load_b128(rw_, wb[j], 0, 0); \
-  }
-#define CS_GLOADX(c_)                                                                            \
-  {                                                                                              \
-    const int c0_ = 16 * (c_);                                                                   \
-    const int left_ = k.Cin - c0_;                                                               \
-    const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc(                        \
-        const_cast<float*>(xn + (long long)c0_ * HWi), 0,                                        \
-        left_ > 0 ? (unsigned)((left_ < 16 ? left_ : 16) * HWi) * 4u : 0u, 0x00020000);          \
-    _Pragma("unroll") for (int s = 0; s < NS; ++s)                                               \
-      _Pragma("unroll") for (int c = 0; c < 8; ++c)                                              \
-        rx[s][c] = __builtin_amdgcn_raw_buffer_load_b32(rx_, gvo[s][c], 0, 0);                   \
-  }
-#define CS_LSTOREW()                                                                             \
-  { _Pragma("unroll") for (int j = 0; j < NW; ++j) if (WUG % 256 == 0 || tid + 256 * j < WUG) Wg[grp][tid + 256 * j] = rw[j]; }
-#define CS_LSTOREX(buf_)                                                                         \
-  {                                                                                              \
-    _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                             \
-      const int pos = tid + 256 * s;                                                             \
-      if (pos < NPOS) {                                                                          \
-        float v[8];                                                                              \
-        _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = __uint_as_float(rx[s][c]);          \
-        CS_NORM_PROBE_OPS()                                                                      \
-        u32x4 sp[NSP];                                                                           \
-        split8_s<NSP>(v, xscale, sp);                                                                      \
-        _Pragma("unroll") for (int q = 0; q < NSP; ++q) Xs[buf_][(q * 2 + grp) * XP + pos] = sp[q]; \
-      }                                                                                          \
-    }                                                                                            \
-  }
-
-  // CS_NORM_PROBE (lab builds, scripts/build_var.sh): what an InstanceNorm + ReLU applied while the patch is staged would
-  // cost the converting wave group -- one fma and one max per value with run-time operands that happen to be the identity
-  // (x * 1 + 0, max with -3e38: results unchanged, instructions real; profiles/r06_cs_norm_probe.txt)
-#ifdef CS_NORM_PROBE
-  const float np_r = fmaf(oscale2, 0.f, 1.f), np_m = oscale2 * 0.f, np_lo = fmaf(oscale2, 0.f, -3.0e38f);
-#define CS_NORM_PROBE_OPS() _Pragma("unroll") for (int c = 0; c < 8; ++c) v[c] = fmaxf(fmaf(v[c], np_r, np_m), np_lo);
-#else
-#define CS_NORM_PROBE_OPS()
-#endif
-  // prologue: X(0) (each group its channel half) and W_A(0) in place; B holds W_B(0), X-half-1(1) in registers
-  CS_GLOADX(0);
-  if (grp == 0) CS_GLOADW(0);
-  CS_LSTOREX(0);
-  if (grp == 0) CS_LSTOREW();
-  if (grp == 1) { CS_GLOADW(0); CS_GLOADX(1); }
-  __syncthreads();
-  WGT(1)
-
-  for (int h = 0; h < 2 * chunks; ++h) {
-    const int c = h >> 1;
-    TRC(0)
-    if ((h & 1) == grp) {
-      // compute chunk c; the prefetch (chunks past the end read zeros) rides behind the MFMAs
-      __builtin_amdgcn_s_setprio(CS_COMPUTE_PRIO);
-      const int qw_ = 2 * (c + 1), lw_ = chunks8 - qw_;
-      const __amdgpu_buffer_rsrc_t rwd = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<u32x4*>(ws + (long long)qw_ * wunits8), 0,
-          lw_ > 0 ? (unsigned)((lw_ < 2 ? lw_ : 2) * wunits8) * 16u : 0u, 0x00020000);
-      const int cx_ = 16 * (c + 1 + grp), lx_ = k.Cin - cx_;
-      const __amdgpu_buffer_rsrc_t rxd = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(xn + (long long)cx_ * HWi), 0,
-          lx_ > 0 ? (unsigned)((lx_ < 16 ? lx_ : 16) * HWi) * 4u : 0u, 0x00020000);
-      if constexpr (RR) cs_mma_chunk_rr<CPG, XP, NW, NS>(Wg[grp], Xs[c & 1], abase, xb, acc, rwd, wb, rw, rxd, gvo, rx);
-      else if constexpr (CPG == 64) cs_mma_chunk(Wg[grp], Xs[c & 1], abase, pb, acc, rwd, wb, rw, rxd, gvo, rx);
-    } else {
-      // store what this group prefetched during its last compute half-step (B at h = 0: the prologue's)
-      __builtin_amdgcn_s_setprio(CS_STORE_PRIO);
-      {
-#ifdef CS_TRACE
-      __builtin_amdgcn_s_waitcnt(0x0f70);                 // vmcnt(0): separates the load wait from the convert + store
-      TRC(3)
-#endif
-#ifdef CS_TRACE
-      CS_LSTOREW();
-      TRC(4)
-      if (c + 1 < chunks) CS_LSTOREX((c + 1) & 1);
-#else
-      if (grp == 0) {
-        if (c + 1 < chunks) { CS_LSTOREW(); CS_LSTOREX((c + 1) & 1); }
-      } else {
-        CS_LSTOREW();
-        if (c + 1 < chunks) CS_LSTOREX((c + 1) & 1);
-      }
-#endif
-      }
-    }
-    TRC(1)
-    // the last half-step is group 1's compute of the last chunk: group 0 has nothing left to stage and goes straight to
-    // its epilogue (its 64 KB of stores leave beside group 1's MFMAs instead of after them: a CU stores at ~12 B/clk)
-#ifndef CS_NO_EARLY_EPI
-    if (h + 1 < 2 * chunks)
-#endif
-    __syncthreads();
-    TRC(2)
-  }
-  WGT(2)
-#ifdef CS_TRACE
-  if (trace_blk) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < 8 * 32 * 8; i += 512) g_cs_trace[i] = trc[i];
-    if (threadIdx.x == 0) {
-      const unsigned long long t1 = __builtin_readcyclecounter(), r1 = wall_clock64();
-      g_cs_trace[2048] = (unsigned)trc_t0; g_cs_trace[2049] = (unsigned)t1;
-      g_cs_trace[2050] = (unsigned)trc_r0; g_cs_trace[2051] = (unsigned)r1;
-    }
-  }
-#endif
-#undef CS_GLOADW
-#undef CS_GLOADX
-#undef CS_LSTOREW
-#undef CS_LSTOREX
-#undef CS_NORM_PROBE_OPS
-
-  // Epilogue.  The MFMAs ran with rows = the 32 pixels of a tile row and columns = 32 output channels, so a lane holds
-  // ONE output channel (l31) and, per accumulator quad q, the 4 consecutive pixels 8q + 4 lhi .. + 3 of each of its 4 tile
-  // rows: 16 16-byte stores per lane instead of 64 4-byte ones (the store tail of a workgroup is bound by the number of
-  // store instructions: 8.9 us of an 84-us workgroup with dword stores).  vec4 needs Wo % 4 == 0 and 16-byte aligned bases.
-  float* yb = y + (long long)n * k.Cout * HWo;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int i = CPG == 32 ? 0 : (RR ? (wid & 1) : (b >> 1));   // 32-cout block of the group's couts
-    const int row = RR ? 4 * rowgrp + b : 2 * wid + (b & 1);
-    const int oy = oy0 + row;
-    const int cc = CPG * grp + i * 32 + l31, co = m0 + cc;
-#ifdef CS_KO_EPI
-    if (oy >= k.Ho || co >= k.Cout || acc[b][0] != 12345.678f) continue;    // knock-out: no epilogue loads / stores
-#else
-    if (oy >= k.Ho || co >= k.Cout) continue;
-#endif
-    const float bv = bs[cc], osc = oscale * oscale2;
-    const long long rowoff = (long long)co * HWo + (long long)oy * k.Wo;
-    const float* rb = k.res ? k.res + (long long)n * k.Cout * HWo + rowoff : nullptr;
-    const float* rg = k.ring ? k.ring + ((long long)n * 4 * k.Cout + co) * k.ring_rl : nullptr;
-    const long long ss = (long long)k.Cout * k.ring_rl;          // strip stride: top, bottom, left, right
-    const bool row_ring = rg != nullptr && (oy == 1 || oy == k.Ho - 2);
-    float4 rv[4];                                                // residual: all loads in flight before the first use
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      rv[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int ox = ox0 + 8 * q + 4 * lhi;
-      if (rb && ox < k.Wo) {
-        if (k.vec4) rv[q] = *reinterpret_cast<const float4*>(rb + ox);
-        else {
-          rv[q].x = rb[ox];
-          if (ox + 1 < k.Wo) rv[q].y = rb[ox + 1];
-          if (ox + 2 < k.Wo) rv[q].z = rb[ox + 2];
-          if (ox + 3 < k.Wo) rv[q].w = rb[ox + 3];
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int ox = ox0 + 8 * q + 4 * lhi;
-      if (ox >= k.Wo) continue;
-      float v[4];
-      const float r4[4] = {rv[q].x, rv[q].y, rv[q].z, rv[q].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float t = acc[b][4 * q + e] * osc + bv;
-        if (k.act == 1) t = t > 0.f ? t : t * k.slope;
-        else if (k.act == 2) t = tanhf(t);
-        v[e] = t + r4[e];
-      }
-      if (rg) {                                                  // the reflection folds frame positions onto ring pixels
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int xx = ox + e;
-          if (xx < k.Wo) {
-            if (row_ring) {
-              if (oy == 1) v[e] += rg[xx + 1] + (xx == 1 ? rg[0] : 0.f) + (xx == k.Wo - 2 ? rg[k.Wo + 1] : 0.f);
-              if (oy == k.Ho - 2) v[e] += rg[ss + xx + 1] + (xx == 1 ? rg[ss] : 0.f) + (xx == k.Wo - 2 ? rg[ss + k.Wo + 1] : 0.f);
-            }
-            if (xx == 1) v[e] += rg[2 * ss + oy + 1];
-            if (xx == k.Wo - 2) v[e] += rg[3 * ss + oy + 1];
-          }
-        }
-      }
-      float* yp = yb + rowoff + ox;
-#ifdef CS_NT_STORE
-      if (k.vec4) __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(yp));
-#else
-      if (k.vec4) *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-#endif
-      else {
-        yp[0] = v[0];
-        if (ox + 1 < k.Wo) yp[1] = v[1];
-        if (ox + 2 < k.Wo) yp[2] = v[2];
-        if (ox + 3 < k.Wo) yp[3] = v[3];
-      }
-    }
-  }
-#ifdef CS_TRACE
-  __builtin_amdgcn_s_waitcnt(0x0f70);       // the stores have left the wave
-#endif
-  WGT(3)
+  const int bix = (int)blockIdx.x, biy = (int)blockIdx.y, gdx = (int)gridDim.x;
+#include "conv3x3s_cs_body.inc"
 }
 
 // (The one-wave-per-SIMD experiment of round 4, conv3x3_split_w1_k, lives in scripts/ubench/conv3x3_split_w1.inc: a lab
@@ -1092,6 +810,49 @@ int df_conv3x3_split_res_ok(const DfConvGeom* g) {
   int th, tx, ty;
   return (df_split_mode() == 2 && split_fwd_geom_ok(g) && cs_plan(g, &th, &tx, &ty)) ? 1 : 0;
 }
+// What df_conv3x3_split_fwd_try launches on the shared-tile kernels: parameters, grid (2-D, or the 1-D XCD-mapped form)
+// and tile form -- 1: <true, 64, 8>, 2: <false, 64, 8>, 3: <true, 32, 16>.  false: the geometry stays on the flat-run kernel.
+struct CsLaunch {
+  ConvCsP kc;
+  dim3 grid;
+  int form;
+};
+static bool cs_setup(const DfConvGeom* g, const float* res, const float* ring, int ring_rl, const float* y, CsLaunch* L) {
+  static DfOptFlag plain_o{"DFMIR_CONV_CS_PLAIN"};
+  const bool rr = !plain_o.get();
+  int th = 0, tlx = 0, tly = 0;
+  if (!cs_plan(g, &th, &tlx, &tly)) return false;
+  // 8 x 32 tiles (128 couts per workgroup) or 16 x 32 tiles (64 couts).  They fit the forward shapes exactly but
+  // waste 37 % on the 66 x 66 padded frames the dgrad of a reflect-padded conv produces (those go through the
+  // zero-padded form + ring kernel instead; what still arrives here unfilled stays on the flat-run kernel below)
+  ConvCsP kc{g->N, g->Cin, g->Cout, g->Hi, g->Wi, g->Ho, g->Wo, g->ph, g->pad_mode, g->act, g->slope, tlx, tly, res,
+             ring, ring_rl, 0, 0, 0};
+  kc.vec4 = (g->Wo % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0) ? 1 : 0;
+  static DfOptInt dephase_o{"DFMIR_CS_DEPHASE", 0};
+  const long long nb = (long long)g->N * tlx * tly;
+  if (nb * ((g->Cout + 127) / 128) >= 512) kc.dephase = dephase_o.get();
+  static DfOptInt xcd_o{"DFMIR_CS_XCD_PAIR", 2};
+  const int xcd_pair = xcd_o.get();
+  if (g->Cout > 64) {
+    dim3 grid((unsigned)nb, (unsigned)((g->Cout + 127) / 128));
+    // the two cout halves of a pixel tile on the same XCD (one L2): measured 83.5 -> 83.0 ms per 2-D step, issued
+    // fraction 0.432 -> 0.438 (DFMIR_CS_XCD_PAIR=0 restores the 2-D grid; =2: contiguous tile runs per XCD)
+    // =2 (default): every XCD walks a contiguous run of tiles (neighbouring tiles share their halo rows in that L2 too):
+    // 83.8 -> 82.3 ms, issued 0.432 -> 0.447
+    if (xcd_pair && grid.y <= 2 && (nb & 7) == 0) {
+      kc.xcd_pair = xcd_pair == 1 ? (grid.y == 2 ? 1 : 0) : (int)grid.y + 1;
+      if (kc.xcd_pair) grid = dim3((unsigned)(grid.y * nb), 1u);
+    }
+    L->grid = grid;
+    L->form = rr ? 1 : 2;
+  } else {
+    if (xcd_pair >= 2 && (nb & 7) == 0) kc.xcd_pair = 2;          // one cout slice: contiguous tile runs per XCD
+    L->grid = dim3((unsigned)nb, 1u);
+    L->form = 3;
+  }
+  L->kc = kc;
+  return true;
+}
 bool df_conv3x3_split_fwd_try(const DfConvGeom* g, const float* x, const float* x_amax, int x_n, const float* w_packed,
                               const float* bias, const float* res, const float* ring, int ring_rl, float* y,
                               hipStream_t st, int* rc) {
@@ -1103,38 +864,17 @@ bool df_conv3x3_split_fwd_try(const DfConvGeom* g, const float* x, const float* 
   Conv3P k{g->N, g->Cin, g->Cout, g->Hi, g->Wi, g->Ho, g->Wo, p, g->pad_mode, g->act, g->slope, 0};
   const u32x4* ws = reinterpret_cast<const u32x4*>(split_section(w_packed, g->Cin, g->Cout));
   const SplitScale sc{x_amax, x_n, split_trailer(w_packed, g->Cin, g->Cout, mode)};
-  static DfOptFlag plain_o{"DFMIR_CONV_CS_PLAIN"};
-  const bool rr = !plain_o.get();
-  int th = 0, tlx = 0, tly = 0;
-  if (mode == 2 && cs_plan(g, &th, &tlx, &tly)) {
-    // 8 x 32 tiles (128 couts per workgroup) or 16 x 32 tiles (64 couts).  They fit the forward shapes exactly but
-    // waste 37 % on the 66 x 66 padded frames the dgrad of a reflect-padded conv produces (those go through the
-    // zero-padded form + ring kernel instead; what still arrives here unfilled stays on the flat-run kernel below)
-    ConvCsP kc{g->N, g->Cin, g->Cout, g->Hi, g->Wi, g->Ho, g->Wo, p, g->pad_mode, g->act, g->slope, tlx, tly, res,
-               ring, ring_rl, 0, 0, 0};
-    kc.vec4 = (g->Wo % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0) ? 1 : 0;
-    static DfOptInt dephase_o{"DFMIR_CS_DEPHASE", 0};
-    const long long nb = (long long)g->N * tlx * tly;
-    if (nb * ((g->Cout + 127) / 128) >= 512) kc.dephase = dephase_o.get();
-    if (g->Cout > 64) {
-      dim3 grid((unsigned)nb, (unsigned)((g->Cout + 127) / 128));
-      // the two cout halves of a pixel tile on the same XCD (one L2): measured 83.5 -> 83.0 ms per 2-D step, issued
-      // fraction 0.432 -> 0.438 (DFMIR_CS_XCD_PAIR=0 restores the 2-D grid; =2: contiguous tile runs per XCD)
-      // =2 (default): every XCD walks a contiguous run of tiles (neighbouring tiles share their halo rows in that L2 too):
-      // 83.8 -> 82.3 ms, issued 0.432 -> 0.447
-      static DfOptInt xcd_o{"DFMIR_CS_XCD_PAIR", 2};
-  const int xcd_pair = xcd_o.get();
-      if (xcd_pair && grid.y <= 2 && (nb & 7) == 0) {
-        kc.xcd_pair = xcd_pair == 1 ? (grid.y == 2 ? 1 : 0) : (int)grid.y + 1;
-        if (kc.xcd_pair) grid = dim3((unsigned)(grid.y * nb), 1u);
-      }
+  CsLaunch cl;
+  if (mode == 2 && cs_setup(g, res, ring, ring_rl, y, &cl)) {
+    const ConvCsP& kc = cl.kc;
+    if (cl.form != 3) {
       // (A persistent form -- one workgroup per CU walking its tiles in one chunk stream, a group's epilogue beside the other
       // group's compute half-step -- was built and measured in round 4: bit-identical, 16 % SLOWER (0.404 vs 0.348 ms at
       // n = 32).  The epilogue is a 33 MB burst of stores issued by all 256 CUs in lockstep, i.e. HBM-write-bound wherever
       // it is placed, and the extra state cost the main loop its registers)
 #ifdef DFMIR_BUILD_W1
       static DfOptFlag w1_o{"DFMIR_CONV_W1"};
-      if (w1_o.get() && rr && kc.vec4 && g->act != 2 && (g->Cin % 16) == 0 && (g->Ho % 16) == 0 && (g->Wo % 32) == 0) {
+      if (w1_o.get() && cl.form == 1 && kc.vec4 && g->act != 2 && (g->Cin % 16) == 0 && (g->Ho % 16) == 0 && (g->Wo % 32) == 0) {
         // experiment: one wave per SIMD, 16 x 32 x 128 tiles (conv3x3_split_w1_k)
         ConvCsP kw = kc;
         kw.tiles_y = g->Ho / 16;
@@ -1146,13 +886,10 @@ bool df_conv3x3_split_fwd_try(const DfConvGeom* g, const float* x, const float* 
         conv3x3_split_w1_k<0><<<gw, 256, 0, st>>>(x, ws, bias, y, kw, sc);
       } else
 #endif
-      if (rr) conv3x3_split_cs_k<true, 64, 8><<<grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
-      else conv3x3_split_cs_k<false, 64, 8><<<grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
+      if (cl.form == 1) conv3x3_split_cs_k<true, 64, 8><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
+      else conv3x3_split_cs_k<false, 64, 8><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
     } else {
-      static DfOptInt xcd1_o{"DFMIR_CS_XCD_PAIR", 2};
-    const int xcd1 = xcd1_o.get();
-      if (xcd1 >= 2 && (nb & 7) == 0) kc.xcd_pair = 2;          // one cout slice: contiguous tile runs per XCD
-      conv3x3_split_cs_k<true, 32, 16><<<dim3((unsigned)nb, 1u), 512, 0, st>>>(x, ws, bias, y, kc, sc);
+      conv3x3_split_cs_k<true, 32, 16><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
     }
     hipError_t e = hipGetLastError();
     *rc = (e == hipSuccess) ? 0 : df_set_error((int)e, __FILE__, __LINE__);
@@ -1611,287 +1348,23 @@ extern "C" int dfmir_w2_trace_dump(unsigned* out) {
 // phase runs with nobody on the matrix pipe (0.440 -> 0.395 ms on 256 -> 256 @64^2, n = 32; profiles/r04_wgrad_prio.txt)
 #define W2_PRIO_G1 2
 #endif
-__global__ __launch_bounds__(512, 1) void conv3x3_wgrad_split2_k(const float* __restrict__ x,
-                                                                 const float* __restrict__ dy,
-                                                                 float* __restrict__ dwt, WS3P k) {
-  constexpr int NSP = 2, BC = 128, CT = 64;
-  using P = Prod<2>;
 #ifndef W2_CTPAD
 #define W2_CTPAD 0
 #endif
-  constexpr int CTP = CT + W2_CTPAD;                 // stride of a half inside a slab
-  constexpr int XSLAB = 2 * CTP;                     // units of one (split, dx, row) slab: [half][ci]
-  constexpr int XCU = NSP * 3 * 4 * XSLAB, DYU = NSP * 2 * 2 * BC;
-  __shared__ __attribute__((aligned(16))) u32x4 Xc[2 * XCU];
-  __shared__ __attribute__((aligned(16))) u32x4 Dy[2 * DYU];
-  __shared__ float bsum[BC];
+// LDS of the kernel, whose body is conv3x3s_w2_body.inc (see CsLds):  Xc[2 * XCU] | Dy[2 * DYU] | edc[128] | red[17]
+struct W2Lds {
+  static constexpr int XCU = 2 * 3 * 4 * 2 * (64 + W2_CTPAD), DYU = 2 * 2 * 2 * 128;
+  static constexpr int DY_OFF = 2 * XCU * 16, EDC_OFF = DY_OFF + 2 * DYU * 16, RED_OFF = EDC_OFF + 128 * 4, BYTES = RED_OFF + 80;
+};
+__global__ __launch_bounds__(512, 1) void conv3x3_wgrad_split2_k(const float* __restrict__ x,
+                                                                 const float* __restrict__ dy,
+                                                                 float* __restrict__ dwt, WS3P k) {
+  __shared__ __attribute__((aligned(16))) u32x4 Xc[2 * W2Lds::XCU];
+  __shared__ __attribute__((aligned(16))) u32x4 Dy[2 * W2Lds::DYU];
   __shared__ float red[17];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const bool want_db = k.db != nullptr && blockIdx.y == 0;
-  if (tid < BC) bsum[tid] = 0.f;
-  float bacc = 0.f, baccx = 0.f;
-  const int wc = wid & 3, wi = wid >> 2;             // wi is also the stagger group
-  const int l31 = lane & 31, lhi = lane >> 5;
-  const int HW = k.H * k.W;
-  const int ci0 = blockIdx.y * CT, co0 = blockIdx.z * BC;
-  const int run_beg = blockIdx.x * k.runs_per_block;
-  int run_end = run_beg + k.runs_per_block;
-  if (run_end > k.runs_total) run_end = k.runs_total;
-
-  const int ex = scale_exp(reduce_absmax(k.x_amax, k.x_n, red));
-  __syncthreads();
-  const int ed = scale_exp(reduce_absmax(k.dy_amax, k.dy_n, red));
-  // dY is scaled per OUTPUT CHANNEL when the per-plane maxima are known: the scale is uniform along the MFMA K (pixels
-  // of one channel), so a channel whose gradient is 1e-6 of the tensor's largest keeps its 22 bits; the column's
-  // factor 2^-ed[co] goes into the epilogue.  Without them: one scale for the tensor.
-  __shared__ int edc[BC];
-  if (tid < BC) {
-    int e = ed;
-    if (k.dy_pmax) {
-      float m = 0.f;
-      if (co0 + tid < k.Cout)
-        for (int n = 0; n < k.N; ++n) m = fmaxf(m, k.dy_pmax[(long long)n * k.Cout + co0 + tid]);
-      e = scale_exp(m);
-    }
-    edc[tid] = e;
-  }
-  __syncthreads();
-
-  // loader roles: X group (patch row xr 0..3, half xu, channel xc 0..63), dY group (k-step dk, half du, channel dc)
-  const int xc = tid & 63, xu = (tid >> 6) & 1, xr = tid >> 7;
-  const int dc = tid & (BC - 1), du = (tid >> 7) & 1, dk = tid >> 8;
-  const bool xin = k.dbx != nullptr && blockIdx.z == 0 && (xr == 1 || xr == 2);     // rows of a run that are not halo
-  const float xscale = pow2f(ex), dscale = pow2f(edc[dc]), oscale = pow2f(-ex), oscale2 = pow2f(-edc[wc * 32 + l31]);
-  const unsigned hw4 = (unsigned)HW * 4u;
-  constexpr unsigned OOB = 0x80000000u;
-
-  f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-
-  u32x4 rxa, rxb, rda, rdb;   // 8 px of X, 8 px of dY
-  unsigned rxl, rxr;          // the pixel left / right of the X group
-
-  // past the last run of this workgroup the descriptors are empty (loads return zeros, stores are harmless)
-#ifndef W2_KO
-#define W2_KO 0           // knock-out builds (timing experiments): 1 no global loads, 2 no LDS stores, 4 no conversion, 8 no MFMA phase
-#endif
-#define W2_GLOAD(run_)                                                                           \
-  if (!(W2_KO & 1) || k.N < 0) {                                                                 \
-    const bool live_ = (run_) < run_end;                                                         \
-    const int n_ = live_ ? (run_) / k.runs_per_img : 0;                                          \
-    const int q_ = live_ ? (run_) - n_ * k.runs_per_img : 0;                                     \
-    const int yp_ = q_ / k.runs_per_row, xs_ = q_ - yp_ * k.runs_per_row;                        \
-    const int y0_ = 2 * yp_, x0_ = 16 * xs_ + 8 * xu;                                            \
-    const __amdgpu_buffer_rsrc_t bx_ = __builtin_amdgcn_make_buffer_rsrc(                        \
-        const_cast<float*>(x + (long long)n_ * k.Cin * HW), 0, live_ ? (unsigned)(k.Cin * HW) * 4u : 0u, 0x00020000); \
-    const __amdgpu_buffer_rsrc_t bd_ = __builtin_amdgcn_make_buffer_rsrc(                        \
-        const_cast<float*>(dy + (long long)n_ * k.Cout * HW), 0, live_ ? (unsigned)(k.Cout * HW) * 4u : 0u, 0x00020000); \
-    const bool cok_ = ci0 + xc < k.Cin;                                                          \
-    const unsigned cb_ = (unsigned)(ci0 + xc) * hw4;                                             \
-    int ry_ = y0_ - 1 + xr;                                                                      \
-    bool rok_ = (unsigned)ry_ < (unsigned)k.H;                                                   \
-    if (k.pad_mode == 1) { ry_ = ry_ < 0 ? -ry_ : (ry_ >= k.H ? 2 * (k.H - 1) - ry_ : ry_); rok_ = true; } \
-    const int rb_ = ry_ * k.W;                                                                   \
-    const bool lin_ = x0_ > 0, rin_ = x0_ + 8 < k.W;                                             \
-    const int ol_ = rb_ + (lin_ ? x0_ - 1 : 1), or_ = rb_ + (rin_ ? x0_ + 8 : k.W - 2);          \
-    const bool lok_ = rok_ && cok_ && (lin_ || k.pad_mode == 1), rrok_ = rok_ && cok_ && (rin_ || k.pad_mode == 1); \
-    const unsigned xb_ = (rok_ && cok_) ? cb_ + (unsigned)(rb_ + x0_) * 4u : OOB;                \
-    rxa = __builtin_amdgcn_raw_buffer_load_b128(bx_, xb_, 0, 0);                                 \
-    rxb = __builtin_amdgcn_raw_buffer_load_b128(bx_, xb_ == OOB ? OOB : xb_ + 16u, 0, 0);        \
-    rxl = __builtin_amdgcn_raw_buffer_load_b32(bx_, lok_ ? cb_ + (unsigned)ol_ * 4u : OOB, 0, 0); \
-    rxr = __builtin_amdgcn_raw_buffer_load_b32(bx_, rrok_ ? cb_ + (unsigned)or_ * 4u : OOB, 0, 0); \
-    const unsigned db_ = (co0 + dc >= k.Cout) ? OOB                                              \
-        : (unsigned)(co0 + dc) * hw4 + (unsigned)((y0_ + dk) * k.W + 16 * xs_ + 8 * du) * 4u;    \
-    rda = __builtin_amdgcn_raw_buffer_load_b128(bd_, db_, 0, 0);                                 \
-    rdb = __builtin_amdgcn_raw_buffer_load_b128(bd_, db_ == OOB ? OOB : db_ + 16u, 0, 0);        \
-  }
-  // W2_NORM_PROBE (lab builds): the cost of an InstanceNorm + ReLU applied while the X operand is converted -- (x - m) * r and a
-  // max per value with run-time operands that happen to be the identity (profiles/r06_cs_norm_probe.txt)
-#ifdef W2_NORM_PROBE
-  const float np_r = fmaf(oscale, 0.f, 1.f), np_m = oscale * 0.f, np_lo = fmaf(oscale, 0.f, -3.0e38f);
-#define W2_NORM_PROBE_OPS() _Pragma("unroll") for (int i = 0; i < 10; ++i) r[i] = fmaxf((r[i] - np_m) * np_r, np_lo);
-#else
-#define W2_NORM_PROBE_OPS()
-#endif
-  // X: r[0] = left neighbour, r[1..8] = the group, r[9] = right neighbour; pairs (0,1)..(8,9) make the units
-  // dx=0 (cols -1..6) and dx=2 (cols 1..8), the odd pairing dx=1 is the even one shifted by a half
-#define W2_LSTORE(buf_)                                                                          \
-  {                                                                                              \
-    float r[10];                                                                                 \
-    r[0] = __uint_as_float(rxl); r[9] = __uint_as_float(rxr);                                    \
-    _Pragma("unroll") for (int e = 0; e < 4; ++e) { r[1 + e] = __uint_as_float(rxa[e]); r[5 + e] = __uint_as_float(rxb[e]); } \
-    W2_NORM_PROBE_OPS()                                                                          \
-    baccx += xin ? ((r[1] + r[2]) + (r[3] + r[4])) + ((r[5] + r[6]) + (r[7] + r[8])) : 0.f;      \
-    unsigned pa[5][NSP], pb[4][NSP];                                                             \
-    if (W2_KO & 4) { _Pragma("unroll") for (int i = 0; i < 5; ++i) { pa[i][0] = __float_as_uint(r[2 * i]); pa[i][1] = __float_as_uint(r[2 * i + 1]); } } \
-    else _Pragma("unroll") for (int i = 0; i < 5; ++i) split_pair_scaled(r[2 * i], r[2 * i + 1], xscale, pa[i][0], pa[i][1]); \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                \
-      _Pragma("unroll") for (int s = 0; s < NSP; ++s) pb[i][s] = __builtin_amdgcn_alignbit(pa[i + 1][s], pa[i][s], 16); \
-    if (!(W2_KO & 2) || k.N < 0) _Pragma("unroll") for (int s = 0; s < NSP; ++s) {                 \
-      u32x4* dst = Xc + (buf_) * XCU + (s * 3 * 4 + xr) * XSLAB + xu * CTP + xc;                    \
-      dst[0] = u32x4{pa[0][s], pa[1][s], pa[2][s], pa[3][s]};                                    \
-      dst[4 * XSLAB] = u32x4{pb[0][s], pb[1][s], pb[2][s], pb[3][s]};                            \
-      dst[8 * XSLAB] = u32x4{pa[1][s], pa[2][s], pa[3][s], pa[4][s]};                            \
-    }                                                                                            \
-    float v[8];                                                                                  \
-    _Pragma("unroll") for (int e = 0; e < 4; ++e) { v[e] = __uint_as_float(rda[e]); v[4 + e] = __uint_as_float(rdb[e]); } \
-    bacc += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));                   \
-    u32x4 sp[NSP];                                                                               \
-    if (W2_KO & 4) { sp[0] = rda; sp[1] = rdb; } else                                            \
-    split8_s<NSP>(v, dscale, sp);                                                                \
-    if (!(W2_KO & 2) || k.N < 0) _Pragma("unroll") for (int s = 0; s < NSP; ++s) Dy[(buf_) * DYU + ((s * 2 + dk) * 2 + du) * BC + dc] = sp[s]; \
-  }
-
-  // operand unit indices of this lane: A = Xc[((s*3 + dx)*4 + row)*2 + lhi][ci], B = Dy[(s*2 + ks)*2 + lhi][co]
-  const int abase = lhi * CTP + wi * 32 + l31;
-  const int bbase = lhi * BC + wc * 32 + l31;
-  // the 12 operand units of a run in an order that never puts two 3-MFMA units (rows 0, 3) next to each other
-  //   unit u -> (dx, row);  MFMAs of a unit: k-steps ks with 0 <= row - ks <= 2, tap = (row - ks)*3 + dx
-#ifndef W2_LEAD
-#define W2_LEAD 1      // operand units read ahead (1-3 measured equal; 1 needs the fewest registers)
-#endif
-#ifdef W2_NOPRIO
-#define W2_PRIO(p_)
-#else
-#define W2_PRIO(p_) __builtin_amdgcn_s_setprio(p_)
-#endif
-#define W2_UDX(u_) ((u_) / 4)
-#define W2_UROW(u_) ((u_) < 4 ? (u_) : ((u_) % 4 == 0 ? 1 : ((u_) % 4 == 1 ? 0 : (u_) % 4)))
-#define W2_LOADA(set_, u_)                                                                       \
-  _Pragma("unroll") for (int s = 0; s < NSP; ++s)                                                \
-    a[set_][s] = Xb[((s * 3 + W2_UDX(u_)) * 4 + W2_UROW(u_)) * XSLAB + abase];
-#define W2_MMA_PHASE(buf_)                                                                       \
-  {                                                                                              \
-    const u32x4* Xb = Xc + (buf_) * XCU;                                                         \
-    const u32x4* Db = Dy + (buf_) * DYU;                                                         \
-    u32x4 b[2][NSP], a[W2_LEAD + 1][NSP];                                                        \
-    _Pragma("unroll") for (int s = 0; s < NSP; ++s) b[0][s] = Db[(s * 2 + 0) * 2 * BC + bbase];  \
-    W2_LOADA(0, 0)                                                                               \
-    _Pragma("unroll") for (int s = 0; s < NSP; ++s) b[1][s] = Db[(s * 2 + 1) * 2 * BC + bbase];  \
-    if (W2_LEAD > 1) W2_LOADA(1, 1)                                                              \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    _Pragma("unroll") for (int u = 0; u < 12; ++u) {                                             \
-      if (u + W2_LEAD < 12) W2_LOADA((u + W2_LEAD) % (W2_LEAD + 1), u + W2_LEAD)                 \
-      const int dx_ = W2_UDX(u), row_ = W2_UROW(u);                                              \
-      /* W2_ALT: the two taps a unit feeds take turns (no two consecutive MFMAs on one accumulator) */ \
-      _Pragma("unroll") for (int qo = 0; qo < (W2_ALT ? P::N : 1); ++qo)                         \
-      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                         \
-        const int ty_ = row_ - ks;                                                               \
-        if (ty_ >= 0 && ty_ <= 2) {                                                              \
-          _Pragma("unroll") for (int q = (W2_ALT ? qo : 0); q < (W2_ALT ? qo + 1 : P::N); ++q)   \
-            acc[ty_ * 3 + dx_] = mma16<NSP>(a[u % (W2_LEAD + 1)][P::A[q]], b[ks][P::B[q]], acc[ty_ * 3 + dx_]); \
-        }                                                                                        \
-      }                                                                                          \
-      const int nm_ = (row_ == 0 || row_ == 3) ? 3 : 6;                                          \
-      _Pragma("unroll") for (int i = 0; i < 6; ++i) {                                            \
-        if (i < nm_) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          \
-        if (i < NSP && u + W2_LEAD < 12) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      \
-      }                                                                                          \
-      __builtin_amdgcn_sched_barrier(0);                                                         \
-    }                                                                                            \
-  }
-
-  if (run_beg < run_end) {
-    W2_GLOAD(run_beg);
-    W2_LSTORE(0);
-    W2_GLOAD(run_beg + 1);
-  }
-  __syncthreads();
-
-  // two copies of the run loop rather than a branch inside one: each group's loop gets its own register allocation
-  // (a branch in the body spilled 270 registers); both execute the same number of barriers
-#ifdef W2_TRACE
-  const bool trace_blk = blockIdx.x == 5 && blockIdx.y == 1 && blockIdx.z == 0;
-#endif
-  if (wi == 0) {
-    for (int run = run_beg; run < run_end; ++run) {
-      const int buf = (run - run_beg) & 1;
-      W2T(0)
-      W2_PRIO(W2_PRIO_C);
-      W2T_VM()
-      W2_LSTORE(buf ^ 1);
-      W2_GLOAD(run + 2);
-      __builtin_amdgcn_sched_barrier(0);
-      W2T(1)
-      W2_PRIO(W2_PRIO_G0);
-      if (!(W2_KO & 8) || k.N < 0) W2_MMA_PHASE(buf);
-      W2T(2)
-      __syncthreads();
-      W2T(3)
-    }
-  } else {
-    for (int run = run_beg; run < run_end; ++run) {
-      const int buf = (run - run_beg) & 1;
-      W2T(0)
-      W2_PRIO(W2_PRIO_G1);
-      if (!(W2_KO & 8) || k.N < 0) W2_MMA_PHASE(buf);
-      __builtin_amdgcn_sched_barrier(0);
-      W2T(1)
-      W2_PRIO(W2_PRIO_C);
-      W2T_VM()
-      W2_LSTORE(buf ^ 1);
-      W2_GLOAD(run + 2);
-      W2T(2)
-      __syncthreads();
-      W2T(3)
-    }
-  }
-#undef W2_GLOAD
-#undef W2_LSTORE
-#undef W2_LOADA
-#undef W2_MMA_PHASE
-#undef W2_UDX
-#undef W2_UROW
-
-  if (want_db) {
-    atomicAdd(&bsum[dc], bacc);
-    __syncthreads();
-    if (tid < BC && co0 + tid < k.Cout) atomicAdd(&k.db[co0 + tid], bsum[tid]);
-  }
-  if (k.dbx != nullptr && blockIdx.z == 0) {
-    atomicAdd(&bsum[xc], baccx);
-    __syncthreads();
-    if (tid < CT && ci0 + tid < k.Cin) atomicAdd(&k.dbx[ci0 + tid], bsum[tid]);
-  }
-  if (k.swap) {
-    // transposed store: the real layout is [8 - t][co][ci] with ci (this kernel's rows) fastest.  Each wave turns its
-    // 32 x 32 tile around through LDS (the operand buffers are free now) so that a half-wave adds to 32 consecutive
-    // floats -- 19 M lane-scattered atomics on 74 K addresses cost 0.4 ms at the 128 -> 64 layer
-    __syncthreads();
-    float* T = reinterpret_cast<float*>(Xc) + wid * (32 * 33);
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) T[(4 * lhi + (r & 3) + 8 * (r >> 2)) * 33 + l31] = acc[t][r] * oscale * oscale2;
-      __syncthreads();
-      const int ci = ci0 + wi * 32 + l31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int col = 4 * lhi + (r & 3) + 8 * (r >> 2);
-        const int co = co0 + wc * 32 + col;
-        const float v = T[l31 * 33 + col];
-        if (ci < k.Cin && co < k.Cout) df_acc(dwt, ((long long)(8 - t) * k.Cout + co) * k.Cin + ci, v, k.fx);
-      }
-      __syncthreads();
-    }
-    return;
-  }
-  const int co = co0 + wc * 32 + l31;
-  if (co < k.Cout) {
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ci = ci0 + wi * 32 + 4 * lhi + (r & 3) + 8 * (r >> 2);
-        if (ci < k.Cin) df_acc(dwt, ((long long)t * k.Cin + ci) * k.Cout + co, acc[t][r] * oscale * oscale2, k.fx);
-      }
-    }
-  }
+  __shared__ int edc[128];
+  const unsigned bix = blockIdx.x, biy = blockIdx.y, biz = blockIdx.z;
+#include "conv3x3s_w2_body.inc"
 }
 
 // (Round 4 built and measured two restructurings of this kernel, both bit-compatible and both SLOWER, so neither is kept
@@ -1909,9 +1382,10 @@ bool df_conv3x3_split_wgrad_swaps(const DfConvGeom* g) {
          g->dil == 1 && g->ph == 1 && g->pw == 1 && g->pd == 0 && g->Ho == g->Hi && g->Wo == g->Wi && g->pad_mode == 0 &&
          g->Cout == 64 && g->Cin > 64;
 }
-bool df_conv3x3_split_wgrad_try(const DfConvGeom* g, const float* x, const float* x_amax, int x_n, const float* dy,
-                                const float* dy_amax, int dy_n, float* dw_tcc, float* db, hipStream_t st, int* rc,
-                                const float* dy_pmax) {
+// What df_conv3x3_split_wgrad_try launches: parameters, grid and kernel -- 1: split2 with swapped roles, 2: split2,
+// 3 / 4: conv3x3_wgrad_split_k<2, 128 / 64>, 5 / 6: <3, 128 / 64>.  false: the geometry is not taken.
+static bool ws_setup(const DfConvGeom* g, const float* x_amax, int x_n, const float* dy_amax, int dy_n, float* db,
+                     const float* dy_pmax, WS3P* kp, dim3* grid, int* which) {
   const int mode = df_split_mode();
   if (mode == 0 || (mode == 2 && !(x_amax && dy_amax && x_n > 0 && dy_n > 0))) return false;
   if (!(g->KD == 1 && g->KH == 3 && g->KW == 3 && g->Di == 1 && g->Do == 1 && g->stride == 1 && g->dil == 1))
@@ -1941,18 +1415,169 @@ bool df_conv3x3_split_wgrad_try(const DfConvGeom* g, const float* x, const float
   if (want > maxs) want = maxs;
   k.runs_per_block = (int)((k.runs_total + want - 1) / want);
   const unsigned nx = (k.runs_total + k.runs_per_block - 1) / k.runs_per_block;
-  const dim3 grid(nx, ny, nz);
+  *grid = dim3(nx, ny, nz);
+  *kp = k;
   if (mode == 2) {
     static DfOptFlag v1_o{"DFMIR_WGRAD_V1"};
     const bool v1 = v1_o.get();      // A/B: the single-buffered kernel
-    if (swap) conv3x3_wgrad_split2_k<<<grid, 512, 0, st>>>(dy, x, dw_tcc, k);
-    else if (wide && !v1) conv3x3_wgrad_split2_k<<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
-    else if (wide) conv3x3_wgrad_split_k<2, 128><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
-    else conv3x3_wgrad_split_k<2, 64><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+    *which = swap ? 1 : (wide && !v1) ? 2 : wide ? 3 : 4;
   } else {
-    if (wide) conv3x3_wgrad_split_k<3, 128><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
-    else conv3x3_wgrad_split_k<3, 64><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+    *which = wide ? 5 : 6;
   }
+  return true;
+}
+bool df_conv3x3_split_wgrad_try(const DfConvGeom* g, const float* x, const float* x_amax, int x_n, const float* dy,
+                                const float* dy_amax, int dy_n, float* dw_tcc, float* db, hipStream_t st, int* rc,
+                                const float* dy_pmax) {
+  WS3P k;
+  dim3 grid;
+  int which = 0;
+  if (!ws_setup(g, x_amax, x_n, dy_amax, dy_n, db, dy_pmax, &k, &grid, &which)) return false;
+  if (which == 1) conv3x3_wgrad_split2_k<<<grid, 512, 0, st>>>(dy, x, dw_tcc, k);
+  else if (which == 2) conv3x3_wgrad_split2_k<<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+  else if (which == 3) conv3x3_wgrad_split_k<2, 128><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+  else if (which == 4) conv3x3_wgrad_split_k<2, 64><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+  else if (which == 5) conv3x3_wgrad_split_k<3, 128><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+  else conv3x3_wgrad_split_k<3, 64><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+  hipError_t e = hipGetLastError();
+  *rc = (e == hipSuccess) ? 0 : df_set_error((int)e, __FILE__, __LINE__);
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Data gradient and weight gradient of one layer as ONE launch.  Both read dY and neither reads what the other writes, but
+// as two launches on one stream the weight gradient waits for the last data-gradient workgroup (a 10-20 us spread) and
+// the next kernel for the weight gradient's atomic tail (9 x 64 x 128 atomic adds per workgroup, all CUs at once).  Here
+// one 1-D grid holds the workgroups of both: a workgroup runs the body of conv3x3_split_cs_k or of conv3x3_wgrad_split2_k by
+// its index, on the one LDS arena, so the tail of one kind drains beside the main loops of the other.  The arithmetic of
+// either side is what its own kernel does: dX is bit-identical, dW keeps its atomic accumulation.
+//   order 0: weight-gradient workgroups first (their atomic tail under the data gradient's main loops);
+//   order 1: data-gradient workgroups first (the weight gradient fills the data gradient's tail);
+//   order 2: groups of 8 workgroups of either kind interleaved in proportion.
+// The data gradient's logical index keeps its value mod 8 in every order (ids go round-robin over the 8 XCDs, and its
+// XCD mapping -- ConvCsP::xcd_pair -- is built on that): whatever shifts it is a multiple of 8.
+struct PairP {
+  int order;
+  int nd, ndx;            // data gradient: workgroups, x extent of its logical grid (1-D form: nd)
+  int nw, nwx, nwy;       // weight gradient: workgroups, x / y extents of its logical grid
+  int gd, gw;             // groups of 8 ids: ceil(nd / 8), ceil(nw / 8)
+};
+template <int CPG, int TH>
+__global__ __launch_bounds__(512, 1) void conv3x3_bwd_pair_k(const float* __restrict__ dyd, const u32x4* __restrict__ ws,
+                                                             float* __restrict__ dx, ConvCsP kc, SplitScale sc,
+                                                             const float* __restrict__ xw, const float* __restrict__ dyw,
+                                                             float* __restrict__ dwt, WS3P kw, PairP pp) {
+  constexpr int LDS_B = CsLds<CPG, TH>::BYTES > W2Lds::BYTES ? CsLds<CPG, TH>::BYTES : W2Lds::BYTES;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_B];
+  const int id = (int)blockIdx.x;
+  bool wg;                // this workgroup belongs to the weight gradient
+  int l;                  // its index among the workgroups of its kind
+  if (pp.order == 0) {
+    wg = id < 8 * pp.gw;
+    l = wg ? id : id - 8 * pp.gw;
+  } else if (pp.order == 1) {
+    wg = id >= 8 * pp.gd;
+    l = wg ? id - 8 * pp.gd : id;
+  } else {
+    // group g of 8 ids is the weight gradient's when floor((g + 1) gw / (gd + gw)) steps past floor(g gw / (gd + gw))
+    const unsigned long long g = (unsigned)id >> 3, tot = (unsigned)(pp.gd + pp.gw);
+    const int wb = (int)(g * (unsigned)pp.gw / tot);
+    wg = (int)((g + 1) * (unsigned)pp.gw / tot) > wb;
+    l = ((wg ? wb : (int)g - wb) << 3) | (id & 7);
+  }
+  if (!wg) {
+    if (l >= pp.nd) return;
+    constexpr bool RR = true;
+    using L = CsLds<CPG, TH>;
+    const float* __restrict__ x = dyd;
+    const float* __restrict__ bias = nullptr;
+    float* __restrict__ y = dx;
+    const ConvCsP& k = kc;
+    const int bix = l % pp.ndx, biy = l / pp.ndx, gdx = pp.ndx;
+    u32x4 (*Wg)[L::WUG] = reinterpret_cast<u32x4 (*)[L::WUG]>(lds);
+    u32x4 (*Xs)[L::XSU] = reinterpret_cast<u32x4 (*)[L::XSU]>(lds + L::XS_OFF);
+    float* bs = reinterpret_cast<float*>(lds + L::BS_OFF);
+#include "conv3x3s_cs_body.inc"
+  } else {
+    if (l >= pp.nw) return;
+    const float* __restrict__ x = xw;
+    const float* __restrict__ dy = dyw;
+    const WS3P& k = kw;
+    const int t = l / pp.nwx;
+    const unsigned bix = (unsigned)(l - t * pp.nwx), biy = (unsigned)(t % pp.nwy), biz = (unsigned)(t / pp.nwy);
+    u32x4* Xc = reinterpret_cast<u32x4*>(lds);
+    u32x4* Dy = reinterpret_cast<u32x4*>(lds + W2Lds::DY_OFF);
+    int* edc = reinterpret_cast<int*>(lds + W2Lds::EDC_OFF);
+    float* red = reinterpret_cast<float*>(lds + W2Lds::RED_OFF);
+#include "conv3x3s_w2_body.inc"
+  }
+}
+
+#ifndef DF_BWD_PAIR_DEFAULT
+#define DF_BWD_PAIR_DEFAULT 1        // DFMIR_BWD_PAIR when unset
+#endif
+#ifndef DF_BWD_PAIR_ORDER_DEFAULT
+#define DF_BWD_PAIR_ORDER_DEFAULT 1  // DFMIR_BWD_PAIR_ORDER when unset (the measured best: profiles/bwd_pair_ab.txt)
+#endif
+static bool bwd_pair_enabled() {
+  static DfOptFlag no_o{"DFMIR_NO_BWD_PAIR"};
+  static DfOptInt on_o{"DFMIR_BWD_PAIR", DF_BWD_PAIR_DEFAULT};
+  return !no_o.get() && on_o.get() != 0;
+}
+// gd: the data gradient as a convolution of dY (Cin = the layer's Cout, zero padding), gw: the layer itself (the weight
+// gradient's geometry).  True when both sides take the kernels the pair kernel carries: the row-reuse shared-tile kernel
+// in either tile form, and conv3x3_wgrad_split2_k in either role assignment, with float (not fixed-point) accumulation.
+static bool bwd_pair_setup(const DfConvGeom* gd, const DfConvGeom* gw, const float* dy_amax, int dy_n, const float* x_amax,
+                           int x_n, const float* res, const float* ring, int ring_rl, const float* dx, float* db,
+                           const float* dy_pmax, CsLaunch* cl, WS3P* kw, dim3* wgrid, int* which) {
+  if (!bwd_pair_enabled() || df_split_mode() != 2) return false;
+  if (!(gd->N == gw->N && gd->Cin == gw->Cout && gd->Cout == gw->Cin && gd->Hi == gw->Ho && gd->Wi == gw->Wo &&
+        gd->Ho == gw->Hi && gd->Wo == gw->Wi && gd->act == 0))
+    return false;
+  if (!(dy_amax && dy_n > 0 && x_amax && x_n > 0)) return false;
+#ifdef DFMIR_BUILD_W1
+  static DfOptFlag w1_o{"DFMIR_CONV_W1"};
+  if (w1_o.get()) return false;
+#endif
+  if (!split_fwd_geom_ok(gd) || !cs_setup(gd, res, ring, ring_rl, dx, cl) || cl->form == 2) return false;
+  if (!ws_setup(gw, x_amax, x_n, dy_amax, dy_n, db, dy_pmax, kw, wgrid, which) || *which > 2 || kw->fx != nullptr) return false;
+  const long long nd = (long long)cl->grid.x * cl->grid.y, nw = (long long)wgrid->x * wgrid->y * wgrid->z;
+  return nd + nw + 16 < (1LL << 31);
+}
+int df_conv3x3_bwd_pair_ok(const DfConvGeom* gd, const DfConvGeom* gw) {
+  static const float one = 1.f;      // stands for the range probes (only their presence matters here)
+  CsLaunch cl;
+  WS3P kw;
+  dim3 wgrid;
+  int which = 0;
+  return bwd_pair_setup(gd, gw, &one, 1, &one, 1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &cl, &kw, &wgrid, &which) ? 1 : 0;
+}
+bool df_conv3x3_bwd_pair_try(const DfConvGeom* gd, const DfConvGeom* gw, const float* dy, const float* dy_amax, int dy_n,
+                             const float* dy_pmax, const float* wd_packed, const float* res, const float* ring, int ring_rl,
+                             float* dx, const float* x, const float* x_amax, int x_n, float* dw_tcc, float* db,
+                             hipStream_t st, int* rc) {
+  CsLaunch cl;
+  WS3P kw;
+  dim3 wgrid;
+  int which = 0;
+  if (!bwd_pair_setup(gd, gw, dy_amax, dy_n, x_amax, x_n, res, ring, ring_rl, dx, db, dy_pmax, &cl, &kw, &wgrid, &which))
+    return false;
+  static DfOptInt order_o{"DFMIR_BWD_PAIR_ORDER", DF_BWD_PAIR_ORDER_DEFAULT};
+  int order = order_o.get();
+  if (order < 0 || order > 2) order = DF_BWD_PAIR_ORDER_DEFAULT;
+  const u32x4* ws = reinterpret_cast<const u32x4*>(split_section(wd_packed, gd->Cin, gd->Cout));
+  const SplitScale sc{dy_amax, dy_n, split_trailer(wd_packed, gd->Cin, gd->Cout, 2)};
+  PairP pp;
+  pp.order = order;
+  pp.nd = (int)(cl.grid.x * cl.grid.y); pp.ndx = (int)cl.grid.x;
+  pp.nw = (int)(wgrid.x * wgrid.y * wgrid.z); pp.nwx = (int)wgrid.x; pp.nwy = (int)wgrid.y;
+  pp.gd = (pp.nd + 7) >> 3; pp.gw = (pp.nw + 7) >> 3;
+  const dim3 grid((unsigned)(8 * (pp.gd + pp.gw)));
+  // swapped roles: the kernel's X operand is dY and its dY operand is X
+  const float* xw = which == 1 ? dy : x;
+  const float* dyw = which == 1 ? x : dy;
+  if (cl.form == 1) conv3x3_bwd_pair_k<64, 8><<<grid, 512, 0, st>>>(dy, ws, dx, cl.kc, sc, xw, dyw, dw_tcc, kw, pp);
+  else conv3x3_bwd_pair_k<32, 16><<<grid, 512, 0, st>>>(dy, ws, dx, cl.kc, sc, xw, dyw, dw_tcc, kw, pp);
   hipError_t e = hipGetLastError();
   *rc = (e == hipSuccess) ? 0 : df_set_error((int)e, __FILE__, __LINE__);
   return true;

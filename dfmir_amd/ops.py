@@ -850,6 +850,10 @@ def _conv_backward_impl(ctx, dy, dskip, x5, weight, y5):
     # dY feeds the dgrad conv (as its input) and the wgrad: one range probe for both
     if want_probe and dy_amax is None:
         dy_amax = amax_of(dy) if (dy.is_contiguous() and (not act or dy5.data_ptr() == dy.data_ptr())) else absmax(dy5)
+    _LAST_BWD_PAIRED[0] = False
+    both = _conv_backward_pair(ctx, dy, dskip, dy5, dy_amax, x5, weight)
+    if both is not None:
+        return both
     if ctx.needs_input_grad[0]:
         wd = owner.packed(1) if owner is not None else weight_pack(weight, 1)
         in_sp = tuple(x5.shape[2:])
@@ -932,6 +936,88 @@ def _conv_backward_impl(ctx, dy, dskip, x5, weight, y5):
     elif db_buf is not None:
         bias_grad(dy5, db_buf)                                                           # accumulates
     return dx, dw, db
+
+
+_LAST_BWD_PAIRED = [False]
+
+
+def last_backward_paired():
+    """Did the LAST conv backward issue its data gradient and its weight gradient as one launch (dfmir_conv3x3_bwd_pair)?"""
+    return _LAST_BWD_PAIRED[0]
+
+
+def _plan_conv_bwd_pair(gd, gw, K, res, ring):
+    """Does the backward of the 2-D 3x3 layer gw (gd = its data gradient as a convolution of dY) go out as ONE launch?  Pure,
+    like the two planners it asks: both must leave the layer to the library's own 2-D dispatch (with the residual, if any,
+    in the epilogue), the library must say that this dispatch ends on the kernels the pair kernel carries, weight gradients
+    must not be in deterministic mode, and no conv profiler may be installed -- bench.py --full keeps timing the two kernels
+    per kind.  (The probe audit reads each operand between the launches: separate, too.)"""
+    if _CONV_PROFILER[0] is not None or _DET["on"] or _PROBE_AUDIT["on"]:
+        return False
+    fwd = _plan_conv_fwd(gd, K, True, res, ring, None, True, None)
+    if fwd.kernel not in ("res2d", "generic") or (res is not None and not fwd.fuse_res):
+        return False
+    if _plan_conv_wgrad(gw, K, True, None) != "generic":
+        return False
+    return bool(lib().dfmir_conv3x3_bwd_pair_ok(ctypes.byref(gd), ctypes.byref(gw)))
+
+
+def _conv_backward_pair(ctx, dy, dskip, dy5, dy_amax, x5, weight):
+    """The dgrad + wgrad part of _conv_backward_impl as one launch where _plan_conv_bwd_pair allows it: (dx, dw, db), or
+    None -- nothing launched -- when the backward goes the two-launch way.  dy5 = the gradient w.r.t. the pre-activation."""
+    nd, K, stride, p3, pad_mode, act, _, owner = ctx.cfg
+    if not (nd == 2 and tuple(K) == (1, 3, 3) and stride == 1 and tuple(p3) == (0, 1, 1) and ctx.needs_input_grad[0]
+            and ctx.needs_input_grad[1] and ctx.x_amax is not None and dy_amax is not None
+            and getattr(ctx, "x_parts", None) is None and not ctx.dead_tail):
+        return None
+    if (pad_mode == 1 and _NO_RING) or (pad_mode == 0 and dskip is not None):
+        return None
+    L = lib()
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    N, H, W = x5.shape[0], x5.shape[3], x5.shape[4]
+    gw = DfConvGeom(N, Cin, Cout, 1, H, W, 1, H, W, 1, 3, 3, 1, 1, 0, 1, 1, pad_mode, 0, 0.0)
+    gd = DfConvGeom(N, Cout, Cin, 1, H, W, 1, H, W, 1, 3, 3, 1, 1, 0, 1, 1, 0, 0, 0.0)   # the zero-padded dgrad as a conv
+    res5 = None
+    if pad_mode == 1:       # reflect: the ring of the padded frame by its own kernel, folded in by the dgrad's epilogue
+        if not (L.dfmir_conv3x3_reflect_ring_ok(ctypes.byref(gw)) and L.dfmir_conv3x3_res_ok(ctypes.byref(gd))):
+            return None
+        if dskip is not None:
+            res5 = _c(dskip).unsqueeze(2)
+    if not _plan_conv_bwd_pair(gd, gw, K, res5, (None, 0) if pad_mode == 1 else None):
+        return None
+    wd = owner.packed(1) if owner is not None else weight_pack(weight, 1)
+    ringbuf, rl = None, 0
+    if pad_mode == 1:
+        rl = L.dfmir_conv3x3_reflect_ring_len(ctypes.byref(gw))
+        ringbuf = torch.empty(N * 4 * Cin * rl, device=dy5.device, dtype=torch.float32)
+        ctag = getattr(dy, "_df_cols", None)
+        cols = ctag[0] if (ctag is not None and ctag[1] == dy._version and ctag[2] == dy.data_ptr()
+                           and dy.is_contiguous() and not act) else None
+        check(L.dfmir_conv3x3_reflect_ring(ctypes.byref(gw), _p(dy5), _p(cols), _p(dy_amax), dy_amax.numel(), _p(wd),
+                                           _p(ringbuf), _st()))
+    # the weight / bias gradient targets, as in _conv_backward_impl
+    defer = (_DEFER["on"] and owner is not None and getattr(owner, "weight", None) is not None
+             and owner.weight.grad is not None and owner.weight.grad.is_contiguous())
+    db = db_buf = None
+    if ctx.has_bias and ctx.needs_input_grad[2]:
+        bg = getattr(owner, "bias", None).grad if defer and getattr(owner, "bias", None) is not None else None
+        if bg is not None and bg.is_contiguous():
+            db_buf = bg
+        else:
+            db = db_buf = zeros(Cout, dy5.device)
+    ptag = getattr(dy, "_df_pmax", None) if not act else None
+    pm = ptag[0] if (ptag is not None and ptag[1] == dy._version and ptag[2] == dy.data_ptr() and dy.is_contiguous()
+                     and not _NO_CH_SCALE and ptag[0].numel() == N * Cout) else None
+    dwt = (_deferred_buffer(owner, 9, Cin, Cout, tuple(weight.shape), dy5.device) if defer
+           else zeros((9, Cin, Cout), dy5.device))
+    dx5 = torch.empty((N, Cin, 1, H, W), device=dy5.device, dtype=torch.float32)
+    paired = ctypes.c_int(0)
+    check(L.dfmir_conv3x3_bwd_pair(ctypes.byref(gd), ctypes.byref(gw), _p(dy5), _p(dy_amax), dy_amax.numel(), _p(pm), _p(wd),
+                                   _p(res5), _p(ringbuf), rl, _p(dx5), _p(x5), _p(ctx.x_amax), ctx.x_amax.numel(), _p(dwt),
+                                   _p(db_buf), ctypes.byref(paired), _st()))
+    _LAST_BWD_PAIRED[0] = bool(paired.value)
+    _LAST_ACTGRAD[0] = False
+    return dx5.squeeze(2), (None if defer else weight_unpack(dwt, tuple(weight.shape))), db
 
 
 _LAST_CONV_AMAX = [None]

@@ -52,7 +52,10 @@ const char* dfmir_last_error(void);
  *     DFMIR_MARCH_NSEG=n, DFMIR_CS_DEPHASE=n, DFMIR_CONV_W1 (lab builds with -DDFMIR_BUILD_W1 only),
  *     DFMIR_UPWGRAD_DIRECT, DFMIR_UPWGRAD_NO_FUSEB, DFMIR_UPWGRAD_8WAVE, DFMIR_UPWGRAD_NSEG=n (dfmir_conv3d_upwgrad),
  *     DFMIR_NCC_NO_WH_FUSE, DFMIR_CONV3D_NO_WGRAD_MARCH, DFMIR_WGRAD_MARCH_NSEG=n, DFMIR_NO_TINYVOL,
- *     DFMIR_NO_1X1_WGRAD, DFMIR_CONV3D_NO_FLOW_WGRAD, DFMIR_CONV3D_NO_S2, DFMIR_RESIZE_NO_ROWS, DFMIR_NCC_NO_D_FUSE, DFMIR_SMOOTH_NO_MARCH.
+ *     DFMIR_NO_1X1_WGRAD, DFMIR_CONV3D_NO_FLOW_WGRAD, DFMIR_CONV3D_NO_S2, DFMIR_RESIZE_NO_ROWS, DFMIR_NCC_NO_D_FUSE, DFMIR_SMOOTH_NO_MARCH,
+ *     DFMIR_NO_BWD_PAIR (dgrad and wgrad of a 3x3 layer as two launches), DFMIR_BWD_PAIR=0|1 (the same switch with an explicit
+ *     value; unset = the build's default), DFMIR_BWD_PAIR_ORDER=n (workgroup order inside dfmir_conv3x3_bwd_pair's grid:
+ *     0 weight gradient first, 1 data gradient first, 2 interleaved in groups of 8).
  * ---------------------------------------------------------------------------------------- */
 int dfmir_set_option(const char* name, const char* value);
 int dfmir_get_option(const char* name, char* buf, int buf_len);
@@ -302,6 +305,23 @@ int dfmir_conv3x3_reflect_ring_ok(const DfConvGeom* g);
 int dfmir_conv3x3_reflect_ring_len(const DfConvGeom* g);
 int dfmir_conv3x3_reflect_ring(const DfConvGeom* g, const float* dy, const float* dy_cols, const float* dy_amax,
                                int dy_amax_n, const float* wd_packed, float* ring, void* stream);
+
+/* Data gradient AND weight gradient of one 3x3 stride-1 layer in ONE launch (csrc/conv3x3s.hip, conv3x3_bwd_pair_k): a
+ * 1-D grid holds the workgroups of both kernels, so the atomic tail of the weight gradient and the last workgroups of the
+ * data gradient no longer each end a launch with idle CUs -- autograd's Conv2d backward (models/networks.py:1201,1214),
+ * whose two halves both read only dy.  gd = the data gradient as a convolution of dy (Cin = the layer's Cout, Cout = its
+ * Cin, zero padding 1; for a reflect-padded layer the zero-padded interior, its ring through `ring` as in
+ * dfmir_conv3x3_fwd_scaled_res), gw = the layer's forward geometry (the weight gradient's).  Arguments as in
+ * dfmir_conv3x3_fwd_scaled_res (dy, dy_amax, wd_packed, res, ring, ring_len, dx) and dfmir_conv_wgrad_scaled_ch (x,
+ * x_amax, dy_pmax, dw_tcc, db; accumulates).  dX is bit-identical to the separate call's, dW / db are accumulated by the
+ * same atomics.  When either side would not run on the kernels the pair carries (dfmir_conv3x3_bwd_pair_ok(gd, gw) == 0:
+ * other geometry, deterministic mode, DFMIR_NO_BWD_PAIR=1, DFMIR_BWD_PAIR=0) the call issues the two separate launches;
+ * *paired tells which happened (1 = one launch). */
+int dfmir_conv3x3_bwd_pair_ok(const DfConvGeom* gd, const DfConvGeom* gw);
+int dfmir_conv3x3_bwd_pair(const DfConvGeom* gd, const DfConvGeom* gw, const float* dy, const float* dy_amax,
+                           int dy_amax_n, const float* dy_pmax, const float* wd_packed, const float* res,
+                           const float* ring, int ring_len, float* dx, const float* x, const float* x_amax,
+                           int x_amax_n, float* dw_tcc, float* db, int* paired, void* stream);
 /* dy_cols (optional): [N*Cout][2][H], the first and last column of dy as left by dfmir_instnorm_bwd_cols. */
 
 /* Every packing of a train step at once (the weights of all layers change together, at the optimizer step): the same
