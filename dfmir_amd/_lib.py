@@ -140,6 +140,9 @@ _SIGS = {
     "dfmir_flow_smooth_fwd_p": [P, P, P] + [c_int] * 6 + [P],
     "dfmir_flow_smooth_bwd_p": [P, P, P] + [c_int] * 6 + [P],
     "dfmir_mul": [P, P, P, c_longlong, P],
+    "dfmir_bend_ws_floats": [c_int] * 5,
+    "dfmir_bend_fwd": [P, P, P] + [c_int] * 5 + [c_float] * 3 + [P],
+    "dfmir_bend_bwd": [P, P, P] + [c_int] * 5 + [c_float] * 3 + [P],
     "dfmir_nmi_ws_floats": [c_longlong, c_int],
     "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
     "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],
@@ -211,6 +214,7 @@ def lib():
         h.dfmir_conv3d_up_dgrad_ws_floats.restype = c_longlong
         h.dfmir_conv3d_upwgrad_ws_floats.restype = c_longlong
         h.dfmir_flow_smooth_ws_floats.restype = c_longlong
+        h.dfmir_bend_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong
         h.dfmir_warp_dice_ws_floats.restype = c_longlong

@@ -1,7 +1,7 @@
 """Registration losses with the reference's interfaces: `smooothing_loss`
 (models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `MSE` /
 `Dice` / `Grad` (models/voxelmorph/torchvoxelmorph/losses.py:7-117; also reachable as `dfmir_amd.voxelmorph.losses`), each
-one fused HIP reduction (dfmir_amd.ops); `MIND_Loss` (build-defined) is the MIND-SSC multi-modal similarity; `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
+one fused HIP reduction (dfmir_amd.ops); `BendingEnergy_Loss` (build-defined) is the second-order flow regulariser; `MIND_Loss` (build-defined) is the MIND-SSC multi-modal similarity; `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
 (util/loss_metrics.py:105-132) and `LabelHausdorff` (build-defined) are evaluation metrics on the HIP distance transform."""
 import numpy as np
 import torch
@@ -41,6 +41,50 @@ class Grad_Loss(_Loss):
             m = kwargs['mask'].to(device=prediction.device, dtype=torch.float32).expand_as(prediction).contiguous()
             prediction = ops.mul(prediction, m)
         loss = ops.flow_smoothness(prediction, 'l2' if self.penalty == 'l2' else 'l1')
+        if self.loss_mult is not None:
+            loss = ops.scale(loss.view(1), self.loss_mult).view(())
+        return loss
+
+
+class BendingEnergy_Loss(_Loss):
+    """Build-defined (the reference's regulariser, util/losses.py:81-130, is first-order only): the bending energy of a
+    field, the second-order companion of Grad_Loss -- it charges nothing for an affine motion.
+    `BendingEnergy_Loss(dim, spacing)(prediction, mask=...)`, Grad_Loss's calling convention.
+
+    Field u [B,C,*vol], fp32, nd = `dim` spatial axes a in the order (z,) y, x with extents n_a; any C >= 1; `spacing` =
+    the voxel spacing h_a > 0 in that order (None = 1).  Omega = the voxels whose whole 3^nd neighbourhood lies inside the
+    volume, 1 <= p_a <= n_a - 2 on every axis.  For p in Omega:
+
+        u_aa(p) = (u(p+e_a) - 2 u(p) + u(p-e_a)) / h_a^2
+        u_ab(p) = (u(p+e_a+e_b) - u(p+e_a-e_b) - u(p-e_a+e_b) + u(p-e_a-e_b)) / (4 h_a h_b),   a < b
+        e(p)    = sum_a u_aa(p)^2 + 2 sum_{a<b} u_ab(p)^2
+        loss    = sum over (b, c, p in Omega) of e / N,   N = B C |Omega|
+
+    The gradient is the exact adjoint; with U = a derivative value extended by 0 outside Omega:
+
+        dL/du(p) = (2 / N) [ sum_a (U_aa(p-e_a) - 2 U_aa(p) + U_aa(p+e_a)) / h_a^2
+                   + 2 sum_{a<b} (U_ab(p-e_a-e_b) - U_ab(p-e_a+e_b) - U_ab(p+e_a-e_b) + U_ab(p+e_a+e_b)) / (4 h_a h_b) ]
+
+    A volume of one plane [B,C,1,H,W] is the 2-D field it is, as for Grad_Loss: the terms run over y and x, the first
+    spacing entry is ignored.  Any other axis shorter than 3 leaves Omega empty and raises a ValueError before anything
+    is launched.  `mask=` multiplies the field first, `loss_mult` scales the result.  Bit-identical from run to run;
+    capturable (ops.bending_energy; dfmir_amd/csrc/bend.hip)."""
+
+    def __init__(self, dim=3, spacing=None, name=None, loss_mult=None, *args, **kwargs):
+        super().__init__(name=name or 'bending')
+        if dim not in (2, 3):
+            raise ValueError("BendingEnergy_Loss: dim must be 2 or 3, got %r" % (dim,))
+        self.dim, self.loss_mult = dim, loss_mult
+        self.spacing = ops.bending_spacing(spacing, (dim,), "BendingEnergy_Loss")
+
+    def forward(self, prediction, *args, **kwargs):
+        if prediction.dim() - 2 != self.dim:
+            raise ValueError("BendingEnergy_Loss(dim=%d) got a %d-D field" % (self.dim, prediction.dim() - 2))
+        ops.bending_geom(prediction, self.spacing, "BendingEnergy_Loss")      # (a bad shape raises before the mask is applied)
+        if 'mask' in kwargs:
+            m = kwargs['mask'].to(device=prediction.device, dtype=torch.float32).expand_as(prediction).contiguous()
+            prediction = ops.mul(prediction, m)
+        loss = ops.bending_energy(prediction, self.spacing)
         if self.loss_mult is not None:
             loss = ops.scale(loss.view(1), self.loss_mult).view(())
         return loss

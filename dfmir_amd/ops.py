@@ -2419,6 +2419,85 @@ def flow_smoothness(flow, penalty='l2'):
     return FlowSmoothFn.apply(flow, 2 if penalty == 'l2' else 1)
 
 
+def bending_spacing(spacing, lengths, what):
+    """The voxel spacing of a bending energy as a tuple of floats: None = all ones (of lengths[0] entries), otherwise a
+    sequence of positive finite numbers whose length is one of `lengths` (ValueError otherwise)."""
+    if spacing is None:
+        return (1.0,) * lengths[0]
+    try:
+        vals = tuple(spacing)
+    except TypeError:
+        vals = None
+    if vals is None or isinstance(spacing, str) or len(vals) not in lengths:
+        raise ValueError("%s: spacing must be a sequence of %s numbers, got %r"
+                         % (what, " or ".join(str(n) for n in lengths), spacing))
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(v) or not 0.0 < float(np.float32(v)) < float('inf'):
+            raise ValueError("%s: spacing must hold positive finite numbers, got %r" % (what, spacing))
+    return tuple(float(v) for v in vals)
+
+
+def bending_geom(flow, spacing, what):
+    """(B, C, D, H, W, hz, hy, hx) of a bending-energy input after the argument checks (ValueError: nothing is launched).
+    A 5-D field of one plane is the 2-D field it is: its spacing has 2 entries, or 3 with the first ignored."""
+    if flow.dim() not in (4, 5):
+        raise ValueError("%s: expects a [B,C,H,W] or [B,C,D,H,W] field, got %d dims" % (what, flow.dim()))
+    nd = flow.dim() - 2
+    B, C = int(flow.shape[0]), int(flow.shape[1])
+    D, H, W = (int(v) for v in (flow.shape[2:] if nd == 3 else (1,) + tuple(flow.shape[2:])))
+    if B < 1 or C < 1:
+        raise ValueError("%s: empty tensor %s" % (what, tuple(flow.shape)))
+    short = [n for n in ((H, W) if D == 1 else (D, H, W)) if n < 3]
+    if short:
+        raise ValueError("%s: every axis needs an extent of at least 3 (a voxel with its whole 3^nd neighbourhood inside "
+                         "the volume), got %s" % (what, tuple(flow.shape[2:])))
+    if B * C * D * H * W >= 2 ** 31:
+        raise ValueError("%s: fields of 2^31 and more elements are not supported, got %s" % (what, tuple(flow.shape)))
+    sp = bending_spacing(spacing, (2,) if nd == 2 else ((2, 3) if D == 1 else (3,)), what)
+    hz, hy, hx = sp if len(sp) == 3 else (1.0,) + sp
+    return B, C, D, H, W, hz, hy, hx
+
+
+class BendingEnergyFn(Function):
+    """dfmir_bend_fwd / _bwd: the forward keeps the field alone, the backward re-forms the second differences in LDS."""
+
+    @staticmethod
+    def forward(ctx, flow, geom):
+        flow = _c(flow)
+        B, C, D, H, W, hz, hy, hx = geom
+        ws = torch.empty(int(lib().dfmir_bend_ws_floats(B, C, D, H, W)), device=flow.device, dtype=torch.float32)
+        out = torch.empty((), device=flow.device, dtype=torch.float32)
+        check(lib().dfmir_bend_fwd(_p(flow), _p(ws), _p(out), B, C, D, H, W, hz, hy, hx, _st()))
+        ctx.save_for_backward(flow)
+        ctx.meta = geom
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (flow,) = ctx.saved_tensors
+        B, C, D, H, W, hz, hy, hx = ctx.meta
+        g = _c(g)
+        df = torch.empty_like(flow)
+        check(lib().dfmir_bend_bwd(_p(flow), _p(g), _p(df), B, C, D, H, W, hz, hy, hx, _st()))
+        return df, None
+
+
+def bending_energy(flow, spacing=None):
+    """Bending energy of a field [B,C,*vol] (2-D or 3-D, any C >= 1; build-defined, the definition: losses.
+    BendingEnergy_Loss): the mean over (B, C, Omega) of sum_a u_aa^2 + 2 sum_{a<b} u_ab^2 with central second differences
+    divided by the voxel spacing (`spacing`, one positive number per axis in the order (z,) y, x; None = 1), Omega = the
+    voxels whose whole 3^nd neighbourhood lies in the volume.  A [B,C,1,H,W] field is the 2-D field it is (spacing of 2
+    entries, or 3 with the first ignored).  ValueError before any launch on a bad rank or spacing, on an axis shorter
+    than 3 and on 2^31 or more elements; a CPU tensor raises the usual "no CPU fallback" error."""
+    geom = bending_geom(flow, spacing, "bending_energy")
+    _need(flow)
+    if flow.dtype != torch.float32:
+        raise DfmirHipError("bending_energy: fp32 tensors only (got %s)" % flow.dtype)
+    return BendingEnergyFn.apply(flow, geom)
+
+
 class MulFn(Function):
     """a * b element-wise, same shapes (`prediction * mask`, util/losses.py:120-121)."""
 

@@ -8,14 +8,15 @@ reference does ship: `VxmDense(ndims=3, int_steps=7, bidir=True)`
 (0.5, 0.999)).  Oracle counterpart: oracle/dfmir_oracle.py::Registration3DStep.  similarity='nmi' swaps the NCC term for
 `NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity; similarity='mind' for the build-defined MIND-SSC loss (`MIND_Loss`).  seg_labels / seg_weight add the segmentation
 term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map against the moving one warped by the flow
-(`losses.LabelDice`).
+(`losses.LabelDice`).  regularizer='bending' swaps the diffusion penalty for the build-defined second-order
+`BendingEnergy_Loss`.
 """
 import numpy as np
 import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import Grad_Loss, LabelDice, MIND_Loss, NCC_Loss, NMI_Loss
+from .losses import BendingEnergy_Loss, Grad_Loss, LabelDice, MIND_Loss, NCC_Loss, NMI_Loss
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
@@ -23,7 +24,8 @@ from .voxelmorph import VxmDense
 class Registration3DModel(object):
     def __init__(self, shape, features=None, lam=1.0, lr=2e-4, betas=(0.5, 0.999), win=9, device="cuda",
                  capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
-                 seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3, mind_radius=2, mind_dilation=2):
+                 seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3, mind_radius=2, mind_dilation=2,
+                 regularizer='diffusion', spacing=None):
         """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window, or with ncc_kernel='gaussian' the Gaussian window of
         sigma = ncc_sigma, whose 3-D form is build-defined: see NCC_Loss; `win` is then unused) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
@@ -34,6 +36,11 @@ class Registration3DModel(object):
         seg_labels (a list of 1..64 label values in [0, 255]; None = no segmentation term): `set_input` then also takes
         data['A_seg'] and data['B_seg'], integer label maps [B,1,*shape] of the moving and the fixed image, and the step
         adds seg_weight * LabelDice(seg_labels).loss(B_seg, A_seg, flow); `get_current_losses()` gains 'dice'.
+        regularizer: 'diffusion' (default: Grad_Loss(penalty='l2'), loss key 'grad') or 'bending': lam *
+        BendingEnergy_Loss(dim=len(shape), spacing=spacing)(flow), the second-order penalty that charges nothing for an
+        affine motion (build-defined: see BendingEnergy_Loss), for 2-D and 3-D shapes; `spacing` is the voxel spacing in
+        the order (z,) y, x (None = 1) and is read by the bending energy only.  The loss key is then 'bending' instead
+        of 'grad'.
         capture_step (build-defined, as REGISTRATIONModel's opt.capture_step): after two eager steps forward +
         losses + backward are captured into ONE hipGraph and replayed; Adam and the gradient all-reduce stay eager.
         Small volumes are host-bound otherwise (128^3: 3.7 ms of Python / autograd / ctypes per 5.2 ms step)."""
@@ -56,14 +63,20 @@ class Registration3DModel(object):
         else:
             bins = np.linspace(0.0, nmi_max_clip, 32) if nmi_bins is None else nmi_bins
             self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)
-        self._outputs = ('regA', 'flow', 'loss_' + similarity, 'loss_grad')
+        if regularizer not in ('diffusion', 'bending'):
+            raise ValueError("regularizer must be 'diffusion' or 'bending', got %r" % (regularizer,))
+        self.regularizer = regularizer
+        self._outputs = ('regA', 'flow', 'loss_' + similarity, 'loss_bending' if regularizer == 'bending' else 'loss_grad')
         self.seg_labels, self.seg_weight = seg_labels, float(seg_weight)
         self.seg_A = self.seg_B = None
         if seg_labels is not None:
             self.criterionDice = LabelDice(seg_labels)
             self.seg_labels = self.criterionDice.labels
             self._outputs += ('loss_dice',)
-        self.criterionGrad = Grad_Loss(dim=len(shape), penalty='l2')
+        if regularizer == 'bending':
+            self.criterionGrad = BendingEnergy_Loss(dim=len(shape), spacing=spacing)
+        else:
+            self.criterionGrad = Grad_Loss(dim=len(shape), penalty='l2')
         self.lam = lam
         self._ddp = False
         self.capture_step = bool(capture_step) and self.device.type == "cuda"
@@ -97,8 +110,11 @@ class Registration3DModel(object):
             self.loss_mind = loss_sim = self.criterionMIND(y_source, self.real_B)
         else:
             self.loss_nmi = loss_sim = self.criterionNMI(self.real_B, y_source)
-        self.loss_grad = self.criterionGrad(flow)
-        total = loss_sim + self.loss_grad * self.lam
+        if self.regularizer == 'bending':
+            self.loss_bending = loss_reg = self.criterionGrad(flow)
+        else:
+            self.loss_grad = loss_reg = self.criterionGrad(flow)
+        total = loss_sim + loss_reg * self.lam
         if self.seg_labels is not None:
             self.loss_dice = self.criterionDice.loss(self.seg_B, self.seg_A, flow)
             total = total + self.loss_dice * self.seg_weight
@@ -169,7 +185,10 @@ class Registration3DModel(object):
 
     def get_current_losses(self):
         sim = getattr(self, 'loss_' + self.similarity)
-        out = {self.similarity: float(sim.detach()), 'grad': float(self.loss_grad.detach())}
+        if self.regularizer == 'bending':
+            out = {self.similarity: float(sim.detach()), 'bending': float(self.loss_bending.detach())}
+        else:
+            out = {self.similarity: float(sim.detach()), 'grad': float(self.loss_grad.detach())}
         if self.seg_labels is not None:
             out['dice'] = float(self.loss_dice.detach())
         return out

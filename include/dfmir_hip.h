@@ -573,6 +573,27 @@ int dfmir_flow_smooth_fwd_p(const float* flow, float* ws, float* out, int B, int
                             int W, int penalty, void* stream);
 int dfmir_flow_smooth_bwd_p(const float* flow, const float* gout, float* dflow, int B, int C, int D,
                             int H, int W, int penalty, void* stream);
+/* Bending energy, the second-order regulariser of a flow (build-defined: the reference's util/losses.py:81-130 is first-order
+ * only).  flow u: [B][C][D][H][W] fp32, any C >= 1; axes a in the order (z,) y, x with extents n_a and voxel spacing
+ * h_a > 0 (hz, hy, hx).  D == 1 is the 2-D field it is: y and x only, hz is not read.  Omega = the voxels whose whole 3^nd
+ * neighbourhood lies in the volume, 1 <= p_a <= n_a - 2 on every axis.  For p in Omega
+ *   u_aa(p) = (u(p+e_a) - 2 u(p) + u(p-e_a)) / h_a^2
+ *   u_ab(p) = (u(p+e_a+e_b) - u(p+e_a-e_b) - u(p-e_a+e_b) + u(p-e_a-e_b)) / (4 h_a h_b),   a < b
+ *   e(p)    = sum_a u_aa(p)^2 + 2 sum_{a<b} u_ab(p)^2
+ * dfmir_bend_fwd: out[0] = sum_{b,c,p in Omega} e / N, N = B C |Omega|.  dfmir_bend_bwd: dflow (every element written) =
+ * gout[0] * the exact adjoint, with U = the derivative value extended by 0 outside Omega:
+ *   dL/du(p) = (2 / N) [ sum_a (U_aa(p-e_a) - 2 U_aa(p) + U_aa(p+e_a)) / h_a^2
+ *              + 2 sum_{a<b} (U_ab(p-e_a-e_b) - U_ab(p-e_a+e_b) - U_ab(p+e_a-e_b) + U_ab(p+e_a+e_b)) / (4 h_a h_b) ]
+ * in gather form: no atomics, no derivative volume in memory, the backward reads u alone.  Refused ("invalid argument",
+ * nothing is launched): a NULL pointer, D == 2 or H, W < 3 (Omega would be empty), a spacing that is not positive and
+ * finite, B * C * D * H * W >= 2^31.  ws: dfmir_bend_ws_floats(B, C, D, H, W) floats (-1 for a refused shape), 8-byte
+ * aligned, need not be zeroed: one double slot per workgroup, added in a fixed order -- loss and gradient are bit-identical
+ * from run to run.  Nothing syncs, allocates or keeps state (gout is read on the device): both calls capture into a hipGraph. */
+long long dfmir_bend_ws_floats(int B, int C, int D, int H, int W);
+int dfmir_bend_fwd(const float* flow, float* ws, float* out, int B, int C, int D, int H, int W, float hz, float hy,
+                   float hx, void* stream);
+int dfmir_bend_bwd(const float* flow, const float* gout, float* dflow, int B, int C, int D, int H, int W, float hz,
+                   float hy, float hx, void* stream);
 /* NMI_Loss (util/losses.py:263-348): out[0] = -MI of the soft-binned (Parzen) joint histogram of y_true and y_pred, both
  * first clamped to [0, max_clip]; all n voxels (batch and channels included) form ONE histogram.  Per voxel
  * a_k = exp(-preterm (y_true - c_k)^2) normalised over k (b_k the same for y_pred), pab[i][j] = sum_v b[i] a[j] / V,
