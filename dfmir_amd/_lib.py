@@ -143,6 +143,10 @@ _SIGS = {
     "dfmir_bend_ws_floats": [c_int] * 5,
     "dfmir_bend_fwd": [P, P, P] + [c_int] * 5 + [c_float] * 3 + [P],
     "dfmir_bend_bwd": [P, P, P] + [c_int] * 5 + [c_float] * 3 + [P],
+    "dfmir_invcons_ws_floats": [c_int] * 5,
+    "dfmir_invcons_fwd": [c_int, P, P, P, P, P, P] + [c_int] * 4 + [P],
+    "dfmir_invcons_bwd_ws_floats": [c_int] * 5,
+    "dfmir_invcons_bwd": [c_int, P, P, P, P, P, P, P] + [c_int] * 4 + [P],
     "dfmir_nmi_ws_floats": [c_longlong, c_int],
     "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
     "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],
@@ -215,6 +219,8 @@ def lib():
         h.dfmir_conv3d_upwgrad_ws_floats.restype = c_longlong
         h.dfmir_flow_smooth_ws_floats.restype = c_longlong
         h.dfmir_bend_ws_floats.restype = c_longlong
+        h.dfmir_invcons_ws_floats.restype = c_longlong
+        h.dfmir_invcons_bwd_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong
         h.dfmir_warp_dice_ws_floats.restype = c_longlong

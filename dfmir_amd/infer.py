@@ -43,3 +43,30 @@ def score_labels(warped_label, fixed_label, labels, percentile=100.0, surface=Fa
     b = fixed_label if fixed_label.dtype == torch.uint8 else ops.as_label_map(fixed_label)
     hd, directed, mean, _ = ops.label_hausdorff(a, b, labels, percentile, surface)
     return dict(hd=hd, directed=directed, mean=mean)
+
+
+@torch.no_grad()
+def inverse_consistency_error(flow_ab, flow_ba, spacing=None):
+    """The invertibility diagnostic of a registration: per sample, the RMS over the voxels of |r|, r(x) = flow_ab(x) +
+    flow_ba(x + flow_ab(x)) -- how far a point lands from where it started after going there and back.  A [B] tensor,
+    sqrt(nd * IC_b) of ops.inverse_consistency_per_sample, in voxels; with an isotropic `spacing` (one positive number,
+    or a sequence of nd equal ones) in physical units.  An anisotropic spacing raises: the kernel sums the squared
+    components of r with equal weights, so a per-axis scale cannot be applied to the sum afterwards."""
+    nd = flow_ab.dim() - 2
+    h = 1.0
+    if spacing is not None:
+        try:                                      # a number (a 0-dim tensor or numpy scalar too), or a sequence of nd
+            sp = torch.as_tensor(spacing, dtype=torch.float64).cpu()
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("inverse_consistency_error: spacing must be %d positive finite numbers, got %r" % (nd, spacing))
+        vals = [float(sp)] * nd if sp.dim() == 0 else sp.flatten().tolist()
+        if len(vals) != nd or not all(0.0 < s < float('inf') for s in vals):
+            raise ValueError("inverse_consistency_error: spacing must be %d positive finite numbers, got %r" % (nd, spacing))
+        if any(s != vals[0] for s in vals):
+            raise ValueError("inverse_consistency_error: anisotropic spacing %r is not supported: the per-sample sum adds "
+                             "the squared components of r with equal weights, so a per-axis scale cannot be applied to it "
+                             "afterwards; resample the fields to isotropic voxels or scale their channels first"
+                             % (spacing,))
+        h = vals[0]
+    ic = ops.inverse_consistency_per_sample(flow_ab, flow_ba)
+    return torch.sqrt(ic * float(nd)) * h

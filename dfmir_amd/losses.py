@@ -224,6 +224,44 @@ class Grad(object):
         return grad
 
 
+class InverseConsistency_Loss(_Loss):
+    """Build-defined (the reference has no such term): how far the composition of two displacement fields is from the
+    identity.  `InverseConsistency_Loss(dim, symmetric)(flow_ab, flow_ba)`.
+
+    u, v [B,nd,*vol], nd = `dim` = 2 or 3, fp32; channel i displaces axis i in voxels, in the order (z,) y, x, exactly as
+    ops.warp reads a flow.
+
+        r(x)    = u(x) + v(x + u(x))        v sampled (bi/tri)linearly, corners outside the volume read as 0:
+                                            r = u + ops.warp(v, u), element for element
+        IC(u,v) = mean over all B*nd*S elements of r^2          (S = voxels per sample)
+
+    A voxel whose sample point leaves the volume contributes |u|^2 (zero padding): the warp's own convention, and one that
+    does not reward pushing points out of the volume.  The gradients are the exact adjoint; with k = 2 gout / (B nd S):
+
+        dIC/du_c(x) = k ( r_c(x) + sum_c' r_c'(x) d_c v_c'(x + u(x)) )
+        dIC/dv      = the transpose of the interpolation applied to k r (a scatter to the up to 2^nd corners)
+
+    where d_c is the derivative of the multilinear interpolant as the warp backward forms it: corner differences, with
+    zero-padded corners taking part as zeros.  symmetric=True (default): 0.5 * (IC(u, v) + IC(v, u)).  `loss_mult` scales
+    the result.  The value and dIC/du are bit-identical from run to run on every shape, dIC/dv wherever ops.warp's backward
+    is (W % 4 == 0) and on the shapes where that is not (see ops.inverse_consistency); capturable
+    (dfmir_amd/csrc/invcons.hip)."""
+
+    def __init__(self, dim=3, symmetric=True, name=None, loss_mult=None, *args, **kwargs):
+        super().__init__(name=name or 'ic')
+        if dim not in (2, 3):
+            raise ValueError("InverseConsistency_Loss: dim must be 2 or 3, got %r" % (dim,))
+        self.dim, self.symmetric, self.loss_mult = dim, bool(symmetric), loss_mult
+
+    def forward(self, flow_ab, flow_ba, *args, **kwargs):
+        if flow_ab.dim() - 2 != self.dim:
+            raise ValueError("InverseConsistency_Loss(dim=%d) got a %d-D field" % (self.dim, flow_ab.dim() - 2))
+        loss = ops.inverse_consistency(flow_ab, flow_ba, symmetric=self.symmetric)
+        if self.loss_mult is not None:
+            loss = ops.scale(loss.view(1), self.loss_mult).view(())
+        return loss
+
+
 class MSE(object):
     """vxm `MSE().loss(y_true, y_pred)` = mean((y_true - y_pred)^2) (models/voxelmorph/torchvoxelmorph/losses.py:70-76);
     gradients to both arguments."""

@@ -2498,6 +2498,90 @@ def bending_energy(flow, spacing=None):
     return BendingEnergyFn.apply(flow, geom)
 
 
+def _invcons_geom(u, v, what):
+    """(nd, B, D, H, W) of an inverse-consistency pair after the argument checks (nothing is launched on a bad one)."""
+    if u.dim() not in (4, 5) or tuple(u.shape) != tuple(v.shape):
+        raise DfmirHipError("%s: u %s / v %s mismatch (expected two [B,nd,*vol] fields of one shape)"
+                            % (what, tuple(u.shape), tuple(v.shape)))
+    nd = u.dim() - 2
+    if u.shape[1] != nd:
+        raise DfmirHipError("%s: a %d-D field needs %d channels, got %s" % (what, nd, nd, tuple(u.shape)))
+    if u.dtype != torch.float32 or v.dtype != torch.float32:
+        raise DfmirHipError("%s: fp32 tensors only (got %s, %s)" % (what, u.dtype, v.dtype))
+    if u.device != v.device:
+        raise DfmirHipError("%s: u on %s, v on %s" % (what, u.device, v.device))
+    _need(u, v)
+    B = int(u.shape[0])
+    D, H, W = (int(n) for n in (u.shape[2:] if nd == 3 else (1,) + tuple(u.shape[2:])))
+    if lib().dfmir_invcons_ws_floats(nd, B, D, H, W) < 0:
+        raise DfmirHipError("%s: needs B >= 1, every extent >= 2 and fewer than 2^31 elements, got %s"
+                            % (what, tuple(u.shape)))
+    return nd, B, D, H, W
+
+
+def _invcons_fwd(u, v, geom):
+    """[B + 2] floats: IC per sample, their mean, max |r_c| (the backward's fixed-point range)."""
+    nd, B, D, H, W = geom
+    ws = torch.empty(int(lib().dfmir_invcons_ws_floats(nd, B, D, H, W)), device=u.device, dtype=torch.float32)
+    out = torch.empty(B + 2, device=u.device, dtype=torch.float32)
+    check(lib().dfmir_invcons_fwd(nd, _p(u), _p(v), _p(ws), _p(out), _p(out[B:]), _p(out[B + 1:]), B, D, H, W, _st()))
+    return out
+
+
+class InverseConsistencyFn(Function):
+    """dfmir_invcons_fwd / _bwd: the forward keeps the two fields and max |r_c|, the backward recomputes r."""
+
+    @staticmethod
+    def forward(ctx, u, v, geom):
+        u, v = _c(u), _c(v)
+        out = _invcons_fwd(u, v, geom)
+        ctx.save_for_backward(u, v, out)
+        ctx.meta = geom
+        return out[geom[1]].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        u, v, out = ctx.saved_tensors
+        nd, B, D, H, W = ctx.meta
+        g = _c(g)
+        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
+        dv = ws = None
+        if ctx.needs_input_grad[1]:
+            dv = torch.empty_like(v)
+            ws = torch.empty(int(lib().dfmir_invcons_bwd_ws_floats(nd, B, D, H, W)), device=u.device, dtype=torch.float32)
+        if du is not None or dv is not None:
+            check(lib().dfmir_invcons_bwd(nd, _p(u), _p(v), _p(g), _p(out[B + 1:]), _p(du), _p(dv), _p(ws), B, D, H, W,
+                                          _st()))
+        return du, dv, None
+
+
+def inverse_consistency(u, v, symmetric=False):
+    """Inverse-consistency loss of two displacement fields [B,nd,*vol] (nd = 2 or 3, fp32; build-defined, the definition:
+    losses.InverseConsistency_Loss): IC(u, v) = the mean over all B * nd * S elements of r^2, r = u + ops.warp(v, u)
+    element for element (v sampled (bi/tri)linearly at x + u(x), corners outside the volume read as 0).  symmetric=True:
+    0.5 * (IC(u, v) + IC(v, u)), two calls of the same kernels.  One fused forward and one backward per direction; r is
+    never stored.  Gradients to both fields, the exact adjoint.  The value and du are bit-identical from run to run on
+    every shape.  dv is bit-identical from run to run wherever ops.warp's backward is -- W % 4 == 0: the same owner-gather
+    adjoint, all but voxels displaced past the neighbouring tiles -- and, unlike it, on every other shape too (W % 4 != 0
+    or a misaligned view: 64-bit fixed-point sums, several times slower; dfmir_amd/csrc/invcons.hip).  Raises before any launch on fields of
+    different shapes, a channel count other than nd, a dtype other than fp32, an extent < 2 and 2^31 or more elements; a
+    CPU tensor raises the usual "no CPU fallback" error."""
+    geom = _invcons_geom(u, v, "inverse_consistency")
+    loss = InverseConsistencyFn.apply(u, v, geom)
+    if symmetric:
+        loss = (loss + InverseConsistencyFn.apply(v, u, geom)) * 0.5
+    return loss
+
+
+@torch.no_grad()
+def inverse_consistency_per_sample(u, v):
+    """IC(u, v) per sample, a [B] tensor without gradient: the mean of r^2 over the nd * S elements of each sample (for
+    evaluation; their mean is inverse_consistency(u, v))."""
+    geom = _invcons_geom(u, v, "inverse_consistency_per_sample")
+    return _invcons_fwd(_c(u), _c(v), geom)[:geom[1]].clone()
+
+
 class MulFn(Function):
     """a * b element-wise, same shapes (`prediction * mask`, util/losses.py:120-121)."""
 

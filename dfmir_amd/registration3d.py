@@ -9,14 +9,15 @@ reference does ship: `VxmDense(ndims=3, int_steps=7, bidir=True)`
 `NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity; similarity='mind' for the build-defined MIND-SSC loss (`MIND_Loss`).  seg_labels / seg_weight add the segmentation
 term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map against the moving one warped by the flow
 (`losses.LabelDice`).  regularizer='bending' swaps the diffusion penalty for the build-defined second-order
-`BendingEnergy_Loss`.
+`BendingEnergy_Loss`.  symmetric=True trains both directions of the bidir network (the similarity is charged both ways);
+inverse_consistency=w adds w * the build-defined `InverseConsistency_Loss` of the two integrated fields.
 """
 import numpy as np
 import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import BendingEnergy_Loss, Grad_Loss, LabelDice, MIND_Loss, NCC_Loss, NMI_Loss
+from .losses import BendingEnergy_Loss, Grad_Loss, InverseConsistency_Loss, LabelDice, MIND_Loss, NCC_Loss, NMI_Loss
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
@@ -25,7 +26,7 @@ class Registration3DModel(object):
     def __init__(self, shape, features=None, lam=1.0, lr=2e-4, betas=(0.5, 0.999), win=9, device="cuda",
                  capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
                  seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3, mind_radius=2, mind_dilation=2,
-                 regularizer='diffusion', spacing=None):
+                 regularizer='diffusion', spacing=None, symmetric=False, inverse_consistency=0.0):
         """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window, or with ncc_kernel='gaussian' the Gaussian window of
         sigma = ncc_sigma, whose 3-D form is build-defined: see NCC_Loss; `win` is then unused) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
@@ -41,6 +42,14 @@ class Registration3DModel(object):
         affine motion (build-defined: see BendingEnergy_Loss), for 2-D and 3-D shapes; `spacing` is the voxel spacing in
         the order (z,) y, x (None = 1) and is read by the bending energy only.  The loss key is then 'bending' instead
         of 'grad'.
+        symmetric (build-defined, VoxelMorph's own bidirectional training; default False = the one-directional step): the
+        target branch of the bidir network is computed and the similarity becomes 0.5 * (sim(y_source, real_B) +
+        sim(y_target, real_A)) under the similarity's own loss key ('nmi' mirrors its argument order: NMI(real_A,
+        y_target)); `regB` (real_B warped onto real_A) and `neg_flow` become outputs.  The regulariser stays on the forward
+        flow and the segmentation term one-directional.
+        inverse_consistency = w > 0 (needs symmetric=True, ValueError otherwise): adds w * InverseConsistency_Loss(
+        symmetric=True)(flow, neg_flow), how far the two integrated fields are from being inverses of each other
+        (build-defined: see InverseConsistency_Loss), for 2-D and 3-D shapes; `get_current_losses()` gains 'ic'.
         capture_step (build-defined, as REGISTRATIONModel's opt.capture_step): after two eager steps forward +
         losses + backward are captured into ONE hipGraph and replayed; Adam and the gradient all-reduce stay eager.
         Small volumes are host-bound otherwise (128^3: 3.7 ms of Python / autograd / ctypes per 5.2 ms step)."""
@@ -48,7 +57,13 @@ class Registration3DModel(object):
         if deterministic_wgrad is not None:     # (process-global switch of dfmir_amd.ops, as REGISTRATIONModel's opt.deterministic_wgrad)
             ops.set_deterministic_wgrad(deterministic_wgrad)
         self.netR = VxmDense(tuple(shape), features, int_steps=7, bidir=True).to(self.device)
-        self.netR.skip_unused_target = True      # the step reads (y_source, flow) only
+        self.symmetric, self.ic_weight = bool(symmetric), float(inverse_consistency)
+        if not self.ic_weight >= 0.0:
+            raise ValueError("inverse_consistency must be a weight >= 0, got %r" % (inverse_consistency,))
+        if self.ic_weight > 0.0 and not self.symmetric:
+            raise ValueError("inverse_consistency > 0 needs symmetric=True: the one-directional step never computes the "
+                             "backward field")
+        self.netR.skip_unused_target = not self.symmetric      # the one-directional step reads (y_source, flow) only
         self.optimizer_R = FlatAdam(self.netR.parameters(), lr=lr, betas=betas)
         if similarity not in ('ncc', 'nmi', 'mind'):
             raise ValueError("similarity must be 'ncc', 'nmi' or 'mind', got %r" % (similarity,))
@@ -67,6 +82,11 @@ class Registration3DModel(object):
             raise ValueError("regularizer must be 'diffusion' or 'bending', got %r" % (regularizer,))
         self.regularizer = regularizer
         self._outputs = ('regA', 'flow', 'loss_' + similarity, 'loss_bending' if regularizer == 'bending' else 'loss_grad')
+        if self.symmetric:
+            self._outputs += ('regB', 'neg_flow')
+        if self.ic_weight > 0.0:
+            self.criterionIC = InverseConsistency_Loss(dim=len(shape), symmetric=True)
+            self._outputs += ('loss_ic',)
         self.seg_labels, self.seg_weight = seg_labels, float(seg_weight)
         self.seg_A = self.seg_B = None
         if seg_labels is not None:
@@ -101,20 +121,36 @@ class Registration3DModel(object):
             self.seg_B = ops.as_label_map(data['B_seg'].to(self.device, non_blocking=True))
 
     def _forward_backward(self):
-        y_source, y_target, flow = self.netR(self.real_A, self.real_B)
+        if self.symmetric:
+            y_source, y_target, flow, neg_flow = self.netR(self.real_A, self.real_B, return_neg_flow=True)
+            self.regB, self.neg_flow = y_target, neg_flow
+        else:
+            y_source, y_target, flow = self.netR(self.real_A, self.real_B)
         self.regA, self.flow = y_source, flow
         self.optimizer_R.zero_grad()
         if self.similarity == 'ncc':
-            self.loss_ncc = loss_sim = self.criterionNCC(y_source, self.real_B)
+            loss_sim = self.criterionNCC(y_source, self.real_B)
+            if self.symmetric:
+                loss_sim = (loss_sim + self.criterionNCC(y_target, self.real_A)) * 0.5
+            self.loss_ncc = loss_sim
         elif self.similarity == 'mind':
-            self.loss_mind = loss_sim = self.criterionMIND(y_source, self.real_B)
+            loss_sim = self.criterionMIND(y_source, self.real_B)
+            if self.symmetric:
+                loss_sim = (loss_sim + self.criterionMIND(y_target, self.real_A)) * 0.5
+            self.loss_mind = loss_sim
         else:
-            self.loss_nmi = loss_sim = self.criterionNMI(self.real_B, y_source)
+            loss_sim = self.criterionNMI(self.real_B, y_source)
+            if self.symmetric:
+                loss_sim = (loss_sim + self.criterionNMI(self.real_A, y_target)) * 0.5
+            self.loss_nmi = loss_sim
         if self.regularizer == 'bending':
             self.loss_bending = loss_reg = self.criterionGrad(flow)
         else:
             self.loss_grad = loss_reg = self.criterionGrad(flow)
         total = loss_sim + loss_reg * self.lam
+        if self.ic_weight > 0.0:
+            self.loss_ic = self.criterionIC(flow, neg_flow)
+            total = total + self.loss_ic * self.ic_weight
         if self.seg_labels is not None:
             self.loss_dice = self.criterionDice.loss(self.seg_B, self.seg_A, flow)
             total = total + self.loss_dice * self.seg_weight
@@ -191,4 +227,6 @@ class Registration3DModel(object):
             out = {self.similarity: float(sim.detach()), 'grad': float(self.loss_grad.detach())}
         if self.seg_labels is not None:
             out['dice'] = float(self.loss_dice.detach())
+        if self.ic_weight > 0.0:
+            out['ic'] = float(self.loss_ic.detach())
         return out

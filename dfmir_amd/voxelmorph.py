@@ -176,7 +176,10 @@ class VxmDense(nn.Module):
         # A model that never reads it sets this and gets None in its place: 7 VecInt warps, a resize and a warp less.
         self.skip_unused_target = False
 
-    def forward(self, source, target, registration=False):
+    def forward(self, source, target, registration=False, return_neg_flow=False):
+        """return_neg_flow (build-defined; bidir training only): the return becomes (y_source, y_target, pos_flow,
+        neg_flow), the second direction's integrated full-resolution field with it -- None where skip_unused_target left
+        it out.  Every other call returns what it always did."""
         x = ops.upcat_channels(source, target)
         x = self.unet_model(x)
         flow_field = self.flow(x)
@@ -202,6 +205,8 @@ class VxmDense(nn.Module):
         y_source = self.transformer(source, pos_flow)
         y_target = self.transformer(target, neg_flow) if (self.bidir and neg_flow is not None) else None
         if not registration:
+            if self.bidir and return_neg_flow:
+                return y_source, y_target, pos_flow, neg_flow
             return (y_source, y_target, pos_flow) if self.bidir else (y_source, preint_flow)
         return y_source, pos_flow
 

@@ -55,7 +55,8 @@ const char* dfmir_last_error(void);
  *     DFMIR_NO_1X1_WGRAD, DFMIR_CONV3D_NO_FLOW_WGRAD, DFMIR_CONV3D_NO_S2, DFMIR_RESIZE_NO_ROWS, DFMIR_NCC_NO_D_FUSE, DFMIR_SMOOTH_NO_MARCH,
  *     DFMIR_NO_BWD_PAIR (dgrad and wgrad of a 3x3 layer as two launches), DFMIR_BWD_PAIR=0|1 (the same switch with an explicit
  *     value; unset = the build's default), DFMIR_BWD_PAIR_ORDER=n (workgroup order inside dfmir_conv3x3_bwd_pair's grid:
- *     0 weight gradient first, 1 data gradient first, 2 interleaved in groups of 8).
+ *     0 weight gradient first, 1 data gradient first, 2 interleaved in groups of 8), DFMIR_INVCONS_FIXED64 (dfmir_invcons_bwd: dv
+ *     through the 64-bit fixed-point scatter on every shape).
  * ---------------------------------------------------------------------------------------- */
 int dfmir_set_option(const char* name, const char* value);
 int dfmir_get_option(const char* name, char* buf, int buf_len);
@@ -594,6 +595,33 @@ int dfmir_bend_fwd(const float* flow, float* ws, float* out, int B, int C, int D
                    float hx, void* stream);
 int dfmir_bend_bwd(const float* flow, const float* gout, float* dflow, int B, int C, int D, int H, int W, float hz,
                    float hy, float hx, void* stream);
+/* Inverse consistency of a pair of displacement fields (build-defined: the reference has no such term).  u, v:
+ * [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when nd == 2); channel i displaces axis i in voxels, in the order
+ * (z,) y, x, exactly as the warp kernels read a flow.
+ *   r(x)    = u(x) + v(x + u(x))      v sampled (bi/tri)linearly, corners outside the volume read as 0: r = u + warp(v, u)
+ *   IC_b    = sum over the nd * S elements of sample b of r^2 / (nd * S)     (S = voxels per sample)
+ * A voxel whose sample point leaves the volume contributes |u|^2.  dfmir_invcons_fwd: per_sample[b] = IC_b, loss[0] = their
+ * mean, rmax[0] = max |r_c| over the call (dfmir_invcons_bwd reads it: keep it between the two calls).
+ * dfmir_invcons_bwd, the exact adjoint with k = 2 gout[0] / (B nd S); du and dv are written entirely, either may be NULL:
+ *   du_c(x) = k ( r_c(x) + sum_c' r_c'(x) d_c v_c'(x + u(x)) )    d_c = the derivative of the interpolant as the warp
+ *             backward forms it: corner differences, zero-padded corners taking part as zeros
+ *   dv      = the transpose of the interpolation applied to k r (a scatter to the up to 2^nd corners).  Where W % 4 == 0 and
+ *             u, du, dv, ws are 16-byte aligned, k r is written once and handed to the owner-gather adjoint of the warp
+ *             (dfmir_warp_bwd_own: no device-scope atomics, bit-reproducible as that call is).  Elsewhere it is summed with
+ *             global atomics as 64-bit fixed-point integers whose unit lies >= 29 bits below max |k r|: bit-identical from run
+ *             to run as well (a max |k r| that is not finite makes dv NaN), but several times slower.
+ * r is recomputed, never stored.  Refused ("invalid argument", nothing is launched): nd outside {2, 3}, B < 1, an extent
+ * < 2, a NULL pointer, B * nd * S >= 2^31.  ws: dfmir_invcons_ws_floats / dfmir_invcons_bwd_ws_floats floats (-1 for a
+ * refused shape), 8-byte aligned, need not be zeroed; the backward's may be NULL when dv is.  The forward sums through one
+ * double slot per workgroup in a fixed order: the values are bit-identical from run to run.  16-byte accesses of u and du
+ * where W % 4 == 0 and both are 16-byte aligned.  Nothing syncs, allocates or keeps state (gout is read on the device): both
+ * calls capture into a hipGraph. */
+long long dfmir_invcons_ws_floats(int nd, int B, int D, int H, int W);
+int dfmir_invcons_fwd(int nd, const float* u, const float* v, float* ws, float* per_sample, float* loss, float* rmax, int B,
+                      int D, int H, int W, void* stream);
+long long dfmir_invcons_bwd_ws_floats(int nd, int B, int D, int H, int W);
+int dfmir_invcons_bwd(int nd, const float* u, const float* v, const float* gout, const float* rmax, float* du, float* dv,
+                      float* ws, int B, int D, int H, int W, void* stream);
 /* NMI_Loss (util/losses.py:263-348): out[0] = -MI of the soft-binned (Parzen) joint histogram of y_true and y_pred, both
  * first clamped to [0, max_clip]; all n voxels (batch and channels included) form ONE histogram.  Per voxel
  * a_k = exp(-preterm (y_true - c_k)^2) normalised over k (b_k the same for y_pred), pab[i][j] = sum_v b[i] a[j] / V,
