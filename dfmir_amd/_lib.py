@@ -147,6 +147,9 @@ _SIGS = {
     "dfmir_invcons_fwd": [c_int, P, P, P, P, P, P] + [c_int] * 4 + [P],
     "dfmir_invcons_bwd_ws_floats": [c_int] * 5,
     "dfmir_invcons_bwd": [c_int, P, P, P, P, P, P, P] + [c_int] * 4 + [P],
+    "dfmir_landmark_ws_floats": [c_int] * 6,
+    "dfmir_landmark_fwd": [c_int] + [P] * 10 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
+    "dfmir_landmark_bwd": [c_int] + [P] * 8 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
     "dfmir_nmi_ws_floats": [c_longlong, c_int],
     "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
     "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],
@@ -221,6 +224,7 @@ def lib():
         h.dfmir_bend_ws_floats.restype = c_longlong
         h.dfmir_invcons_ws_floats.restype = c_longlong
         h.dfmir_invcons_bwd_ws_floats.restype = c_longlong
+        h.dfmir_landmark_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong
         h.dfmir_warp_dice_ws_floats.restype = c_longlong

@@ -70,3 +70,20 @@ def inverse_consistency_error(flow_ab, flow_ba, spacing=None):
         h = vals[0]
     ic = ops.inverse_consistency_per_sample(flow_ab, flow_ba)
     return torch.sqrt(ic * float(nd)) * h
+
+
+@torch.no_grad()
+def landmark_error(flow, fixed_pts, moving_pts, spacing=None, weight=None):
+    """The target registration error of corresponding landmarks, the headline number of multi-modal registration:
+    dict(tre [B,K], initial [B,K], mean [B]).  `tre` = |h * (q + flow(q) - p)| per landmark from the landmark kernel
+    (ops.landmark_distances; q = fixed_pts, p = moving_pts [B,K,nd] in voxel coordinates, axis order (z,) y, x as the flow's
+    channels, h = `spacing`, nd positive numbers, None = 1: anisotropic spacing is applied per axis), NaN for an invalid
+    landmark (weight 0, a non-finite coordinate, q outside the volume); `initial` = |h * (q - p)|, the error before
+    registration, with the same NaN pattern; `mean` = per sample the weighted mean of `tre` over its valid landmarks (NaN
+    without one).  The definition: losses.Landmark_Loss."""
+    tre, mean = ops.landmark_distances(flow, fixed_pts, moving_pts, weight, spacing)
+    nd = flow.dim() - 2
+    h = torch.tensor(ops.bending_spacing(spacing, (nd,), "landmark_error"), dtype=torch.float32, device=tre.device)
+    initial = ((fixed_pts - moving_pts) * h).square().sum(2).sqrt()
+    initial = torch.where(torch.isnan(tre), tre, initial)
+    return dict(tre=tre, initial=initial, mean=mean)

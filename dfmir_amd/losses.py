@@ -262,6 +262,53 @@ class InverseConsistency_Loss(_Loss):
         return loss
 
 
+class Landmark_Loss(_Loss):
+    """Build-defined (the reference has no landmark code): the registration error of corresponding landmarks carried
+    through a displacement field, the keypoint supervision of multi-modal registration.
+    `Landmark_Loss(dim, penalty, spacing)(flow, fixed_pts, moving_pts, weight=None)`.
+
+    flow u [B,nd,*vol], nd = `dim` = 2 or 3, fp32, read exactly as ops.warp reads it: channel a displaces axis a in voxels,
+    in the order (z,) y, x, and warped(x) = moving(x + u(x)) with x in the fixed image's grid -- so a point q of the FIXED
+    image corresponds to q + u(q) in the MOVING image.  fixed_pts q and moving_pts p: [B,K,nd] fp32 voxel coordinates, axis
+    order as the flow's channels, 1 <= K <= 4096; weight w [B,K] fp32 (None = all ones; 0 marks a padding entry, so samples
+    with different landmark counts share one K); `spacing` = nd positive finite numbers h (None = 1), applied per axis.
+    With S_a the extent of axis a, per landmark:
+
+        m_bk = q + u_b(q)         u_b sampled (bi/tri)linearly at q in the cell i0_a = min(floor(q_a), S_a - 2): a point on
+                                  the upper face q_a = S_a - 1 reads the last cell with weight 1 on its upper corner
+        r_bk = h * (m_bk - p),    d_bk = |r_bk|_2, the target registration error (TRE) of that landmark
+        valid: w > 0, every coordinate of q and p finite, 0 <= q_a <= S_a - 1 on every axis
+
+    An invalid landmark contributes to no sum and gets no gradient (its d is NaN in ops.landmark_distances).  Over the whole
+    call, with Wsum the sum of w over the valid landmarks:
+
+        penalty='l2':   loss = sum w d^2 / Wsum
+        penalty='tre':  loss = sum w d / Wsum          (the derivative at d = 0 is defined as 0)
+        Wsum = 0 (no valid landmark): loss 0 and an all-zero gradient, not NaN
+
+    The gradient goes to the flow only: dflow[b, a, corner] += gout * (w / Wsum) * dl/dr_a * h_a * cornerweight, dl/dr_a =
+    2 r_a ('l2') or r_a / d ('tre'); zeros at every voxel no valid landmark touches.  `loss_mult` scales the result.  Value
+    and gradient are bit-identical from run to run, landmarks in one cell or at one position included; validity is decided
+    on the device, so the call captures into a hipGraph (ops.landmark_loss; dfmir_amd/csrc/landmark.hip)."""
+
+    def __init__(self, dim=3, penalty='l2', spacing=None, name=None, loss_mult=None, *args, **kwargs):
+        super().__init__(name=name or 'landmark')
+        if dim not in (2, 3):
+            raise ValueError("Landmark_Loss: dim must be 2 or 3, got %r" % (dim,))
+        if penalty not in ops.LANDMARK_PENALTIES:
+            raise ValueError("Landmark_Loss: penalty must be 'l2' or 'tre', got %r" % (penalty,))
+        self.dim, self.penalty, self.loss_mult = dim, penalty, loss_mult
+        self.spacing = ops.bending_spacing(spacing, (dim,), "Landmark_Loss")
+
+    def forward(self, flow, fixed_pts, moving_pts, weight=None, *args, **kwargs):
+        if flow.dim() - 2 != self.dim:
+            raise ValueError("Landmark_Loss(dim=%d) got a %d-D field" % (self.dim, flow.dim() - 2))
+        loss = ops.landmark_loss(flow, fixed_pts, moving_pts, weight, self.spacing, self.penalty)
+        if self.loss_mult is not None:
+            loss = ops.scale(loss.view(1), self.loss_mult).view(())
+        return loss
+
+
 class MSE(object):
     """vxm `MSE().loss(y_true, y_pred)` = mean((y_true - y_pred)^2) (models/voxelmorph/torchvoxelmorph/losses.py:70-76);
     gradients to both arguments."""

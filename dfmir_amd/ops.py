@@ -2582,6 +2582,125 @@ def inverse_consistency_per_sample(u, v):
     return _invcons_fwd(_c(u), _c(v), geom)[:geom[1]].clone()
 
 
+LANDMARK_PENALTIES = {'l2': 0, 'tre': 1}
+LANDMARK_MAX_K = 4096
+
+
+def _landmark_geom(flow, fixed_pts, moving_pts, weight, spacing, what):
+    """(nd, B, K, D, H, W, hz, hy, hx) of a landmark call after the argument checks (nothing is launched on a bad one).
+    moving_pts and weight may be None."""
+    if flow.dim() not in (4, 5):
+        raise DfmirHipError("%s: expects a [B,nd,*vol] flow, got %d dims" % (what, flow.dim()))
+    nd = flow.dim() - 2
+    if flow.shape[1] != nd:
+        raise DfmirHipError("%s: a %d-D flow needs %d channels, got %s" % (what, nd, nd, tuple(flow.shape)))
+    B = int(flow.shape[0])
+    for name, t in (("fixed_pts", fixed_pts), ("moving_pts", moving_pts)):
+        if t is None:
+            continue
+        if t.dim() != 3 or int(t.shape[0]) != B or int(t.shape[2]) != nd or tuple(t.shape) != tuple(fixed_pts.shape):
+            raise DfmirHipError("%s: %s %s mismatch (expected [B,K,nd] = [%d,K,%d] points for a flow %s, both sets of one "
+                                "shape)" % (what, name, tuple(t.shape), B, nd, tuple(flow.shape)))
+    K = int(fixed_pts.shape[1])
+    if weight is not None and tuple(weight.shape) != (B, K):
+        raise DfmirHipError("%s: weight %s mismatch (expected [B,K] = [%d,%d])" % (what, tuple(weight.shape), B, K))
+    for name, t in (("flow", flow), ("fixed_pts", fixed_pts), ("moving_pts", moving_pts), ("weight", weight)):
+        if t is not None and t.dtype != torch.float32:
+            raise DfmirHipError("%s: fp32 tensors only (%s is %s)" % (what, name, t.dtype))
+    if not 1 <= K <= LANDMARK_MAX_K:
+        raise DfmirHipError("%s: K must lie in [1, %d], got %d landmarks" % (what, LANDMARK_MAX_K, K))
+    hs = bending_spacing(spacing, (nd,), what)
+    hz, hy, hx = hs if nd == 3 else (1.0,) + hs
+    for t in (fixed_pts, moving_pts, weight):
+        if t is not None and t.device != flow.device:
+            raise DfmirHipError("%s: flow on %s, points on %s" % (what, flow.device, t.device))
+    _need(flow, fixed_pts, moving_pts, weight)
+    D, H, W = (int(n) for n in (flow.shape[2:] if nd == 3 else (1,) + tuple(flow.shape[2:])))
+    if lib().dfmir_landmark_ws_floats(nd, B, K, D, H, W) < 0:
+        raise DfmirHipError("%s: needs B >= 1, every extent >= 2 and fewer than 2^31 flow elements, got %s"
+                            % (what, tuple(flow.shape)))
+    return nd, B, K, D, H, W, hz, hy, hx
+
+
+def _landmark_fwd(flow, fixed_pts, moving_pts, weight, geom, penalty, want_mapped=False):
+    """(out [2] = loss, Wsum; d [B,K]; per_sample [B]; mapped [B,K,nd] or None) of contiguous inputs."""
+    nd, B, K, D, H, W, hz, hy, hx = geom
+    dev = flow.device
+    ws = torch.empty(int(lib().dfmir_landmark_ws_floats(nd, B, K, D, H, W)), device=dev, dtype=torch.float32)
+    out = torch.empty(2, device=dev, dtype=torch.float32)
+    d = torch.empty((B, K), device=dev, dtype=torch.float32)
+    per = torch.empty(B, device=dev, dtype=torch.float32)
+    mapped = torch.empty((B, K, nd), device=dev, dtype=torch.float32) if want_mapped else None
+    check(lib().dfmir_landmark_fwd(nd, _p(flow), _p(fixed_pts), _p(moving_pts), _p(weight), _p(ws), _p(mapped), _p(d), _p(per),
+                                   _p(out), _p(out[1:]), B, K, D, H, W, hz, hy, hx, penalty, _st()))
+    return out, d, per, mapped
+
+
+class LandmarkFn(Function):
+    """dfmir_landmark_fwd / _bwd: the forward keeps the flow, the points and Wsum; the backward recomputes the residuals."""
+
+    @staticmethod
+    def forward(ctx, flow, fixed_pts, moving_pts, weight, geom, penalty):
+        flow, fixed_pts, moving_pts = _c(flow), _c(fixed_pts), _c(moving_pts)
+        weight = None if weight is None else _c(weight)
+        out = _landmark_fwd(flow, fixed_pts, moving_pts, weight, geom, penalty)[0]
+        ctx.save_for_backward(flow, fixed_pts, moving_pts, weight, out)
+        ctx.meta = (geom, penalty)
+        return out[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        flow, fixed_pts, moving_pts, weight, out = ctx.saved_tensors
+        (nd, B, K, D, H, W, hz, hy, hx), penalty = ctx.meta
+        g = _c(g)
+        dflow = torch.empty_like(flow)
+        ws = torch.empty(int(lib().dfmir_landmark_ws_floats(nd, B, K, D, H, W)), device=flow.device, dtype=torch.float32)
+        check(lib().dfmir_landmark_bwd(nd, _p(flow), _p(fixed_pts), _p(moving_pts), _p(weight), _p(g), _p(out[1:]), _p(dflow),
+                                       _p(ws), B, K, D, H, W, hz, hy, hx, penalty, _st()))
+        return dflow, None, None, None, None, None
+
+
+def landmark_loss(flow, fixed_pts, moving_pts, weight=None, spacing=None, penalty='l2'):
+    """Landmark loss of a flow [B,nd,*vol] (nd = 2 or 3, fp32; build-defined, the definition: losses.Landmark_Loss) against K
+    pairs of corresponding points per sample: fixed_pts q and moving_pts p [B,K,nd] in voxel coordinates, axis order as the
+    flow's channels ((z,) y, x); weight [B,K] (None = 1; 0 marks a padding entry); spacing = nd positive numbers (None = 1).
+    m = q + flow(q) (sampled (bi/tri)linearly), d = |spacing * (m - p)|; penalty 'l2': sum w d^2 / Wsum, 'tre': sum w d /
+    Wsum over the valid landmarks (w > 0, finite coordinates, q inside the volume), Wsum their sum of w; no valid landmark:
+    0 with a zero gradient.  A scalar with a gradient to `flow` only; value and gradient are bit-identical from run to run
+    (dfmir_amd/csrc/landmark.hip).  Raises before any launch on mismatched batch or nd, a dtype other than fp32, K outside
+    [1, 4096], a bad spacing (ValueError) and an unknown penalty (ValueError); a CPU tensor raises the usual "no CPU
+    fallback" error."""
+    if penalty not in LANDMARK_PENALTIES:
+        raise ValueError("landmark_loss: penalty must be 'l2' or 'tre', got %r" % (penalty,))
+    if moving_pts is None:
+        raise DfmirHipError("landmark_loss: moving_pts is required")
+    geom = _landmark_geom(flow, fixed_pts, moving_pts, weight, spacing, "landmark_loss")
+    return LandmarkFn.apply(flow, fixed_pts, moving_pts, weight, geom, LANDMARK_PENALTIES[penalty])
+
+
+@torch.no_grad()
+def landmark_distances(flow, fixed_pts, moving_pts, weight=None, spacing=None):
+    """(d [B,K], per_sample [B]) without gradient: the target registration error d = |spacing * (q + flow(q) - p)| of every
+    landmark (NaN for an invalid one) and per sample the weighted mean of d over its valid landmarks (NaN without one).
+    Arguments and checks as landmark_loss."""
+    if moving_pts is None:
+        raise DfmirHipError("landmark_distances: moving_pts is required")
+    geom = _landmark_geom(flow, fixed_pts, moving_pts, weight, spacing, "landmark_distances")
+    weight = None if weight is None else _c(weight)
+    _, d, per, _ = _landmark_fwd(_c(flow), _c(fixed_pts), _c(moving_pts), weight, geom, 0)
+    return d, per
+
+
+@torch.no_grad()
+def warp_points(points, flow):
+    """Points [B,K,nd] of the fixed image carried into the moving image by a flow [B,nd,*vol]: q + flow(q), the flow sampled
+    (bi/tri)linearly, [B,K,nd] without gradient.  A point with a non-finite coordinate or outside [0, S_a - 1] on an axis
+    gives a NaN row.  The same kernel as landmark_loss, the same checks."""
+    geom = _landmark_geom(flow, points, None, None, None, "warp_points")
+    return _landmark_fwd(_c(flow), _c(points), None, None, geom, 0, want_mapped=True)[3]
+
+
 class MulFn(Function):
     """a * b element-wise, same shapes (`prediction * mask`, util/losses.py:120-121)."""
 

@@ -11,13 +11,15 @@ term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map aga
 (`losses.LabelDice`).  regularizer='bending' swaps the diffusion penalty for the build-defined second-order
 `BendingEnergy_Loss`.  symmetric=True trains both directions of the bidir network (the similarity is charged both ways);
 inverse_consistency=w adds w * the build-defined `InverseConsistency_Loss` of the two integrated fields.
+landmark_weight=w adds w * the build-defined `Landmark_Loss` of corresponding keypoints carried through the flow.
 """
 import numpy as np
 import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import BendingEnergy_Loss, Grad_Loss, InverseConsistency_Loss, LabelDice, MIND_Loss, NCC_Loss, NMI_Loss
+from .losses import (BendingEnergy_Loss, Grad_Loss, InverseConsistency_Loss, LabelDice, Landmark_Loss, MIND_Loss, NCC_Loss,
+                     NMI_Loss)
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
@@ -26,7 +28,8 @@ class Registration3DModel(object):
     def __init__(self, shape, features=None, lam=1.0, lr=2e-4, betas=(0.5, 0.999), win=9, device="cuda",
                  capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
                  seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3, mind_radius=2, mind_dilation=2,
-                 regularizer='diffusion', spacing=None, symmetric=False, inverse_consistency=0.0):
+                 regularizer='diffusion', spacing=None, symmetric=False, inverse_consistency=0.0, landmark_weight=0.0,
+                 landmark_penalty='l2'):
         """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window, or with ncc_kernel='gaussian' the Gaussian window of
         sigma = ncc_sigma, whose 3-D form is build-defined: see NCC_Loss; `win` is then unused) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
@@ -40,8 +43,8 @@ class Registration3DModel(object):
         regularizer: 'diffusion' (default: Grad_Loss(penalty='l2'), loss key 'grad') or 'bending': lam *
         BendingEnergy_Loss(dim=len(shape), spacing=spacing)(flow), the second-order penalty that charges nothing for an
         affine motion (build-defined: see BendingEnergy_Loss), for 2-D and 3-D shapes; `spacing` is the voxel spacing in
-        the order (z,) y, x (None = 1) and is read by the bending energy only.  The loss key is then 'bending' instead
-        of 'grad'.
+        the order (z,) y, x (None = 1) and is read by the bending energy and by the landmark term.  The loss key is then
+        'bending' instead of 'grad'.
         symmetric (build-defined, VoxelMorph's own bidirectional training; default False = the one-directional step): the
         target branch of the bidir network is computed and the similarity becomes 0.5 * (sim(y_source, real_B) +
         sim(y_target, real_A)) under the similarity's own loss key ('nmi' mirrors its argument order: NMI(real_A,
@@ -50,6 +53,13 @@ class Registration3DModel(object):
         inverse_consistency = w > 0 (needs symmetric=True, ValueError otherwise): adds w * InverseConsistency_Loss(
         symmetric=True)(flow, neg_flow), how far the two integrated fields are from being inverses of each other
         (build-defined: see InverseConsistency_Loss), for 2-D and 3-D shapes; `get_current_losses()` gains 'ic'.
+        landmark_weight = w > 0 (default 0 = no landmark term): `set_input` then also takes data['A_pts'] (landmarks of
+        the moving image A) and data['B_pts'] (the corresponding landmarks of the fixed image B), [B,K,nd] fp32 voxel
+        coordinates in the order (z,) y, x, and optionally data['pts_weight'] [B,K] (0 marks a padding entry), and the
+        step adds w * Landmark_Loss(penalty=landmark_penalty, spacing=spacing)(flow, B_pts, A_pts, pts_weight)
+        (build-defined: see Landmark_Loss; landmark_penalty 'l2' or 'tre'), for 2-D and 3-D shapes; with symmetric=True
+        the term is 0.5 * (L(flow, B_pts, A_pts) + L(neg_flow, A_pts, B_pts)); `get_current_losses()` gains 'landmark'.
+        Which landmarks count is decided on the device, so the captured step needs no host check.
         capture_step (build-defined, as REGISTRATIONModel's opt.capture_step): after two eager steps forward +
         losses + backward are captured into ONE hipGraph and replayed; Adam and the gradient all-reduce stay eager.
         Small volumes are host-bound otherwise (128^3: 3.7 ms of Python / autograd / ctypes per 5.2 ms step)."""
@@ -87,6 +97,13 @@ class Registration3DModel(object):
         if self.ic_weight > 0.0:
             self.criterionIC = InverseConsistency_Loss(dim=len(shape), symmetric=True)
             self._outputs += ('loss_ic',)
+        self.landmark_weight = float(landmark_weight)
+        if not self.landmark_weight >= 0.0:
+            raise ValueError("landmark_weight must be a weight >= 0, got %r" % (landmark_weight,))
+        self.pts_A = self.pts_B = self.pts_w = None
+        if self.landmark_weight > 0.0:
+            self.criterionLandmark = Landmark_Loss(dim=len(shape), penalty=landmark_penalty, spacing=spacing)
+            self._outputs += ('loss_landmark',)
         self.seg_labels, self.seg_weight = seg_labels, float(seg_weight)
         self.seg_A = self.seg_B = None
         if seg_labels is not None:
@@ -119,6 +136,15 @@ class Registration3DModel(object):
             # (the range check of as_label_map may sync with the host: here, outside any captured region)
             self.seg_A = ops.as_label_map(data['A_seg'].to(self.device, non_blocking=True))
             self.seg_B = ops.as_label_map(data['B_seg'].to(self.device, non_blocking=True))
+        if self.landmark_weight > 0.0:
+            for k in ('A_pts', 'B_pts'):
+                if k not in data:
+                    raise KeyError("Registration3DModel(landmark_weight=...) needs data[%r]: [B,K,nd] landmark coordinates"
+                                   % k)
+            self.pts_A = data['A_pts'].to(self.device, non_blocking=True)
+            self.pts_B = data['B_pts'].to(self.device, non_blocking=True)
+            w = data.get('pts_weight')
+            self.pts_w = None if w is None else w.to(self.device, non_blocking=True)
 
     def _forward_backward(self):
         if self.symmetric:
@@ -151,6 +177,12 @@ class Registration3DModel(object):
         if self.ic_weight > 0.0:
             self.loss_ic = self.criterionIC(flow, neg_flow)
             total = total + self.loss_ic * self.ic_weight
+        if self.landmark_weight > 0.0:
+            loss_lm = self.criterionLandmark(flow, self.pts_B, self.pts_A, self.pts_w)
+            if self.symmetric:
+                loss_lm = (loss_lm + self.criterionLandmark(neg_flow, self.pts_A, self.pts_B, self.pts_w)) * 0.5
+            self.loss_landmark = loss_lm
+            total = total + loss_lm * self.landmark_weight
         if self.seg_labels is not None:
             self.loss_dice = self.criterionDice.loss(self.seg_B, self.seg_A, flow)
             total = total + self.loss_dice * self.seg_weight
@@ -176,6 +208,9 @@ class Registration3DModel(object):
         seg = self.seg_labels is not None
         if seg:
             shape += (tuple(self.seg_A.shape), tuple(self.seg_B.shape))
+        lm = self.landmark_weight > 0.0
+        if lm:
+            shape += (tuple(self.pts_A.shape), tuple(self.pts_B.shape), None if self.pts_w is None else tuple(self.pts_w.shape))
         if st['graph'] is not None and st['shape'] != shape:
             st.update(graph=None, eager_steps=0)
         if st['force_eager'] or (st['graph'] is None and st['eager_steps'] < 2):
@@ -191,6 +226,9 @@ class Registration3DModel(object):
             if seg:
                 st['in_segA'], st['in_segB'] = self.seg_A.clone(), self.seg_B.clone()
                 self.seg_A, self.seg_B = st['in_segA'], st['in_segB']
+            if lm:
+                st['in_pts'] = [None if t is None else t.clone() for t in (self.pts_A, self.pts_B, self.pts_w)]
+                self.pts_A, self.pts_B, self.pts_w = st['in_pts']
             for k in self._outputs:                                       # drop the previous step's autograd graph
                 v = getattr(self, k, None)
                 if torch.is_tensor(v) and v.grad_fn is not None:
@@ -212,10 +250,16 @@ class Registration3DModel(object):
             if seg and self.seg_A is not st['in_segA']:
                 st['in_segA'].copy_(self.seg_A, non_blocking=True)
                 st['in_segB'].copy_(self.seg_B, non_blocking=True)
+            if lm:
+                for buf, t in zip(st['in_pts'], (self.pts_A, self.pts_B, self.pts_w)):
+                    if buf is not None and t is not buf:
+                        buf.copy_(t, non_blocking=True)
             vars(self).update(st['outputs'])
             self.real_A, self.real_B = st['in_A'], st['in_B']
             if seg:
                 self.seg_A, self.seg_B = st['in_segA'], st['in_segB']
+            if lm:
+                self.pts_A, self.pts_B, self.pts_w = st['in_pts']
         st['graph'].replay()
         self._apply_updates()
 
@@ -229,4 +273,6 @@ class Registration3DModel(object):
             out['dice'] = float(self.loss_dice.detach())
         if self.ic_weight > 0.0:
             out['ic'] = float(self.loss_ic.detach())
+        if self.landmark_weight > 0.0:
+            out['landmark'] = float(self.loss_landmark.detach())
         return out

@@ -622,6 +622,42 @@ int dfmir_invcons_fwd(int nd, const float* u, const float* v, float* ws, float* 
 long long dfmir_invcons_bwd_ws_floats(int nd, int B, int D, int H, int W);
 int dfmir_invcons_bwd(int nd, const float* u, const float* v, const float* gout, const float* rmax, float* du, float* dv,
                       float* ws, int B, int D, int H, int W, void* stream);
+/* Landmark (keypoint) registration error of a displacement field (build-defined: the reference has no landmark code).
+ * flow u: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when nd == 2); channel a displaces axis a in voxels, in the
+ * order (z,) y, x, exactly as the warp kernels read a flow: warped(x) = moving(x + u(x)) with x in the fixed image's grid,
+ * so a point q of the FIXED image corresponds to q + u(q) in the MOVING image.  fixed_pts q, moving_pts p: [B][K][nd] fp32
+ * voxel coordinates, axis order as the flow's channels; weight w: [B][K] fp32 or NULL (= all ones; 0 marks a padding entry);
+ * spacing h = (hz, hy, hx) > 0, applied per axis (hz is not read when nd == 2).  With S_a the extent of axis a:
+ *   m_bk = q + u_b(q)      u_b sampled (bi/tri)linearly at q in the cell i0_a = min(floor(q_a), S_a - 2): a point on the
+ *                          upper face q_a = S_a - 1 reads the last cell with weight 1 on its upper corner, never outside
+ *   r_bk = h (.) (m_bk - p),   d_bk = |r_bk|_2, the target registration error of the landmark
+ *   valid: w > 0, every coordinate of q and p finite, 0 <= q_a <= S_a - 1 on every axis.  An invalid landmark has d = NaN
+ *          (and a NaN row in `mapped`), contributes to no sum and gets no gradient.
+ *   loss  = sum w d^2 / Wsum (penalty 0, 'l2') or sum w d / Wsum (penalty 1, 'tre'; the derivative at d = 0 is 0), over the
+ *           valid landmarks of the whole call, Wsum = their sum of w.  Wsum = 0: loss 0 and an all-zero gradient, not NaN.
+ * dfmir_landmark_fwd: mapped[b][k][:] = m (may be NULL), d[b][k] = d, per_sample[b] = the w-weighted mean of d over the valid
+ * landmarks of sample b (NaN without one), loss[0], wsum[0] = Wsum (dfmir_landmark_bwd reads it: keep it between the two
+ * calls).  moving_pts == NULL: the call only maps points -- `mapped` must be given; d, per_sample, loss, wsum and ws are not
+ * written and may be NULL; validity is then that of q and w alone.
+ * dfmir_landmark_bwd: the gradient to the flow only, dflow[b][a][corner] += gout[0] (w / Wsum) dl/dr_a h_a cornerweight with
+ * dl/dr_a = 2 r_a ('l2') or r_a / d ('tre'); dflow is written entirely, zeros elsewhere.  After the zero fill every landmark's
+ * cell, corner weights and gradient coefficients are formed once in ws, then an owner-gather over landmark pairs: a thread
+ * owns one landmark and sums, per corner voxel of its cell and in landmark-index order, the
+ * contributions of every landmark of its sample that touches that voxel; the lowest-index toucher stores the sum.  No
+ * atomics, no volume-sized scratch: bit-identical from run to run on every input, collisions included.
+ * Refused ("invalid argument", nothing is launched): nd outside {2, 3}, B < 1, K outside [1, 4096], an extent < 2,
+ * B * nd * S >= 2^31, a spacing that is not positive and finite, a penalty outside {0, 1}, a NULL pointer other than the
+ * optional ones.  ws: dfmir_landmark_ws_floats floats for either call (-1 for a refused shape), 8-byte aligned, need not be
+ * zeroed or kept between the calls.  The sums
+ * go through double slots added in a fixed order: every output is bit-identical from run to run.  Nothing syncs, allocates
+ * or keeps state (gout is read on the device): both calls capture into a hipGraph. */
+long long dfmir_landmark_ws_floats(int nd, int B, int K, int D, int H, int W);
+int dfmir_landmark_fwd(int nd, const float* flow, const float* fixed_pts, const float* moving_pts, const float* weight,
+                       float* ws, float* mapped, float* d, float* per_sample, float* loss, float* wsum, int B, int K, int D,
+                       int H, int W, float hz, float hy, float hx, int penalty, void* stream);
+int dfmir_landmark_bwd(int nd, const float* flow, const float* fixed_pts, const float* moving_pts, const float* weight,
+                       const float* gout, const float* wsum, float* dflow, float* ws, int B, int K, int D, int H, int W,
+                       float hz, float hy, float hx, int penalty, void* stream);
 /* NMI_Loss (util/losses.py:263-348): out[0] = -MI of the soft-binned (Parzen) joint histogram of y_true and y_pred, both
  * first clamped to [0, max_clip]; all n voxels (batch and channels included) form ONE histogram.  Per voxel
  * a_k = exp(-preterm (y_true - c_k)^2) normalised over k (b_k the same for y_pred), pab[i][j] = sum_v b[i] a[j] / V,
