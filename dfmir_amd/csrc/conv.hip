@@ -844,9 +844,7 @@ static int conv_fwd_impl(const DfConvGeom* g, const float* x, const float* x_ama
     float* ys = y + (long long)n0 * (out_img / 4);
     long long Ps = (long long)k.g.N * g->Do * g->Ho * g->Wo;
     // dgrad of a stride-2 conv: parity-class enumeration (taps that only meet the inserted zeros are skipped)
-    static DfOptFlag dil2_o{"DFMIR_NO_DIL2"};
-  const bool dil2_off = dil2_o.get();
-    const bool dil2 = g->dil == 2 && g->stride == 1 && g->pad_mode == 0 && g->KD * g->KH * g->KW <= 128 && g->Cout <= 64 && !dil2_off;
+    const bool dil2 = g->dil == 2 && g->stride == 1 && g->pad_mode == 0 && g->KD * g->KH * g->KW <= 128 && g->Cout <= 64;
     k.ncx = k.ncy = k.ncz = 1;
     k.Dm = g->Do; k.Hm = g->Ho; k.Wm = g->Wo;
     if (dil2) {
@@ -858,9 +856,7 @@ static int conv_fwd_impl(const DfConvGeom* g, const float* x, const float* x_ama
     }
     // few output voxels (the deep U-Net levels: 8^2 .. 32^2 x 16 images, 10x12x14 voxels): 256-pixel tiles leave most
     // CUs idle while each workgroup walks the whole K loop; 64 x 64 tiles give 4x the workgroups at a quarter of the work
-    static DfOptFlag small_o{"DFMIR_NO_SMALL_TILES"};
-  const bool small_off = small_o.get();
-    const bool small_p = !small_off && (Ps + 255) / 256 < 192 && g->Cout > 8;
+    const bool small_p = (Ps + 255) / 256 < 192 && g->Cout > 8;
     if (dil2) {
       if (small_p) {
         dim3 grid((unsigned)((Ps + 63) / 64), (unsigned)((g->Cout + 63) / 64));
@@ -875,8 +871,7 @@ static int conv_fwd_impl(const DfConvGeom* g, const float* x, const float* x_ama
       conv_mfma_k<2, 2, 1, 1><<<grid, 256, 0, st>>>(xs, w_tcc, bias, ys, k);
     } else if (g->Cout > 64) {
       const long long big = ((Ps + 127) / 128) * ((g->Cout + 127) / 128);
-      static DfOptInt big_o{"DFMIR_GEMM_BIG_MIN", 256};
-  const int big_min = big_o.get();
+      constexpr int big_min = 256;
       if (big < big_min) {   // small GEMMs (PatchNCE MLP: 4096 rows x 256): 64x64 tiles fill the 256 CUs
         dim3 grid((unsigned)((Ps + 63) / 64), (unsigned)((g->Cout + 63) / 64));
         conv_mfma_k<2, 2, 1, 1><<<grid, 256, 0, st>>>(xs, w_tcc, bias, ys, k);

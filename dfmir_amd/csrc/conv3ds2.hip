@@ -442,8 +442,7 @@ extern "C" int dfmir_conv3d_s2_wgrad(const DfConvGeom* g, const float* x, const 
   k.npatch = (long long)g->N * g->Do * k.ny * k.nx;
   long long want = 512 / k.ngroups;                          // two workgroups per CU
   if (want < 1) want = 1;
-  static DfOptInt minp_o{"DFMIR_S2W_MINP", 2};               // patches per workgroup at least (every workgroup ends in 27 Cin Cout atomics)
-  const long long minp = minp_o.get() > 0 ? minp_o.get() : 2;
+  constexpr long long minp = 2;                              // patches per workgroup at least (every workgroup ends in 27 Cin Cout atomics)
   long long maxs = (k.npatch + minp - 1) / minp;
   if (maxs < 1) maxs = 1;
   if (want > maxs) want = maxs;

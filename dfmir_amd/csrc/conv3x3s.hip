@@ -579,62 +579,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_pp_k(const float* __rest
 //   X(c+1) is complete at the end of h = 2c+1; its buffer was last read (chunk c-1) at h = 2c-1.
 constexpr int CS_TH = 8, CS_TW = 32, CS_PW = CS_TW + 2, CS_XP = 352;   // 10 x 34 = 340 patch positions
 
-// One compute half-step: 9 taps x 12 MFMAs.  Per tap, in one fenced scheduling region: the ds_reads of the next
-// tap's operands, a slice of the caller's prefetch (the 9 weight + 16 patch loads of the chunk this group stores
-// next), and the MFMAs, interleaved by sched_group_barrier.  Without the fences the scheduler hoisted all 25
-// buffer loads in front of the first MFMA and the half-step paid their issue time (16 % of the kernel).
-__device__ __forceinline__ void cs_mma_chunk(const u32x4* __restrict__ Ab, const u32x4* __restrict__ Xb, int abase,
-                                             const int (&pb)[2], f32x16 (&acc)[4],
-                                             const __amdgpu_buffer_rsrc_t rw_, const unsigned (&wb)[9], u32x4 (&rw)[9],
-                                             const __amdgpu_buffer_rsrc_t rx_, const unsigned (&gvo)[2][8],
-                                             unsigned (&rx)[2][8]) {
-  constexpr int SA = 9 * 2 * 64, SX = 2 * CS_XP;          // units per split in W_g / X
-  using P = Prod<2>;
-  u32x4 a[2][2][2], b[2][2][2];                           // [set][tile][split]
-#define CS_LOAD(set_, t_)                                                                        \
-  {                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                \
-      _Pragma("unroll") for (int s = 0; s < 2; ++s) a[set_][i][s] = Ab[s * SA + (t_) * 128 + abase + i * 32]; \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                \
-      _Pragma("unroll") for (int s = 0; s < 2; ++s) b[set_][j][s] = Xb[s * SX + pb[j] + ((t_) / 3) * CS_PW + (t_) % 3]; \
-  }
-  CS_LOAD(0, 0)
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    if (t < 8) CS_LOAD((t + 1) & 1, t + 1)
-    // prefetch slice: loads 3t .. 3t+2 of the flattened list [9 weight units | 2 x 8 patch channels]
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int L = 3 * t + q;
-      if (L < 9) rw[L] = __builtin_amdgcn_raw_buffer_load_b128(rw_, wb[L], 0, 0);
-      else if (L < 25) rx[(L - 9) >> 3][(L - 9) & 7] = __builtin_amdgcn_raw_buffer_load_b32(rx_, gvo[(L - 9) >> 3][(L - 9) & 7], 0, 0);
-    }
-#pragma unroll
-    for (int q = 0; q < P::N; ++q)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[2 * i + j] = mma16<2>(b[t & 1][j][P::B[q]], a[t & 1][i][P::A[q]], acc[2 * i + j]);   // rows = pixels, columns = couts
-    const int nds = t < 8 ? 8 : 0, nvm = (3 * t + 3 <= 25) ? 3 : (25 - 3 * t > 0 ? 25 - 3 * t : 0);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      if (i < nds) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      else if (i - nds < nvm) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#undef CS_LOAD
-}
-
-// Row-reuse form of the same half-step.  A wave owns 32 output channels x 4 tile rows instead of 64 x 2: the X
-// operand of tap (ky, kx) for tile row r is the operand of tap (ky+1, kx) for row r-1, so per kx the wave reads 6
-// patch rows once (instead of 3 taps x 4 rows) and one weight block per tap: 54 ds_read_b128 per 108 MFMAs
-// instead of 72 -- the LDS operand traffic is what bounds this kernel (profiles/r01_conv3x3s_pmc.md).
+// One compute half-step: 9 taps x 12 MFMAs.  A wave owns 32 output channels x 4 tile rows: the X operand of tap (ky, kx)
+// for tile row r is the operand of tap (ky+1, kx) for row r-1, so per kx the wave reads 6 patch rows once (instead of
+// 3 taps x 4 rows) and one weight block per tap: 54 ds_read_b128 per 108 MFMAs -- the LDS operand traffic is what
+// bounds this kernel (profiles/r01_conv3x3s_pmc.md).
 // Stage order: kx outer, ky inner; the reads of stage s+1 (row ky+4 and the next weight block, or the next kx's
-// first four rows) and a slice of the prefetch ride between the MFMAs of stage s.
+// first four rows) and a slice of the caller's prefetch (the weight + patch loads of the chunk this group stores next)
+// ride between the MFMAs of stage s, in one fenced scheduling region interleaved by sched_group_barrier.  Without the
+// fences the scheduler hoisted all buffer loads in front of the first MFMA and the half-step paid their issue time
+// (16 % of the kernel).
 // CPG = output channels per wave group (64: tile 8 x 32, 32: tile 16 x 32), XP = patch positions (padded),
 // NW / NS = weight units / patch positions a thread prefetches per chunk.
 template <int CPG, int XP, int NW, int NS>
@@ -745,8 +698,8 @@ extern "C" int dfmir_cs_wg_dump(unsigned* out) {
 #define WGT(slot_)
 #define TRC(slot_)
 #endif
-// <RR, CPG, TH>: <*, 64, 8> = 128 output channels per workgroup on an 8 x 32 tile (RR: row-reuse compute phase);
-// <true, 32, 16> = 64 output channels on a 16 x 32 tile (the 128->64 / 64<-128 layers at 256^2): a wave still owns
+// <CPG, TH>: <64, 8> = 128 output channels per workgroup on an 8 x 32 tile;
+// <32, 16> = 64 output channels on a 16 x 32 tile (the 128->64 / 64<-128 layers at 256^2): a wave still owns
 // 32 couts x 4 tile rows, a group its 32 couts over all 16 rows.
 // LDS of the kernel: Wg[2][WUG] | Xs[2][NSP * 2 * XP] | bs[2 * CPG].  The kernel body (conv3x3s_cs_body.inc) only names the three
 // arrays: the stand-alone kernel declares them as static __shared__ arrays, conv3x3_bwd_pair_k -- which includes this body next
@@ -759,7 +712,7 @@ struct CsLds {
   static constexpr int XSU = 2 * 2 * XP;                  // 16-B units of one patch buffer
   static constexpr int XS_OFF = 2 * WUG * 16, BS_OFF = XS_OFF + 2 * XSU * 16, BYTES = BS_OFF + 2 * CPG * 4;
 };
-template <bool RR, int CPG, int TH>
+template <int CPG, int TH>
 __global__ __launch_bounds__(512, 1) void conv3x3_split_cs_k(const float* __restrict__ x, const u32x4* __restrict__ ws,
                                                              const float* __restrict__ bias, float* __restrict__ y,
                                                              ConvCsP k, SplitScale sc) {
@@ -781,11 +734,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_cs_k(const float* __rest
 // res != NULL (y = act(conv + bias) + res): only the shared-tile kernel has that epilogue -- df_conv3x3_split_res_ok(g)
 // tells whether this geometry takes it; otherwise *rc is an error
 static bool cs_plan(const DfConvGeom* g, int* th_out, int* tx_out, int* ty_out) {
-  static DfOptFlag nocs_o{"DFMIR_CONV_NO_CS"};
-  const bool use_cs = !nocs_o.get();
-  static DfOptFlag plain_o{"DFMIR_CONV_CS_PLAIN"};
-  const bool rr = !plain_o.get();
-  if (!(df_split_mode() == 2 && use_cs && (g->Cout > 64 || rr))) return false;
+  if (df_split_mode() != 2) return false;
   const int th = g->Cout > 64 ? 8 : 16;
   const int tx = (g->Wo + CS_TW - 1) / CS_TW, ty = (g->Ho + th - 1) / th;
   const double fill = (double)g->Ho * g->Wo / ((double)tx * CS_TW * ty * th);
@@ -811,15 +760,13 @@ int df_conv3x3_split_res_ok(const DfConvGeom* g) {
   return (df_split_mode() == 2 && split_fwd_geom_ok(g) && cs_plan(g, &th, &tx, &ty)) ? 1 : 0;
 }
 // What df_conv3x3_split_fwd_try launches on the shared-tile kernels: parameters, grid (2-D, or the 1-D XCD-mapped form)
-// and tile form -- 1: <true, 64, 8>, 2: <false, 64, 8>, 3: <true, 32, 16>.  false: the geometry stays on the flat-run kernel.
+// and tile form -- 1: <64, 8>, 2: <32, 16>.  false: the geometry stays on the flat-run kernel.
 struct CsLaunch {
   ConvCsP kc;
   dim3 grid;
   int form;
 };
 static bool cs_setup(const DfConvGeom* g, const float* res, const float* ring, int ring_rl, const float* y, CsLaunch* L) {
-  static DfOptFlag plain_o{"DFMIR_CONV_CS_PLAIN"};
-  const bool rr = !plain_o.get();
   int th = 0, tlx = 0, tly = 0;
   if (!cs_plan(g, &th, &tlx, &tly)) return false;
   // 8 x 32 tiles (128 couts per workgroup) or 16 x 32 tiles (64 couts).  They fit the forward shapes exactly but
@@ -844,11 +791,11 @@ static bool cs_setup(const DfConvGeom* g, const float* res, const float* ring, i
       if (kc.xcd_pair) grid = dim3((unsigned)(grid.y * nb), 1u);
     }
     L->grid = grid;
-    L->form = rr ? 1 : 2;
+    L->form = 1;
   } else {
     if (xcd_pair >= 2 && (nb & 7) == 0) kc.xcd_pair = 2;          // one cout slice: contiguous tile runs per XCD
     L->grid = dim3((unsigned)nb, 1u);
-    L->form = 3;
+    L->form = 2;
   }
   L->kc = kc;
   return true;
@@ -867,14 +814,14 @@ bool df_conv3x3_split_fwd_try(const DfConvGeom* g, const float* x, const float* 
   CsLaunch cl;
   if (mode == 2 && cs_setup(g, res, ring, ring_rl, y, &cl)) {
     const ConvCsP& kc = cl.kc;
-    if (cl.form != 3) {
+    if (cl.form == 1) {
       // (A persistent form -- one workgroup per CU walking its tiles in one chunk stream, a group's epilogue beside the other
       // group's compute half-step -- was built and measured in round 4: bit-identical, 16 % SLOWER (0.404 vs 0.348 ms at
       // n = 32).  The epilogue is a 33 MB burst of stores issued by all 256 CUs in lockstep, i.e. HBM-write-bound wherever
       // it is placed, and the extra state cost the main loop its registers)
 #ifdef DFMIR_BUILD_W1
       static DfOptFlag w1_o{"DFMIR_CONV_W1"};
-      if (w1_o.get() && cl.form == 1 && kc.vec4 && g->act != 2 && (g->Cin % 16) == 0 && (g->Ho % 16) == 0 && (g->Wo % 32) == 0) {
+      if (w1_o.get() && kc.vec4 && g->act != 2 && (g->Cin % 16) == 0 && (g->Ho % 16) == 0 && (g->Wo % 32) == 0) {
         // experiment: one wave per SIMD, 16 x 32 x 128 tiles (conv3x3_split_w1_k)
         ConvCsP kw = kc;
         kw.tiles_y = g->Ho / 16;
@@ -886,10 +833,9 @@ bool df_conv3x3_split_fwd_try(const DfConvGeom* g, const float* x, const float* 
         conv3x3_split_w1_k<0><<<gw, 256, 0, st>>>(x, ws, bias, y, kw, sc);
       } else
 #endif
-      if (cl.form == 1) conv3x3_split_cs_k<true, 64, 8><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
-      else conv3x3_split_cs_k<false, 64, 8><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
+      conv3x3_split_cs_k<64, 8><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
     } else {
-      conv3x3_split_cs_k<true, 32, 16><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
+      conv3x3_split_cs_k<32, 16><<<cl.grid, 512, 0, st>>>(x, ws, bias, y, kc, sc);
     }
     hipError_t e = hipGetLastError();
     *rc = (e == hipSuccess) ? 0 : df_set_error((int)e, __FILE__, __LINE__);
@@ -1376,14 +1322,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_split2_k(const float* __
 // MFMA phases themselves (operand reads one unit ahead, one barrier per 2 x 54 MFMAs, the atomic tail) are what is left.)
 // does df_conv3x3_split_wgrad_try run this geometry with swapped roles (and therefore leave db to the caller)?
 bool df_conv3x3_split_wgrad_swaps(const DfConvGeom* g) {
-  static DfOptFlag ns_o{"DFMIR_WGRAD_NO_SWAP"}, v1_o{"DFMIR_WGRAD_V1"};
-  const bool off = ns_o.get() || v1_o.get();
-  return !off && df_split_mode() == 2 && g->KD == 1 && g->KH == 3 && g->KW == 3 && g->Di == 1 && g->Do == 1 && g->stride == 1 &&
+  return df_split_mode() == 2 && g->KD == 1 && g->KH == 3 && g->KW == 3 && g->Di == 1 && g->Do == 1 && g->stride == 1 &&
          g->dil == 1 && g->ph == 1 && g->pw == 1 && g->pd == 0 && g->Ho == g->Hi && g->Wo == g->Wi && g->pad_mode == 0 &&
          g->Cout == 64 && g->Cin > 64;
 }
 // What df_conv3x3_split_wgrad_try launches: parameters, grid and kernel -- 1: split2 with swapped roles, 2: split2,
-// 3 / 4: conv3x3_wgrad_split_k<2, 128 / 64>, 5 / 6: <3, 128 / 64>.  false: the geometry is not taken.
+// 3: conv3x3_wgrad_split_k<2, 64>, 4 / 5: <3, 128 / 64>.  false: the geometry is not taken.
 static bool ws_setup(const DfConvGeom* g, const float* x_amax, int x_n, const float* dy_amax, int dy_n, float* db,
                      const float* dy_pmax, WS3P* kp, dim3* grid, int* which) {
   const int mode = df_split_mode();
@@ -1417,13 +1361,8 @@ static bool ws_setup(const DfConvGeom* g, const float* x_amax, int x_n, const fl
   const unsigned nx = (k.runs_total + k.runs_per_block - 1) / k.runs_per_block;
   *grid = dim3(nx, ny, nz);
   *kp = k;
-  if (mode == 2) {
-    static DfOptFlag v1_o{"DFMIR_WGRAD_V1"};
-    const bool v1 = v1_o.get();      // A/B: the single-buffered kernel
-    *which = swap ? 1 : (wide && !v1) ? 2 : wide ? 3 : 4;
-  } else {
-    *which = wide ? 5 : 6;
-  }
+  if (mode == 2) *which = swap ? 1 : wide ? 2 : 3;
+  else *which = wide ? 4 : 5;
   return true;
 }
 bool df_conv3x3_split_wgrad_try(const DfConvGeom* g, const float* x, const float* x_amax, int x_n, const float* dy,
@@ -1435,9 +1374,8 @@ bool df_conv3x3_split_wgrad_try(const DfConvGeom* g, const float* x, const float
   if (!ws_setup(g, x_amax, x_n, dy_amax, dy_n, db, dy_pmax, &k, &grid, &which)) return false;
   if (which == 1) conv3x3_wgrad_split2_k<<<grid, 512, 0, st>>>(dy, x, dw_tcc, k);
   else if (which == 2) conv3x3_wgrad_split2_k<<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
-  else if (which == 3) conv3x3_wgrad_split_k<2, 128><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
-  else if (which == 4) conv3x3_wgrad_split_k<2, 64><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
-  else if (which == 5) conv3x3_wgrad_split_k<3, 128><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+  else if (which == 3) conv3x3_wgrad_split_k<2, 64><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
+  else if (which == 4) conv3x3_wgrad_split_k<3, 128><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
   else conv3x3_wgrad_split_k<3, 64><<<grid, 512, 0, st>>>(x, dy, dw_tcc, k);
   hipError_t e = hipGetLastError();
   *rc = (e == hipSuccess) ? 0 : df_set_error((int)e, __FILE__, __LINE__);
@@ -1487,7 +1425,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_bwd_pair_k(const float* __rest
   }
   if (!wg) {
     if (l >= pp.nd) return;
-    constexpr bool RR = true;
     using L = CsLds<CPG, TH>;
     const float* __restrict__ x = dyd;
     const float* __restrict__ bias = nullptr;
@@ -1539,7 +1476,7 @@ static bool bwd_pair_setup(const DfConvGeom* gd, const DfConvGeom* gw, const flo
   static DfOptFlag w1_o{"DFMIR_CONV_W1"};
   if (w1_o.get()) return false;
 #endif
-  if (!split_fwd_geom_ok(gd) || !cs_setup(gd, res, ring, ring_rl, dx, cl) || cl->form == 2) return false;
+  if (!split_fwd_geom_ok(gd) || !cs_setup(gd, res, ring, ring_rl, dx, cl)) return false;
   if (!ws_setup(gw, x_amax, x_n, dy_amax, dy_n, db, dy_pmax, kw, wgrid, which) || *which > 2 || kw->fx != nullptr) return false;
   const long long nd = (long long)cl->grid.x * cl->grid.y, nw = (long long)wgrid->x * wgrid->y * wgrid->z;
   return nd + nw + 16 < (1LL << 31);

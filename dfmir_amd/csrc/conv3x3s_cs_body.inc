@@ -1,10 +1,10 @@
 // Body of conv3x3_split_cs_k (conv3x3s.hip), included once into that kernel and once into conv3x3_bwd_pair_k -- as TEXT, not as
 // a function: a __device__ function, even a forced-inline one, is canonicalised on its own before it is inlined, without what a
 // kernel knows about its workgroup ids, and both kernels came out slower that way (the weight gradient by 1.4 %).
-// The including scope provides: RR, CPG, TH (constants); x, ws, bias, y, k (ConvCsP), sc (SplitScale);
+// The including scope provides: CPG, TH (constants); x, ws, bias, y, k (ConvCsP), sc (SplitScale);
 // bix, biy, gdx (int: the workgroup's index in the logical grid of gdx x (1 or 2) workgroups);
 // Wg[2][WUG], Xs[2][NSP * 2 * XP], bs[2 * CPG] in LDS (arrays or pointers to arrays: CsLds<CPG, TH>).
-  static_assert((CPG == 64 && TH == 8) || (RR && CPG == 32 && TH == 16), "tile forms");
+  static_assert((CPG == 64 && TH == 8) || (CPG == 32 && TH == 16), "tile forms");
   constexpr int CS_TH = TH;
   constexpr int NSP = 2, XP = CsLds<CPG, TH>::XP, NPOS = (CS_TH + 2) * CS_PW;
   constexpr int WUG = NSP * 9 * 2 * CPG;                  // 16-B units of one group's weight chunk (16 channels)
@@ -69,16 +69,12 @@
   }
   if (threadIdx.x < 2 * CPG) bs[threadIdx.x] = (bias && (m0 + (int)threadIdx.x) < k.Cout) ? bias[m0 + threadIdx.x] : 0.f;
 
-  // MFMA operand indices.  Plain form: wave w of a group owns 64 couts x tile rows 2w, 2w+1 (32 pixels each);
-  // row-reuse form: 32 couts (w & 1) x tile rows 4(w >> 1) .. +3
-  int pb[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) pb[j] = lhi * XP + (2 * wid + j) * CS_PW + l31;
+  // MFMA operand indices: wave w of a group owns 32 couts (w & 1) x tile rows 4(w >> 1) .. +3
   const int rowgrp = CPG == 64 ? (wid >> 1) : wid;        // this wave's 4 tile rows
   const int xb = lhi * XP + 4 * rowgrp * CS_PW + l31;
-  const int abase = lhi * CPG + l31 + ((RR && CPG == 64) ? 32 * (wid & 1) : 0);
+  const int abase = lhi * CPG + l31 + (CPG == 64 ? 32 * (wid & 1) : 0);
 
-  f32x16 acc[4];                                          // plain: [cout block i][row j] at 2i + j; row-reuse: [row]
+  f32x16 acc[4];                                          // [row]
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -168,8 +164,7 @@
       const __amdgpu_buffer_rsrc_t rxd = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<float*>(xn + (long long)cx_ * HWi), 0,
           lx_ > 0 ? (unsigned)((lx_ < 16 ? lx_ : 16) * HWi) * 4u : 0u, 0x00020000);
-      if constexpr (RR) cs_mma_chunk_rr<CPG, XP, NW, NS>(Wg[grp], Xs[c & 1], abase, xb, acc, rwd, wb, rw, rxd, gvo, rx);
-      else if constexpr (CPG == 64) cs_mma_chunk(Wg[grp], Xs[c & 1], abase, pb, acc, rwd, wb, rw, rxd, gvo, rx);
+      cs_mma_chunk_rr<CPG, XP, NW, NS>(Wg[grp], Xs[c & 1], abase, xb, acc, rwd, wb, rw, rxd, gvo, rx);
     } else {
       // store what this group prefetched during its last compute half-step (B at h = 0: the prologue's)
       __builtin_amdgcn_s_setprio(CS_STORE_PRIO);
@@ -226,8 +221,8 @@
   float* yb = y + (long long)n * k.Cout * HWo;
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
-    const int i = CPG == 32 ? 0 : (RR ? (wid & 1) : (b >> 1));   // 32-cout block of the group's couts
-    const int row = RR ? 4 * rowgrp + b : 2 * wid + (b & 1);
+    const int i = CPG == 32 ? 0 : (wid & 1);                     // 32-cout block of the group's couts
+    const int row = 4 * rowgrp + b;
     const int oy = oy0 + row;
     const int cc = CPG * grp + i * 32 + l31, co = m0 + cc;
 #ifdef CS_KO_EPI

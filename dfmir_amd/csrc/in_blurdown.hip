@@ -1,16 +1,16 @@
 // InstanceNorm + ReLU + Downsample (models/networks.py:984-996) on the 256 x 256 planes of the generator's first encoder
-// stage -- the ring-free form of norm_resample.hip's in_relu_blurdown_{fwd,bwd}_k.  Its own translation unit because it is
+// stage, behind norm_resample.hip's dfmir_in_relu_blurdown_{fwd,bwd}.  Its own translation unit because it is
 // built WITHOUT packed-fp32 VALU instructions (csrc/Makefile): paired registers for v_pk_* cost 13 (forward) / 15 (backward)
 // spilled registers next to the 64 that hold the plane.
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------
-// The 256 x 256 planes again, with the plane laid over the workgroup so that NO band ring is needed: wave w (16 of them)
+// The plane is laid over the workgroup so that NO band ring is needed: wave w (16 of them)
 // holds rows 16 w .. 16 w + 15 (register i = row 16 w + i, lane l = columns 4 l .. 4 l + 3; a global load instruction of a
 // wave is still one contiguous 1 KB row).  The horizontal [1 2 1] / 4 stride-2 blur needs one value of the neighbouring lane
 // (a shuffle), the vertical one the rows of the SAME thread -- except row 16 w - 1, which is the previous wave's last
-// horizontally-blurred row: 512 bytes per wave through LDS, one barrier.  (The banded form above pushed the whole
-// normalised plane through a 2 x 16-row LDS ring with two barriers per band: 2.6 TB/s against 4.4 TB/s of the plain
+// horizontally-blurred row: 512 bytes per wave through LDS, one barrier.  (A banded form that pushed the whole
+// normalised plane through a 2 x 16-row LDS ring with two barriers per band reached 2.6 TB/s against 4.4 TB/s of the plain
 // InstanceNorm kernel on the same planes.)  Backward likewise: x stays in registers for both passes, each wave reads the 9
 // dz rows its 16 rows touch straight from global memory, the blur's adjoint is evaluated from registers (static tap
 // geometry per register index), no LDS besides the reductions.

@@ -225,10 +225,6 @@ def init_net(net, init_type='normal', init_gain=0.02, gpu_ids=[], debug=False, i
 # ------------------------------------------------------------------------------------------------
 # generator
 # ------------------------------------------------------------------------------------------------
-_NO_SHARE_TAP = ops._env_on("DFMIR_NO_SHARE_TAP")   # A/B switch: dense gradients of the sampled features
-_NO_SKIP_FOLD = ops._env_on("DFMIR_NO_SKIP_FOLD")   # A/B switch: skip gradient summed by autograd's add
-
-
 class ResnetBlock(nn.Module):
     """x + [pad,conv,IN,ReLU,pad,conv,IN](x) (models/networks.py:1164-1221) as 4 fused launches."""
 
@@ -242,7 +238,7 @@ class ResnetBlock(nn.Module):
 
     def forward(self, x):
         cb = self.conv_block
-        if torch.is_grad_enabled() and x.requires_grad and x.is_contiguous() and not _NO_SKIP_FOLD:
+        if torch.is_grad_enabled() and x.requires_grad and x.is_contiguous():
             # the skip branch leaves through the first conv's autograd node, whose backward sums its gradient
             # inside the halo-fold kernel (one pass instead of fold + add)
             h, xs = ops.conv(x, cb[1].weight, cb[1].bias, cb[1], cb[1].stride, cb[0].padding, 1, 0, 0.0, skip=True)
@@ -309,7 +305,7 @@ class ResnetGenerator(nn.Module):
             nonlocal feat
             stop = encode_only and idx == last
             if idx in want:
-                if shared and not stop and not _NO_SHARE_TAP and t is feat:
+                if shared and not stop and t is feat:
                     feat, t = ops.fork_tap(t)     # t also feeds the next layer: see ops.TapForkFn
                 feats.append(t)
             return stop

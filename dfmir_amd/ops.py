@@ -225,9 +225,7 @@ _NO_S2 = _env_on("DFMIR_CONV3D_NO_S2")        # A/B switch: the stride-2 encoder
 _NO_FLOW_MARCH = _env_on("DFMIR_CONV3D_NO_FLOW_MARCH")  # A/B switch: the flow head's forward on the fp32-FMA kernel
 _NO_ACTGRAD = _env_on("DFMIR_NO_ACTGRAD")     # A/B switch: LeakyReLU backward always as its own pass
 _NO_RES = _env_on("DFMIR_NO_RES")       # A/B switch: residual added by a separate kernel
-_NO_DEAD_TAIL = _env_on("DFMIR_NO_DEAD_TAIL")   # A/B switch: dgrad also for skip channels that need none
 _NO_CH_SCALE = _env_on("DFMIR_NO_CH_SCALE")   # A/B switch: one dY scale per tensor in the split wgrad
-_NO_RING = _env_on("DFMIR_NO_RING")     # A/B switch: reflect dgrad as padded-frame conv + fold
 _LAST_ACTGRAD = [False]     # did the last conv_raw() apply an activation derivative in its epilogue?
 
 
@@ -689,7 +687,7 @@ _DEFER = {"on": False, "pending": {}}
 
 class deferred_weight_grads:
     def __enter__(self):
-        _DEFER["on"] = not _env_on("DFMIR_NO_DEFER")   # A/B switch
+        _DEFER["on"] = True
         return self
 
     def __exit__(self, *exc):
@@ -709,7 +707,7 @@ def begin_deferred():
     """deferred_weight_grads as two calls, for a backward that runs in several pieces (registration_model's staged step:
     the pieces are separate autograd calls on two streams, captured into separate hipGraphs): begin_deferred() before the
     first piece, end_deferred() -- the one flush -- after the last, on a stream that has waited for all of them."""
-    _DEFER["on"] = not _env_on("DFMIR_NO_DEFER")
+    _DEFER["on"] = True
 
 
 def end_deferred(failed=False):
@@ -858,7 +856,7 @@ def _conv_backward_impl(ctx, dy, dskip, x5, weight, y5):
         wd = owner.packed(1) if owner is not None else weight_pack(weight, 1)
         in_sp = tuple(x5.shape[2:])
         gf = None
-        if stride == 1 and pad_mode == 1 and dy_amax is not None and not _NO_RING:
+        if stride == 1 and pad_mode == 1 and dy_amax is not None:
             gf = DfConvGeom(x5.shape[0], Cin, Cout, 1, in_sp[1], in_sp[2], 1, in_sp[1], in_sp[2], K[0], K[1], K[2],
                             1, 1, p3[0], p3[1], p3[2], 1, 0, 0.0)
             gd = DfConvGeom(x5.shape[0], Cout, Cin, 1, in_sp[1], in_sp[2], 1, in_sp[1], in_sp[2], K[0], K[1], K[2],
@@ -899,7 +897,7 @@ def _conv_backward_impl(ctx, dy, dskip, x5, weight, y5):
                                                     p3[1], _st()))
         else:
             padp = tuple(K[i] - 1 - p3[i] for i in range(3))
-            used = Cin - ctx.dead_tail if (ctx.dead_tail and stride == 1 and not _NO_DEAD_TAIL) else None
+            used = Cin - ctx.dead_tail if (ctx.dead_tail and stride == 1) else None
             ia = ctx.in_act if (stride == 1 and nd == 3) else None
             dx5 = conv_raw(dy5, wd, None, Cin, K, 1, padp, stride, 0, 0, 0.0, in_sp, dy_amax, cout_used=used,
                            act_src=x5 if ia else None, act_slope=ia[1] if ia else 0.0)
@@ -970,7 +968,7 @@ def _conv_backward_pair(ctx, dy, dskip, dy5, dy_amax, x5, weight):
             and ctx.needs_input_grad[1] and ctx.x_amax is not None and dy_amax is not None
             and getattr(ctx, "x_parts", None) is None and not ctx.dead_tail):
         return None
-    if (pad_mode == 1 and _NO_RING) or (pad_mode == 0 and dskip is not None):
+    if pad_mode == 0 and dskip is not None:
         return None
     L = lib()
     Cout, Cin = weight.shape[0], weight.shape[1]
@@ -1148,14 +1146,11 @@ class Stem7Fn(Function):
         return dx, dw, db, None
 
 
-_NO_STEM7 = _env_on("DFMIR_NO_STEM7")    # A/B switch: the stem through tap stack + 1x1 GEMM
-
-
 def conv_taps(x, weight, bias, pad, pad_mode, act=0, slope=0.0):
     """KxK conv with Cin == 1 or Cout <= 4 as a 1x1 GEMM over K*K tap planes (see csrc/taps.hip)."""
     Cout, Cin, K = weight.shape[0], weight.shape[1], weight.shape[2]
     T = K * K
-    if Cin == 1 and K == 7 and pad == 3 and Cout <= 64 and act == 0 and x.dim() == 4 and not _NO_STEM7:
+    if Cin == 1 and K == 7 and pad == 3 and Cout <= 64 and act == 0 and x.dim() == 4:
         return Stem7Fn.apply(x, weight, bias, pad_mode)
     if Cin == 1:
         s = TapStackFn.apply(x, K, pad, pad_mode)
@@ -1230,9 +1225,6 @@ def instance_norm(x, res=None, relu=False, eps=1e-5):
     return tag_amax(y, _LAST_AMAX[0])
 
 
-_NO_IN_BLUR = _env_on("DFMIR_NO_IN_BLUR")     # A/B switch: InstanceNorm+ReLU and Downsample as two passes
-
-
 class InstNormReluBlurDownFn(Function):
     """Downsample(ReLU(InstanceNorm2d(x))) in one pass per plane (csrc/norm_resample.hip in_relu_blurdown_*): the
     full-resolution normalised tensor is never written -- it feeds only the blur and no backward needs it."""
@@ -1269,7 +1261,7 @@ class InstNormReluBlurDownFn(Function):
 
 
 def in_relu_blurdown_ok(x):
-    return (not _NO_IN_BLUR and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
             and bool(lib().dfmir_in_relu_blurdown_ok(int(x.shape[2]), int(x.shape[3]))))
 
 
@@ -1402,17 +1394,10 @@ def upcat(a, b):
     return y
 
 
-_NO_UPWGRAD = _env_on("DFMIR_CONV3D_NO_UPWGRAD")     # A/B switch: weight gradient from the materialised cat
-_NO_UPDGRAD = _env_on("DFMIR_CONV3D_NO_UPDGRAD")     # A/B switch: d(a) through the full-resolution dgrad + pool
-_NO_UPSKIP2 = _env_on("DFMIR_CONV3D_NO_UPSKIP2")     # A/B switch: <= 2 skip channels as a second launch
-_NO_UPPHASE = _env_on("DFMIR_CONV3D_NO_UPPHASE")     # A/B switch: materialise nearest_up2 + cat, one conv
-
-
 # Registry of the split-weight workspaces of persistent packed buffers: after the batched re-pack of an optimizer step
 # (_repack_all) every registered split is re-made by ONE launch (dfmir_conv3d_wsplit_batch) instead of one launch per
 # layer and mode at its first use.
 _WS3D = {"entries": {}, "key": None, "dev": None}
-_NO_WS_BATCH = _env_on("DFMIR_NO_WSPLIT_BATCH")
 
 
 def _ws3d_register(w_tcc, key, ws, job):
@@ -1429,7 +1414,7 @@ def _resplit_all_3d(dev):
         del ents[k_]
         _WS3D["key"] = None
     live = [e for e in ents.values() if e["ws"].device == dev and getattr(e["ref"](), "_df_gen", None) is not None]
-    if not live or _NO_WS_BATCH:
+    if not live:
         return
     key = tuple((e["ref"]().data_ptr(), e["ws"].data_ptr()) + tuple(e["job"]) for e in live)
     if _WS3D["key"] != key:
@@ -1497,7 +1482,7 @@ class UpCatConv3dFn(Function):
         pb = _probe64(b) if pb is None else pb
         y = torch.empty((N, Cout, 2 * D, 2 * H, 2 * W), device=a.device, dtype=torch.float32)
         g = DfConvGeom(N, Cb, Cout, 2 * D, 2 * H, 2 * W, 2 * D, 2 * H, 2 * W, 3, 3, 3, 1, 1, 1, 1, 1, 0, act, float(slope))
-        fused = Cb <= 2 and act in (0, 1) and not _NO_UPSKIP2
+        fused = Cb <= 2 and act in (0, 1)
         ws_up, split_up = _ws_cached(w_tcc, ("up", Ca, Cout, Cb if fused else 0), lib().dfmir_conv3d_up_ws_floats(Ca, Cout),
                                      a.device, job=(1, Ca, Cout, 0, Ca + Cb, 0, Cb if fused else 0))
         ws_sk, split_sk = (None, False) if fused else \
@@ -1564,12 +1549,12 @@ class UpCatConv3dFn(Function):
                 check(lib().dfmir_act_bwd(_p(dy), _p(y), _p(dpre), dy.numel(), act, float(slope), _st()))
             dy = dpre
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        up_dgrad = need_a and not need_b and Cout % 8 == 0 and not _NO_UPDGRAD
+        up_dgrad = need_a and not need_b and Cout % 8 == 0
         xp = amax_slot(a.device, PROBE_SLOTS)
         check(lib().dfmir_probe_merge(_p(ctx.probes[0]), _p(ctx.probes[1]), _p(xp), _st()))
         c = _Ctx()
         gfull = DfConvGeom(N, Ca + Cb, Cout, 2 * D, 2 * H, 2 * W, 2 * D, 2 * H, 2 * W, 3, 3, 3, 1, 1, 1, 1, 1, 0, 0, 0.0)
-        gather = (up_dgrad and not _NO_UPWGRAD and W % 4 == 0 and ctx.needs_input_grad[2]
+        gather = (up_dgrad and W % 4 == 0 and ctx.needs_input_grad[2]
                   and bool(lib().dfmir_conv3d_split_wgrad_ok(ctypes.byref(gfull))) and Cout >= 8)
         if gather:
             # the weight gradient stages its operand patch from a (at half the coordinates) and b: no concatenation
@@ -1621,7 +1606,7 @@ class UpCatConv3dFn(Function):
 
 
 def upcat_conv3d_ok(a, b, weight):
-    if _NO_UPPHASE or _NO_SPLIT3D or a.dim() != 5 or not (a.is_cuda and b.is_cuda):
+    if _NO_SPLIT3D or a.dim() != 5 or not (a.is_cuda and b.is_cuda):
         return False
     N, Ca, D, H, W = a.shape
     return (tuple(weight.shape[2:]) == (3, 3, 3) and tuple(b.shape[2:]) == (2 * D, 2 * H, 2 * W)
@@ -1831,9 +1816,6 @@ def vecint_step(v):
     return VecIntStepFn.apply(v)
 
 
-_RESIZE_ONEPASS = _env_on("DFMIR_RESIZE_ONEPASS")     # A/B switch: the one-pass gather adjoint
-
-
 class ResizeFn(Function):
     @staticmethod
     def forward(ctx, x, out_sp, mult):
@@ -1856,7 +1838,7 @@ class ResizeFn(Function):
         dy = _c(dy)
         dx = torch.empty(xs, device=dy.device, dtype=torch.float32)
         n = lib().dfmir_resize_bwd_ws_floats(planes, isp[0], isp[1], isp[2], osp[0], osp[1], osp[2])
-        if n > 0 and not _RESIZE_ONEPASS:
+        if n > 0:
             ws = torch.empty(n + 4, device=dy.device, dtype=torch.float32)
             check(lib().dfmir_resize_bwd_sep(_p(dy), _p(dx), planes, isp[0], isp[1], isp[2], osp[0], osp[1], osp[2],
                                              mult, _p(ws), _st()))
@@ -2228,11 +2210,8 @@ def patch_gather_multi(srcs, ids):
     return out
 
 
-_NO_NCE_FUSED = _env_on("DFMIR_NO_NCE_FUSED")     # A/B switch: gather, two 1x1 convs and l2norm as 4 launches
-
-
 def nce_head_ok(C, nc, use_mlp):
-    return use_mlp and not _NO_NCE_FUSED and nc == 256 and 1 <= C <= 256
+    return use_mlp and nc == 256 and 1 <= C <= 256
 
 
 def _nce_head_launch(ptrs, G, ids, mlp0, mlp2, Bper, C, S, Pn, eps, device, save):

@@ -405,8 +405,7 @@ class REGISTRATIONModel(BaseModel):
             return l1_reg, l1_idt, smooothing_loss(y_pred[1])
 
         # ... which follow netR on ITS stream, beside the NCE query pass (not when the masked-L1 normalisation is a collective)
-        side_losses = (rs is not None and not ops._env_on('DFMIR_NO_SIDE_LOSSES')
-                       and not (getattr(self.opt, 'global_mask_norm', False) and getattr(self, '_ddp', False)))
+        side_losses = (rs is not None and not (getattr(self.opt, 'global_mask_norm', False) and getattr(self, '_ddp', False)))
         if side_losses:
             rs.wait_stream(cur)                            # fake_B / idt_B exist
             with torch.cuda.stream(rs):
@@ -425,8 +424,7 @@ class REGISTRATIONModel(BaseModel):
 
         self._nce_terms = None
         idt = bool(self.opt.nce_idt)
-        if (getattr(self.opt, 'batch_query_passes', True) and not ops._env_on('DFMIR_NO_STACKED_Q')
-                and self.opt.lambda_NCE > 0.0 and self.opt.lambda_GAN <= 0.0):
+        if getattr(self.opt, 'batch_query_passes', True) and self.opt.lambda_NCE > 0.0 and self.opt.lambda_GAN <= 0.0:
             # The three NCE terms each run G's encoder on their own query batch (fake_B, idt_B, regA) with the same
             # weights: one pass over the three stacked along the batch instead (per-sample kernels; same random
             # draws in the same order -- only the key side draws).  Terms in the reference's order; without nce_idt
@@ -496,8 +494,8 @@ class REGISTRATIONModel(BaseModel):
     def _staged_ok(self):
         gmn = getattr(self.opt, 'global_mask_norm', False) and getattr(self, '_ddp', False)
         return (getattr(self.opt, 'staged_step', True) and not ops._env_on('DFMIR_NO_STAGED') and self._overlap_registration()
-                and not ops._env_on('DFMIR_NO_SIDE_LOSSES') and not ops._env_on('DFMIR_BUCKET_IN_GRAPH') and not gmn
-                and getattr(self.opt, 'batch_query_passes', True) and not ops._env_on('DFMIR_NO_STACKED_Q')
+                and not ops._env_on('DFMIR_BUCKET_IN_GRAPH') and not gmn
+                and getattr(self.opt, 'batch_query_passes', True)
                 and self.opt.lambda_NCE > 0.0 and self.opt.lambda_GAN <= 0.0 and self.opt.netF == 'mlp_sample')
 
     def _loss_seeds(self, idt):
@@ -773,8 +771,7 @@ class REGISTRATIONModel(BaseModel):
         # opt.nce_sequential_keys (build-defined, default False): the key side term by term through netF.forward, in the
         # reference's call order with host-drawn ids (torch.randperm).  A netF.forward replaced on the instance (how older
         # tests pin ids) implies it; `model.patch_id_source` is the hook that pins ids on the default path.
-        sequential = (getattr(self.opt, 'nce_sequential_keys', False) or 'forward' in vars(self.netF)
-                      or ops._env_on('DFMIR_NCE_SEQUENTIAL_KEYS'))
+        sequential = getattr(self.opt, 'nce_sequential_keys', False) or 'forward' in vars(self.netF)
         if not sequential and self.opt.netF == 'mlp_sample' and all(S >= 2 * P or P <= S <= 4096 for S in sizes):
             id_src = getattr(self, 'patch_id_source', None)
             # a captured step may hold the ids only by device address: the device generator, or a source that declares

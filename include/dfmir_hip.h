@@ -44,13 +44,10 @@ const char* dfmir_last_error(void);
  * anything but "" or "0" -- set_option(name, "0") switches a flag off like set_option(name, NULL) does.  Reads are
  * thread-safe: values are copied out under the table's lock, the per-site caches are single atomic words.
  *   kernel selection: DFMIR_CONV_FP32, DFMIR_CONV_SPLIT=bf16x3, DFMIR_CONV3D_FP32, DFMIR_CONV_GENERIC=1,
- *     DFMIR_CONV_NO_CS, DFMIR_CONV_CS_PLAIN, DFMIR_CS_XCD_PAIR=n, DFMIR_WGRAD_V1, DFMIR_WGRAD_NO_SWAP,
- *     DFMIR_NO_SMALL_WGRAD, DFMIR_NO_DIL2, DFMIR_NO_SMALL_TILES, DFMIR_GEMM_BIG_MIN=n,
- *     DFMIR_CONV3D_NO_PAIR, DFMIR_CONV3D_NO_M16, DFMIR_CONV3D_NO_TINY, DFMIR_CONV3D_NO_VEC,
- *     DFMIR_CONV3D_NO_MULTI, DFMIR_CONV3D_WGS=n, DFMIR_WSPLIT_WGS=n, DFMIR_CONV3D_NO_UPPHASE,
- *     DFMIR_CONV3D_WGRAD_COPIES, DFMIR_CONV3D_WGRAD_NO_PAIR, DFMIR_IN_BLUR_BANDED, DFMIR_CONV3D_NO_MARCH,
+ *     DFMIR_CS_XCD_PAIR=n, DFMIR_CONV3D_NO_PAIR, DFMIR_CONV3D_NO_M16, DFMIR_CONV3D_NO_TINY,
+ *     DFMIR_CONV3D_NO_MULTI, DFMIR_CONV3D_WGS=n, DFMIR_CONV3D_NO_MARCH,
  *     DFMIR_MARCH_NSEG=n, DFMIR_CS_DEPHASE=n, DFMIR_CONV_W1 (lab builds with -DDFMIR_BUILD_W1 only),
- *     DFMIR_UPWGRAD_DIRECT, DFMIR_UPWGRAD_NO_FUSEB, DFMIR_UPWGRAD_8WAVE, DFMIR_UPWGRAD_NSEG=n (dfmir_conv3d_upwgrad),
+ *     DFMIR_UPWGRAD_8WAVE, DFMIR_UPWGRAD_NSEG=n (dfmir_conv3d_upwgrad),
  *     DFMIR_NCC_NO_WH_FUSE, DFMIR_CONV3D_NO_WGRAD_MARCH, DFMIR_WGRAD_MARCH_NSEG=n, DFMIR_NO_TINYVOL,
  *     DFMIR_NO_1X1_WGRAD, DFMIR_CONV3D_NO_FLOW_WGRAD, DFMIR_CONV3D_NO_S2, DFMIR_RESIZE_NO_ROWS, DFMIR_NCC_NO_D_FUSE, DFMIR_SMOOTH_NO_MARCH,
  *     DFMIR_NO_BWD_PAIR (dgrad and wgrad of a 3x3 layer as two launches), DFMIR_BWD_PAIR=0|1 (the same switch with an explicit
@@ -234,9 +231,8 @@ int dfmir_conv3d_split_wgrad_upcat(const DfConvGeom* g, const float* a, const fl
  * D, H even, W % 8 == 0; ws = dfmir_conv3d_upwgrad_ws_floats() floats, owned by the call until the stream has passed it.
  * Two skip channels (the network's input images at the top level) and db are FUSED into the same launch (rows = (tap,
  * channel) from x- and y-paired images of b; db as the row of a constant operand); wider skips and db go through the direct
- * kernel on rows Ca.. of dw_tcc.  A/B switches: DFMIR_UPWGRAD_DIRECT=1 (dfmir_conv3d_upwgrad_ok then answers 0: the direct
- * kernel over both parts), DFMIR_UPWGRAD_NO_FUSEB=1 (skip share always direct), DFMIR_UPWGRAD_8WAVE=1 (two waves per SIMD, not
- * fused), DFMIR_UPWGRAD_NSEG=n forces the z split. */
+ * kernel on rows Ca.. of dw_tcc.  A/B switches: DFMIR_UPWGRAD_8WAVE=1 (two waves per SIMD, not fused), DFMIR_UPWGRAD_NSEG=n
+ * forces the z split. */
 int dfmir_conv3d_upwgrad_ok(const DfConvGeom* g, int Ca);
 long long dfmir_conv3d_upwgrad_ws_floats(void);
 int dfmir_conv3d_upwgrad(const DfConvGeom* g, const float* a, const float* b, int Ca, const float* x_amax, int x_amax_n,

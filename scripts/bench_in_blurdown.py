@@ -12,5 +12,5 @@ tf = tb = 0.0
 for _ in range(10):
     ev[0].record(); z = ops.instance_norm_relu_blur_down(xa); ev[1].record(); z.backward(cot); ev[2].record()
     torch.cuda.synchronize(); tf += ev[0].elapsed_time(ev[1]); tb += ev[1].elapsed_time(ev[2]); xa.grad = None
-print("banded" if os.environ.get("DFMIR_IN_BLUR_BANDED") else "ring-free", "fwd %.3f ms (%.2f TB/s)  bwd %.3f ms (%.2f TB/s)" % (
+print("ring-free", "fwd %.3f ms (%.2f TB/s)  bwd %.3f ms (%.2f TB/s)" % (
     tf / 10, 1.342e9 / (tf / 10) / 1e9, tb / 10, 2.416e9 / (tb / 10) / 1e9))

@@ -18,7 +18,7 @@ def timeit(fn, reps=20):
     torch.cuda.synchronize()
     return s.elapsed_time(e) / reps
 
-print("DFMIR_CONV3D_NO_S2 =", os.environ.get("DFMIR_CONV3D_NO_S2"), " DFMIR_S2W_MINP =", os.environ.get("DFMIR_S2W_MINP"))
+print("DFMIR_CONV3D_NO_S2 =", os.environ.get("DFMIR_CONV3D_NO_S2"))
 for Cin, Cout, sp in ((16, 32, (80, 96, 112)), (32, 32, (40, 48, 56)), (32, 32, (20, 24, 28)), (16, 32, (64, 64, 64)), (32, 32, (32, 32, 32))):
     g = torch.Generator(device=dev); g.manual_seed(1)
     osp = tuple((s + 1) // 2 for s in sp)

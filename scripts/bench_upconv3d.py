@@ -1,6 +1,6 @@
 """GPU box: the ConvBlock over cat(nearest_up2(a), b) at the top of the 3-D U-Net (a [1,32,80,96,112], b = the two input
-volumes [1,2,160,192,224], 34 -> 32 channels; torchvoxelmorph/networks.py:64,97-100,1506-1521) -- the parity-class
-kernels against the materialising path (DFMIR_CONV3D_NO_UPPHASE=1): forward, forward + backward, error vs fp64 on a crop.
+volumes [1,2,160,192,224], 34 -> 32 channels; torchvoxelmorph/networks.py:64,97-100,1506-1521) on the parity-class
+kernels: forward, forward + backward, error vs fp64 on a crop.
 Also the run rocprofv3 --pmc profiles (scripts/prof_upconv3d.sh)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,9 +43,8 @@ def fwd_bwd():
 ref_gf = 2.0 * Cout * hi[0] * hi[1] * hi[2] * (Ca + Cb) * 27 / 1e9
 ms_f = timeit(fwd)
 ms_fb = timeit(fwd_bwd, 3)
-tag = "materialised" if os.environ.get("DFMIR_CONV3D_NO_UPPHASE") else "parity-class"
-print("%s: forward %.3f ms (%.0f TF reference-equivalent)   forward + backward %.3f ms (%.0f TF)" % (
-    tag, ms_f, ref_gf / ms_f, ms_fb, 3 * ref_gf / ms_fb))
+print("parity-class: forward %.3f ms (%.0f TF reference-equivalent)   forward + backward %.3f ms (%.0f TF)" % (
+    ms_f, ref_gf / ms_f, ms_fb, 3 * ref_gf / ms_fb))
 # error vs fp64 on a crop (interior outputs depend on the crop only)
 c = 12
 y = fwd()

@@ -58,6 +58,26 @@ def test_options_table_is_settable_and_falls_back_to_the_environment(monkeypatch
     assert b"invalid argument" in h.dfmir_last_error()
 
 
+def test_option_census():
+    """Every option the library reads is listed in the header's Options block and nothing else is; every DFMIR_* variable the
+    Python layer reads is named in INTEGRATION.md."""
+    import glob
+    name = r"\b(DFMIR_[A-Z0-9_]+)"
+    read = set()
+    for path in glob.glob(os.path.join(REPO, "dfmir_amd", "csrc", "*")):
+        if path.endswith((".hip", ".inc", ".h")):
+            for line in open(path):
+                if re.search(r"\b(DfOptFlag|DfOptInt|df_opt_on|df_opt_get)\b", line):
+                    read.update(re.findall('"' + name + '"', line))
+    header = open(os.path.join(REPO, "include", "dfmir_hip.h")).read()
+    block = header[header.index(" * Options --"):header.index("int dfmir_set_option")]
+    assert sorted(read) == sorted(set(re.findall(name, block)))
+    doc = set(re.findall(name, open(os.path.join(REPO, "INTEGRATION.md")).read()))
+    for path in glob.glob(os.path.join(REPO, "dfmir_amd", "*.py")):
+        used = re.findall(r"(?:_env_on\(|os\.environ(?:\.get\(|\[)|os\.getenv\()\s*['\"]" + name, open(path).read())
+        assert set(used) <= doc, (os.path.basename(path), sorted(set(used) - doc))
+
+
 def test_library_is_loaded_after_pytorch_rocm():
     """dfmir_amd.lib() imports torch before it dlopens libdfmir_hip.so: PyTorch-ROCm carries its own HIP runtime, and a
     process that loaded this library first ended up with two runtimes -- the kernels here were then launched on one that had
