@@ -16,7 +16,7 @@
 // lanes).  The next plane of u travels global -> registers -> LDS while the current one is computed (BendStage: 16-byte
 // loads of the 64 interior columns when W % 4 == 0, scalars otherwise; zeros outside the volume).
 //   bend_fwd_k<ND3, VEC>  u with a halo of 1, three open planes; e per voxel (0 outside Omega) added in double per thread,
-//                         one double slot per workgroup.  bend_fin_k (one workgroup) adds the slots in a fixed order.
+//                         one double slot per workgroup.  df_slot_mean_k (one workgroup) adds the slots in a fixed order.
 //   bend_bwd_k<ND3, VEC>  gather form, no atomics, no derivative volume in HBM: u with a halo of 2 (three open planes); the
 //                         derivative values of tile + 1, times the Omega indicator, are formed in LDS -- u_zz, u_zy, u_zx
 //                         as a rolling window of three planes, u_yy, u_xx, u_yx of the output plane alone -- and every
@@ -38,23 +38,6 @@ struct BendGeom {
   int nzc, nty, ntx;                         // z chunks, tiles along y and x
   float czz, cyy, cxx, czy, czx, cyx;        // 1 / h_a^2 and 1 / (4 h_a h_b)
 };
-
-__device__ __forceinline__ double bend_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-// sum over the workgroup, valid in thread 0; the same order every run
-__device__ __forceinline__ double bend_block_sum(double v, double* sm /* BEND_T / 64 */) {
-  v = bend_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < BEND_T / 64; ++w) t += sm[w];
-  return t;
-}
 
 // One plane of u around a tile, with HALO voxels per side: fetch() brings it into registers (zeros outside the volume),
 // commit() stores it to an LDS plane of (BEND_TY + 2 HALO) rows of BEND_RS floats.
@@ -192,18 +175,8 @@ __global__ __launch_bounds__(BEND_T) void bend_fwd_k(const float* __restrict__ u
       const int o = ia; ia = ib; ib = ic; ic = o;
     }
   }
-  acc = bend_block_sum(acc, red);
+  acc = block_sum_ordered<BEND_T>(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// loss = (the slots, added in a fixed order) / N
-__global__ __launch_bounds__(BEND_T) void bend_fin_k(const double* __restrict__ part, int nslots, double count,
-                                                     float* __restrict__ out) {
-  __shared__ double red[BEND_T / 64];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nslots; i += BEND_T) s += part[i];
-  s = bend_block_sum(s, red);
-  if (threadIdx.x == 0) out[0] = (float)(s / count);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -350,7 +323,7 @@ extern "C" int dfmir_bend_fwd(const float* flow, float* ws, float* out, int B, i
     else bend_fwd_k<false, false><<<nwg, BEND_T, 0, st>>>(flow, g, part);
   }
   DF_LAUNCH_CHECK();
-  bend_fin_k<<<1, BEND_T, 0, st>>>(part, (int)nwg, count, out);
+  df_slot_mean_k<BEND_T><<<1, BEND_T, 0, st>>>(part, (int)nwg, count, out);      // loss = (the slots, in a fixed order) / N
   DF_LAUNCH_CHECK();
   return 0;
 }

@@ -108,6 +108,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
@@ -129,6 +134,31 @@ __device__ __forceinline__ float block_sum(float v, float* sm /* >= 17 floats */
   }
   __syncthreads();
   return sm[16];
+}
+// Sum in double over a workgroup of T threads.  A DIFFERENT contract from block_sum, not a variant of it: the result is
+// valid in thread 0 ONLY (the other threads get 0), and thread 0 adds the waves' partial sums in wave order, so the sum is
+// bit-identical from run to run and needs no third barrier.
+template <int T>
+__device__ __forceinline__ double block_sum_ordered(double v, double* sm /* T / 64 */) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < T / 64; ++w) t += sm[w];
+  return t;
+}
+// out[0] = (the nslots doubles of part, added in a fixed order) / count: the last step of a loss whose workgroups each
+// left one partial sum.  ONE workgroup of T threads.  A template, so that only the files that launch it carry it.
+template <int T>
+static __global__ __launch_bounds__(T) void df_slot_mean_k(const double* __restrict__ part, int nslots, double count,
+                                                           float* __restrict__ out) {
+  __shared__ double red[T / 64];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nslots; i += T) s += part[i];
+  s = block_sum_ordered<T>(s, red);
+  if (threadIdx.x == 0) out[0] = (float)(s / count);
 }
 __device__ __forceinline__ float block_max(float v, float* sm) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;

@@ -42,11 +42,6 @@ struct IcGeom {
   int sh;                                    // fixed point: bits above the binary point that the sums may need
 };
 
-__device__ __forceinline__ double ic_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ unsigned ic_wave_max(unsigned v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -57,7 +52,7 @@ __device__ __forceinline__ unsigned ic_wave_max(unsigned v) {
 }
 // sum and maximum over the workgroup, valid in thread 0; the same order every run
 __device__ __forceinline__ void ic_block_reduce(double& s, unsigned& m, double* ss, unsigned* sm /* IC_T / 64 each */) {
-  s = ic_wave_sum(s);
+  s = wave_sum(s);
   m = ic_wave_max(m);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) { ss[threadIdx.x >> 6] = s; sm[threadIdx.x >> 6] = m; }

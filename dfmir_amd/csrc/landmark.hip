@@ -54,16 +54,11 @@ struct LmGeom {
 
 __device__ __forceinline__ float lm_nan() { return __uint_as_float(0x7fc00000u); }
 
-__device__ __forceinline__ double lm_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 // sums over the workgroup, valid in thread 0; the same order every run
 template <int N>
 __device__ __forceinline__ void lm_block_sum(double (&s)[N], double* sm /* N * LM_T / 64 */) {
 #pragma unroll
-  for (int i = 0; i < N; ++i) s[i] = lm_wave_sum(s[i]);
+  for (int i = 0; i < N; ++i) s[i] = wave_sum(s[i]);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll

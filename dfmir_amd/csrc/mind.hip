@@ -10,7 +10,7 @@
 //               LDS once and serves all channels; per channel s = (I(. + p) - I(. + q))^2 over the tile with a halo of r,
 //               then the box sum as three separable LDS passes; D_k stays in registers, the epilogue writes m_k = D_k - min_j D_j
 //               and adds V = mean_k m_k (in double) into the workgroup's partial slot.
-//   mind_mu_k   adds the slots in index order: mu = sum V / voxels (one scalar per image tensor, on the device).
+//   df_slot_mean_k  adds the slots in index order: mu = sum V / voxels (one scalar per image tensor, on the device).
 //   mind_desc_k / mind_loss_k   apply mu: M_k = exp(-m_k / clamp(V, 0.001 mu, 1000 mu)); the loss kernel reduces
 //               mask * mean_k (Ma_k - Mb_k)^2 and the mask itself into per-workgroup double slots, mind_fin_k adds them in
 //               index order.  No atomics anywhere: loss and gradients are bit-identical from run to run.
@@ -57,23 +57,6 @@ __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n
 __device__ __forceinline__ int mind_chan(int n, int n2) {
   const int i = n < n2 ? n : n2, j = n < n2 ? n2 : n;
   return i < 2 ? 4 * i + (j - 2) : 8 + 2 * (i - 2) + (j - 4);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-// sum over the workgroup (MIND_T threads), valid in thread 0; the same order every run
-__device__ __forceinline__ double block_sum_d(double v, double* sm /* MIND_T / 64 */) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < MIND_T / 64; ++w) t += sm[w];
-  return t;
 }
 
 // V, Vc and M of one voxel from its C values of m: the ONE place these are formed, so forward and backward agree bit for bit
@@ -180,18 +163,8 @@ __global__ __launch_bounds__(MIND_T) void mind_a_k(const float* __restrict__ I, 
 #pragma unroll
     for (int k = 0; k < C; ++k) mo[k * vol] = mk[k];
   }
-  vs = block_sum_d(vs, red);
+  vs = block_sum_ordered<MIND_T>(vs, red);
   if (tid == 0) partV[blockIdx.x] = vs;
-}
-
-// mu = (sum of the slots, in index order) / count
-__global__ __launch_bounds__(MIND_T) void mind_mu_k(const double* __restrict__ part, int nslots, double count,
-                                                    float* __restrict__ mu) {
-  __shared__ double red[MIND_T / 64];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nslots; i += MIND_T) s += part[i];
-  s = block_sum_d(s, red);
-  if (threadIdx.x == 0) mu[0] = (float)(s / count);
 }
 
 // ------------------------------------------------------------------------------------------------ forward, pass B
@@ -233,8 +206,8 @@ __global__ __launch_bounds__(MIND_T) void mind_loss_k(const float* __restrict__ 
     if (w != 0.f) acc += (double)w * (double)(s / (float)C);       // (a zero weight also hides a NaN descriptor)
     wacc += (double)w;
   }
-  acc = block_sum_d(acc, red);
-  wacc = block_sum_d(wacc, red);
+  acc = block_sum_ordered<MIND_T>(acc, red);
+  wacc = block_sum_ordered<MIND_T>(wacc, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = acc; part[2 * blockIdx.x + 1] = wacc; }
 }
 
@@ -244,8 +217,8 @@ __global__ __launch_bounds__(MIND_T) void mind_fin_k(const double* __restrict__ 
   __shared__ double red[MIND_T / 64];
   double s = 0.0, w = 0.0;
   for (int i = threadIdx.x; i < nslots; i += MIND_T) { s += part[2 * i]; w += part[2 * i + 1]; }
-  s = block_sum_d(s, red);
-  w = block_sum_d(w, red);
+  s = block_sum_ordered<MIND_T>(s, red);
+  w = block_sum_ordered<MIND_T>(w, red);
   if (threadIdx.x == 0) {
     const bool ok = w > 0.0;
     out[0] = ok ? (float)(s / w) : 0.f;
@@ -484,7 +457,7 @@ int mind_pass_a(const float* I, int nd, const MindGeom& g, float* m, double* par
   if (nd == 3) mind_a_k<3><<<tiles, MIND_T, mind_lds_bytes(g, true), st>>>(I, g, m, part);
   else mind_a_k<2><<<tiles, MIND_T, mind_lds_bytes(g, true), st>>>(I, g, m, part);
   DF_LAUNCH_CHECK();
-  mind_mu_k<<<1, MIND_T, 0, st>>>(part, (int)tiles, (double)g.B * g.D * g.H * g.W, mu);
+  df_slot_mean_k<MIND_T><<<1, MIND_T, 0, st>>>(part, (int)tiles, (double)g.B * g.D * g.H * g.W, mu);
   DF_LAUNCH_CHECK();
   return 0;
 }

@@ -13,6 +13,8 @@ term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map aga
 inverse_consistency=w adds w * the build-defined `InverseConsistency_Loss` of the two integrated fields.
 landmark_weight=w adds w * the build-defined `Landmark_Loss` of corresponding keypoints carried through the flow.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -80,41 +82,59 @@ class Registration3DModel(object):
         if ncc_kernel not in ('mean', 'gaussian'):
             raise ValueError("ncc_kernel must be 'mean' or 'gaussian', got %r" % (ncc_kernel,))
         self.similarity = similarity
+        symmetric = self.symmetric
+
+        def sym(fwd, rev):      # a term that symmetric=True charges both ways: its forward value, rev() the mirrored one
+            return (fwd + rev()) * 0.5 if symmetric else fwd
+
         if similarity == 'ncc':
             kernel_var = [win if ncc_kernel == 'mean' else ncc_sigma] * len(shape)
-            self.criterionNCC = NCC_Loss(self.device, kernel_var=kernel_var, kernel_type=ncc_kernel)
+            ncc = self.criterionNCC = NCC_Loss(self.device, kernel_var=kernel_var, kernel_type=ncc_kernel)
+            sim = lambda s: sym(ncc(s.y_source, s.real_B), lambda: ncc(s.y_target, s.real_A))
         elif similarity == 'mind':
-            self.criterionMIND = MIND_Loss(radius=mind_radius, dilation=mind_dilation)
+            mind = self.criterionMIND = MIND_Loss(radius=mind_radius, dilation=mind_dilation)
+            sim = lambda s: sym(mind(s.y_source, s.real_B), lambda: mind(s.y_target, s.real_A))
         else:
             bins = np.linspace(0.0, nmi_max_clip, 32) if nmi_bins is None else nmi_bins
-            self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)
+            nmi = self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)
+            sim = lambda s: sym(nmi(s.real_B, s.y_source), lambda: nmi(s.real_A, s.y_target))
         if regularizer not in ('diffusion', 'bending'):
             raise ValueError("regularizer must be 'diffusion' or 'bending', got %r" % (regularizer,))
         self.regularizer = regularizer
-        self._outputs = ('regA', 'flow', 'loss_' + similarity, 'loss_bending' if regularizer == 'bending' else 'loss_grad')
-        if self.symmetric:
-            self._outputs += ('regB', 'neg_flow')
+        # The step's loss, one entry per term: (key, weight, fn) in the order the terms are added up.  fn(step) is the
+        # term's scalar from the step's tensors: y_source, y_target, flow, neg_flow and the inputs named in self._inputs.
+        # The first term opens the total as it is, every later one adds term * weight.  `reg` is criterionGrad, which is
+        # constructed last (below).  The outputs and get_current_losses() follow from this table; the captured step takes
+        # its static buffers from self._inputs (attribute names; pts_w may hold None).
+        self._terms = [(similarity, 1, sim), ('bending' if regularizer == 'bending' else 'grad', lam, lambda s: reg(s.flow))]
+        self._inputs = ('real_A', 'real_B')
         if self.ic_weight > 0.0:
-            self.criterionIC = InverseConsistency_Loss(dim=len(shape), symmetric=True)
-            self._outputs += ('loss_ic',)
+            ic = self.criterionIC = InverseConsistency_Loss(dim=len(shape), symmetric=True)
+            self._terms.append(('ic', self.ic_weight, lambda s: ic(s.flow, s.neg_flow)))
         self.landmark_weight = float(landmark_weight)
         if not self.landmark_weight >= 0.0:
             raise ValueError("landmark_weight must be a weight >= 0, got %r" % (landmark_weight,))
         self.pts_A = self.pts_B = self.pts_w = None
         if self.landmark_weight > 0.0:
-            self.criterionLandmark = Landmark_Loss(dim=len(shape), penalty=landmark_penalty, spacing=spacing)
-            self._outputs += ('loss_landmark',)
+            lmk = self.criterionLandmark = Landmark_Loss(dim=len(shape), penalty=landmark_penalty, spacing=spacing)
+            self._terms.append(('landmark', self.landmark_weight,
+                                lambda s: sym(lmk(s.flow, s.pts_B, s.pts_A, s.pts_w),
+                                              lambda: lmk(s.neg_flow, s.pts_A, s.pts_B, s.pts_w))))
+            self._inputs += ('pts_A', 'pts_B', 'pts_w')
         self.seg_labels, self.seg_weight = seg_labels, float(seg_weight)
         self.seg_A = self.seg_B = None
         if seg_labels is not None:
-            self.criterionDice = LabelDice(seg_labels)
-            self.seg_labels = self.criterionDice.labels
-            self._outputs += ('loss_dice',)
+            dice = self.criterionDice = LabelDice(seg_labels)
+            self.seg_labels = dice.labels
+            self._terms.append(('dice', self.seg_weight, lambda s: dice.loss(s.seg_B, s.seg_A, s.flow)))
+            self._inputs += ('seg_A', 'seg_B')
         if regularizer == 'bending':
-            self.criterionGrad = BendingEnergy_Loss(dim=len(shape), spacing=spacing)
+            reg = self.criterionGrad = BendingEnergy_Loss(dim=len(shape), spacing=spacing)
         else:
-            self.criterionGrad = Grad_Loss(dim=len(shape), penalty='l2')
+            reg = self.criterionGrad = Grad_Loss(dim=len(shape), penalty='l2')
         self.lam = lam
+        keys = tuple('loss_' + k for k, _, _ in self._terms)
+        self._outputs = ('regA', 'flow') + keys[:2] + (('regB', 'neg_flow') if symmetric else ()) + keys[2:]
         self._ddp = False
         self.capture_step = bool(capture_step) and self.device.type == "cuda"
         self._graph = {'eager_steps': 0, 'graph': None, 'shape': None, 'force_eager': False,
@@ -151,41 +171,16 @@ class Registration3DModel(object):
             y_source, y_target, flow, neg_flow = self.netR(self.real_A, self.real_B, return_neg_flow=True)
             self.regB, self.neg_flow = y_target, neg_flow
         else:
-            y_source, y_target, flow = self.netR(self.real_A, self.real_B)
+            (y_source, y_target, flow), neg_flow = self.netR(self.real_A, self.real_B), None
         self.regA, self.flow = y_source, flow
         self.optimizer_R.zero_grad()
-        if self.similarity == 'ncc':
-            loss_sim = self.criterionNCC(y_source, self.real_B)
-            if self.symmetric:
-                loss_sim = (loss_sim + self.criterionNCC(y_target, self.real_A)) * 0.5
-            self.loss_ncc = loss_sim
-        elif self.similarity == 'mind':
-            loss_sim = self.criterionMIND(y_source, self.real_B)
-            if self.symmetric:
-                loss_sim = (loss_sim + self.criterionMIND(y_target, self.real_A)) * 0.5
-            self.loss_mind = loss_sim
-        else:
-            loss_sim = self.criterionNMI(self.real_B, y_source)
-            if self.symmetric:
-                loss_sim = (loss_sim + self.criterionNMI(self.real_A, y_target)) * 0.5
-            self.loss_nmi = loss_sim
-        if self.regularizer == 'bending':
-            self.loss_bending = loss_reg = self.criterionGrad(flow)
-        else:
-            self.loss_grad = loss_reg = self.criterionGrad(flow)
-        total = loss_sim + loss_reg * self.lam
-        if self.ic_weight > 0.0:
-            self.loss_ic = self.criterionIC(flow, neg_flow)
-            total = total + self.loss_ic * self.ic_weight
-        if self.landmark_weight > 0.0:
-            loss_lm = self.criterionLandmark(flow, self.pts_B, self.pts_A, self.pts_w)
-            if self.symmetric:
-                loss_lm = (loss_lm + self.criterionLandmark(neg_flow, self.pts_A, self.pts_B, self.pts_w)) * 0.5
-            self.loss_landmark = loss_lm
-            total = total + loss_lm * self.landmark_weight
-        if self.seg_labels is not None:
-            self.loss_dice = self.criterionDice.loss(self.seg_B, self.seg_A, flow)
-            total = total + self.loss_dice * self.seg_weight
+        step = SimpleNamespace(y_source=y_source, y_target=y_target, flow=flow, neg_flow=neg_flow,
+                               **{k: getattr(self, k) for k in self._inputs})
+        total = None
+        for key, weight, fn in self._terms:
+            term = fn(step)
+            setattr(self, 'loss_' + key, term)
+            total = term if total is None else total + term * weight
         with ops.deferred_weight_grads():
             total.backward()
 
@@ -203,14 +198,9 @@ class Registration3DModel(object):
         # static buffers, the outputs are the capture's tensors; a change of shape or arena re-captures.
         st = self._graph
         side, cur = st['stream'], torch.cuda.current_stream()
-        shape = (tuple(self.real_A.shape), tuple(self.real_B.shape), self.optimizer_R.flat_p.data_ptr(),
-                 self.optimizer_R.flat_g.data_ptr())
-        seg = self.seg_labels is not None
-        if seg:
-            shape += (tuple(self.seg_A.shape), tuple(self.seg_B.shape))
-        lm = self.landmark_weight > 0.0
-        if lm:
-            shape += (tuple(self.pts_A.shape), tuple(self.pts_B.shape), None if self.pts_w is None else tuple(self.pts_w.shape))
+        inputs = {k: getattr(self, k) for k in self._inputs}
+        shape = tuple(None if t is None else tuple(t.shape) for t in inputs.values()) + (
+            self.optimizer_R.flat_p.data_ptr(), self.optimizer_R.flat_g.data_ptr())
         if st['graph'] is not None and st['shape'] != shape:
             st.update(graph=None, eager_steps=0)
         if st['force_eager'] or (st['graph'] is None and st['eager_steps'] < 2):
@@ -221,14 +211,8 @@ class Registration3DModel(object):
             cur.wait_stream(side)
             return self._apply_updates()
         if st['graph'] is None:
-            st['in_A'], st['in_B'] = self.real_A.clone(), self.real_B.clone()
-            self.real_A, self.real_B = st['in_A'], st['in_B']
-            if seg:
-                st['in_segA'], st['in_segB'] = self.seg_A.clone(), self.seg_B.clone()
-                self.seg_A, self.seg_B = st['in_segA'], st['in_segB']
-            if lm:
-                st['in_pts'] = [None if t is None else t.clone() for t in (self.pts_A, self.pts_B, self.pts_w)]
-                self.pts_A, self.pts_B, self.pts_w = st['in_pts']
+            st['inputs'] = {k: None if t is None else t.clone() for k, t in inputs.items()}
+            vars(self).update(st['inputs'])
             for k in self._outputs:                                       # drop the previous step's autograd graph
                 v = getattr(self, k, None)
                 if torch.is_tensor(v) and v.grad_fn is not None:
@@ -244,35 +228,13 @@ class Registration3DModel(object):
             st['outputs'] = {k: getattr(self, k) for k in self._outputs}
             st.update(graph=graph, shape=shape)
         else:
-            if self.real_A is not st['in_A']:
-                st['in_A'].copy_(self.real_A, non_blocking=True)
-                st['in_B'].copy_(self.real_B, non_blocking=True)
-            if seg and self.seg_A is not st['in_segA']:
-                st['in_segA'].copy_(self.seg_A, non_blocking=True)
-                st['in_segB'].copy_(self.seg_B, non_blocking=True)
-            if lm:
-                for buf, t in zip(st['in_pts'], (self.pts_A, self.pts_B, self.pts_w)):
-                    if buf is not None and t is not buf:
-                        buf.copy_(t, non_blocking=True)
+            for k, buf in st['inputs'].items():
+                if buf is not None and inputs[k] is not buf:
+                    buf.copy_(inputs[k], non_blocking=True)
             vars(self).update(st['outputs'])
-            self.real_A, self.real_B = st['in_A'], st['in_B']
-            if seg:
-                self.seg_A, self.seg_B = st['in_segA'], st['in_segB']
-            if lm:
-                self.pts_A, self.pts_B, self.pts_w = st['in_pts']
+            vars(self).update(st['inputs'])
         st['graph'].replay()
         self._apply_updates()
 
     def get_current_losses(self):
-        sim = getattr(self, 'loss_' + self.similarity)
-        if self.regularizer == 'bending':
-            out = {self.similarity: float(sim.detach()), 'bending': float(self.loss_bending.detach())}
-        else:
-            out = {self.similarity: float(sim.detach()), 'grad': float(self.loss_grad.detach())}
-        if self.seg_labels is not None:
-            out['dice'] = float(self.loss_dice.detach())
-        if self.ic_weight > 0.0:
-            out['ic'] = float(self.loss_ic.detach())
-        if self.landmark_weight > 0.0:
-            out['landmark'] = float(self.loss_landmark.detach())
-        return out
+        return {k: float(getattr(self, 'loss_' + k).detach()) for k, _, _ in self._terms}

@@ -495,8 +495,8 @@ def test_registration3d_dice_step_vs_oracle(shape):
 def test_registration3d_dice_captured_step_matches_eager():
     """seg_labels under capture_step=True: a replayed step equals the same step enqueued eagerly; a changed label shape
     re-captures."""
-    from dfmir_amd import ops
     from dfmir_amd.registration3d import Registration3DModel
+    from tests import step3d
     shape = (32, 32, 32)
     torch.manual_seed(0)
     m = Registration3DModel(shape, None, capture_step=True, device=DEV, seg_labels=SEG_LABELS, seg_weight=SEG_WEIGHT)
@@ -505,31 +505,11 @@ def test_registration3d_dice_captured_step_matches_eager():
     B = (0.5 * A + 0.5 * C.rand(142, 1, 1, *shape).to(DEV))
     A_seg, B_seg = (x.to(DEV) for x in _seg_pair(shape, 143))
     data = {"A": A, "B": B, "A_seg": A_seg, "B_seg": B_seg}
-    for _ in range(3):                                    # two eager steps, then the capture
+    for _ in range(3):                                    # two eager steps, then the capture: the label maps are its buffers
         m.set_input(data); m.optimize_parameters()
     assert m._graph['graph'] is not None
-    assert m.seg_A is m._graph['in_segA'] and m.seg_B is m._graph['in_segB']
-    o = m.optimizer_R
-    for _ in range(2):
-        snap = (o.flat_p.clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), o._steps)
-        m.set_input(data); m.optimize_parameters()          # replay
-        torch.cuda.synchronize()
-        got = (m.get_current_losses(), m.regA.clone(), m.flow.clone(), o.flat_g.clone(), o.flat_p.clone())
-        with torch.no_grad():
-            o.flat_p.copy_(snap[0]); o.exp_avg.copy_(snap[1]); o.exp_avg_sq.copy_(snap[2])
-        o._steps = snap[3]
-        ops.bump_weights_epoch()
-        m._graph['force_eager'] = True
-        m.set_input(data); m.optimize_parameters()          # the same step, eager
-        m._graph['force_eager'] = False
-        torch.cuda.synchronize()
-        ref = (m.get_current_losses(), m.regA, m.flow, o.flat_g, o.flat_p)
-        assert sorted(ref[0]) == ["dice", "grad", "ncc"]
-        for k in ref[0]:
-            assert abs(got[0][k] - ref[0][k]) <= 1e-5 * max(abs(ref[0][k]), 1e-8), (k, got[0][k], ref[0][k])
-        for a, b, tol, what in ((got[1], ref[1], 1e-6, "regA"), (got[2], ref[2], 1e-5, "flow"), (got[3], ref[3], 5e-5, "grads")):
-            err = float((a - b).abs().max())
-            assert err <= tol * float(b.abs().max()) + 1e-12, (what, err, float(b.abs().max()))
+    assert m.seg_A is m._graph['inputs']['seg_A'] and m.seg_B is m._graph['inputs']['seg_B']
+    step3d.assert_replay_matches_eager(m, data, ["dice", "grad", "ncc"])
 
 
 @pytest.mark.gpu

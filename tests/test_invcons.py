@@ -47,6 +47,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import step3d
 from tests.golden import common as C
 
 DEV = "cuda"
@@ -596,23 +597,12 @@ def test_inverse_consistency_error_on_a_hand_checked_case():
 MODEL_CASES = [((16, 16, 16), 'ncc'), ((32, 32), 'mind')]
 
 
-def _step_model(shape, similarity, capture=False, **kw):
-    from dfmir_amd.registration3d import Registration3DModel
-    from tests.test_mind import mind_inputs
-    torch.manual_seed(0)
-    m = Registration3DModel(shape, None, capture_step=capture, device=DEV, similarity=similarity, **kw)
-    with torch.no_grad():
-        m.netR.flow.weight.mul_(3e4)              # a flow of voxels, not of 1e-5 voxels
-    A, B = (t.to(DEV) for t in mind_inputs((1, 1) + shape, 640))
-    return m, A, B
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,similarity", MODEL_CASES, ids=["3d-ncc", "2d-mind"])
 def test_registration3d_symmetric_ic_step_matches_restatement(shape, similarity):
     """Two eager steps: finite losses, 'ic' present and equal to the restatement on the model's own pair of fields (neither
     family: the bound is the larger of the two loss bounds)."""
-    m, A, B = _step_model(shape, similarity, symmetric=True, inverse_consistency=0.1)
+    m, A, B = step3d.step_model(shape, similarity, symmetric=True, inverse_consistency=0.1)
     for _ in range(2):
         m.set_input({"A": A, "B": B})
         m.optimize_parameters()
@@ -635,7 +625,7 @@ def test_registration3d_symmetric_nmi_with_seg_labels():
     evaluated again on the step's own outputs by the same kernels (fp32 sums of the same numbers: 1e-6)."""
     from tests.test_dice import SEG_LABELS, _seg_pair
     shape = (16, 16, 16)
-    m, A, B = _step_model(shape, 'nmi', symmetric=True, inverse_consistency=0.1, seg_labels=SEG_LABELS, seg_weight=0.7)
+    m, A, B = step3d.step_model(shape, 'nmi', symmetric=True, inverse_consistency=0.1, seg_labels=SEG_LABELS, seg_weight=0.7)
     A_seg, B_seg = (x.to(DEV) for x in _seg_pair(shape, 143))
     for _ in range(2):
         m.set_input({"A": A, "B": B, "A_seg": A_seg, "B_seg": B_seg})
@@ -655,36 +645,10 @@ def test_registration3d_symmetric_nmi_with_seg_labels():
 def test_registration3d_symmetric_ic_captured_step_matches_eager(shape, similarity):
     """symmetric=True, inverse_consistency=0.1 under capture_step=True: a replayed step equals the same step enqueued eagerly
     (the pattern and the tolerances of test_bending.py's captured-step test), for two steps."""
-    from dfmir_amd import ops
-    m, A, B = _step_model(shape, similarity, capture=True, symmetric=True, inverse_consistency=0.1)
+    m, A, B = step3d.step_model(shape, similarity, capture=True, symmetric=True, inverse_consistency=0.1)
     m.parallelize()
-    for _ in range(3):                                    # two eager steps, then the capture
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()
-    assert m._graph['graph'] is not None
-    o = m.optimizer_R
-    for _ in range(2):
-        snap = (o.flat_p.clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), o._steps)
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()          # replay
-        torch.cuda.synchronize()
-        got = (m.get_current_losses(), m.regA.clone(), m.flow.clone(), o.flat_g.clone(), m.regB.clone(), m.neg_flow.clone())
-        with torch.no_grad():
-            o.flat_p.copy_(snap[0]); o.exp_avg.copy_(snap[1]); o.exp_avg_sq.copy_(snap[2])
-        o._steps = snap[3]
-        ops.bump_weights_epoch()
-        m._graph['force_eager'] = True
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()          # the same step, eager
-        m._graph['force_eager'] = False
-        torch.cuda.synchronize()
-        ref = (m.get_current_losses(), m.regA, m.flow, o.flat_g, m.regB, m.neg_flow)
-        assert sorted(ref[0]) == sorted(["grad", "ic", similarity])
-        for k in ref[0]:
-            assert math.isfinite(got[0][k])
-            assert abs(got[0][k] - ref[0][k]) <= 1e-5 * max(abs(ref[0][k]), 1e-8), (k, got[0][k], ref[0][k])
-        for x, y, tol, what in ((got[1], ref[1], 1e-6, "regA"), (got[2], ref[2], 1e-5, "flow"), (got[3], ref[3], 5e-5, "grads"),
-                                (got[4], ref[4], 1e-6, "regB"), (got[5], ref[5], 1e-5, "neg_flow")):
-            err = float((x - y).detach().abs().max())
-            ymax = float(y.detach().abs().max())
-            assert err <= tol * ymax + 1e-12, (what, err, ymax)
+    step3d.assert_replay_matches_eager(m, {"A": A, "B": B}, ["grad", "ic", similarity],
+                                       extra=(("regB", 1e-6), ("neg_flow", 1e-5)))
 
 
 @pytest.mark.gpu
@@ -697,7 +661,7 @@ def test_registration3d_defaults_reproduce_the_one_directional_step(shape, simil
     try:
         res = []
         for kw in ({}, dict(symmetric=False, inverse_consistency=0.0)):
-            m, A, B = _step_model(shape, similarity, deterministic_wgrad=True, **kw)
+            m, A, B = step3d.step_model(shape, similarity, deterministic_wgrad=True, **kw)
             m.set_input({"A": A, "B": B})
             m.optimize_parameters()
             torch.cuda.synchronize()

@@ -39,6 +39,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import step3d
 from tests.golden import common as C
 
 DEV = "cuda"
@@ -735,17 +736,6 @@ def _model_points(shape, K=24, seed=820):
     return a_pts, b_pts, w
 
 
-def _step_model(shape, similarity, capture=False, **kw):
-    from dfmir_amd.registration3d import Registration3DModel
-    from tests.test_mind import mind_inputs
-    torch.manual_seed(0)
-    m = Registration3DModel(shape, None, capture_step=capture, device=DEV, similarity=similarity, **kw)
-    with torch.no_grad():
-        m.netR.flow.weight.mul_(3e4)              # a flow of voxels, not of 1e-5 voxels
-    A, B = (t.to(DEV) for t in mind_inputs((1, 1) + shape, 640))
-    return m, A, B
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,similarity", MODEL_CASES, ids=["3d-ncc", "2d-mind"])
 def test_registration3d_landmark_step_eager_and_captured(shape, similarity):
@@ -761,7 +751,7 @@ def test_registration3d_landmark_step_eager_and_captured(shape, similarity):
     try:
         res = []
         for capture in (False, True):
-            m, A, B = _step_model(shape, similarity, capture=capture, deterministic_wgrad=True, landmark_weight=1.0,
+            m, A, B = step3d.step_model(shape, similarity, capture=capture, deterministic_wgrad=True, landmark_weight=1.0,
                                   landmark_penalty='tre')
             with pytest.raises(KeyError, match="B_pts"):
                 m.set_input({"A": A, "B": B, "A_pts": a_pts})
@@ -794,7 +784,7 @@ def test_registration3d_landmark_symmetric_adds_the_reverse_term(shape, similari
     from dfmir_amd import ops
     a_pts, b_pts, w = _model_points(shape)
     sp = (1.5, 1.0, 0.8)[:len(shape)]
-    m, A, B = _step_model(shape, similarity, symmetric=True, landmark_weight=0.5, spacing=sp)
+    m, A, B = step3d.step_model(shape, similarity, symmetric=True, landmark_weight=0.5, spacing=sp)
     for _ in range(2):
         m.set_input({"A": A, "B": B, "A_pts": a_pts, "B_pts": b_pts, "pts_weight": w})
         m.optimize_parameters()
@@ -822,7 +812,7 @@ def test_registration3d_landmark_defaults_reproduce_the_step(shape, similarity):
     try:
         res = []
         for kw in ({}, dict(landmark_weight=0.0, landmark_penalty='l2')):
-            m, A, B = _step_model(shape, similarity, deterministic_wgrad=True, **kw)
+            m, A, B = step3d.step_model(shape, similarity, deterministic_wgrad=True, **kw)
             m.set_input({"A": A, "B": B, "A_pts": a_pts, "B_pts": b_pts} if kw else {"A": A, "B": B})
             m.optimize_parameters()
             torch.cuda.synchronize()

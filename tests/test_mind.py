@@ -352,14 +352,8 @@ def test_mind_bit_reproducible(shape):
 
 
 def _step_model(capture):
-    from dfmir_amd.registration3d import Registration3DModel
-    shape = (16, 16, 16)
-    torch.manual_seed(0)
-    m = Registration3DModel(shape, None, capture_step=capture, device=DEV, similarity='mind')
-    with torch.no_grad():
-        m.netR.flow.weight.mul_(3e4)              # a flow of voxels, not of 1e-5 voxels
-    A, B = (t.to(DEV) for t in mind_inputs((1, 1) + shape, 640))
-    return m, A, B
+    from tests import step3d
+    return step3d.step_model((16, 16, 16), 'mind', capture=capture)
 
 
 @pytest.mark.gpu
@@ -381,30 +375,7 @@ def test_registration3d_mind_step_matches_restatement():
 def test_registration3d_mind_captured_step_matches_eager():
     """similarity='mind' under capture_step=True: a replayed step equals the same step enqueued eagerly (the pattern of
     test_nmi.py's captured-step test)."""
-    from dfmir_amd import ops
+    from tests import step3d
     m, A, B = _step_model(True)
     m.parallelize()
-    for _ in range(3):                                    # two eager steps, then the capture
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()
-    assert m._graph['graph'] is not None
-    o = m.optimizer_R
-    for _ in range(2):
-        snap = (o.flat_p.clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), o._steps)
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()          # replay
-        torch.cuda.synchronize()
-        got = (m.get_current_losses(), m.regA.clone(), m.flow.clone(), o.flat_g.clone(), o.flat_p.clone())
-        with torch.no_grad():
-            o.flat_p.copy_(snap[0]); o.exp_avg.copy_(snap[1]); o.exp_avg_sq.copy_(snap[2])
-        o._steps = snap[3]
-        ops.bump_weights_epoch()
-        m._graph['force_eager'] = True
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()          # the same step, eager
-        m._graph['force_eager'] = False
-        torch.cuda.synchronize()
-        ref = (m.get_current_losses(), m.regA, m.flow, o.flat_g, o.flat_p)
-        assert sorted(ref[0]) == ["grad", "mind"]
-        for k in ref[0]:
-            assert abs(got[0][k] - ref[0][k]) <= 1e-5 * max(abs(ref[0][k]), 1e-8), (k, got[0][k], ref[0][k])
-        for x, y, tol, what in ((got[1], ref[1], 1e-6, "regA"), (got[2], ref[2], 1e-5, "flow"), (got[3], ref[3], 5e-5, "grads")):
-            err = float((x - y).abs().max())
-            assert err <= tol * float(y.abs().max()) + 1e-12, (what, err, float(y.abs().max()))
+    step3d.assert_replay_matches_eager(m, {"A": A, "B": B}, ["grad", "mind"])

@@ -343,33 +343,11 @@ def test_registration3d_gaussian_step_and_unchanged_default(golden):
 def test_registration3d_gaussian_captured_step_matches_eager():
     """ncc_kernel='gaussian' under capture_step=True, by the criterion of test_registration3d_captured_step_matches_eager:
     two eager steps, the capture, then each replayed step equals the same step enqueued eagerly from the restored state."""
-    from dfmir_amd import ops
     from dfmir_amd.registration3d import Registration3DModel
+    from tests import step3d
     shape = (16, 16, 16)
     torch.manual_seed(0)
     m = Registration3DModel(shape, None, capture_step=True, device=DEV, ncc_kernel='gaussian')
     A, B = (t.to(DEV) for t in _volumes(shape))
-    for _ in range(3):                                    # two eager steps, then the capture
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()
-    assert m._graph['graph'] is not None
-    o = m.optimizer_R
-    for _ in range(2):
-        snap = (o.flat_p.clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), o._steps)
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()          # replay
-        torch.cuda.synchronize()
-        got = (m.get_current_losses(), m.regA.clone(), m.flow.clone(), o.flat_g.clone(), o.flat_p.clone())
-        with torch.no_grad():
-            o.flat_p.copy_(snap[0]); o.exp_avg.copy_(snap[1]); o.exp_avg_sq.copy_(snap[2])
-        o._steps = snap[3]
-        ops.bump_weights_epoch()
-        m._graph['force_eager'] = True
-        m.set_input({"A": A, "B": B}); m.optimize_parameters()          # the same step, eager
-        m._graph['force_eager'] = False
-        torch.cuda.synchronize()
-        ref = (m.get_current_losses(), m.regA, m.flow, o.flat_g, o.flat_p)
-        assert sorted(ref[0]) == ["grad", "ncc"] and ref[0]["ncc"] < 0.0
-        for k in ref[0]:
-            assert abs(got[0][k] - ref[0][k]) <= 1e-5 * max(abs(ref[0][k]), 1e-8), (k, got[0][k], ref[0][k])
-        for a, b, tol, what in ((got[1], ref[1], 1e-6, "regA"), (got[2], ref[2], 1e-5, "flow"), (got[3], ref[3], 5e-5, "grads")):
-            err = float((a - b).abs().max())
-            assert err <= tol * float(b.abs().max()) + 1e-12, (what, err, float(b.abs().max()))
+    refs = step3d.assert_replay_matches_eager(m, {"A": A, "B": B}, ["grad", "ncc"])
+    assert all(r["ncc"] < 0.0 for r in refs)
