@@ -147,6 +147,11 @@ _SIGS = {
     "dfmir_invcons_fwd": [c_int, P, P, P, P, P, P] + [c_int] * 4 + [P],
     "dfmir_invcons_bwd_ws_floats": [c_int] * 5,
     "dfmir_invcons_bwd": [c_int, P, P, P, P, P, P, P] + [c_int] * 4 + [P],
+    "dfmir_warp_ssd_ws_floats": [c_int] * 6,
+    "dfmir_warp_ssd_pack": [c_int, P, P] + [c_int] * 5 + [P],
+    "dfmir_warp_ssd_fwd": [c_int] + [P] * 9 + [c_int] * 5 + [P],
+    "dfmir_warp_ssd_fwd_grad": [c_int] + [P] * 10 + [c_int] * 5 + [P],
+    "dfmir_warp_ssd_bwd": [P, P, P, P, c_longlong, P],
     "dfmir_landmark_ws_floats": [c_int] * 6,
     "dfmir_landmark_fwd": [c_int] + [P] * 10 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
     "dfmir_landmark_bwd": [c_int] + [P] * 8 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
@@ -224,6 +229,7 @@ def lib():
         h.dfmir_bend_ws_floats.restype = c_longlong
         h.dfmir_invcons_ws_floats.restype = c_longlong
         h.dfmir_invcons_bwd_ws_floats.restype = c_longlong
+        h.dfmir_warp_ssd_ws_floats.restype = c_longlong
         h.dfmir_landmark_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong

@@ -4,7 +4,120 @@ warp to the CPU, test.py:80-81)."""
 import torch
 
 from . import ops
+from .losses import BendingEnergy_Loss, Grad_Loss
 from .voxelmorph import SpatialTransformer
+
+
+def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
+                regularizer='diffusion', lam, spacing=None, grid_downsize=2, iters=50, lr, betas=(0.9, 0.999)):
+    """Instance optimisation: `iters` Adam iterations on the displacement field of ONE pair (build-defined), the step
+    between a network's flow and the reported number.  Returns dict(flow, warped, history).
+
+    moving, fixed: [B,1,*vol] fp32 images, 2-D or 3-D; flow: the starting field [B,nd,*vol] in voxels (ops.warp's
+    convention), None = zeros.  features: 'mind' = ops.mind_descriptor(., mind_radius, mind_dilation) of both images (12
+    channels in 3-D, 4 in 2-D), 'intensity' = the images themselves, or a pair (moving features, fixed features) of
+    [B,C,*vol] tensors, 1 <= C <= 16.  The unknown is a residual delta [B,nd,*(vol // grid_downsize)], zero at the start:
+
+        flow_k = flow + ops.resize_linear(delta_k, vol)                     (iteration 0 evaluates `flow` itself)
+        J_k    = ops.warp_ssd(Mm, Mf, flow_k, mask) + lam * R(flow_k)        R = Grad_Loss('l2') ('diffusion') or
+                                                                             BendingEnergy_Loss(spacing) ('bending')
+        delta_{k+1} = Adam(lr, betas, eps 1e-8)(delta_k, dJ_k / d delta)     (ops.adam_step)
+
+    The moving features are packed once (ops.pack_features).  history: a device tensor [iters + 1, 2] of (similarity,
+    regulariser) at flow_0 .. flow_iters; the returned flow is flow_iters (with iters = 0: `flow` bit for bit) and warped =
+    ops.warp(moving, flow).  Nothing in the loop syncs with the host.  ValueError on an unknown option, on shapes that
+    disagree and on a coarse dimension < 2."""
+    what = "refine_flow"
+    if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
+            or tuple(moving.shape) != tuple(fixed.shape):
+        raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
+    nd = moving.dim() - 2
+    B, vol = int(moving.shape[0]), tuple(int(n) for n in moving.shape[2:])
+    if isinstance(grid_downsize, bool) or not isinstance(grid_downsize, int) or grid_downsize < 1:
+        raise ValueError("%s: grid_downsize must be an integer >= 1, got %r" % (what, grid_downsize))
+    coarse = tuple(n // grid_downsize for n in vol)
+    if min(coarse) < 2:
+        raise ValueError("%s: every dimension of the coarse grid %s = %s // %d must be >= 2"
+                         % (what, coarse, vol, grid_downsize))
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError("%s: iters must be an integer >= 0, got %r" % (what, iters))
+    if regularizer not in ('diffusion', 'bending'):
+        raise ValueError("%s: regularizer must be 'diffusion' or 'bending', got %r" % (what, regularizer))
+    if flow is not None and (not torch.is_tensor(flow) or tuple(flow.shape) != (B, nd) + vol):
+        raise ValueError("%s: flow must be [B,%d,*vol] = %s" % (what, nd, (B, nd) + vol))
+    if isinstance(features, str):
+        if features not in ('mind', 'intensity'):
+            raise ValueError("%s: features must be 'mind', 'intensity' or a pair of tensors, got %r" % (what, features))
+        if moving.shape[1] != 1:
+            raise ValueError("%s: features=%r needs single-channel images, got %d channels" % (what, features, moving.shape[1]))
+    else:
+        try:
+            Mm, Mf = features
+        except (TypeError, ValueError):
+            raise ValueError("%s: features must be 'mind', 'intensity' or a pair of [B,C,*vol] tensors" % what)
+        for t in (Mm, Mf):
+            if not torch.is_tensor(t) or t.dim() != nd + 2 or (int(t.shape[0]),) + tuple(t.shape[2:]) != (B,) + vol:
+                raise ValueError("%s: the feature tensors must be [B,C,*vol] over the images' volume %s" % (what, vol))
+    reg = Grad_Loss(dim=nd, penalty='l2') if regularizer == 'diffusion' else BendingEnergy_Loss(dim=nd, spacing=spacing)
+    with torch.no_grad():
+        if features == 'mind':
+            Mm = ops.mind_descriptor(moving, mind_radius, mind_dilation)
+            Mf = ops.mind_descriptor(fixed, mind_radius, mind_dilation)
+        elif features == 'intensity':
+            Mm, Mf = moving.detach(), fixed.detach()
+        else:
+            Mm, Mf = Mm.detach(), Mf.detach()
+        handle = ops.pack_features(Mm)
+        flow0 = None if flow is None else flow.detach()
+        delta = ops.zeros((B, nd) + coarse, handle.packed.device)
+        m, v = ops.zeros_like(delta), ops.zeros_like(delta)
+        history = torch.empty((iters + 1, 2), device=delta.device, dtype=torch.float32)
+
+    def flow_of(d):
+        up = ops.resize_linear(d, vol)
+        return up if flow0 is None else flow0 + up
+
+    for k in range(iters):
+        d = delta.detach().requires_grad_(True)
+        with torch.enable_grad():
+            flow_k = flow_of(d)
+            sim = ops.warp_ssd(handle, Mf, flow_k, mask)
+            r = reg(flow_k)
+            (g,) = torch.autograd.grad(sim + r * float(lam), d)
+        with torch.no_grad():
+            history[k, 0], history[k, 1] = sim.detach(), r.detach()
+            ops.adam_step(delta, g, m, v, lr, betas[0], betas[1], 1e-8, k + 1, bump=False)
+    with torch.no_grad():
+        if iters == 0:
+            out = ops.zeros((B, nd) + vol, delta.device) if flow0 is None else flow0.clone()
+        else:
+            out = flow_of(delta)
+        history[iters, 0] = ops.warp_ssd(handle, Mf, out, mask)
+        history[iters, 1] = reg(out)
+        warped = ops.warp(moving, out)
+    return dict(flow=out, warped=warped, history=history)
+
+
+def _refine_kwargs(refine, what):
+    if not isinstance(refine, dict):
+        raise ValueError("%s: refine must be None or a dict of refine_flow keywords, got %s" % (what, type(refine).__name__))
+    return refine
+
+
+@torch.no_grad()
+def register_volume(model, data, refine=None):
+    """The inference entry of Registration3DModel: register data['A'] onto data['B'].  Returns dict(warped_A, flow) of
+    netR(real_A, real_B, registration=True); with refine = a dict of refine_flow keywords (lam and lr at least) the flow is
+    then refined on this pair and 'refined_flow', 'refined_A' (real_A warped by it) and 'history' are added."""
+    if refine is not None:
+        _refine_kwargs(refine, "register_volume")
+    model.set_input(data)
+    warped_A, flow = model.netR(model.real_A, model.real_B, registration=True)
+    out = dict(warped_A=warped_A, flow=flow)
+    if refine is not None:
+        res = refine_flow(model.real_A, model.real_B, flow, **refine)
+        out.update(refined_flow=res['flow'], refined_A=res['warped'], history=res['history'])
+    return out
 
 
 @torch.no_grad()
@@ -29,6 +142,19 @@ def register_pair(model, data, label=None, fixed_label=None, labels=None):
             mov = ops.as_label_map(label.to(flow.device))
             fix = ops.as_label_map(fixed_label.to(flow.device))
             out['dice'] = ops.warp_dice(mov, fix, flow.detach(), labels, mode='nearest')[1]
+    return out
+
+
+@torch.no_grad()
+def register_pair_refined(model, data, refine, label=None, fixed_label=None, labels=None):
+    """register_pair followed by instance optimisation of its flow: register_pair's own dict (every key as it is, 'warped_label'
+    and 'dice' those of the network's flow) plus 'refined_flow', 'refined_A' and 'history' of refine_flow(real_A, real_B,
+    flow, **refine); refine = a dict of refine_flow keywords (lam and lr at least).  A function of its own because
+    register_pair's signature is pinned."""
+    _refine_kwargs(refine, "register_pair_refined")
+    out = register_pair(model, data, label, fixed_label, labels)
+    res = refine_flow(model.real_A, model.real_B, out['flow'], **refine)
+    out.update(refined_flow=res['flow'], refined_A=res['warped'], history=res['history'])
     return out
 
 

@@ -262,6 +262,43 @@ class InverseConsistency_Loss(_Loss):
         return loss
 
 
+class WarpedSSD_Loss(_Loss):
+    """Build-defined (the reference has no such term): the SSD between fixed-image features and warped moving-image
+    features, the data term of instance optimisation (infer.refine_flow), value and flow gradient in one fused pass.
+    `WarpedSSD_Loss(dim)(moving_features, fixed_features, flow, mask=None)`.
+
+    M, F [B,C,*vol], fp32, nd = `dim` = 2 or 3, 1 <= C <= 16 (M may be the handle of ops.pack_features(M): the voxel-major
+    copy the gather reads, made once per loop); phi [B,nd,*vol] a displacement in voxels, channel d displacing axis d in
+    the order (z,) y, x, exactly as ops.warp reads a flow.
+
+        e_c(x) = M_c(x + phi(x)) - F_c(x)      M sampled (bi/tri)linearly, align_corners=True, corners outside the volume
+                                               read as 0: e = ops.warp(M, phi) - F, element for element
+        L      = mean over (B, C, voxels) of e^2
+        with `mask` m (float weights that broadcast to [B,1,*vol]):  L = sum m * mean_c e^2 / sum m,  0 for an empty mask
+        (a device scalar, no host sync); per sample (ops.warp_ssd_per_sample) the same over sample b alone
+
+        dL/dphi_d(x) = k(x) sum_c e_c(x) d_d M_c(x + phi(x)),   k = 2 gout / (B C S), masked 2 gout m(x) / (C sum m)
+
+    where d_d is the derivative of the multilinear interpolant in the cell floor() selects: corner differences, with
+    zero-padded corners taking part as zeros.  Gradients go to phi ONLY: features or a mask that require grad raise a
+    ValueError instead of being dropped silently.  `loss_mult` scales the result.  Bit-identical from run to run;
+    capturable (ops.warp_ssd; dfmir_amd/csrc/warpssd.hip)."""
+
+    def __init__(self, dim=3, name=None, loss_mult=None, *args, **kwargs):
+        super().__init__(name=name or 'warped_ssd')
+        if dim not in (2, 3):
+            raise ValueError("WarpedSSD_Loss: dim must be 2 or 3, got %r" % (dim,))
+        self.dim, self.loss_mult = dim, loss_mult
+
+    def forward(self, moving_features, fixed_features, flow, mask=None, *args, **kwargs):
+        if flow.dim() - 2 != self.dim:
+            raise ValueError("WarpedSSD_Loss(dim=%d) got a %d-D field" % (self.dim, flow.dim() - 2))
+        loss = ops.warp_ssd(moving_features, fixed_features, flow, mask=mask)
+        if self.loss_mult is not None:
+            loss = ops.scale(loss.view(1), self.loss_mult).view(())
+        return loss
+
+
 class Landmark_Loss(_Loss):
     """Build-defined (the reference has no landmark code): the registration error of corresponding landmarks carried
     through a displacement field, the keypoint supervision of multi-modal registration.

@@ -2561,6 +2561,138 @@ def inverse_consistency_per_sample(u, v):
     return _invcons_fwd(_c(u), _c(v), geom)[:geom[1]].clone()
 
 
+WARP_SSD_MAX_C = 16
+
+# What ops.pack_features returns: `packed` [B,*vol,Cp] voxel-major (Cp = C rounded up to 4, zeros in the padding channels),
+# `planar` the contiguous [B,C,*vol] tensor it was made from (the DFMIR_WARPSSD_PLANAR gather reads it), `shape` = planar's.
+PackedFeatures = collections.namedtuple("PackedFeatures", "packed planar shape")
+
+
+def _features_geom(M, what, name="mov"):
+    """(nd, B, C, D, H, W) of a [B,C,*vol] feature tensor after the argument checks (ValueError: nothing is launched)."""
+    if not torch.is_tensor(M) or M.dim() not in (4, 5):
+        raise ValueError("%s: %s must be a [B,C,H,W] or [B,C,D,H,W] tensor, got %s"
+                         % (what, name, tuple(M.shape) if torch.is_tensor(M) else type(M).__name__))
+    nd = M.dim() - 2
+    B, C = int(M.shape[0]), int(M.shape[1])
+    if not 1 <= C <= WARP_SSD_MAX_C:
+        raise ValueError("%s: %s needs 1 to %d channels, got %d" % (what, name, WARP_SSD_MAX_C, C))
+    D, H, W = (int(n) for n in (M.shape[2:] if nd == 3 else (1,) + tuple(M.shape[2:])))
+    if B < 1 or min(M.shape[2:]) < 2:
+        raise ValueError("%s: %s needs B >= 1 and every extent >= 2, got %s" % (what, name, tuple(M.shape)))
+    if M.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (%s is %s)" % (what, name, M.dtype))
+    if B * ((C + 3) // 4 * 4) * D * H * W >= 2 ** 31 or B * nd * D * H * W >= 2 ** 31:
+        raise ValueError("%s: %s %s has 2^31 or more elements (packed)" % (what, name, tuple(M.shape)))
+    if M.requires_grad:
+        raise ValueError("%s: %s requires grad, but the op has no gradient to the features (detach it)" % (what, name))
+    return nd, B, C, D, H, W
+
+
+def pack_features(M):
+    """The moving-side features of ops.warp_ssd laid out for its gather: M [B,C,*vol] (fp32, 1 <= C <= 16, 2-D or 3-D) ->
+    PackedFeatures(packed [B,*vol,Cp], planar, shape), Cp = C rounded up to 4.  Made once for as many warp_ssd calls as the
+    features live (a refinement loop).  ValueError on a bad rank, channel count, extent < 2, dtype, 2^31 or more elements
+    or a tensor that requires grad; a CPU tensor raises the usual "no CPU fallback" error."""
+    nd, B, C, D, H, W = _features_geom(M, "pack_features", "M")
+    _need(M)
+    M = _c(M)
+    packed = torch.empty((B,) + tuple(M.shape[2:]) + ((C + 3) // 4 * 4,), device=M.device, dtype=torch.float32)
+    check(lib().dfmir_warp_ssd_pack(nd, _p(M), _p(packed), B, C, D, H, W, _st()))
+    return PackedFeatures(packed, M, tuple(M.shape))
+
+
+def _warp_ssd_args(mov, fix, flow, mask, what):
+    """(geom, handle, fix, flow, mask [B,1,*vol] or None) of a warp_ssd call after the argument checks; a [B,C,*vol] `mov`
+    is packed here.  Everything a CPU tensor can get wrong raises ValueError before the device is asked for."""
+    packed = isinstance(mov, PackedFeatures)
+    if packed:
+        shape = tuple(mov.shape)
+        geom = _features_geom(mov.planar, what)
+        if tuple(mov.planar.shape) != shape or tuple(mov.packed.shape) != (shape[0],) + shape[2:] + ((shape[1] + 3) // 4 * 4,):
+            raise ValueError("%s: mov is not a handle ops.pack_features made" % what)
+    else:
+        geom = _features_geom(mov, what)
+        shape = tuple(mov.shape)
+    nd, B, C, D, H, W = geom
+    if not torch.is_tensor(fix) or tuple(fix.shape) != shape:
+        raise ValueError("%s: mov %s / fix %s differ in shape" % (what, shape, tuple(fix.shape) if torch.is_tensor(fix) else fix))
+    _features_geom(fix, what, "fix")
+    if not torch.is_tensor(flow) or tuple(flow.shape) != (B, nd) + shape[2:]:
+        raise ValueError("%s: the flow of %s features is [B,%d,*vol] = %s, got %s"
+                         % (what, shape, nd, (B, nd) + shape[2:], tuple(flow.shape) if torch.is_tensor(flow) else flow))
+    if flow.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (flow is %s)" % (what, flow.dtype))
+    if mask is not None:
+        if not torch.is_tensor(mask):
+            raise ValueError("%s: mask must be a tensor" % what)
+        if mask.requires_grad:
+            raise ValueError("%s: mask requires grad, but the op has no gradient to the mask (detach it)" % what)
+        try:
+            mask = mask.expand((B, 1) + shape[2:])
+        except RuntimeError:
+            raise ValueError("%s: mask %s does not broadcast to %s" % (what, tuple(mask.shape), (B, 1) + shape[2:]))
+    _need(mov.packed if packed else mov, fix, flow)
+    if mask is not None:
+        mask = mask.to(device=flow.device, dtype=torch.float32).contiguous()
+    return geom, (mov if packed else pack_features(mov)), _c(fix), _c(flow), mask
+
+
+def _warp_ssd_launch(geom, h, fix, flow, mask, unit):
+    """[B + 2] floats: L_b per sample, L, and the factor the unit gradient is still to be multiplied with."""
+    nd, B, C, D, H, W = geom
+    ws = torch.empty(int(lib().dfmir_warp_ssd_ws_floats(nd, B, C, D, H, W)), device=flow.device, dtype=torch.float32)
+    out = torch.empty(B + 2, device=flow.device, dtype=torch.float32)
+    if unit is None:
+        check(lib().dfmir_warp_ssd_fwd(nd, _p(h.packed), _p(h.planar), _p(fix), _p(flow), _p(mask), _p(ws), _p(out),
+                                       _p(out[B:]), _p(out[B + 1:]), B, C, D, H, W, _st()))
+    else:
+        check(lib().dfmir_warp_ssd_fwd_grad(nd, _p(h.packed), _p(h.planar), _p(fix), _p(flow), _p(mask), _p(ws), _p(out),
+                                            _p(out[B:]), _p(out[B + 1:]), _p(unit), B, C, D, H, W, _st()))
+    return out
+
+
+class WarpSSDFn(Function):
+    """dfmir_warp_ssd_fwd_grad / _bwd: the forward's one pass leaves the unit gradient, the backward scales it by gout."""
+
+    @staticmethod
+    def forward(ctx, flow, geom, h, fix, mask):
+        unit = torch.empty_like(flow) if ctx.needs_input_grad[0] else None
+        out = _warp_ssd_launch(geom, h, fix, flow, mask, unit)
+        if unit is not None:
+            ctx.save_for_backward(unit, out)
+        ctx.B = geom[1]
+        return out[geom[1]].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        unit, out = ctx.saved_tensors
+        dflow = torch.empty_like(unit)
+        check(lib().dfmir_warp_ssd_bwd(_p(unit), _p(_c(g)), _p(out[ctx.B + 1:]), _p(dflow), unit.numel(), _st()))
+        return dflow, None, None, None, None
+
+
+def warp_ssd(mov, fix, flow, mask=None):
+    """The SSD between fixed-image features and warped moving-image features, the data term of instance optimisation
+    (build-defined; the definition: losses.WarpedSSD_Loss): the mean over (B, C, voxels) of (mov_c(x + flow(x)) - fix_c(x))^2,
+    or with `mask` (float weights that broadcast to [B,1,*vol]) sum mask * mean_c (.)^2 / sum mask -- 0 for an empty mask, as
+    a device scalar without a host sync.  mov: [B,C,*vol] (packed per call) or the handle of ops.pack_features(mov); fix:
+    [B,C,*vol]; flow: [B,nd,*vol] in voxels, ops.warp's convention.  One fused pass, no warped tensor; the gradient goes to
+    the flow ONLY: a `mov`, `fix` or `mask` that requires grad raises.  Bit-identical from run to run.  ValueError before
+    any launch on a bad rank, C outside 1..16, shapes that disagree, a dtype other than fp32, an extent < 2 and 2^31 or
+    more elements; a CPU tensor raises the usual "no CPU fallback" error."""
+    geom, h, fix, flow_c, mask = _warp_ssd_args(mov, fix, flow, mask, "warp_ssd")
+    return WarpSSDFn.apply(flow_c, geom, h, fix, mask)
+
+
+@torch.no_grad()
+def warp_ssd_per_sample(mov, fix, flow, mask=None):
+    """warp_ssd per sample, a [B] tensor without gradient: sample b's own (masked) mean, 0 where its mask is empty."""
+    geom, h, fix, flow_c, mask = _warp_ssd_args(mov, fix, flow, mask, "warp_ssd_per_sample")
+    return _warp_ssd_launch(geom, h, fix, flow_c, mask, None)[:geom[1]].clone()
+
+
 LANDMARK_PENALTIES = {'l2': 0, 'tre': 1}
 LANDMARK_MAX_K = 4096
 
@@ -3293,10 +3425,13 @@ def mean(x):
     return MeanFn.apply(x)
 
 
-def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, bump=True):
+    """One Adam update of p in place (dfmir_adam_step).  bump=False: p is no conv weight (the flow of infer.refine_flow), so
+    the packed weights derived from the parameters stay valid and the weights epoch is left alone."""
     _need(p, g, m, v)
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
     check(lib().dfmir_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2),
                                 float(eps), float(bc1), float(bc2), float(grad_scale), _st()))
-    bump_weights_epoch()
+    if bump:
+        bump_weights_epoch()

@@ -53,7 +53,8 @@ const char* dfmir_last_error(void);
  *     DFMIR_NO_BWD_PAIR (dgrad and wgrad of a 3x3 layer as two launches), DFMIR_BWD_PAIR=0|1 (the same switch with an explicit
  *     value; unset = the build's default), DFMIR_BWD_PAIR_ORDER=n (workgroup order inside dfmir_conv3x3_bwd_pair's grid:
  *     0 weight gradient first, 1 data gradient first, 2 interleaved in groups of 8), DFMIR_INVCONS_FIXED64 (dfmir_invcons_bwd: dv
- *     through the 64-bit fixed-point scatter on every shape).
+ *     through the 64-bit fixed-point scatter on every shape), DFMIR_WARPSSD_PLANAR (dfmir_warp_ssd_fwd / _fwd_grad: gather the
+ *     moving features from the channel-major tensor M instead of the voxel-major packed copy Mp).
  * ---------------------------------------------------------------------------------------- */
 int dfmir_set_option(const char* name, const char* value);
 int dfmir_get_option(const char* name, char* buf, int buf_len);
@@ -618,6 +619,38 @@ int dfmir_invcons_fwd(int nd, const float* u, const float* v, float* ws, float* 
 long long dfmir_invcons_bwd_ws_floats(int nd, int B, int D, int H, int W);
 int dfmir_invcons_bwd(int nd, const float* u, const float* v, const float* gout, const float* rmax, float* du, float* dv,
                       float* ws, int B, int D, int H, int W, void* stream);
+/* Warped-feature SSD, the data term of instance optimisation (build-defined: the reference has no such term).  M, F:
+ * [B][C][(D)][H][W] fp32 features of the moving / fixed image, 1 <= C <= 16; phi: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is
+ * not read when nd == 2), channel d displaces axis d in voxels, in the order (z,) y, x, exactly as the warp kernels read a
+ * flow; mask m: [B][S] fp32 weights or NULL (S = voxels per sample).
+ *   e_c(x) = M_c(x + phi(x)) - F_c(x)      M sampled (bi/tri)linearly, align_corners, corners outside the volume read as 0
+ *   L      = sum over (b, c, x) of e^2 / (B C S);  with a mask  L = sum m(x) mean_c e_c(x)^2 / sum m,  0 for an empty mask
+ *   L_b    = the same over sample b alone
+ *   dL/dphi_d(x) = k(x) sum_c e_c(x) d_d M_c(x + phi(x)),  k = 2 gout / (B C S), masked 2 gout m(x) / (C sum m);  d_d = the
+ *            derivative of the interpolant in the cell floor() selects: corner differences, zero-padded corners taking part
+ *            as zeros.  There is no gradient to M, F or m.
+ * dfmir_warp_ssd_pack: Mp = M voxel-major, [B][(D)][H][W][Cp] with Cp = C rounded up to 4 and zeros in the padding channels
+ * (B * S * Cp floats, 16-byte aligned): made once for as many calls as M lives, a corner then costs Cp / 4 16-byte loads.
+ * dfmir_warp_ssd_fwd_grad, ONE pass over the voxels: per_sample[b] = L_b, loss[0] = L, unit = the gradient for gout = 1
+ * (masked: not yet divided by sum m) and scale[0] = what is left to multiply it with (1; masked 1 / sum m, 0 for an empty
+ * mask).  unit may be NULL; dfmir_warp_ssd_fwd is that call.  dfmir_warp_ssd_bwd: dflow = unit * gout[0] * scale[0] over n
+ * floats, both read on the device.  Mp or M may be NULL: the gather reads Mp unless it is NULL or DFMIR_WARPSSD_PLANAR is on
+ * and M is given.  No warped tensor, no e tensor, no atomics: e^2 is added in double per thread into one double slot per
+ * workgroup (and sum m into a second), and the slots are added in a fixed order -- every output is bit-identical from run to
+ * run.  No float is converted to int for a NaN or a far-away sample point and every address formed lies inside its tensor.
+ * 16-byte accesses of phi, F and unit where W % 4 == 0 and the three are 16-byte aligned.  Refused ("invalid argument",
+ * nothing is launched): nd outside {2, 3}, B < 1, C outside [1, 16], an extent < 2, a NULL pointer other than the optional
+ * ones, B * Cp * S >= 2^31 or B * nd * S >= 2^31.  ws: dfmir_warp_ssd_ws_floats floats (-1 for a refused shape), 8-byte
+ * aligned, need not be zeroed.  Nothing syncs, allocates or keeps state: every call captures into a hipGraph. */
+long long dfmir_warp_ssd_ws_floats(int nd, int B, int C, int D, int H, int W);
+int dfmir_warp_ssd_pack(int nd, const float* M, float* Mp, int B, int C, int D, int H, int W, void* stream);
+int dfmir_warp_ssd_fwd(int nd, const float* Mp, const float* M, const float* F, const float* phi, const float* mask,
+                       float* ws, float* per_sample, float* loss, float* scale, int B, int C, int D, int H, int W,
+                       void* stream);
+int dfmir_warp_ssd_fwd_grad(int nd, const float* Mp, const float* M, const float* F, const float* phi, const float* mask,
+                            float* ws, float* per_sample, float* loss, float* scale, float* unit, int B, int C, int D, int H,
+                            int W, void* stream);
+int dfmir_warp_ssd_bwd(const float* unit, const float* gout, const float* scale, float* dflow, long long n, void* stream);
 /* Landmark (keypoint) registration error of a displacement field (build-defined: the reference has no landmark code).
  * flow u: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when nd == 2); channel a displaces axis a in voxels, in the
  * order (z,) y, x, exactly as the warp kernels read a flow: warped(x) = moving(x + u(x)) with x in the fixed image's grid,
