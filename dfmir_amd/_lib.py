@@ -147,6 +147,11 @@ _SIGS = {
     "dfmir_invcons_fwd": [c_int, P, P, P, P, P, P] + [c_int] * 4 + [P],
     "dfmir_invcons_bwd_ws_floats": [c_int] * 5,
     "dfmir_invcons_bwd": [c_int, P, P, P, P, P, P, P] + [c_int] * 4 + [P],
+    "dfmir_compose_fwd": [c_int, P, P, P] + [c_int] * 4 + [P],
+    "dfmir_compose_bwd_ws_floats": [c_int] * 5,
+    "dfmir_compose_bwd": [c_int, P, P, P, P, P, P] + [c_int] * 4 + [P],
+    "dfmir_flow_invert_ws_floats": [c_int] * 7,
+    "dfmir_flow_invert": [c_int, P, P, P, P, P] + [c_int] * 5 + [c_float, c_int, P],
     "dfmir_warp_ssd_ws_floats": [c_int] * 6,
     "dfmir_warp_ssd_pack": [c_int, P, P] + [c_int] * 5 + [P],
     "dfmir_warp_ssd_fwd": [c_int] + [P] * 9 + [c_int] * 5 + [P],
@@ -229,6 +234,8 @@ def lib():
         h.dfmir_bend_ws_floats.restype = c_longlong
         h.dfmir_invcons_ws_floats.restype = c_longlong
         h.dfmir_invcons_bwd_ws_floats.restype = c_longlong
+        h.dfmir_compose_bwd_ws_floats.restype = c_longlong
+        h.dfmir_flow_invert_ws_floats.restype = c_longlong
         h.dfmir_warp_ssd_ws_floats.restype = c_longlong
         h.dfmir_landmark_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong

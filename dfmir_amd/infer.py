@@ -9,7 +9,8 @@ from .voxelmorph import SpatialTransformer
 
 
 def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
-                regularizer='diffusion', lam, spacing=None, grid_downsize=2, iters=50, lr, betas=(0.9, 0.999)):
+                regularizer='diffusion', lam, spacing=None, grid_downsize=2, iters=50, lr, betas=(0.9, 0.999),
+                update='add'):
     """Instance optimisation: `iters` Adam iterations on the displacement field of ONE pair (build-defined), the step
     between a network's flow and the reported number.  Returns dict(flow, warped, history).
 
@@ -26,8 +27,16 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
     The moving features are packed once (ops.pack_features).  history: a device tensor [iters + 1, 2] of (similarity,
     regulariser) at flow_0 .. flow_iters; the returned flow is flow_iters (with iters = 0: `flow` bit for bit) and warped =
     ops.warp(moving, flow).  Nothing in the loop syncs with the host.  ValueError on an unknown option, on shapes that
-    disagree and on a coarse dimension < 2."""
+    disagree and on a coarse dimension < 2.
+
+    update: how the correction meets the starting flow.  'add' (the default) is the sum above.  'compose' combines the two as
+    deformations do: flow_k = ops.compose_flows(ops.resize_linear(delta_k, vol), flow) = up + flow(x + up(x)) -- the correction
+    is applied in the fixed image's frame and then the starting flow, so warp(moving, flow_k) = warp(warp(moving, flow), up).
+    With flow=None the two are the same computation (bit-identical results); iteration 0 evaluates `flow` itself either way
+    (compose_flows(0, flow) is flow bit for bit).  ValueError on any other value."""
     what = "refine_flow"
+    if update not in ('add', 'compose'):
+        raise ValueError("%s: update must be 'add' or 'compose', got %r" % (what, update))
     if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
             or tuple(moving.shape) != tuple(fixed.shape):
         raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
@@ -75,7 +84,9 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
 
     def flow_of(d):
         up = ops.resize_linear(d, vol)
-        return up if flow0 is None else flow0 + up
+        if flow0 is None:
+            return up
+        return ops.compose_flows(up, flow0) if update == 'compose' else flow0 + up
 
     for k in range(iters):
         d = delta.detach().requires_grad_(True)
@@ -196,6 +207,33 @@ def inverse_consistency_error(flow_ab, flow_ba, spacing=None):
         h = vals[0]
     ic = ops.inverse_consistency_per_sample(flow_ab, flow_ba)
     return torch.sqrt(ic * float(nd)) * h
+
+
+@torch.no_grad()
+def invert_flow(flow, iters=20, tol=0.0):
+    """The inverse of a registration's flow by fixed-point iteration (ops.invert_flow, which states the definition and where
+    the iteration converges): register_pair / register_volume map A onto B, the inverse carries what lives in B's space --
+    labels, landmarks -- back into A's.  Returns dict(inverse [B,nd,*vol]; residual [B] = the RMS over the voxels of |r|, r =
+    inverse + flow(x + inverse(x)), in voxels; residual_max [B] = max |r_c|; history [iters + 1, B, 2] = (rms, max) of every
+    iteration; roundtrip [B] = inverse_consistency_error(flow, inverse), the OTHER direction flow + inverse(x + flow(x)),
+    which the iteration does not drive to zero by itself: a diagnostic).  A residual that stays large says the flow is no
+    contraction somewhere, typically at the volume border (zero padding) or where it folds."""
+    inverse, history = ops.invert_flow(flow, iters=iters, tol=tol, history=True)
+    return dict(inverse=inverse, residual=history[-1, :, 0].clone(), residual_max=history[-1, :, 1].clone(), history=history,
+                roundtrip=inverse_consistency_error(flow, inverse))
+
+
+@torch.no_grad()
+def pull_back_label(fixed_label, flow, iters=20, tol=0.0):
+    """Carry B's label map into A's space: `flow` registers A onto B (warped_A(x) = A(x + flow(x)), x in B's grid), so B's
+    labels are sampled with nearest-neighbour interpolation under the INVERSE flow (ops.invert_flow(flow, iters, tol)):
+    label(y) = fixed_label(y + inverse(y)), y in A's grid, by SpatialTransformer(mode='nearest').  fixed_label: [B,1,*vol], any
+    dtype that converts to float exactly.  Returns dict(label (fp32), inverse, residual [B], residual_max [B]) -- the
+    residuals of the inversion as infer.invert_flow reports them: check them before trusting the labels."""
+    inverse, stats = ops.invert_flow(flow, iters=iters, tol=tol)
+    st = SpatialTransformer(tuple(flow.shape[2:]), mode='nearest').to(flow.device)
+    label = st(fixed_label.to(flow.device).float(), inverse)
+    return dict(label=label, inverse=inverse, residual=stats[:, 0].clone(), residual_max=stats[:, 1].clone())
 
 
 @torch.no_grad()

@@ -2561,6 +2561,129 @@ def inverse_consistency_per_sample(u, v):
     return _invcons_fwd(_c(u), _c(v), geom)[:geom[1]].clone()
 
 
+INVERT_MAX_ITERS = 64                        # INV_MAX_ITERS of dfmir_amd/csrc/compose.hip: one LDS slot per iteration
+
+
+def _flow_geom(fields, what):
+    """(nd, B, D, H, W) of one or more displacement fields [B,nd,*vol] of one shape after the argument checks (ValueError:
+    nothing is launched on a bad one).  `fields`: (name, tensor) pairs."""
+    name0, u = fields[0]
+    for name, t in fields:
+        if not torch.is_tensor(t):
+            raise ValueError("%s: %s must be a [B,nd,*vol] tensor, got %s" % (what, name, type(t).__name__))
+        if t.dim() not in (4, 5):
+            raise ValueError("%s: %s must be a [B,2,H,W] or [B,3,D,H,W] field, got %s" % (what, name, tuple(t.shape)))
+    nd = u.dim() - 2
+    if u.shape[1] != nd:
+        raise ValueError("%s: a %d-D field needs %d channels, got %s %s" % (what, nd, nd, name0, tuple(u.shape)))
+    for name, t in fields[1:]:
+        if tuple(t.shape) != tuple(u.shape):
+            raise ValueError("%s: %s %s / %s %s mismatch (expected [B,nd,*vol] fields of one shape)"
+                             % (what, name0, tuple(u.shape), name, tuple(t.shape)))
+    if min(int(n) for n in u.shape[2:]) < 2:
+        raise ValueError("%s: every extent must be >= 2, got %s" % (what, tuple(u.shape)))
+    for name, t in fields:
+        if t.dtype != torch.float32:
+            raise DfmirHipError("%s: fp32 tensors only (%s is %s)" % (what, name, t.dtype))
+        if t.device != u.device:
+            raise DfmirHipError("%s: %s on %s, %s on %s" % (what, name0, u.device, name, t.device))
+    _need(*[t for _, t in fields])
+    B = int(u.shape[0])
+    D, H, W = (int(n) for n in (u.shape[2:] if nd == 3 else (1,) + tuple(u.shape[2:])))
+    if lib().dfmir_compose_bwd_ws_floats(nd, B, D, H, W) < 0:
+        raise ValueError("%s: needs B >= 1 and fewer than 2^31 elements, got %s" % (what, tuple(u.shape)))
+    return nd, B, D, H, W
+
+
+class ComposeFlowsFn(Function):
+    """dfmir_compose_fwd / _bwd: the forward keeps the two fields, the backward gathers v again."""
+
+    @staticmethod
+    def forward(ctx, u, v, geom):
+        u, v = _c(u), _c(v)
+        nd, B, D, H, W = geom
+        out = torch.empty_like(u)
+        check(lib().dfmir_compose_fwd(nd, _p(u), _p(v), _p(out), B, D, H, W, _st()))
+        ctx.save_for_backward(u, v)
+        ctx.meta = geom
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        u, v = ctx.saved_tensors
+        nd, B, D, H, W = ctx.meta
+        g = _c(g)
+        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
+        dv = ws = None
+        if ctx.needs_input_grad[1]:                   # the dv pass is not launched for a v that needs no gradient
+            dv = torch.empty_like(v)
+            ws = torch.empty(int(lib().dfmir_compose_bwd_ws_floats(nd, B, D, H, W)), device=u.device, dtype=torch.float32)
+        if du is not None or dv is not None:
+            check(lib().dfmir_compose_bwd(nd, _p(u), _p(v), _p(g), _p(du), _p(dv), _p(ws), B, D, H, W, _st()))
+        return du, dv, None
+
+
+def compose_flows(u, v):
+    """Composition of two displacement fields [B,nd,*vol] (nd = 2 or 3, fp32, in voxels, channel order (z,) y, x;
+    build-defined): c(x) = u(x) + v(x + u(x)), v sampled (bi/tri)linearly at x + u(x) with corners outside the volume read
+    as 0 -- ops.warp's convention, c = u + ops.warp(v, u) element for element in one launch and without the warped tensor.
+    Then warp(src, c) is warp(warp(src, v), u) in the continuum: u is the warp applied LAST.  Differentiable in both:
+    du_c = g_c + sum_c' g_c' d_c v_c'(x + u) (d_c: corner differences, padded corners as zeros), dv = the transpose of the
+    interpolation applied to g; a gradient is computed only for the input that needs one.  The value and du are
+    bit-identical from run to run on every shape, dv exactly where ops.inverse_consistency's is (W % 4 == 0 and aligned:
+    the owner-gather adjoint of ops.warp's backward; elsewhere 64-bit fixed-point sums, slower; dfmir_amd/csrc/compose.hip).
+    Non-contiguous inputs are copied, misaligned ones take the scalar launch.  ValueError before any launch on a non-tensor,
+    a rank other than 4 or 5, a channel count other than nd, shapes that disagree, an extent < 2 and 2^31 or more elements; a
+    CPU tensor raises the usual "no CPU fallback" error."""
+    geom = _flow_geom((("u", u), ("v", v)), "compose_flows")
+    return ComposeFlowsFn.apply(u, v, geom)
+
+
+@torch.no_grad()
+def invert_flow(u, iters=20, tol=0.0, init=None, history=False):
+    """Fixed-point inverse of a displacement field [B,nd,*vol] (fp32, in voxels; build-defined): the w with
+    compose_flows(w, u) = 0, i.e. warp(warp(src, u), w) = src in the continuum.  From w_0 = `init` (None = zeros):
+
+        r_k(x)  = w_k(x) + u(x + w_k(x))         = compose_flows(w_k, u), the residual
+        w_{k+1} = w_k - r_k                      = -u(x + w_k(x)) up to rounding
+
+    for `iters` iterations (an int in [0, 64]); a voxel stops updating once max_c |r_k,c| <= tol (tol = 0, the default: every
+    voxel does exactly `iters` updates).  Returns (w, stats): w = w_iters, and stats = a device tensor [B, 2] of (rms, max) of
+    r_iters per sample -- rms = sqrt(sum |r|^2 / S), the RMS over the voxels of the vector length, the quantity
+    infer.inverse_consistency_error reports; max = max |r_c| -- or, with history=True, [iters + 1, B, 2] for r_0 .. r_iters.
+    iters = 0 returns `init` (or zeros) and the statistics of r_0.  All iterations run in ONE launch with w in registers
+    (every voxel iterates on its own: it reads its own w and a gather of u); nothing syncs with the host, there is no
+    autograd through it, and w and stats are bit-identical from run to run.
+
+    Where it stands: the iteration converges where u is a contraction (Lipschitz constant < 1, i.e. |grad u| < 1: any
+    diffeomorphic field of moderate strain).  At the volume border the zero padding makes u drop to 0 within one cell, so a
+    field that is not small at the border does not converge there -- read the returned residual.  ValueError before any
+    launch as compose_flows, and on iters not an int in [0, 64] and a negative or non-finite tol."""
+    fields = (("u", u),) if init is None else (("u", u), ("init", init))
+    what = "invert_flow"
+    for name, t in fields:                            # the tensor checks that need no library call come before the scalars'
+        if not torch.is_tensor(t):
+            raise ValueError("%s: %s must be a [B,nd,*vol] tensor, got %s" % (what, name, type(t).__name__))
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= INVERT_MAX_ITERS:
+        raise ValueError("%s: iters must be an integer in [0, %d], got %r" % (what, INVERT_MAX_ITERS, iters))
+    try:
+        tol = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError("%s: tol must be a finite number >= 0, got %r" % (what, tol))
+    if not 0.0 <= tol < float('inf'):
+        raise ValueError("%s: tol must be a finite number >= 0, got %r" % (what, tol))
+    nd, B, D, H, W = _flow_geom(fields, what)
+    u = _c(u.detach())
+    init = None if init is None else _c(init.detach())
+    hist = 1 if history else 0
+    w = torch.empty_like(u)
+    stats = torch.empty((iters + 1, B, 2) if history else (B, 2), device=u.device, dtype=torch.float32)
+    ws = torch.empty(int(lib().dfmir_flow_invert_ws_floats(nd, B, D, H, W, iters, hist)), device=u.device, dtype=torch.float32)
+    check(lib().dfmir_flow_invert(nd, _p(u), _p(init), _p(w), _p(stats), _p(ws), B, D, H, W, iters, tol, hist, _st()))
+    return w, stats
+
+
 WARP_SSD_MAX_C = 16
 
 # What ops.pack_features returns: `packed` [B,*vol,Cp] voxel-major (Cp = C rounded up to 4, zeros in the padding channels),

@@ -52,8 +52,8 @@ const char* dfmir_last_error(void);
  *     DFMIR_NO_1X1_WGRAD, DFMIR_CONV3D_NO_FLOW_WGRAD, DFMIR_CONV3D_NO_S2, DFMIR_RESIZE_NO_ROWS, DFMIR_NCC_NO_D_FUSE, DFMIR_SMOOTH_NO_MARCH,
  *     DFMIR_NO_BWD_PAIR (dgrad and wgrad of a 3x3 layer as two launches), DFMIR_BWD_PAIR=0|1 (the same switch with an explicit
  *     value; unset = the build's default), DFMIR_BWD_PAIR_ORDER=n (workgroup order inside dfmir_conv3x3_bwd_pair's grid:
- *     0 weight gradient first, 1 data gradient first, 2 interleaved in groups of 8), DFMIR_INVCONS_FIXED64 (dfmir_invcons_bwd: dv
- *     through the 64-bit fixed-point scatter on every shape), DFMIR_WARPSSD_PLANAR (dfmir_warp_ssd_fwd / _fwd_grad: gather the
+ *     0 weight gradient first, 1 data gradient first, 2 interleaved in groups of 8), DFMIR_INVCONS_FIXED64 (dfmir_invcons_bwd and
+ *     dfmir_compose_bwd: dv through the 64-bit fixed-point scatter on every shape), DFMIR_WARPSSD_PLANAR (dfmir_warp_ssd_fwd / _fwd_grad: gather the
  *     moving features from the channel-major tensor M instead of the voxel-major packed copy Mp).
  * ---------------------------------------------------------------------------------------- */
 int dfmir_set_option(const char* name, const char* value);
@@ -619,6 +619,44 @@ int dfmir_invcons_fwd(int nd, const float* u, const float* v, float* ws, float* 
 long long dfmir_invcons_bwd_ws_floats(int nd, int B, int D, int H, int W);
 int dfmir_invcons_bwd(int nd, const float* u, const float* v, const float* gout, const float* rmax, float* du, float* dv,
                       float* ws, int B, int D, int H, int W, void* stream);
+/* Composition of two displacement fields and fixed-point inversion of one (build-defined: the reference has neither).  Fields
+ * as above: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when nd == 2), channel i displaces axis i in voxels, order
+ * (z,) y, x; sampling (bi/tri)linear, corners outside the volume read as 0, the sampling of dfmir_invcons_* and of the warp
+ * kernels, with the same guard: no float is converted to int for a NaN or a far-away sample point and every address formed
+ * lies inside its tensor.
+ * dfmir_compose_fwd:   out(x) = u(x) + v(x + u(x)) = u + warp(v, u): warp(src, out) is warp(warp(src, v), u) in the
+ *   continuum, u is the warp applied last.  Replaces u + dfmir_warp_fwd(v, u) (a warped tensor written and read again).
+ * dfmir_compose_bwd, for an incoming gradient g of out; du and dv are written entirely, either may be NULL:
+ *   du_c(x) = g_c(x) + sum_c' g_c'(x) d_c v_c'(x + u(x))    d_c = corner differences, zero-padded corners taking part as zeros
+ *   dv      = the transpose of the interpolation applied to g.  Where W % 4 == 0 and u, g, dv, ws are 16-byte aligned g is
+ *             handed to the owner-gather adjoint of the warp as it is (dfmir_warp_bwd_own: no device-scope atomics,
+ *             bit-reproducible as that call is).  Elsewhere, and everywhere under DFMIR_INVCONS_FIXED64, it is summed with
+ *             global atomics as 64-bit fixed-point integers whose unit lies >= 29 bits below max |g|, which is taken on the
+ *             device: bit-identical from run to run as well (a max |g| that is not finite makes dv NaN), several times slower.
+ *   These are dfmir_invcons_bwd's formulas with k r replaced by g, and the same kernel body.  ws: dfmir_compose_bwd_ws_floats
+ *   floats, 8-byte aligned, need not be zeroed, may be NULL when dv is.  out and du are bit-identical from run to run.
+ * dfmir_flow_invert:   w_0 = init (NULL = zeros),  r_k(x) = w_k(x) + u(x + w_k(x)),  w_{k+1} = w_k - r_k (= -u(x + w_k) up to
+ *   rounding); a voxel stops updating once max_c |r_k,c| <= tol and keeps its w and r from then on (tol = 0: every voxel does
+ *   `iters` updates; a voxel with a NaN never stops).  w = w_iters.  stats: with history != 0 [iters + 1][B][2], row k =
+ *   (rms_k, max_k) of r_k, rms_k = sqrt(sum over the voxels and channels of sample b of r_k^2 / S), max_k = max |r_k,c| (NaN
+ *   if any is); with history == 0 [B][2], those of r_iters alone.  ONE launch runs every iteration with w in registers (each
+ *   voxel's iteration reads only its own w and a gather of u) and a second one adds the per-workgroup double sums in a fixed
+ *   order: w and stats are bit-identical from run to run.  Replaces `iters` rounds of dfmir_warp_fwd + dfmir_scale, which
+ *   write and re-read a field twice per iteration.  The iteration converges where u is a contraction (Lipschitz constant
+ *   < 1); at the volume border the zero padding makes u drop to 0 within one cell, so a field that is not small there does
+ *   not converge there -- the residual says so.  ws: dfmir_flow_invert_ws_floats(.., iters, history) floats, 8-byte aligned,
+ *   need not be zeroed.
+ * Refused ("invalid argument", nothing is launched): nd outside {2, 3}, B < 1, an extent < 2, B * nd * S >= 2^31, a NULL
+ * pointer other than the optional ones, iters outside [0, 64], a tol that is negative or not finite; the _ws_floats calls
+ * return -1 for these.  16-byte accesses of u, out / u, g, du / init, w where W % 4 == 0 and those are 16-byte aligned.
+ * Nothing syncs, allocates or keeps state: every call captures into a hipGraph. */
+int dfmir_compose_fwd(int nd, const float* u, const float* v, float* out, int B, int D, int H, int W, void* stream);
+long long dfmir_compose_bwd_ws_floats(int nd, int B, int D, int H, int W);
+int dfmir_compose_bwd(int nd, const float* u, const float* v, const float* g, float* du, float* dv, float* ws, int B, int D,
+                      int H, int W, void* stream);
+long long dfmir_flow_invert_ws_floats(int nd, int B, int D, int H, int W, int iters, int history);
+int dfmir_flow_invert(int nd, const float* u, const float* init, float* w, float* stats, float* ws, int B, int D, int H,
+                      int W, int iters, float tol, int history, void* stream);
 /* Warped-feature SSD, the data term of instance optimisation (build-defined: the reference has no such term).  M, F:
  * [B][C][(D)][H][W] fp32 features of the moving / fixed image, 1 <= C <= 16; phi: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is
  * not read when nd == 2), channel d displaces axis d in voxels, in the order (z,) y, x, exactly as the warp kernels read a
