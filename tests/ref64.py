@@ -1,12 +1,15 @@
 """Plain float64 references (torch, CPU) of the operations around the convolutions: masked L1, flow smoothness
-(Grad_Loss), windowed NCC, InstanceNorm (+ReLU, +residual), Adam.  TEST infrastructure, written from the formulas in the
-docstrings of oracle/dfmir_oracle.py; tests/test_ref64.py checks each one against the fp32 oracle on small inputs, the GPU
-tests (tests/test_gpu_pointwise_fp64.py) compare the HIP kernels with them.
+(Grad_Loss), windowed NCC, InstanceNorm (+ReLU, +residual), Adam, the displacement-field warp, the VecInt step and the linear
+resize.  TEST infrastructure, written from the formulas in the docstrings of oracle/dfmir_oracle.py; tests/test_ref64.py checks
+each one against the fp32 oracle on small inputs, the GPU tests (tests/test_gpu_pointwise_fp64.py, tests/test_gpu_warp_fp64.py)
+compare the HIP kernels with them.
 
 Every function takes tensors of any float dtype and computes in `dtype` (float64 by default); gradients come from
 autograd on the returned value.  `dtype=torch.float32` turns a function into a plain fp32 restatement (another valid
 summation order), which the GPU tests use as the fp32 yardstick where the fp32 oracle itself is too slow.
 """
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -156,3 +159,56 @@ class Adam(object):
         bc1, bc2 = 1 - self.b1 ** self.t, 1 - self.b2 ** self.t
         den = self.v.sqrt().div_(bc2 ** 0.5).add_(self.eps)
         self.p.addcdiv_(self.m, den, value=-self.lr / bc1)
+
+
+# ------------------------------------------------------------------------------------- warp, VecInt, resize
+def warp(src, flow, mode='bilinear', add_identity=False, dtype=torch.float64):
+    """out_c(x) = src_c sampled at x + flow(x), flow in voxels, [B, C, *vol] and [B, nd, *vol], any C.  'bilinear': the 2^nd
+    corners of the cell around the sample point (plain floor), weights the products of the per-axis distances, a corner
+    outside the volume reads 0 -- explicit floor / gather indexing on tests.test_invcons._corners, of which ic_residual is the
+    case C = nd, add_identity on flow itself.  'nearest': the voxel nearest to the sample point, halves to the even one
+    (torch.round, the kernels' nearbyintf), 0 outside; no gradient to flow.  add_identity adds src(x)."""
+    from tests.test_invcons import _corners, _grid
+    src, flow = _t(src, dtype), _t(flow, dtype)
+    B, Cn = src.shape[:2]
+    vol = tuple(src.shape[2:])
+    S = math.prod(vol)
+    sf = src.reshape(B, Cn, S)
+    pick = lambda flat: torch.gather(sf, 2, flat.reshape(B, 1, S).expand(B, Cn, S)).reshape(src.shape)
+    if mode == 'nearest':
+        idx = torch.round((_grid(vol, dtype)[None] + flow).detach()).long()
+        flat = torch.zeros((B,) + vol, dtype=torch.long)
+        valid = torch.ones((B,) + vol, dtype=torch.bool)
+        for a in range(len(vol)):
+            valid &= (idx[:, a] >= 0) & (idx[:, a] < vol[a])
+            flat += idx[:, a].clamp(0, vol[a] - 1) * math.prod(vol[a + 1:])
+        out = pick(flat) * valid.to(dtype)[:, None]
+    else:
+        out = 0.0
+        for flat, valid, w, _ in _corners(flow):
+            out = out + (w.prod(1) * valid.to(dtype))[:, None] * pick(flat)
+    return out + src if add_identity else out
+
+
+def vecint_step(v, dtype=torch.float64):
+    """v + warp(v, v): one scaling-and-squaring step."""
+    v = _t(v, dtype)
+    return warp(v, v, add_identity=True, dtype=dtype)
+
+
+def resize_linear(x, out_sp, mult=1.0, dtype=torch.float64):
+    """mult * the (bi | tri)linear resize of [B, C, *in_sp] to out_sp with aligned corners: along every axis output o reads
+    the source coordinate c = o (in - 1) / (out - 1) (0 when out == 1), i.e. (1 - l) x[i0] + l x[i1] with i0 = floor(c),
+    i1 = min(i0 + 1, in - 1), l = c - i0.  Explicit indices and weights, one axis after the other."""
+    y = _t(x, dtype)
+    for a, n_out in enumerate(out_sp):
+        ax = 2 + a
+        n_in = y.shape[ax]
+        o = torch.arange(n_out, dtype=dtype)
+        c = o * (n_in - 1) / (n_out - 1) if n_out > 1 else torch.zeros(n_out, dtype=dtype)
+        i0 = torch.floor(c).clamp(0, n_in - 1)
+        l = (c - i0).reshape([-1 if d == ax else 1 for d in range(y.dim())])
+        i0 = i0.long()
+        i1 = (i0 + 1).clamp(max=n_in - 1)
+        y = (1.0 - l) * y.index_select(ax, i0) + l * y.index_select(ax, i1)
+    return y * mult

@@ -3,8 +3,15 @@ of the reference) and plain torch, values and autograd gradients, on small seede
 the GPU tests trust are themselves verified.  Agreement is to fp32 round-off of the ORACLE: 2e-5 on scalars, 1e-4 of the
 maximum on gradients, 1e-3 on the NCC gradient (the oracle's conv over win^nd taps in fp32).
 
-The last tests evaluate, with the oracle alone, the ill-conditioned inputs of tests/test_gpu_pointwise_fp64.py: the bound
+The warp, VecInt and resize restatements are compared with the oracle's functions evaluated in float64 (1e-11: the oracle's
+round trip through normalised coordinates), with the documented adjoint formulas and with F.interpolate; the two host-only
+size functions that choose the warp and resize backward forms are checked at their boundaries through ctypes.
+
+The tests after those evaluate, with the oracle alone, the ill-conditioned inputs of tests/test_gpu_pointwise_fp64.py: the bound
 `max(bar, 2 x oracle error)` they lead to must stay within 10 x the bar, else the input tests nothing."""
+import ctypes
+import math
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -187,3 +194,154 @@ def test_ncc_volume_flag_matches_the_header():
     from dfmir_amd import ops
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dfmir_hip.h")).read()
     assert int(re.search(r"#define\s+DFMIR_NCC_VOLUME\s+(\d+)", text).group(1)) == ops.NCC_VOLUME
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# warp, VecInt, resize
+WARP_CPU_SHAPES = [(2, 3, 5, 6, 7), (1, 1, 3, 4, 9), (2, 2, 9, 11), (1, 4, 6, 7)]
+
+
+def _warp_module():
+    from tests import warp_cases as W
+    return W
+
+
+def warp_adjoint(src, flow, g):
+    """(d(src), d(flow)) of sum(g * warp(src, flow)) by the documented formulas: d(src) = the interpolation's transpose applied to
+    g; d(flow)_a = sum over channels and corners of g * (+-1 along a) * the other axes' weights * the corner's value, corners
+    outside the volume as zeros."""
+    from tests.test_invcons import _corners
+    B, Cn = src.shape[:2]
+    nd = flow.shape[1]
+    S = math.prod(src.shape[2:])
+    sf = src.reshape(B, Cn, S)
+    dsrc = torch.zeros(B, Cn, S, dtype=src.dtype)
+    dflow = torch.zeros_like(flow)
+    for flat, valid, w, bits in _corners(flow):
+        idx = flat.reshape(B, 1, S).expand(B, Cn, S)
+        ok = valid.to(src.dtype)
+        val = torch.gather(sf, 2, idx).reshape(src.shape) * ok[:, None]
+        for a in range(nd):
+            others = torch.ones_like(w[:, 0])
+            for b in range(nd):
+                if b != a:
+                    others = others * w[:, b]
+            dflow[:, a] += (1.0 if bits[a] else -1.0) * others * (g * val).sum(1)
+        dsrc.scatter_add_(2, idx, (g * (w.prod(1) * ok)[:, None]).reshape(B, Cn, S))
+    return dsrc.reshape(src.shape), dflow
+
+
+@pytest.mark.parametrize("shape", WARP_CPU_SHAPES, ids=lambda s: "x".join(str(v) for v in s))
+@pytest.mark.parametrize("family", ["lattice", "smooth"])
+def test_warp_against_the_oracle_in_float64_and_the_adjoint_formulas(shape, family):
+    """d(flow) against grid_sample's on the lattice family only: elsewhere a sample point may lie so close to a cell boundary
+    that the normalised-coordinate round trip takes the other cell."""
+    W = _warp_module()
+    src, flow, g = (t.double() for t in (W.noise(41, shape, 2.0), W.flow_field(shape, family, seed=43), W.noise(47, shape, 1.0)))
+    out, dsrc, dflow = W.warp_eval(src, flow, g)
+    a, b = src.clone().requires_grad_(), flow.clone().requires_grad_()
+    ref = O.spatial_transform(a, b)
+    (ref * g).sum().backward()
+    assert ref.dtype == torch.float64 and float(out.abs().max()) > 0.0
+    assert rel(out, ref) <= 1e-11 and rel(dsrc, a.grad) <= 1e-11
+    if family == "lattice":
+        assert rel(dflow, b.grad) <= 1e-11
+    fs, ff = warp_adjoint(src, flow, g)
+    assert rel(fs, dsrc) <= 1e-13 and rel(ff, dflow) <= 1e-13
+    assert rel(R.warp(src, flow, add_identity=True), ref + src) <= 1e-11
+    if shape[1] == len(shape) - 2:                                  # C = nd: ic_residual is this warp plus the flow
+        from tests.test_invcons import ic_residual
+        assert rel(ic_residual(flow, src), flow + R.warp(src, flow)) <= 1e-14
+    near = W.flow_field(shape, "nearest", seed=53).double()
+    assert torch.equal(R.warp(src, near, mode="nearest"), O.spatial_transform(src, near, mode="nearest"))
+    assert rel(R.warp(src.float(), flow.float(), dtype=torch.float32), out) <= 1e-4      # dtype=float32: the fp32 yardstick
+
+
+@pytest.mark.parametrize("shape", [(1, 3, 5, 6, 7), (2, 2, 9, 11)], ids=["3d", "2d"])
+def test_vecint_against_the_oracle_in_float64(shape):
+    W = _warp_module()
+    g = W.noise(59, shape, 1.0).double()
+    for family in ("chain", "lattice"):          # chain: seven steps behind 1 / 128; lattice: one step (d(flow) on the lattice only)
+        v = W.flow_field(shape, family, seed=61).double()
+        steps = 7 if family == "chain" else 1
+        out, dv = W.vecint_eval(v, g, steps=steps, pre=1.0 / 2 ** steps)
+        a = v.clone().requires_grad_()
+        ref = O.vec_int(a, steps)
+        (ref * g).sum().backward()
+        assert rel(out, ref) <= 1e-11 and rel(dv, a.grad) <= 1e-11, family
+    v = W.flow_field(shape, "lattice", seed=61).double()
+    fs, ff = warp_adjoint(v, v, g)
+    assert rel(g + fs + ff, W.vecint_eval(v, g)[1]) <= 1e-13
+    assert torch.equal(R.vecint_step(v), v + R.warp(v, v))
+
+
+@pytest.mark.parametrize("isp,osp", [((6, 10, 12), (12, 20, 24)), ((12, 20, 24), (6, 10, 12)), ((7, 9, 13), (3, 4, 6)), ((9, 37), (23, 50)),
+                                     ((3, 5), (24, 40)), ((4, 30), (4, 1)), ((5, 1, 8), (5, 1, 16)), ((2, 2, 1), (4, 4, 8))],
+                         ids=lambda sp: "x".join(str(v) for v in sp))
+def test_resize_against_interpolate_and_the_oracle_in_float64(isp, osp):
+    x, cot = C.randn(67, 2, 3, *isp).double(), C.randn(68, 2, 3, *osp).double()
+    mode = "trilinear" if len(isp) == 3 else "bilinear"
+    for mult in (0.5, 2.0, -1.5):
+        got = val_and_grads(lambda t: (R.resize_linear(t, osp, mult) * cot).sum(), x)
+        ref = val_and_grads(lambda t: (mult * F.interpolate(t, size=osp, mode=mode, align_corners=True) * cot).sum(), x)
+        assert rel(R.resize_linear(x, osp, mult), mult * F.interpolate(x, size=osp, mode=mode, align_corners=True)) <= 1e-13
+        assert rel(got[1], ref[1]) <= 1e-13
+    if all(o == 2 * i for i, o in zip(isp, osp)):
+        assert rel(R.resize_linear(x, osp, 2.0), O.resize_transform(x, 0.5)) <= 1e-13
+    if all(i == 2 * o for i, o in zip(isp, osp)):
+        assert rel(R.resize_linear(x, osp, 0.5), O.resize_transform(x, 2.0)) <= 1e-13
+    assert R.resize_linear(x.float(), osp).dtype == torch.float64 and R.resize_linear(x, osp, dtype=torch.float32).dtype == torch.float32
+
+
+def _own_eligible(nd, B, C_, D, H, W):
+    """What dfmir_warp_bwd_own_ws_floats documents: the owner-gather backward takes a shape when W % 4 == 0, a sample's flow
+    stays below 2^31 bytes, the voxel count below 2^31 and the tile count (tiles 8 x 8 x 32 / 64 x 32) below 2^30."""
+    D = D if nd == 3 else 1
+    ty, tz = (8, 8) if nd == 3 else (64, 1)
+    tiles = -(-W // 32) * -(-H // ty) * -(-D // tz) * B
+    return W % 4 == 0 and D * H * W * nd * 4 < 2 ** 31 and B * D * H * W < 2 ** 31 and tiles < 2 ** 30
+
+
+def test_warp_and_resize_size_functions_at_their_boundaries():
+    """No tensor is allocated: both functions are host arithmetic."""
+    import dfmir_amd
+    lib = dfmir_amd.lib()
+    own = lib.dfmir_warp_bwd_own_ws_floats
+    cases = [(3, 1, 1, 8, 8, 32), (3, 1, 1, 8, 8, 30), (3, 1, 1, 8, 8, 31), (3, 1, 1, 8, 8, 33), (3, 1, 1, 8, 8, 4), (2, 1, 2, 1, 64, 32),
+             (2, 3, 2, 999, 130, 68), (2, 1, 2, 1, 9, 11), (3, 2, 5, 1, 1, 4),
+             # a sample's flow at 2^31 bytes: 3-D D H W < 2^31 / 12, 2-D H W < 2^28
+             (3, 1, 1, 1, 1, 178956968), (3, 1, 1, 1, 1, 178956972), (3, 1, 1, 2, 2, 44739240), (3, 1, 1, 2, 2, 44739244),
+             (2, 1, 2, 1, 1, 268435452), (2, 1, 2, 1, 1, 268435456), (2, 1, 2, 1, 4096, 65532), (2, 1, 2, 1, 4096, 65536),
+             # the voxel count at 2^31
+             (2, 15, 2, 1, 1, 1 << 27), (2, 16, 2, 1, 1, 1 << 27), (3, 31, 3, 4, 4096, 4096), (3, 32, 3, 4, 4096, 4096),
+             (2, (1 << 29) - 1, 2, 1, 1, 4), (2, 1 << 29, 2, 1, 1, 4), (3, (1 << 29) - 1, 3, 1, 1, 4), (3, 1 << 29, 3, 1, 1, 4)]
+    seen = set()
+    for c in cases:
+        want = _own_eligible(*c)
+        seen.add(want)
+        assert (own(*c) > 0) == want, (c, own(*c))
+        assert own(*c) >= 0
+    assert seen == {True, False}
+    # (a tile holds at least 4 voxels of a W % 4 == 0 volume, so below 2^31 voxels the tile count stays below 2^29: the fourth
+    # condition never decides alone)
+    T_, Cn = 2 * 2 * 2 * 3, 5                                        # (3, 5, 9, 9, 36): 8 ragged tiles per sample
+    assert own(3, 3, Cn, 9, 9, 36) == ((8 * T_ + 2048 * T_ + 3) & ~3) + T_ * Cn * 12 * 12 * 40
+    assert own(2, 1, 2, 77, 65, 36) == ((8 * 4 + 2048 * 4 + 3) & ~3) + 4 * 2 * 68 * 40          # 2-D: D is not read
+    for bad in ((1, 1, 1, 8, 8, 32), (4, 1, 1, 8, 8, 32), (3, 0, 1, 8, 8, 32), (3, 1, 0, 8, 8, 32), (3, 1, 1, 0, 8, 32),
+                (3, 1, 1, 8, 0, 32), (3, 1, 1, 8, 8, 0), (2, 1, 1, 8, 8, -4)):
+        assert own(*bad) == -1, bad
+    buf = (ctypes.c_float * 64)()                      # host memory: a refused call never dereferences it
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    for c in ((3, 1, 1, 8, 8, 30), (3, 1, 1, 1, 1, 178956972), (2, 16, 2, 1, 1, 1 << 27)):
+        nd, dims = c[0], c[1:]
+        assert lib.dfmir_warp_bwd_own(nd, p, p, p, p, p, *dims, 0, 0, p, None) != 0, c
+        assert b"invalid argument" in lib.dfmir_last_error()
+    ws = lib.dfmir_resize_bwd_ws_floats
+    assert ws(6, 5, 6, 7, 10, 12, 14) == 6 * 10 * 12 * 7 + 6 * 10 * 6 * 7             # planes Do Ho Wi + planes Do Hi Wi
+    assert ws(1, 1, 1, 1, 1, 1, 1) == 2 and ws(2, 1, 4, 300, 1, 4, 1) == 2 * 4 * 300 * 2
+    assert ws(3, 1024, 1024, 1024, 2048, 2048, 2048) == 3 * 2048 * 2048 * 1024 + 3 * 2048 * 1024 * 1024    # past 2^32: 64-bit
+    for hole in range(7):                               # positive for every valid size, 0 for any other: ResizeFn takes
+        for v in (0, -1):                               # the separable adjoint whenever the count is positive
+            args = [2, 3, 4, 5, 6, 7, 8]
+            args[hole] = v
+            assert ws(*args) == 0, args
