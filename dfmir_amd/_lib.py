@@ -152,6 +152,10 @@ _SIGS = {
     "dfmir_compose_bwd": [c_int, P, P, P, P, P, P] + [c_int] * 4 + [P],
     "dfmir_flow_invert_ws_floats": [c_int] * 7,
     "dfmir_flow_invert": [c_int, P, P, P, P, P] + [c_int] * 5 + [c_float, c_int, P],
+    "dfmir_dsearch_pool": [c_int, P, P, P] + [c_int] * 6 + [P],
+    "dfmir_dsearch_cost": [c_int, P, P, P] + [c_int] * 6 + [P],
+    "dfmir_dsearch_argmin": [c_int, P, P, c_float, P, P] + [c_int] * 5 + [P],
+    "dfmir_dsearch_smooth": [c_int, P, P] + [c_int] * 4 + [P],
     "dfmir_warp_ssd_ws_floats": [c_int] * 6,
     "dfmir_warp_ssd_pack": [c_int, P, P] + [c_int] * 5 + [P],
     "dfmir_warp_ssd_fwd": [c_int] + [P] * 9 + [c_int] * 5 + [P],

@@ -8,6 +8,33 @@ from .losses import BendingEnergy_Loss, Grad_Loss
 from .voxelmorph import SpatialTransformer
 
 
+def _check_features(what, features, moving, nd, B, vol):
+    """The `features` argument of refine_flow / convex_init: 'mind', 'intensity' or a pair of [B,C,*vol] tensors."""
+    if isinstance(features, str):
+        if features not in ('mind', 'intensity'):
+            raise ValueError("%s: features must be 'mind', 'intensity' or a pair of tensors, got %r" % (what, features))
+        if moving.shape[1] != 1:
+            raise ValueError("%s: features=%r needs single-channel images, got %d channels" % (what, features, moving.shape[1]))
+    else:
+        try:
+            Mm, Mf = features
+        except (TypeError, ValueError):
+            raise ValueError("%s: features must be 'mind', 'intensity' or a pair of [B,C,*vol] tensors" % what)
+        for t in (Mm, Mf):
+            if not torch.is_tensor(t) or t.dim() != nd + 2 or (int(t.shape[0]),) + tuple(t.shape[2:]) != (B,) + vol:
+                raise ValueError("%s: the feature tensors must be [B,C,*vol] over the images' volume %s" % (what, vol))
+
+
+def _resolve_features(features, moving, fixed, mind_radius, mind_dilation):
+    """(moving features, fixed features) of a checked `features` argument, detached."""
+    if isinstance(features, str) and features == 'mind':
+        return (ops.mind_descriptor(moving, mind_radius, mind_dilation), ops.mind_descriptor(fixed, mind_radius, mind_dilation))
+    if isinstance(features, str):
+        return moving.detach(), fixed.detach()
+    Mm, Mf = features
+    return Mm.detach(), Mf.detach()
+
+
 def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
                 regularizer='diffusion', lam, spacing=None, grid_downsize=2, iters=50, lr, betas=(0.9, 0.999),
                 update='add'):
@@ -54,28 +81,10 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         raise ValueError("%s: regularizer must be 'diffusion' or 'bending', got %r" % (what, regularizer))
     if flow is not None and (not torch.is_tensor(flow) or tuple(flow.shape) != (B, nd) + vol):
         raise ValueError("%s: flow must be [B,%d,*vol] = %s" % (what, nd, (B, nd) + vol))
-    if isinstance(features, str):
-        if features not in ('mind', 'intensity'):
-            raise ValueError("%s: features must be 'mind', 'intensity' or a pair of tensors, got %r" % (what, features))
-        if moving.shape[1] != 1:
-            raise ValueError("%s: features=%r needs single-channel images, got %d channels" % (what, features, moving.shape[1]))
-    else:
-        try:
-            Mm, Mf = features
-        except (TypeError, ValueError):
-            raise ValueError("%s: features must be 'mind', 'intensity' or a pair of [B,C,*vol] tensors" % what)
-        for t in (Mm, Mf):
-            if not torch.is_tensor(t) or t.dim() != nd + 2 or (int(t.shape[0]),) + tuple(t.shape[2:]) != (B,) + vol:
-                raise ValueError("%s: the feature tensors must be [B,C,*vol] over the images' volume %s" % (what, vol))
+    _check_features(what, features, moving, nd, B, vol)
     reg = Grad_Loss(dim=nd, penalty='l2') if regularizer == 'diffusion' else BendingEnergy_Loss(dim=nd, spacing=spacing)
     with torch.no_grad():
-        if features == 'mind':
-            Mm = ops.mind_descriptor(moving, mind_radius, mind_dilation)
-            Mf = ops.mind_descriptor(fixed, mind_radius, mind_dilation)
-        elif features == 'intensity':
-            Mm, Mf = moving.detach(), fixed.detach()
-        else:
-            Mm, Mf = Mm.detach(), Mf.detach()
+        Mm, Mf = _resolve_features(features, moving, fixed, mind_radius, mind_dilation)
         handle = ops.pack_features(Mm)
         flow0 = None if flow is None else flow.detach()
         delta = ops.zeros((B, nd) + coarse, handle.packed.device)
@@ -107,6 +116,75 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         history[iters, 1] = reg(out)
         warped = ops.warp(moving, out)
     return dict(flow=out, warped=warped, history=history)
+
+
+CONVEX_COEFFS = (0.003, 0.01, 0.03, 0.1, 0.3, 1.0)
+
+
+@torch.no_grad()
+def convex_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=2, grid_sp=4, disp_hw=3,
+                coeffs=CONVEX_COEFFS):
+    """Discrete displacement search with coupled-convex regularisation (build-defined), the first stage of the two-stage
+    scheme whose second stage is refine_flow: it has no gradient to get stuck on, so it captures displacements of up to
+    grid_sp * disp_hw voxels that a local descent started from zero cannot.  Returns dict(flow, coarse, idx).
+
+    moving, fixed: [B,1,*vol] fp32 images, 2-D or 3-D; features as in refine_flow: 'mind' = ops.mind_descriptor(.,
+    mind_radius, mind_dilation) of both images, 'intensity' = the images themselves, or a pair (moving features, fixed
+    features) of [B,C,*vol] tensors, 1 <= C <= 16.  grid_sp: an integer >= 1, the stride of the search grid; disp_hw: the
+    half width of the search window in coarse voxels, an integer in 1..ops.DSEARCH_MAX_RADIUS[nd] (8 in 2-D, 4 in 3-D);
+    coeffs: the coupling coefficients, finite floats >= 0, in the order they are applied.
+
+        mov_p, fix_p = ops.pool_features(., grid_sp)                        both sides, [B,C,*(vol // grid_sp)]
+        cost   = ops.ssd_cost_volume(fix_p, mov_p, disp_hw)                 [B,(2 disp_hw + 1)^nd,*(vol // grid_sp)]
+        soft_0 = ops.box_smooth_flow(ops.cost_argmin(cost, disp_hw)[1])
+        soft   <- ops.box_smooth_flow(ops.cost_argmin(cost, disp_hw, soft, coeff)[1])        for each coeff in coeffs
+        coarse = the last soft, in COARSE voxels;  idx = the index field of the last argmin, int32 [B,*(vol // grid_sp)]
+        flow   = ops.resize_linear(coarse, vol, mult=grid_sp)               fine voxels, ops.warp's convention
+
+    so `flow` is ready for refine_flow(moving, fixed, flow, ..., update='compose').  Nothing here syncs with the host, and
+    every output is bit-identical from run to run.
+
+    Where the field lands: the stride-g pooling puts coarse sample i at fine coordinate g i + (g - 1) / 2, while
+    ops.resize_linear aligns corners, so the field lands up to (g - 1) / 2 voxels from where it was estimated -- the same
+    approximation refine_flow makes for its coarse `delta`.  The box mean divides by the in-volume count
+    (ops.box_smooth_flow), where the published code divides by 3^nd.
+
+    The default `coeffs` are the numbers of the published coupled-convex schedule.  The cost here is a channel MEAN and the
+    displacements are in coarse voxels, so their scale is not the published one, and nobody has measured registration
+    quality with them.
+
+    ValueError before any launch on images that are not two [B,1,*vol] tensors of one shape (any channel count with a
+    feature pair), an unknown `features`, a grid_sp that is not an integer >= 1 or leaves a coarse extent < 2, a disp_hw
+    outside its range and a coefficient that is negative or not finite."""
+    what = "convex_init"
+    if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
+            or tuple(moving.shape) != tuple(fixed.shape):
+        raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
+    nd = moving.dim() - 2
+    B, vol = int(moving.shape[0]), tuple(int(n) for n in moving.shape[2:])
+    if isinstance(grid_sp, bool) or not isinstance(grid_sp, int) or grid_sp < 1:
+        raise ValueError("%s: grid_sp must be an integer >= 1, got %r" % (what, grid_sp))
+    if min(n // grid_sp for n in vol) < 2:
+        raise ValueError("%s: every dimension of the search grid %s // %d must be >= 2" % (what, vol, grid_sp))
+    if isinstance(disp_hw, bool) or not isinstance(disp_hw, int) or not 1 <= disp_hw <= ops.DSEARCH_MAX_RADIUS[nd]:
+        raise ValueError("%s: disp_hw must be an integer in [1, %d] in %d-D, got %r"
+                         % (what, ops.DSEARCH_MAX_RADIUS[nd], nd, disp_hw))
+    try:
+        coeffs = tuple(float(c) for c in coeffs)
+    except (TypeError, ValueError):
+        raise ValueError("%s: coeffs must be a sequence of finite numbers >= 0, got %r" % (what, coeffs))
+    if not all(0.0 <= c < float('inf') for c in coeffs):
+        raise ValueError("%s: coeffs must be a sequence of finite numbers >= 0, got %r" % (what, coeffs))
+    _check_features(what, features, moving, nd, B, vol)
+    Mm, Mf = _resolve_features(features, moving, fixed, mind_radius, mind_dilation)
+    mov_p, fix_p = ops.pool_features(Mm, grid_sp), ops.pool_features(Mf, grid_sp)
+    cost = ops.ssd_cost_volume(fix_p, mov_p, disp_hw)
+    idx, disp = ops.cost_argmin(cost, disp_hw)
+    soft = ops.box_smooth_flow(disp)
+    for c in coeffs:
+        idx, disp = ops.cost_argmin(cost, disp_hw, soft, c)
+        soft = ops.box_smooth_flow(disp)
+    return dict(flow=ops.resize_linear(soft, vol, mult=float(grid_sp)), coarse=soft, idx=idx)
 
 
 def _refine_kwargs(refine, what):

@@ -2816,6 +2816,160 @@ def warp_ssd_per_sample(mov, fix, flow, mask=None):
     return _warp_ssd_launch(geom, h, fix, flow_c, mask, None)[:geom[1]].clone()
 
 
+DSEARCH_MAX_RADIUS = {2: 8, 3: 4}              # dfmir_amd/csrc/dsearch.hip: what the cost kernel's staged window is sized for
+
+
+def _dsearch_radius(radius, nd, what):
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= DSEARCH_MAX_RADIUS[nd]:
+        raise ValueError("%s: radius must be an integer in [1, %d] for %d-D features, got %r"
+                         % (what, DSEARCH_MAX_RADIUS[nd], nd, radius))
+    return radius
+
+
+def _dsearch_pool(M, geom, g, planar, packed):
+    """dfmir_dsearch_pool of a checked [B,C,*vol] tensor: (planar [B,C,*(vol // g)] or None, packed [B,*(vol // g),Cp] or
+    None)."""
+    nd, B, C, D, H, W = geom
+    _need(M)
+    M = _c(M)
+    sp = tuple(int(n) // g for n in M.shape[2:])
+    out = torch.empty((B, C) + sp, device=M.device, dtype=torch.float32) if planar else None
+    pk = torch.empty((B,) + sp + ((C + 3) // 4 * 4,), device=M.device, dtype=torch.float32) if packed else None
+    check(lib().dfmir_dsearch_pool(nd, _p(M), _p(out), _p(pk), B, C, D, H, W, g, _st()))
+    return out, pk
+
+
+@torch.no_grad()
+def pool_features(M, g):
+    """Average pooling of features onto a search grid (build-defined): M [B,C,*vol] (fp32, 1 <= C <= 16, 2-D or 3-D) ->
+    [B,C,*(vol // g)], out[b,c,X] = the mean of M[b,c,g X + {0 .. g-1}^nd] -- window g^nd, stride g, the remainder at the far
+    faces dropped (F.avg_pool with kernel = stride = g).  Coarse sample i therefore sits at fine coordinate g i + (g - 1) / 2.
+    The window is added in double in a fixed order and rounded once; g = 1 copies.  No gradient.  ValueError before any launch
+    on a g that is not an integer >= 1, a pooled extent < 2, and what ops.pack_features refuses (rank, C outside 1..16, dtype,
+    2^31 or more elements, a tensor that requires grad); a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "pool_features"
+    geom = _features_geom(M, what, "M")
+    if isinstance(g, bool) or not isinstance(g, int) or g < 1:
+        raise ValueError("%s: g must be an integer >= 1, got %r" % (what, g))
+    if min(int(n) // g for n in M.shape[2:]) < 2:
+        raise ValueError("%s: every pooled extent must be >= 2, got %s // %d" % (what, tuple(M.shape[2:]), g))
+    return _dsearch_pool(M, geom, g, True, False)[0]
+
+
+@torch.no_grad()
+def ssd_cost_volume(fix, mov, radius):
+    """The SSD cost volume of a discrete displacement search (build-defined): fix, mov [B,C,*vol] features that already live
+    on the search grid (fp32, 1 <= C <= 16, 2-D or 3-D, one shape) -> cost [B,K,*vol], K = (2 radius + 1)^nd,
+
+        cost[b,k,x] = (1/C) sum_c (fix[b,c,x] - mov[b,c,x + d_k])^2         mov reads 0 outside the volume (ops.warp's padding)
+
+    where k enumerates the displacements d_k in {-radius .. radius}^nd in row-major order (dz,) dy, dx with -radius first; d_k
+    is in voxels of this grid and in the flow's channel order, so the minimiser is a flow in ops.warp's convention.  The
+    channels are added in one order for every k: displacements whose sample lies outside the volume tie bit for bit.  Both
+    sides are packed voxel-major once, then one launch writes every cost once (dfmir_amd/csrc/dsearch.hip); bit-identical
+    from run to run.  No gradient: an input that requires grad raises.  ValueError before any launch on shapes that
+    disagree, a radius that is not an integer in 1..DSEARCH_MAX_RADIUS[nd] (8 in 2-D, 4 in 3-D), B K S >= 2^31, B > 65535 and what
+    ops.pack_features refuses; a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "ssd_cost_volume"
+    geom = _features_geom(fix, what, "fix")
+    if not torch.is_tensor(mov) or tuple(mov.shape) != tuple(fix.shape):
+        raise ValueError("%s: fix %s / mov %s differ in shape"
+                         % (what, tuple(fix.shape), tuple(mov.shape) if torch.is_tensor(mov) else mov))
+    _features_geom(mov, what, "mov")
+    nd, B, C, D, H, W = geom
+    r = _dsearch_radius(radius, nd, what)
+    K = (2 * r + 1) ** nd
+    if B * K * D * H * W >= 2 ** 31:
+        raise ValueError("%s: the cost volume [%d,%d,*%s] has 2^31 or more elements" % (what, B, K, tuple(fix.shape[2:])))
+    if B > 65535:
+        raise ValueError("%s: B must be <= 65535, got %s" % (what, tuple(fix.shape)))
+    if mov.device != fix.device:
+        raise DfmirHipError("%s: fix on %s, mov on %s" % (what, fix.device, mov.device))
+    fp = _dsearch_pool(fix, geom, 1, False, True)[1]
+    mp = _dsearch_pool(mov, geom, 1, False, True)[1]
+    cost = torch.empty((B, K) + tuple(fix.shape[2:]), device=fix.device, dtype=torch.float32)
+    check(lib().dfmir_dsearch_cost(nd, _p(fp), _p(mp), _p(cost), B, C, D, H, W, r, _st()))
+    return cost
+
+
+def _dsearch_field(t, what, name, chan=None):
+    """(nd, B, D, H, W) of a [B,chan,*vol] fp32 tensor (chan None: nd channels) after the checks a CPU tensor can fail."""
+    if not torch.is_tensor(t) or t.dim() not in (4, 5):
+        raise ValueError("%s: %s must be a [B,.,H,W] or [B,.,D,H,W] tensor, got %s"
+                         % (what, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    nd = t.dim() - 2
+    if t.shape[1] != (nd if chan is None else chan(nd)):
+        raise ValueError("%s: %s %s must have %d channels" % (what, name, tuple(t.shape), nd if chan is None else chan(nd)))
+    if t.shape[0] < 1 or min(t.shape[2:]) < 2:
+        raise ValueError("%s: %s needs B >= 1 and every extent >= 2, got %s" % (what, name, tuple(t.shape)))
+    if t.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (%s is %s)" % (what, name, t.dtype))
+    if t.numel() >= 2 ** 31:
+        raise ValueError("%s: %s %s has 2^31 or more elements" % (what, name, tuple(t.shape)))
+    if t.requires_grad:
+        raise ValueError("%s: %s requires grad, but the op has no gradient (detach it)" % (what, name))
+    D, H, W = (int(n) for n in (t.shape[2:] if nd == 3 else (1,) + tuple(t.shape[2:])))
+    return nd, int(t.shape[0]), D, H, W
+
+
+@torch.no_grad()
+def cost_argmin(cost, radius, soft=None, coeff=0.0):
+    """The coupled argmin of a displacement cost volume (build-defined) -> (idx int32 [B,*vol], disp fp32 [B,nd,*vol]):
+
+        idx[b,x] = argmin_k ( cost[b,k,x] + coeff * sum_a (d_k[a] - soft[b,a,x])^2 ),        disp[b,a,x] = d_idx[a]
+
+    cost: [B,K,*vol] as ops.ssd_cost_volume lays it out, K = (2 radius + 1)^nd; soft: a field [B,nd,*vol] in voxels, None =
+    the plain argmin (coeff is then not read); coeff: a finite float >= 0.  The LOWEST k wins a tie (a strict < walking k
+    upwards); a NaN is never selected, and where every value is NaN the result is index 0.  One thread per voxel reads the
+    cost volume once.  ValueError before any launch on a radius outside 1..DSEARCH_MAX_RADIUS[nd], a channel count other than
+    K, a soft of another shape, a coeff that is negative or not finite, 2^31 or more elements, a dtype other than fp32 and a
+    tensor that requires grad; a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "cost_argmin"
+    if not torch.is_tensor(cost) or cost.dim() not in (4, 5):
+        raise ValueError("%s: cost must be a [B,K,H,W] or [B,K,D,H,W] tensor, got %s"
+                         % (what, tuple(cost.shape) if torch.is_tensor(cost) else type(cost).__name__))
+    r = _dsearch_radius(radius, cost.dim() - 2, what)
+    nd, B, D, H, W = _dsearch_field(cost, what, "cost", chan=lambda n: (2 * r + 1) ** n)
+    vol = tuple(cost.shape[2:])
+    if soft is not None:
+        if not torch.is_tensor(soft) or tuple(soft.shape) != (B, nd) + vol:
+            raise ValueError("%s: soft must be [B,nd,*vol] = %s, got %s"
+                             % (what, (B, nd) + vol, tuple(soft.shape) if torch.is_tensor(soft) else type(soft).__name__))
+        _dsearch_field(soft, what, "soft")
+    try:
+        coeff = float(coeff)
+    except (TypeError, ValueError):
+        raise ValueError("%s: coeff must be a finite number >= 0, got %r" % (what, coeff))
+    if not 0.0 <= coeff < float('inf'):
+        raise ValueError("%s: coeff must be a finite number >= 0, got %r" % (what, coeff))
+    _need(cost, soft)
+    if soft is not None and soft.device != cost.device:
+        raise DfmirHipError("%s: cost on %s, soft on %s" % (what, cost.device, soft.device))
+    cost = _c(cost)
+    soft = None if soft is None else _c(soft)
+    idx = torch.empty((B,) + vol, device=cost.device, dtype=torch.int32)
+    disp = torch.empty((B, nd) + vol, device=cost.device, dtype=torch.float32)
+    check(lib().dfmir_dsearch_argmin(nd, _p(cost), _p(soft), coeff, _p(idx), _p(disp), B, D, H, W, r, _st()))
+    return idx, disp
+
+
+@torch.no_grad()
+def box_smooth_flow(disp):
+    """The 3^nd box mean of a field [B,nd,*vol] (fp32, 2-D or 3-D; build-defined): out[b,a,x] = the mean of disp[b,a,.] over
+    those of the 3^nd neighbours of x (x included) that lie inside the volume -- the divisor is the in-volume count
+    (F.avg_pool(3, stride 1, padding 1, count_include_pad=False)).  A stated divergence: the published coupled-convex code
+    divides by 3^nd everywhere and so pulls the field towards zero at the faces; here a constant field comes back constant.
+    No gradient.  ValueError before any launch on a rank other than 4 or 5, a channel count other than nd, an extent < 2, a
+    dtype other than fp32, 2^31 or more elements and a tensor that requires grad; a CPU tensor raises the usual "no CPU
+    fallback" error."""
+    nd, B, D, H, W = _dsearch_field(disp, "box_smooth_flow", "disp")
+    _need(disp)
+    disp = _c(disp)
+    out = torch.empty_like(disp)
+    check(lib().dfmir_dsearch_smooth(nd, _p(disp), _p(out), B, D, H, W, _st()))
+    return out
+
+
 LANDMARK_PENALTIES = {'l2': 0, 'tre': 1}
 LANDMARK_MAX_K = 4096
 

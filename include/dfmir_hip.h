@@ -657,6 +657,39 @@ int dfmir_compose_bwd(int nd, const float* u, const float* v, const float* g, fl
 long long dfmir_flow_invert_ws_floats(int nd, int B, int D, int H, int W, int iters, int history);
 int dfmir_flow_invert(int nd, const float* u, const float* init, float* w, float* stats, float* ws, int B, int D, int H,
                       int W, int iters, float tol, int history, void* stream);
+/* Discrete displacement search: the first stage of a two-stage (discrete search, then Adam) instance registration
+ * (build-defined: the reference has no such stage).  Everything fp32, nd = 2 or 3 (D is not read when nd == 2), S = voxels per
+ * sample.  The displacement index k = 0 .. K - 1, K = (2r + 1)^nd, enumerates d_k in {-r .. r}^nd in row-major order (dz,) dy,
+ * dx with -r first; d_k is in voxels of the grid the features live on, in the flow's channel order (z,) y, x.
+ * dfmir_dsearch_pool:   in [B][C][(D)][H][W], 1 <= C <= 16, window g^nd, stride g, the remainder at the far faces dropped:
+ *   out[b][c][X] = the mean of in[b][c][g X + {0 .. g-1}^nd] over [B][C][(D/g)][H/g][W/g] (added in double in a fixed order,
+ *   rounded once); packed = the same values voxel-major, [B][(D/g)][H/g][W/g][Cp] with Cp = C rounded up to 4 and zeros in the
+ *   padding channels (dfmir_warp_ssd_pack's layout), what dfmir_dsearch_cost reads.  Either of out / packed may be NULL, not
+ *   both; g = 1 copies (packs).
+ * dfmir_dsearch_cost:   fixp, movp packed as above (16-byte aligned) on [(D)][H][W]; cost [B][K][(D)][H][W] contiguous,
+ *   cost[b][k][x] = (1 / C) sum_c (fix[b][c][x] - mov[b][c][x + d_k])^2,  mov reading 0 outside the volume (the zero padding of
+ *   the warp kernels).  The channels are added in the order c = 0 .. Cp - 1 with one fma each for every k, so displacements
+ *   whose sample lies outside the volume tie bit for bit at sum_c fix_c^2 / C.  Every cost is written once (no atomics, no
+ *   read-modify-write); r in [1, 4] (nd = 3) or [1, 8] (nd = 2).
+ * dfmir_dsearch_argmin: idx[b][x] = argmin_k ( cost[b][k][x] + coeff * sum_a (d_k[a] - soft[b][a][x])^2 ) as int32 [B][S],
+ *   the squares added in the order (z,) y, x; the LOWEST k wins a tie (a strict < walking k upwards from +inf); a NaN is never
+ *   selected, and where every value is NaN (or +inf) the result is index 0.  disp[b][a][x] = d_idx[a], fp32 [B][nd][S].
+ *   soft [B][nd][S] or NULL = the plain argmin (coeff is then not read); coeff finite and >= 0.
+ * dfmir_dsearch_smooth: out[b][a][x] = the mean of disp[b][a][.] over those of the 3^nd neighbours of x (x included) that lie
+ *   inside the volume, added in the order (dz,) dy, dx and divided by their number -- not by 3^nd: a constant field comes back
+ *   constant at the faces.  out must not alias disp.
+ * Refused ("invalid argument", nothing is launched): nd outside {2, 3}, B < 1, C outside [1, 16], an extent (for the pooling:
+ * a pooled extent) < 2, g < 1, r outside its range, a coeff that is negative or not finite, a NULL pointer other than the
+ * optional ones, 2^31 or more elements in any tensor (B * K * S for the cost volume, B * Cp * S for packed features), and for
+ * dfmir_dsearch_cost B above 65535.  Nothing syncs, allocates or keeps state, and every output is bit-identical from run to
+ * run: every call captures into a hipGraph. */
+int dfmir_dsearch_pool(int nd, const float* in, float* out, float* packed, int B, int C, int D, int H, int W, int g,
+                       void* stream);
+int dfmir_dsearch_cost(int nd, const float* fixp, const float* movp, float* cost, int B, int C, int D, int H, int W, int r,
+                       void* stream);
+int dfmir_dsearch_argmin(int nd, const float* cost, const float* soft, float coeff, int* idx, float* disp, int B, int D, int H,
+                         int W, int r, void* stream);
+int dfmir_dsearch_smooth(int nd, const float* disp, float* out, int B, int D, int H, int W, void* stream);
 /* Warped-feature SSD, the data term of instance optimisation (build-defined: the reference has no such term).  M, F:
  * [B][C][(D)][H][W] fp32 features of the moving / fixed image, 1 <= C <= 16; phi: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is
  * not read when nd == 2), channel d displaces axis d in voxels, in the order (z,) y, x, exactly as the warp kernels read a
