@@ -37,7 +37,7 @@ def _resolve_features(features, moving, fixed, mind_radius, mind_dilation):
 
 def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
                 regularizer='diffusion', lam, spacing=None, grid_downsize=2, iters=50, lr, betas=(0.9, 0.999),
-                update='add'):
+                update='add', parametrisation='linear'):
     """Instance optimisation: `iters` Adam iterations on the displacement field of ONE pair (build-defined), the step
     between a network's flow and the reported number.  Returns dict(flow, warped, history).
 
@@ -60,21 +60,38 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
     deformations do: flow_k = ops.compose_flows(ops.resize_linear(delta_k, vol), flow) = up + flow(x + up(x)) -- the correction
     is applied in the fixed image's frame and then the starting flow, so warp(moving, flow_k) = warp(warp(moving, flow), up).
     With flow=None the two are the same computation (bit-identical results); iteration 0 evaluates `flow` itself either way
-    (compose_flows(0, flow) is flow bit for bit).  ValueError on any other value."""
+    (compose_flows(0, flow) is flow bit for bit).  ValueError on any other value.
+
+    parametrisation: what `delta` is.  'linear' (the default) is the coarse grid above, interpolated linearly.  'bspline' makes
+    it the control grid of a cubic B-spline free-form deformation: grid_downsize is then the control spacing in voxels, an
+    int or nd ints in [1, ops.BSPLINE_MAX_STRIDE]; delta is [B,nd,*ops.bspline_control_shape(vol, grid_downsize)], zero at
+    the start; ops.bspline_flow(delta_k, vol, grid_downsize) stands where ops.resize_linear(delta_k, vol) does above, under
+    both values of `update` (a zero grid expands to +0.0, so iteration 0 still evaluates `flow` itself); there is no lower
+    limit on the volume (one smaller than a control cell is legal); and the returned dict gains 'control', the final delta.
+    Everything else is the same loop.  ValueError on any other value."""
     what = "refine_flow"
     if update not in ('add', 'compose'):
         raise ValueError("%s: update must be 'add' or 'compose', got %r" % (what, update))
+    if parametrisation not in ('linear', 'bspline'):
+        raise ValueError("%s: parametrisation must be 'linear' or 'bspline', got %r" % (what, parametrisation))
     if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
             or tuple(moving.shape) != tuple(fixed.shape):
         raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
     nd = moving.dim() - 2
     B, vol = int(moving.shape[0]), tuple(int(n) for n in moving.shape[2:])
-    if isinstance(grid_downsize, bool) or not isinstance(grid_downsize, int) or grid_downsize < 1:
-        raise ValueError("%s: grid_downsize must be an integer >= 1, got %r" % (what, grid_downsize))
-    coarse = tuple(n // grid_downsize for n in vol)
-    if min(coarse) < 2:
-        raise ValueError("%s: every dimension of the coarse grid %s = %s // %d must be >= 2"
-                         % (what, coarse, vol, grid_downsize))
+    if parametrisation == 'bspline':
+        try:
+            coarse = ops.bspline_control_shape(vol, grid_downsize)
+        except ValueError:
+            raise ValueError("%s: with parametrisation='bspline' grid_downsize must be an integer in [1, %d] or %d of them, "
+                             "got %r" % (what, ops.BSPLINE_MAX_STRIDE, nd, grid_downsize)) from None
+    else:
+        if isinstance(grid_downsize, bool) or not isinstance(grid_downsize, int) or grid_downsize < 1:
+            raise ValueError("%s: grid_downsize must be an integer >= 1, got %r" % (what, grid_downsize))
+        coarse = tuple(n // grid_downsize for n in vol)
+        if min(coarse) < 2:
+            raise ValueError("%s: every dimension of the coarse grid %s = %s // %d must be >= 2"
+                             % (what, coarse, vol, grid_downsize))
     if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
         raise ValueError("%s: iters must be an integer >= 0, got %r" % (what, iters))
     if regularizer not in ('diffusion', 'bending'):
@@ -92,7 +109,7 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         history = torch.empty((iters + 1, 2), device=delta.device, dtype=torch.float32)
 
     def flow_of(d):
-        up = ops.resize_linear(d, vol)
+        up = ops.bspline_flow(d, vol, grid_downsize) if parametrisation == 'bspline' else ops.resize_linear(d, vol)
         if flow0 is None:
             return up
         return ops.compose_flows(up, flow0) if update == 'compose' else flow0 + up
@@ -115,7 +132,10 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         history[iters, 0] = ops.warp_ssd(handle, Mf, out, mask)
         history[iters, 1] = reg(out)
         warped = ops.warp(moving, out)
-    return dict(flow=out, warped=warped, history=history)
+    res = dict(flow=out, warped=warped, history=history)
+    if parametrisation == 'bspline':
+        res['control'] = delta
+    return res
 
 
 CONVEX_COEFFS = (0.003, 0.01, 0.03, 0.1, 0.3, 1.0)
@@ -197,7 +217,8 @@ def _refine_kwargs(refine, what):
 def register_volume(model, data, refine=None):
     """The inference entry of Registration3DModel: register data['A'] onto data['B'].  Returns dict(warped_A, flow) of
     netR(real_A, real_B, registration=True); with refine = a dict of refine_flow keywords (lam and lr at least) the flow is
-    then refined on this pair and 'refined_flow', 'refined_A' (real_A warped by it) and 'history' are added."""
+    then refined on this pair and 'refined_flow', 'refined_A' (real_A warped by it) and 'history' are added.  The dict may
+    carry any refine_flow keyword, parametrisation='bspline' among them."""
     if refine is not None:
         _refine_kwargs(refine, "register_volume")
     model.set_input(data)
@@ -238,8 +259,8 @@ def register_pair(model, data, label=None, fixed_label=None, labels=None):
 def register_pair_refined(model, data, refine, label=None, fixed_label=None, labels=None):
     """register_pair followed by instance optimisation of its flow: register_pair's own dict (every key as it is, 'warped_label'
     and 'dice' those of the network's flow) plus 'refined_flow', 'refined_A' and 'history' of refine_flow(real_A, real_B,
-    flow, **refine); refine = a dict of refine_flow keywords (lam and lr at least).  A function of its own because
-    register_pair's signature is pinned."""
+    flow, **refine); refine = a dict of refine_flow keywords (lam and lr at least; parametrisation='bspline' is accepted like
+    any other).  A function of its own because register_pair's signature is pinned."""
     _refine_kwargs(refine, "register_pair_refined")
     out = register_pair(model, data, label, fixed_label, labels)
     res = refine_flow(model.real_A, model.real_B, out['flow'], **refine)

@@ -1852,6 +1852,87 @@ def resize_linear(x, out_sp, mult=1.0):
     return ResizeFn.apply(x, tuple(int(s) for s in out_sp), mult)
 
 
+BSPLINE_MAX_STRIDE = 8                             # dfmir_amd/csrc/bspline.hip: what the weight tables are sized for
+
+
+def _bspline_geometry(vol, stride, what):
+    """(vol, stride) as tuples of nd ints, checked: nd = 2 or 3, every extent >= 1, every stride an integer in
+    [1, BSPLINE_MAX_STRIDE] (a bool is no integer)."""
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if not isinstance(vol, (tuple, list, torch.Size)) or len(vol) not in (2, 3) \
+            or not all(is_int(n) and n >= 1 for n in vol):
+        raise ValueError("%s: vol must be 2 or 3 integer extents >= 1, got %r" % (what, vol))
+    nd = len(vol)
+    st = (stride,) * nd if is_int(stride) else stride
+    if not isinstance(st, (tuple, list)) or len(st) != nd \
+            or not all(is_int(s) and 1 <= s <= BSPLINE_MAX_STRIDE for s in st):
+        raise ValueError("%s: stride must be an integer in [1, %d] or %d of them, got %r"
+                         % (what, BSPLINE_MAX_STRIDE, nd, stride))
+    return tuple(int(n) for n in vol), tuple(st)
+
+
+def bspline_control_shape(vol, stride):
+    """The control grid of a cubic B-spline deformation over a volume `vol` (nd ints) at control spacing `stride` (an int or
+    nd ints in [1, 8]): m_a = (n_a - 1) // s_a + 4 points per axis, point j at voxel coordinate s_a (j - 1) -- one point
+    before the first voxel and enough after the last."""
+    vol, st = _bspline_geometry(vol, stride, "bspline_control_shape")
+    return tuple((n - 1) // s + 4 for n, s in zip(vol, st))
+
+
+class BSplineFn(Function):
+    @staticmethod
+    def forward(ctx, ctrl, vol, st):
+        _need(ctrl)
+        ctrl = _c(ctrl)
+        nd = len(vol)
+        planes = ctrl.shape[0] * ctrl.shape[1]
+        geom = ((1,) + vol if nd == 2 else vol) + ((1,) + st if nd == 2 else st)
+        ws = lib().dfmir_bspline_bwd_ws_floats(nd, planes, *geom) if ctx.needs_input_grad[0] else 0
+        if ws < 0:
+            raise DfmirHipError("bspline_flow: the backward refuses the field %s (W > 7944 or more than 65535 * 256 control "
+                                "points per plane); detach ctrl if no gradient is wanted" % (tuple(ctrl.shape[:2]) + vol,))
+        y = torch.empty(tuple(ctrl.shape[:2]) + vol, device=ctrl.device, dtype=torch.float32)
+        check(lib().dfmir_bspline_fwd(nd, _p(ctrl), _p(y), planes, *geom, _st()))
+        ctx.meta = (tuple(ctrl.shape), nd, planes, geom, ws)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        shape, nd, planes, geom, n = ctx.meta
+        dy = _c(dy)
+        dctrl = torch.empty(shape, device=dy.device, dtype=torch.float32)
+        ws = torch.empty(n + 4, device=dy.device, dtype=torch.float32)
+        check(lib().dfmir_bspline_bwd(nd, _p(dy), _p(dctrl), planes, *geom, _p(ws), _st()))
+        return dctrl, None, None
+
+
+def bspline_flow(ctrl, vol, stride):
+    """The dense field of a cubic B-spline control grid, the free-form deformation of Rueckert et al. 1999 (build-defined,
+    dfmir_amd/csrc/bspline.hip).  ctrl: [B,C,*m] fp32, any C >= 1, m = bspline_control_shape(vol, stride); vol: nd = 2 or 3
+    ints; stride: the control spacing in voxels, an int or nd ints in [1, BSPLINE_MAX_STRIDE].  Returns [B,C,*vol]:
+
+        y[b,c,x] = sum over l in {0,1,2,3}^nd of prod_a B_{l_a}(t_a) ctrl[b,c,q + l],   q_a = x_a // s_a, t_a = (x_a % s_a) / s_a
+        B_0 = (1-t)^3 / 6   B_1 = (3t^3 - 6t^2 + 4) / 6   B_2 = (-3t^3 + 3t^2 + 3t + 1) / 6   B_3 = t^3 / 6
+
+    which is a depthwise conv_transpose of ctrl with stride s and the separable kernel k_a[(3 - l) s_a + r] = B_l(r / s_a),
+    cropped to [3 s_a, 3 s_a + n_a) on every axis.  The B*C planes are independent.  A zero grid gives +0.0 everywhere.  The
+    gradient goes to ctrl only (once differentiable): the adjoint in gather form, no atomics, bit-identical from run to run;
+    where (n_a - 1) % s_a == 0 the last control point of that axis only meets B_3(0) = 0 and its gradient is exactly 0.
+    ValueError, before the library or the device is touched, on a bad vol or stride and on a ctrl that is not fp32 or not of
+    the control shape.  The backward handles W <= 7944 and at most 65535 * 256 control points per plane: a ctrl that requires
+    grad beyond that raises DfmirHipError at the forward; without a gradient the forward has neither limit."""
+    what = "bspline_flow"
+    vol, st = _bspline_geometry(vol, stride, what)
+    m = tuple((n - 1) // s + 4 for n, s in zip(vol, st))
+    if not torch.is_tensor(ctrl) or ctrl.dtype != torch.float32:
+        raise ValueError("%s: ctrl must be an fp32 tensor, got %s" % (what, getattr(ctrl, 'dtype', type(ctrl).__name__)))
+    if ctrl.dim() != len(vol) + 2 or tuple(ctrl.shape[2:]) != m or ctrl.shape[0] < 1 or ctrl.shape[1] < 1:
+        raise ValueError("%s: ctrl must be [B,C,*%s], the control grid of volume %s at stride %s, got %s"
+                         % (what, m, vol, st, tuple(ctrl.shape)))
+    return BSplineFn.apply(ctrl, vol, st)
+
+
 # ------------------------------------------------------------------------------------------------
 # PatchNCE
 # ------------------------------------------------------------------------------------------------

@@ -479,6 +479,23 @@ long long dfmir_resize_bwd_ws_floats(int planes, int Di, int Hi, int Wi, int Do,
 int dfmir_resize_bwd_sep(const float* dy, float* dx, int planes, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
                          float mult, float* ws, void* stream);
 
+/* Cubic B-spline free-form deformation (build-defined; Rueckert et al. 1999), nd = 2 or 3 (nd == 2: D, sz are not read).
+ * Per axis a: integer spacing s_a in 1 .. 8, extent n_a >= 1, m_a = (n_a - 1) / s_a + 4 control points, point j at voxel
+ * s_a (j - 1).  With q_a = x_a / s_a, t_a = (x_a % s_a) / s_a and the uniform cubic B-spline basis B_0 = (1-t)^3 / 6,
+ * B_1 = (3t^3 - 6t^2 + 4) / 6, B_2 = (-3t^3 + 3t^2 + 3t + 1) / 6, B_3 = t^3 / 6:
+ *   fwd  y[p,x] = sum over l in {0..3}^nd of prod_a B_{l_a}(t_a) ctrl[p,q + l]      ctrl [planes][(m_z)][m_y][m_x] -> y
+ *        [planes][(D)][H][W]; a zero grid gives +0.0 everywhere.
+ *   bwd  the adjoint in gather form, dctrl[p,j] = sum over the x with q_a(x) in {j_a - 3 .. j_a} of prod_a B_{j_a - q_a}(t_a)
+ *        dy[p,x], as one pass per axis (x, y, z); no atomics, a fixed summation order: bit-identical from run to run.  dctrl
+ *        is written entirely.  ws = dfmir_bspline_bwd_ws_floats(...) floats of 16-byte aligned scratch for the
+ *        intermediates (-1: the library refuses the shape: planes > 65535, 2^31 elements or more, W > 7944, more than
+ *        65535 * 256 control points per plane). */
+int dfmir_bspline_fwd(int nd, const float* ctrl, float* y, int planes, int D, int H, int W, int sz, int sy, int sx,
+                      void* stream);
+long long dfmir_bspline_bwd_ws_floats(int nd, int planes, int D, int H, int W, int sz, int sy, int sx);
+int dfmir_bspline_bwd(int nd, const float* dy, float* dctrl, int planes, int D, int H, int W, int sz, int sy, int sx,
+                      float* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * PatchNCE path -- models/networks.py:602-619 (PatchSampleF.forward), :493-502 (Normalize),
  * models/patchnce.py:14-55 (PatchNCELoss.forward).
