@@ -5,7 +5,7 @@ call raises.  Nothing here imports `oracle/`.
 """
 import ctypes
 import os
-from ctypes import c_float, c_int, c_longlong, c_void_p, POINTER, Structure
+from ctypes import c_double, c_float, c_int, c_longlong, c_void_p, POINTER, Structure
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DFMIR_HIP_LIB: an alternative build of the same C ABI (A/B experiments); default = the in-tree library
@@ -146,6 +146,11 @@ _SIGS = {
     "dfmir_bend_ws_floats": [c_int] * 5,
     "dfmir_bend_fwd": [P, P, P] + [c_int] * 5 + [c_float] * 3 + [P],
     "dfmir_bend_bwd": [P, P, P] + [c_int] * 5 + [c_float] * 3 + [P],
+    "dfmir_jacdet_ws_floats": [c_int] * 5,
+    "dfmir_jacdet_fwd": [c_int, P, P, P] + [c_int] * 5 + [c_float, c_int, P],
+    "dfmir_jacdet_bwd": [c_int, P, P, P] + [c_int] * 5 + [c_float, c_int, P],
+    "dfmir_jacdet_map": [c_int, P, P] + [c_int] * 5 + [P],
+    "dfmir_jacdet_stats": [c_int, P, P, P] + [c_int] * 5 + [c_double, c_double, P],
     "dfmir_invcons_ws_floats": [c_int] * 5,
     "dfmir_invcons_fwd": [c_int, P, P, P, P, P, P] + [c_int] * 4 + [P],
     "dfmir_invcons_bwd_ws_floats": [c_int] * 5,
@@ -239,6 +244,7 @@ def lib():
         h.dfmir_conv3d_upwgrad_ws_floats.restype = c_longlong
         h.dfmir_flow_smooth_ws_floats.restype = c_longlong
         h.dfmir_bend_ws_floats.restype = c_longlong
+        h.dfmir_jacdet_ws_floats.restype = c_longlong
         h.dfmir_invcons_ws_floats.restype = c_longlong
         h.dfmir_invcons_bwd_ws_floats.restype = c_longlong
         h.dfmir_compose_bwd_ws_floats.restype = c_longlong

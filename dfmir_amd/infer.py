@@ -4,7 +4,7 @@ warp to the CPU, test.py:80-81)."""
 import torch
 
 from . import ops
-from .losses import BendingEnergy_Loss, Grad_Loss
+from .losses import BendingEnergy_Loss, Grad_Loss, JacobianDet_Loss
 from .voxelmorph import SpatialTransformer
 
 
@@ -37,7 +37,7 @@ def _resolve_features(features, moving, fixed, mind_radius, mind_dilation):
 
 def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
                 regularizer='diffusion', lam, spacing=None, grid_downsize=2, iters=50, lr, betas=(0.9, 0.999),
-                update='add', parametrisation='linear'):
+                update='add', parametrisation='linear', fold_weight=0.0, fold_eps=0.0, fold_power=2):
     """Instance optimisation: `iters` Adam iterations on the displacement field of ONE pair (build-defined), the step
     between a network's flow and the reported number.  Returns dict(flow, warped, history).
 
@@ -68,8 +68,17 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
     the start; ops.bspline_flow(delta_k, vol, grid_downsize) stands where ops.resize_linear(delta_k, vol) does above, under
     both values of `update` (a zero grid expands to +0.0, so iteration 0 still evaluates `flow` itself); there is no lower
     limit on the volume (one smaller than a control cell is legal); and the returned dict gains 'control', the final delta.
-    Everything else is the same loop.  ValueError on any other value."""
+    Everything else is the same loop.  ValueError on any other value.
+
+    fold_weight: a weight >= 0 on the fold penalty (build-defined: losses.JacobianDet_Loss).  0.0 (the default) launches
+    nothing more and the result is bit-identical to a call without the keyword.  With fold_weight > 0, J_k gains
+    fold_weight * ops.jacobian_penalty(flow_k, fold_eps, fold_power) and the returned dict gains 'fold_history', a device
+    tensor [iters + 1] of that penalty (unweighted) at flow_0 .. flow_iters; `history` keeps its two columns.  ValueError on
+    a negative or non-finite weight and on a fold_eps / fold_power that ops.jacobian_penalty refuses."""
     what = "refine_flow"
+    if isinstance(fold_weight, bool) or not isinstance(fold_weight, (int, float)) or not 0.0 <= fold_weight < float('inf'):
+        raise ValueError("%s: fold_weight must be a finite weight >= 0, got %r" % (what, fold_weight))
+    fold = float(fold_weight) > 0.0
     if update not in ('add', 'compose'):
         raise ValueError("%s: update must be 'add' or 'compose', got %r" % (what, update))
     if parametrisation not in ('linear', 'bspline'):
@@ -100,6 +109,10 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         raise ValueError("%s: flow must be [B,%d,*vol] = %s" % (what, nd, (B, nd) + vol))
     _check_features(what, features, moving, nd, B, vol)
     reg = Grad_Loss(dim=nd, penalty='l2') if regularizer == 'diffusion' else BendingEnergy_Loss(dim=nd, spacing=spacing)
+    if fold:
+        if min(vol) < 3:
+            raise ValueError("%s: fold_weight > 0 needs a volume of at least 3 voxels per axis, got %s" % (what, vol))
+        jd = JacobianDet_Loss(dim=nd, eps=fold_eps, power=fold_power)      # (a bad fold_eps / fold_power raises here)
     with torch.no_grad():
         Mm, Mf = _resolve_features(features, moving, fixed, mind_radius, mind_dilation)
         handle = ops.pack_features(Mm)
@@ -107,6 +120,7 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         delta = ops.zeros((B, nd) + coarse, handle.packed.device)
         m, v = ops.zeros_like(delta), ops.zeros_like(delta)
         history = torch.empty((iters + 1, 2), device=delta.device, dtype=torch.float32)
+        fold_history = torch.empty((iters + 1,), device=delta.device, dtype=torch.float32) if fold else None
 
     def flow_of(d):
         up = ops.bspline_flow(d, vol, grid_downsize) if parametrisation == 'bspline' else ops.resize_linear(d, vol)
@@ -120,9 +134,15 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
             flow_k = flow_of(d)
             sim = ops.warp_ssd(handle, Mf, flow_k, mask)
             r = reg(flow_k)
-            (g,) = torch.autograd.grad(sim + r * float(lam), d)
+            total = sim + r * float(lam)
+            if fold:
+                f = jd(flow_k)
+                total = total + f * float(fold_weight)
+            (g,) = torch.autograd.grad(total, d)
         with torch.no_grad():
             history[k, 0], history[k, 1] = sim.detach(), r.detach()
+            if fold:
+                fold_history[k] = f.detach()
             ops.adam_step(delta, g, m, v, lr, betas[0], betas[1], 1e-8, k + 1, bump=False)
     with torch.no_grad():
         if iters == 0:
@@ -131,8 +151,12 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
             out = flow_of(delta)
         history[iters, 0] = ops.warp_ssd(handle, Mf, out, mask)
         history[iters, 1] = reg(out)
+        if fold:
+            fold_history[iters] = jd(out)
         warped = ops.warp(moving, out)
     res = dict(flow=out, warped=warped, history=history)
+    if fold:
+        res['fold_history'] = fold_history
     if parametrisation == 'bspline':
         res['control'] = delta
     return res
@@ -320,6 +344,27 @@ def invert_flow(flow, iters=20, tol=0.0):
     inverse, history = ops.invert_flow(flow, iters=iters, tol=tol, history=True)
     return dict(inverse=inverse, residual=history[-1, :, 0].clone(), residual_max=history[-1, :, 1].clone(), history=history,
                 roundtrip=inverse_consistency_error(flow, inverse))
+
+
+@torch.no_grad()
+def flow_regularity(flow, border=1, log_offset=0.0):
+    """The regularity of a deformation, the number reported beside Dice / HD95 / TRE: where phi = x + flow folds and how far
+    its volume change spreads.  flow: [B,nd,*vol] fp32 in voxels (ops.warp's convention).  With d = det J, J = I + the central
+    differences of the flow, on Omega = the voxels at least `border` away from every face (the definition:
+    losses.JacobianDet_Loss), returns dict(folded [B] = the fraction of Omega with d <= 0, folded_count [B], min [B], max
+    [B], mean [B] of d, sdlogj [B] = the population standard deviation of log(max(d + log_offset, 1e-9)), all float64;
+    detmap [B,1,*vol] fp32 = d on Omega and exactly 1.0 outside).  flow_regularity(flow, border=2, log_offset=3.0) gives the
+    Learn2Reg numbers (SDlogJ of the determinant shifted by 3 and clipped, two voxels cropped per face); the defaults give
+    the plain log on the largest domain the central differences allow.  The determinant does not depend on the voxel
+    spacing, so there is no spacing argument.  This is the check behind invert_flow's remark that a residual which stays
+    large typically means a fold."""
+    stats = ops.jacobian_stats(flow, border, log_offset)
+    omega = 1
+    for n in flow.shape[2:]:
+        omega *= int(n) - 2 * int(border)
+    return dict(folded=stats[:, 0] / float(omega), folded_count=stats[:, 0].clone(), min=stats[:, 1].clone(),
+                max=stats[:, 2].clone(), mean=stats[:, 3].clone(), sdlogj=stats[:, 5].clone(),
+                detmap=ops.jacobian_determinant(flow, border))
 
 
 @torch.no_grad()

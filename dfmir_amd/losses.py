@@ -1,7 +1,7 @@
 """Registration losses with the reference's interfaces: `smooothing_loss`
 (models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `MSE` /
 `Dice` / `Grad` (models/voxelmorph/torchvoxelmorph/losses.py:7-117; also reachable as `dfmir_amd.voxelmorph.losses`), each
-one fused HIP reduction (dfmir_amd.ops); `BendingEnergy_Loss` (build-defined) is the second-order flow regulariser; `MIND_Loss` (build-defined) is the MIND-SSC multi-modal similarity; `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
+one fused HIP reduction (dfmir_amd.ops); `BendingEnergy_Loss` (build-defined) is the second-order flow regulariser; `JacobianDet_Loss` (build-defined) is the fold penalty of a flow; `MIND_Loss` (build-defined) is the MIND-SSC multi-modal similarity; `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
 (util/loss_metrics.py:105-132) and `LabelHausdorff` (build-defined) are evaluation metrics on the HIP distance transform."""
 import numpy as np
 import torch
@@ -85,6 +85,59 @@ class BendingEnergy_Loss(_Loss):
             m = kwargs['mask'].to(device=prediction.device, dtype=torch.float32).expand_as(prediction).contiguous()
             prediction = ops.mul(prediction, m)
         loss = ops.bending_energy(prediction, self.spacing)
+        if self.loss_mult is not None:
+            loss = ops.scale(loss.view(1), self.loss_mult).view(())
+        return loss
+
+
+class JacobianDet_Loss(_Loss):
+    """Build-defined (the reference has no Jacobian code): the fold penalty of a displacement field.  Grad_Loss,
+    BendingEnergy_Loss and InverseConsistency_Loss charge roughness; this one charges a fold as such.
+    `JacobianDet_Loss(dim, eps, power, border)(prediction, mask=...)`, Grad_Loss's calling convention.
+
+    Field u [B,nd,*vol], fp32, nd = `dim` = 2 or 3.  Channel a is the displacement in voxels along axis a, in the order
+    (z,) y, x (ops.warp's convention); phi(x) = x + u(x).  `border` = m >= 1 (an integer); Omega_m = the voxels with
+    m <= p_a <= n_a - 1 - m on every axis (m = 1 is BendingEnergy_Loss's Omega; Learn2Reg's evaluation crops 2).  For p in
+    Omega_m:
+
+        J_ab(p) = delta_ab + (u_a(p + e_b) - u_a(p - e_b)) / 2          central differences
+        d(p)    = det J(p)                                              2x2 or 3x3, written out
+        psi(d)  = max(0, eps - d)^power                                 power 1 or 2, eps >= 0 finite
+        loss    = sum over (b, p in Omega_m) of psi(d(p)) / N,   N = B |Omega_m|
+
+    The determinant does not depend on the voxel spacing: in physical units J_phys = H J H^-1 with H = diag(h), which has
+    the same determinant.  That is why there is no `spacing` argument.
+
+    The gradient is the exact adjoint; with W_ab(p) = psi'(d(p)) cof(J(p))_ab on Omega_m and 0 outside, cof = the cofactor
+    matrix dd/dJ_ab, psi'(d) = -power max(0, eps - d)^(power - 1) (power 1: -1 where d < eps and 0 otherwise, 0 at d == eps):
+
+        dL/du_a(q) = (1 / 2N) sum_b [ W_ab(q - e_b) - W_ab(q + e_b) ]
+
+    The channel count must be nd: a one-plane volume [B,3,1,H,W] is refused, not reinterpreted.  An axis shorter than
+    2 m + 1 leaves Omega_m empty and raises a ValueError before anything is launched.  `mask=` multiplies the field first,
+    `loss_mult` scales the result.  Bit-identical from run to run; capturable (ops.jacobian_penalty;
+    dfmir_amd/csrc/jacdet.hip).  The map and the statistics of d: ops.jacobian_determinant, ops.jacobian_stats,
+    infer.flow_regularity."""
+
+    def __init__(self, dim=3, eps=0.0, power=2, border=1, name=None, loss_mult=None, *args, **kwargs):
+        super().__init__(name=name or 'jacdet')
+        if dim not in (2, 3):
+            raise ValueError("JacobianDet_Loss: dim must be 2 or 3, got %r" % (dim,))
+        if isinstance(power, bool) or power not in (1, 2):
+            raise ValueError("JacobianDet_Loss: power must be 1 or 2, got %r" % (power,))
+        if isinstance(border, bool) or not isinstance(border, (int, np.integer)) or border < 1:
+            raise ValueError("JacobianDet_Loss: border must be an integer >= 1, got %r" % (border,))
+        self.dim, self.power, self.border, self.loss_mult = dim, int(power), int(border), loss_mult
+        self.eps = ops._finite_ge0("JacobianDet_Loss", "eps", eps)
+
+    def forward(self, prediction, *args, **kwargs):
+        if torch.is_tensor(prediction) and prediction.dim() - 2 != self.dim:
+            raise ValueError("JacobianDet_Loss(dim=%d) got a %d-D field" % (self.dim, prediction.dim() - 2))
+        ops._jacobian_geom(prediction, self.border, "JacobianDet_Loss")    # (a bad argument raises before the mask is applied)
+        if 'mask' in kwargs:
+            m = kwargs['mask'].to(device=prediction.device, dtype=torch.float32).expand_as(prediction).contiguous()
+            prediction = ops.mul(prediction, m)
+        loss = ops.jacobian_penalty(prediction, self.eps, self.power, self.border)
         if self.loss_mult is not None:
             loss = ops.scale(loss.view(1), self.loss_mult).view(())
         return loss

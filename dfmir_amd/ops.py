@@ -2558,6 +2558,121 @@ def bending_energy(flow, spacing=None):
     return BendingEnergyFn.apply(flow, geom)
 
 
+def _jacobian_geom(flow, border, what):
+    """(nd, B, D, H, W, border) of a Jacobian-determinant input after the argument checks: ValueError on a bad rank, channel
+    count, border, extent or size (nothing is launched), then the usual errors for a CPU tensor and a dtype other than fp32."""
+    if not torch.is_tensor(flow) or flow.dim() not in (4, 5):
+        raise ValueError("%s: expects a [B,2,H,W] or [B,3,D,H,W] displacement field, got %s"
+                         % (what, "%d dims" % flow.dim() if torch.is_tensor(flow) else type(flow).__name__))
+    nd = flow.dim() - 2
+    if int(flow.shape[1]) != nd:
+        raise ValueError("%s: a %d-D field needs %d channels, one displacement per axis, got %s"
+                         % (what, nd, nd, tuple(flow.shape)))
+    if isinstance(border, bool) or not isinstance(border, (int, np.integer)) or border < 1:
+        raise ValueError("%s: border must be an integer >= 1, got %r" % (what, border))
+    border = int(border)
+    B = int(flow.shape[0])
+    D, H, W = (int(v) for v in (flow.shape[2:] if nd == 3 else (1,) + tuple(flow.shape[2:])))
+    if B < 1:
+        raise ValueError("%s: empty tensor %s" % (what, tuple(flow.shape)))
+    if min(int(n) for n in flow.shape[2:]) < 2 * border + 1:
+        raise ValueError("%s: every axis needs an extent of at least 2 * border + 1 = %d, got %s%s"
+                         % (what, 2 * border + 1, tuple(flow.shape[2:]),
+                            " (a one-plane volume [B,3,1,H,W] is refused, not reinterpreted as a 2-D field: pass "
+                            "flow[:, 1:, 0])" if nd == 3 and D == 1 else ""))
+    if B * nd * D * H * W >= 2 ** 31:
+        raise ValueError("%s: fields of 2^31 and more elements are not supported, got %s" % (what, tuple(flow.shape)))
+    _need(flow)
+    if flow.dtype != torch.float32:
+        raise DfmirHipError("%s: fp32 tensors only (got %s)" % (what, flow.dtype))
+    return nd, B, D, H, W, border
+
+
+def _jacobian_ws(flow, geom):
+    nd, B, D, H, W, _ = geom
+    return torch.empty(int(lib().dfmir_jacdet_ws_floats(nd, B, D, H, W)), device=flow.device, dtype=torch.float32)
+
+
+def _finite_ge0(what, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+        raise ValueError("%s: %s must be a finite number >= 0, got %r" % (what, name, v))
+    return float(v)
+
+
+class JacobianPenaltyFn(Function):
+    """dfmir_jacdet_fwd / _bwd: the forward keeps the field alone, the backward re-forms the cofactors in LDS."""
+
+    @staticmethod
+    def forward(ctx, flow, geom, eps, power):
+        flow = _c(flow)
+        nd, B, D, H, W, border = geom
+        ws = _jacobian_ws(flow, geom)
+        out = torch.empty((), device=flow.device, dtype=torch.float32)
+        check(lib().dfmir_jacdet_fwd(nd, _p(flow), _p(ws), _p(out), B, D, H, W, border, eps, power, _st()))
+        ctx.save_for_backward(flow)
+        ctx.meta = (geom, eps, power)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (flow,) = ctx.saved_tensors
+        (nd, B, D, H, W, border), eps, power = ctx.meta
+        g = _c(g)
+        df = torch.empty_like(flow)
+        check(lib().dfmir_jacdet_bwd(nd, _p(flow), _p(g), _p(df), B, D, H, W, border, eps, power, _st()))
+        return df, None, None, None
+
+
+def jacobian_penalty(flow, eps=0.0, power=2, border=1):
+    """The fold penalty of a displacement field [B,nd,*vol] (2-D or 3-D, fp32; build-defined, the definition:
+    losses.JacobianDet_Loss): the mean over (B, Omega) of max(0, eps - det J)^power, J = I + the central differences of the
+    field, Omega = the voxels at least `border` away from every face; power 1 or 2, eps >= 0.  A scalar with the exact
+    adjoint as its gradient.  No spacing argument: the determinant does not depend on the voxel spacing (J_phys = H J
+    H^-1).  ValueError before any launch on a bad rank, a channel count other than nd (a [B,3,1,H,W] field is refused),
+    an axis shorter than 2 border + 1, 2^31 or more elements, a bad eps, power or border; a CPU tensor raises the usual
+    "no CPU fallback" error."""
+    what = "jacobian_penalty"
+    if isinstance(power, bool) or power not in (1, 2):
+        raise ValueError("%s: power must be 1 or 2, got %r" % (what, power))
+    eps = _finite_ge0(what, "eps", eps)
+    geom = _jacobian_geom(flow, border, what)
+    return JacobianPenaltyFn.apply(flow, geom, eps, int(power))
+
+
+def jacobian_determinant(flow, border=1):
+    """det J of phi = x + flow, J = I + the central differences of the field [B,nd,*vol] (ops.warp's convention: channel a
+    displaces axis a in voxels, order (z,) y, x): a map [B,1,*vol] that holds the determinant on Omega (the voxels at
+    least `border` away from every face) and exactly 1.0, the identity's value, outside, so a plot needs no mask.  Not
+    differentiable (ops.jacobian_penalty is).  The determinant does not depend on the voxel spacing, so there is no
+    spacing argument.  Argument checks as ops.jacobian_penalty."""
+    nd, B, D, H, W, border = _jacobian_geom(flow, border, "jacobian_determinant")
+    flow = _c(flow.detach())
+    out = torch.empty((B, 1) + tuple(flow.shape[2:]), device=flow.device, dtype=torch.float32)
+    check(lib().dfmir_jacdet_map(nd, _p(flow), _p(out), B, D, H, W, border, _st()))
+    return out
+
+
+def jacobian_stats(flow, border=1, log_offset=0.0, log_floor=1e-9):
+    """Regularity statistics of a displacement field [B,nd,*vol], per sample over Omega (the voxels at least `border` away
+    from every face): a float64 tensor [B,6] of (the count of det J <= 0, min, max and mean of det J, mean and population
+    standard deviation of l = log(max(det J + log_offset, log_floor))).  border=2, log_offset=3 is the Learn2Reg
+    convention for SDlogJ.  The sums are taken in double in a fixed order.  The determinant does not depend on the voxel
+    spacing, so there is no spacing argument.  Argument checks as ops.jacobian_penalty; log_offset >= 0 and log_floor > 0,
+    both finite."""
+    what = "jacobian_stats"
+    log_offset = _finite_ge0(what, "log_offset", log_offset)
+    if _finite_ge0(what, "log_floor", log_floor) == 0.0:
+        raise ValueError("%s: log_floor must be a finite number > 0, got %r" % (what, log_floor))
+    geom = _jacobian_geom(flow, border, what)
+    nd, B, D, H, W, border = geom
+    flow = _c(flow.detach())
+    out = torch.empty((B, 6), device=flow.device, dtype=torch.float64)
+    check(lib().dfmir_jacdet_stats(nd, _p(flow), _p(_jacobian_ws(flow, geom)), _p(out), B, D, H, W, border, log_offset,
+                                   float(log_floor), _st()))
+    return out
+
+
 def _invcons_geom(u, v, what):
     """(nd, B, D, H, W) of an inverse-consistency pair after the argument checks (nothing is launched on a bad one)."""
     if u.dim() not in (4, 5) or tuple(u.shape) != tuple(v.shape):

@@ -12,6 +12,7 @@ term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map aga
 `BendingEnergy_Loss`.  symmetric=True trains both directions of the bidir network (the similarity is charged both ways);
 inverse_consistency=w adds w * the build-defined `InverseConsistency_Loss` of the two integrated fields.
 landmark_weight=w adds w * the build-defined `Landmark_Loss` of corresponding keypoints carried through the flow.
+fold_weight=w adds w * the build-defined `JacobianDet_Loss`, the penalty on folds (det J <= fold_eps) of the forward flow.
 """
 from types import SimpleNamespace
 
@@ -20,8 +21,8 @@ import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import (BendingEnergy_Loss, Grad_Loss, InverseConsistency_Loss, LabelDice, Landmark_Loss, MIND_Loss, NCC_Loss,
-                     NMI_Loss)
+from .losses import (BendingEnergy_Loss, Grad_Loss, InverseConsistency_Loss, JacobianDet_Loss, LabelDice, Landmark_Loss,
+                     MIND_Loss, NCC_Loss, NMI_Loss)
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
@@ -31,7 +32,7 @@ class Registration3DModel(object):
                  capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
                  seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3, mind_radius=2, mind_dilation=2,
                  regularizer='diffusion', spacing=None, symmetric=False, inverse_consistency=0.0, landmark_weight=0.0,
-                 landmark_penalty='l2'):
+                 landmark_penalty='l2', fold_weight=0.0, fold_eps=0.0, fold_power=2):
         """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window, or with ncc_kernel='gaussian' the Gaussian window of
         sigma = ncc_sigma, whose 3-D form is build-defined: see NCC_Loss; `win` is then unused) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
@@ -62,6 +63,11 @@ class Registration3DModel(object):
         (build-defined: see Landmark_Loss; landmark_penalty 'l2' or 'tre'), for 2-D and 3-D shapes; with symmetric=True
         the term is 0.5 * (L(flow, B_pts, A_pts) + L(neg_flow, A_pts, B_pts)); `get_current_losses()` gains 'landmark'.
         Which landmarks count is decided on the device, so the captured step needs no host check.
+        fold_weight = w > 0 (default 0 = no fold term, nothing about the model changes): the step adds w *
+        JacobianDet_Loss(dim=len(shape), eps=fold_eps, power=fold_power)(flow), the mean over the interior voxels of
+        max(0, fold_eps - det J)^fold_power with J = I + the central differences of the flow (build-defined: see
+        JacobianDet_Loss), for 2-D and 3-D shapes, as the LAST term; `get_current_losses()` gains 'fold'.  It stays on the
+        forward flow under symmetric=True, as the regulariser does.
         capture_step (build-defined, as REGISTRATIONModel's opt.capture_step): after two eager steps forward +
         losses + backward are captured into ONE hipGraph and replayed; Adam and the gradient all-reduce stay eager.
         Small volumes are host-bound otherwise (128^3: 3.7 ms of Python / autograd / ctypes per 5.2 ms step)."""
@@ -128,6 +134,12 @@ class Registration3DModel(object):
             self.seg_labels = dice.labels
             self._terms.append(('dice', self.seg_weight, lambda s: dice.loss(s.seg_B, s.seg_A, s.flow)))
             self._inputs += ('seg_A', 'seg_B')
+        self.fold_weight = float(fold_weight)
+        if not 0.0 <= self.fold_weight < float('inf'):
+            raise ValueError("fold_weight must be a finite weight >= 0, got %r" % (fold_weight,))
+        if self.fold_weight > 0.0:
+            jd = self.criterionFold = JacobianDet_Loss(dim=len(shape), eps=fold_eps, power=fold_power)
+            self._terms.append(('fold', self.fold_weight, lambda s: jd(s.flow)))
         if regularizer == 'bending':
             reg = self.criterionGrad = BendingEnergy_Loss(dim=len(shape), spacing=spacing)
         else:

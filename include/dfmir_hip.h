@@ -609,6 +609,38 @@ int dfmir_bend_fwd(const float* flow, float* ws, float* out, int B, int C, int D
                    float hx, void* stream);
 int dfmir_bend_bwd(const float* flow, const float* gout, float* dflow, int B, int C, int D, int H, int W, float hz,
                    float hy, float hx, void* stream);
+/* Jacobian determinant of the deformation phi(x) = x + u(x): fold penalty, determinant map and regularity statistics
+ * (build-defined: the reference has no Jacobian code).  flow u: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when
+ * nd == 2); channel a is the displacement in voxels along axis a, in the order (z,) y, x, as the warp kernels read a flow.
+ * border m >= 1; Omega_m = the voxels with m <= p_a <= n_a - 1 - m on every axis (m = 1 is the bending energy's Omega).  For
+ * p in Omega_m
+ *   J_ab(p) = delta_ab + (u_a(p + e_b) - u_a(p - e_b)) / 2          central differences
+ *   d(p)    = det J(p)                                              2x2 or 3x3, written out (no pivoting)
+ * The determinant does not depend on the voxel spacing: in physical units J_phys = H J H^-1 with H = diag(h), which has
+ * the same determinant, so no call here takes a spacing.
+ * dfmir_jacdet_fwd: out[0] = sum_{b, p in Omega_m} psi(d(p)) / N, psi(d) = max(0, eps - d)^power, N = B |Omega_m|.
+ * dfmir_jacdet_bwd: dflow (every element written) = gout[0] * the exact adjoint in gather form (no atomics, no derivative
+ * volume in memory, the backward reads u alone): with W_ab(p) = psi'(d(p)) cof(J(p))_ab on Omega_m and 0 outside, cof = the
+ * cofactor matrix dd/dJ_ab, psi'(d) = -power max(0, eps - d)^(power - 1) (power 1: -1 where d < eps, 0 otherwise),
+ *   dL/du_a(q) = (1 / 2N) sum_b [ W_ab(q - e_b) - W_ab(q + e_b) ]
+ * dfmir_jacdet_map: detmap [B][1][(D)][H][W] = d(p) on Omega_m and exactly 1.0f, the identity's value, outside.
+ * dfmir_jacdet_stats: stats [B][6] doubles, per sample over Omega_m: the count of d <= 0, min d, max d, mean d, mean l and
+ * std l (the population standard deviation), l = log(max(d + log_offset, log_floor)); the sums are taken in double, those
+ * of l about l at the first voxel of Omega_m, std = sqrt(max(0, S2/n - (S1/n)^2)).
+ * Refused ("invalid argument", nothing is launched): a NULL pointer, nd outside {2, 3}, B < 1, border < 1, an axis shorter
+ * than 2 border + 1, power outside {1, 2}, eps negative or not finite, log_offset < 0, log_floor <= 0 or either not
+ * finite, B * nd * voxels >= 2^31.  ws: dfmir_jacdet_ws_floats(nd, B, D, H, W) floats (-1 for a geometry that every border
+ * refuses), 8-byte aligned as `stats` is, need not be zeroed: one slot set per workgroup, added in a fixed order -- every
+ * output is bit-identical from run to run.  16-byte loads where W % 4 == 0 and flow is 16-byte aligned.  Nothing syncs,
+ * allocates or keeps state (gout is read on the device): all four calls capture into a hipGraph. */
+long long dfmir_jacdet_ws_floats(int nd, int B, int D, int H, int W);
+int dfmir_jacdet_fwd(int nd, const float* flow, float* ws, float* out, int B, int D, int H, int W, int border, float eps,
+                     int power, void* stream);
+int dfmir_jacdet_bwd(int nd, const float* flow, const float* gout, float* dflow, int B, int D, int H, int W, int border,
+                     float eps, int power, void* stream);
+int dfmir_jacdet_map(int nd, const float* flow, float* detmap, int B, int D, int H, int W, int border, void* stream);
+int dfmir_jacdet_stats(int nd, const float* flow, float* ws, double* stats, int B, int D, int H, int W, int border,
+                       double log_offset, double log_floor, void* stream);
 /* Inverse consistency of a pair of displacement fields (build-defined: the reference has no such term).  u, v:
  * [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when nd == 2); channel i displaces axis i in voxels, in the order
  * (z,) y, x, exactly as the warp kernels read a flow.
