@@ -179,6 +179,10 @@ _SIGS = {
     "dfmir_mind_desc": [P] + [c_int] * 7 + [P, P, P],
     "dfmir_mind_fwd": [P, P, P] + [c_int] * 7 + [P, P, P],
     "dfmir_mind_bwd": [P, P, P] + [c_int] * 7 + [P, P, P, P, P, P],
+    "dfmir_gradfield_ws_floats": [c_int] * 5,
+    "dfmir_gradfield_fwd": [P, P, P] + [c_int] * 5 + [c_float] * 3 + [c_int] + [c_double] * 3 + [P, P, P],
+    "dfmir_gradfield_bwd": [P] * 7 + [c_int] * 5 + [c_float] * 3 + [P],
+    "dfmir_gradfield_field": [P] + [c_int] * 5 + [c_float] * 3 + [c_int] + [c_double] * 2 + [P, P, P],
     "dfmir_warp_dice_ws_floats": [c_int] * 6,
     "dfmir_warp_dice_fwd": [c_int, P, P, P, P] + [c_int] * 6 + [P, P, P, P, P],
     "dfmir_warp_dice_bwd": [c_int, P, P, P, P] + [c_int] * 5 + [P, P, P, P],
@@ -253,6 +257,7 @@ def lib():
         h.dfmir_landmark_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong
+        h.dfmir_gradfield_ws_floats.restype = c_longlong
         h.dfmir_warp_dice_ws_floats.restype = c_longlong
         h.dfmir_label_hausdorff_ws_bytes.restype = c_longlong
         h.dfmir_dice_ws_floats.restype = c_longlong

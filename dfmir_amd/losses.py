@@ -1,7 +1,7 @@
 """Registration losses with the reference's interfaces: `smooothing_loss`
 (models/registration_model.py:25-32), `NCC_Loss` / `Grad_Loss` / `NMI_Loss` (util/losses.py:81-348) and vxm `NCC` / `MSE` /
 `Dice` / `Grad` (models/voxelmorph/torchvoxelmorph/losses.py:7-117; also reachable as `dfmir_amd.voxelmorph.losses`), each
-one fused HIP reduction (dfmir_amd.ops); `BendingEnergy_Loss` (build-defined) is the second-order flow regulariser; `JacobianDet_Loss` (build-defined) is the fold penalty of a flow; `MIND_Loss` (build-defined) is the MIND-SSC multi-modal similarity; `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
+one fused HIP reduction (dfmir_amd.ops); `BendingEnergy_Loss` (build-defined) is the second-order flow regulariser; `JacobianDet_Loss` (build-defined) is the fold penalty of a flow; `MIND_Loss` (build-defined) is the MIND-SSC multi-modal similarity; `GradField_Loss` (build-defined) is the normalised-gradient-field multi-modal similarity; `LabelDice` (build-defined) is the Dice of label maps under a flow.  `HausdorffDistance`
 (util/loss_metrics.py:105-132) and `LabelHausdorff` (build-defined) are evaluation metrics on the HIP distance transform."""
 import numpy as np
 import torch
@@ -242,6 +242,58 @@ class MIND_Loss(_Loss):
 
     def forward(self, prediction, target, mask=None, *args, **kwargs):
         return ops.mind_loss(prediction, target, self.radius, self.dilation, mask=mask)
+
+
+class GradField_Loss(_Loss):
+    """Build-defined (the reference ships no such loss): the normalised-gradient-field distance of Haber & Modersitzki
+    (MICCAI 2006).  It rewards image edges that are parallel or anti-parallel, whatever the contrast: the purely local
+    multi-modal companion of MIND_Loss (wider capture range) and the global NMI_Loss.
+    `GradField_Loss(eps, eta, dim, spacing)(prediction, target, mask=None)`.
+
+    Images A, B [B,1,*vol], fp32, 2-D or 3-D; axes a in the order (z,) y, x of extent n_a with the voxel spacing h_a > 0
+    (`spacing`, None = 1).  A volume of one plane [B,1,1,H,W] is legal and keeps three axes.  Per sample and axis, with
+    replicate clamping:
+
+        g_a(I)(x) = ( I(min(x_a + 1, n_a - 1)) - I(max(x_a - 1, 0)) ) / (2 h_a)
+
+    -- half a one-sided difference on the border, 0 on an axis of extent 1 -- and
+
+        dot = <g(A), g(B)>,   D_A = |g(A)|^2 + eps_A^2,   D_B = |g(B)|^2 + eps_B^2
+        s(x) = dot^2 / (D_A D_B)  in [0, 1),   s = 0 with no gradient where D_A D_B == 0
+        loss = mean over (B, voxels) of (1 - s)
+
+    With `mask` (anything that broadcasts to [B,1,*vol], used as float weights) the loss is sum mask (1 - s) / sum mask;
+    an empty mask gives 0 (a device scalar, no host sync) and zero gradients.
+
+    `eps`: a positive float (both images), a pair (eps_A, eps_B) of positive floats, or 'auto' (default): eps_I = eta *
+    the mean over the whole tensor (batch included) of |g(I)|_2 with eta > 0 (default 1) -- the usual automatic edge
+    parameter, formed on the device in double in a fixed order and A CONSTANT IN THE BACKWARD (as mu is in MIND_Loss).
+    With 'auto' the loss is invariant under I -> alpha I + beta for any alpha != 0; a constant image gets eps = 0, hence
+    s = 0, loss 1 and a zero gradient.  No NaN anywhere.
+
+    Gradients go to both images.  With w(x) = 1 / N, or mask(x) / sum mask, times the upstream gradient:
+
+        G^A(x) = dL/dg(A)(x) = -2 w dot / (D_A D_B) * ( g(B) - (dot / D_A) g(A) )       (G^B: the mirror expression)
+        dI(y)  = sum_a (1 / 2 h_a) * (   [y_a >= 1] G_a(y - e_a)     + [y_a == n_a - 1] G_a(y)
+                                       - [y_a <= n_a - 2] G_a(y + e_a) - [y_a == 0] G_a(y) )
+
+    the exact adjoint of the clamped difference (on an axis of extent 1 the terms cancel to 0).  `dim` (None = either)
+    pins the number of spatial axes.  Bit-identical from run to run; capturable (ops.gradfield_loss;
+    dfmir_amd/csrc/gradfield.hip)."""
+
+    def __init__(self, eps='auto', eta=1.0, dim=None, spacing=None, name='gradfield', *args, **kwargs):
+        super().__init__(name=name)
+        if dim not in (None, 2, 3):
+            raise ValueError("GradField_Loss: dim must be None, 2 or 3, got %r" % (dim,))
+        ops.gradfield_eps(eps, eta, "GradField_Loss")
+        self.eps, self.eta, self.dim = eps, eta, dim
+        self.spacing = None if spacing is None else ops.bending_spacing(spacing, (2, 3) if dim is None else (dim,),
+                                                                        "GradField_Loss")
+
+    def forward(self, prediction, target, mask=None, *args, **kwargs):
+        if self.dim is not None and prediction.dim() - 2 != self.dim:
+            raise ValueError("GradField_Loss(dim=%d) got %d-D images" % (self.dim, prediction.dim() - 2))
+        return ops.gradfield_loss(prediction, target, self.eps, self.eta, self.spacing, mask=mask)
 
 
 class NCC(object):

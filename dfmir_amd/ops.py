@@ -3577,6 +3577,118 @@ def mind_loss(a, b, radius=2, dilation=2, mask=None):
     return MINDFn.apply(a, b, int(radius), int(dilation), mask)
 
 
+def _gradfield_geom(I, spacing, what):
+    """(nd, B, D, H, W, hz, hy, hx) of a gradient-field input after the argument checks (ValueError: nothing is launched)."""
+    if not torch.is_tensor(I) or I.dim() not in (4, 5):
+        raise ValueError("%s: expects [B,1,H,W] or [B,1,D,H,W] tensors, got %s" %
+                         (what, "%d dims" % I.dim() if torch.is_tensor(I) else type(I).__name__))
+    if I.shape[1] != 1:
+        raise ValueError("%s: expects single-channel images, got %d channels" % (what, I.shape[1]))
+    if I.numel() == 0:
+        raise ValueError("%s: empty tensor %s" % (what, tuple(I.shape)))
+    if I.numel() >= 2 ** 31:
+        raise ValueError("%s: images of 2^31 and more voxels are not supported, got %s" % (what, tuple(I.shape)))
+    nd = I.dim() - 2
+    sp = bending_spacing(spacing, (nd,), what)
+    hz, hy, hx = sp if nd == 3 else (1.0,) + sp
+    D, H, W = (int(v) for v in (I.shape[2:] if nd == 3 else (1,) + tuple(I.shape[2:])))
+    return nd, int(I.shape[0]), D, H, W, hz, hy, hx
+
+
+def _gradfield_pos(v, what, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(v) or not 0.0 < float(v) <= 3.0e38:
+        raise ValueError("%s: %s must be a positive finite number, got %r" % (what, name, v))
+    return float(v)
+
+
+def gradfield_eps(eps, eta, what, pair=True):
+    """(auto, eta, eps_A, eps_B) of the `eps` / `eta` arguments of the gradient-field term: eps = 'auto' (eta > 0 is then
+    read), a positive float or, with `pair`, a pair of positive floats.  ValueError otherwise."""
+    if isinstance(eps, str):
+        if eps != 'auto':
+            raise ValueError("%s: eps must be 'auto', a positive number%s, got %r"
+                             % (what, " or a pair of them" if pair else "", eps))
+        return 1, _gradfield_pos(eta, what, "eta"), 0.0, 0.0
+    if pair and isinstance(eps, (tuple, list)):
+        if len(eps) != 2:
+            raise ValueError("%s: eps must be 'auto', a positive number or a pair of them, got %r" % (what, eps))
+        return 0, 0.0, _gradfield_pos(eps[0], what, "eps"), _gradfield_pos(eps[1], what, "eps")
+    e = _gradfield_pos(eps, what, "eps")
+    return 0, 0.0, e, e
+
+
+def _gradfield_ws(geom, device):
+    n = int(lib().dfmir_gradfield_ws_floats(*geom[:5]))
+    if n < 0:
+        raise DfmirHipError("gradfield: unsupported shape %s" % (geom[1:5],))
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+class GradFieldFn(Function):
+    """dfmir_gradfield_fwd / _bwd; gradients to both images.  The workspace that lives until the backward holds eps_A,
+    eps_B and the sum of the mask at its head."""
+
+    @staticmethod
+    def forward(ctx, a, b, geom, eps, mask=None):
+        a, b = _c(a), _c(b)
+        ws = _gradfield_ws(geom, a.device)
+        out = torch.empty((), device=a.device, dtype=torch.float32)
+        check(lib().dfmir_gradfield_fwd(_p(a), _p(b), _p(mask), *geom, *eps, _p(ws), _p(out), _st()))
+        ctx.save_for_backward(a, b, mask, ws)
+        ctx.meta = geom
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, b, mask, ws = ctx.saved_tensors
+        g = _c(g)
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            check(lib().dfmir_gradfield_bwd(_p(a), _p(b), _p(mask), _p(g), _p(ws), _p(da), _p(db), *ctx.meta, _st()))
+        return da, db, None, None, None
+
+
+def gradfield_loss(a, b, eps='auto', eta=1.0, spacing=None, mask=None):
+    """Normalised-gradient-field distance of two single-channel images [B,1,*vol] (2-D or 3-D; the definition:
+    losses.GradField_Loss): the mean over (B, voxels) of 1 - <g(a), g(b)>^2 / ((|g(a)|^2 + eps_a^2) (|g(b)|^2 + eps_b^2))
+    with the clamped central differences g divided by the voxel spacing (`spacing`, one positive number per axis in the
+    order (z,) y, x; None = 1); with `mask` (anything that broadcasts to [B,1,*vol], used as float weights)
+    sum mask (1 - s) / sum mask -- 0 for an empty mask, as a device scalar without a host sync.  eps: 'auto' (eta * the
+    mean gradient magnitude of each image, a constant in the backward), a positive float, or a pair (eps_a, eps_b).
+    Gradients go to both images.  ValueError before any launch on a bad rank, channel count, shape mismatch, eps, eta or
+    spacing; a CPU tensor raises the usual "no CPU fallback" error."""
+    geom = _gradfield_geom(a, spacing, "gradfield_loss")
+    if not torch.is_tensor(b) or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("gradfield_loss: the two images differ in shape (%s, %s)"
+                         % (tuple(a.shape), tuple(b.shape) if torch.is_tensor(b) else type(b).__name__))
+    e = gradfield_eps(eps, eta, "gradfield_loss")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise DfmirHipError("gradfield_loss: fp32 tensors only (got %s, %s)" % (a.dtype, b.dtype))
+    _need(a, b)
+    if mask is not None:
+        mask = mask.to(device=a.device, dtype=torch.float32).expand_as(a).contiguous()
+    return GradFieldFn.apply(a, b, geom, e, mask)
+
+
+def gradfield_normals(I, eps='auto', eta=1.0, spacing=None):
+    """The normalised gradient field n(I) = g(I) / sqrt(|g(I)|^2 + eps^2) [B,nd,*vol] of I [B,1,*vol], channels in the order
+    (z,) y, x (the definition: losses.GradField_Loss; eps: 'auto' or one positive float).  No gradient: for inspection and
+    tests."""
+    geom = _gradfield_geom(I, spacing, "gradfield_normals")
+    auto, eta, e, _ = gradfield_eps(eps, eta, "gradfield_normals", pair=False)
+    if I.dtype != torch.float32:
+        raise DfmirHipError("gradfield_normals: fp32 tensors only (got %s)" % I.dtype)
+    _need(I)
+    I = _c(I.detach())
+    ws = _gradfield_ws(geom, I.device)
+    out = torch.empty((geom[1], geom[0]) + tuple(I.shape[2:]), device=I.device, dtype=torch.float32)
+    check(lib().dfmir_gradfield_field(_p(I), *geom, auto, eta, e, _p(ws), _p(out), _st()))
+    return out
+
+
 def as_label_map(t):
     """An integer label map as the contiguous uint8 tensor the Dice kernels read, on the tensor's own device: any integer
     dtype, bool, or a float tensor with integral values; every value must lie in [0, 255].  The range check reads the

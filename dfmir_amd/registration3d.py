@@ -6,7 +6,8 @@ reference does ship: `VxmDense(ndims=3, int_steps=7, bidir=True)`
 (models/voxelmorph/torchvoxelmorph/networks.py:1028-1145) + `NCC_Loss(kernel_var=[9,9,9], 'mean')`
 (util/losses.py:132-261; ncc_kernel='gaussian' swaps in its Gaussian window) + lambda * `Grad_Loss(dim=3, 'l2')` (util/losses.py:81-130), Adam(2e-4,
 (0.5, 0.999)).  Oracle counterpart: oracle/dfmir_oracle.py::Registration3DStep.  similarity='nmi' swaps the NCC term for
-`NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity; similarity='mind' for the build-defined MIND-SSC loss (`MIND_Loss`).  seg_labels / seg_weight add the segmentation
+`NMI_Loss` (util/losses.py:263-348), the reference's multi-modal similarity; similarity='mind' for the build-defined MIND-SSC loss (`MIND_Loss`), similarity='gradfield' for the build-defined
+normalised-gradient-field distance (`GradField_Loss`).  seg_labels / seg_weight add the segmentation
 term of semi-supervised VoxelMorph: seg_weight * Dice of the fixed label map against the moving one warped by the flow
 (`losses.LabelDice`).  regularizer='bending' swaps the diffusion penalty for the build-defined second-order
 `BendingEnergy_Loss`.  symmetric=True trains both directions of the bidir network (the similarity is charged both ways);
@@ -21,8 +22,8 @@ import torch
 
 from . import distributed as dfdist
 from . import ops
-from .losses import (BendingEnergy_Loss, Grad_Loss, InverseConsistency_Loss, JacobianDet_Loss, LabelDice, Landmark_Loss,
-                     MIND_Loss, NCC_Loss, NMI_Loss)
+from .losses import (BendingEnergy_Loss, Grad_Loss, GradField_Loss, InverseConsistency_Loss, JacobianDet_Loss, LabelDice,
+                     Landmark_Loss, MIND_Loss, NCC_Loss, NMI_Loss)
 from .optim import FlatAdam
 from .voxelmorph import VxmDense
 
@@ -32,21 +33,25 @@ class Registration3DModel(object):
                  capture_step=False, deterministic_wgrad=None, similarity='ncc', nmi_bins=None, nmi_max_clip=1.0,
                  seg_labels=None, seg_weight=0.0, ncc_kernel='mean', ncc_sigma=3, mind_radius=2, mind_dilation=2,
                  regularizer='diffusion', spacing=None, symmetric=False, inverse_consistency=0.0, landmark_weight=0.0,
-                 landmark_penalty='l2', fold_weight=0.0, fold_eps=0.0, fold_power=2):
+                 landmark_penalty='l2', fold_weight=0.0, fold_eps=0.0, fold_power=2, gradfield_eps='auto',
+                 gradfield_eta=1.0):
         """similarity: 'ncc' (default: NCC_Loss with a `win`^3 window, or with ncc_kernel='gaussian' the Gaussian window of
         sigma = ncc_sigma, whose 3-D form is build-defined: see NCC_Loss; `win` is then unused) or 'nmi': NMI_Loss(real_B, warped real_A) with the
         bin centers `nmi_bins` (None = 32 uniform centers on [0, nmi_max_clip]) and max_clip = nmi_max_clip.  NMI clamps
         both images to [0, nmi_max_clip] first, as the reference does: data in [-1, 1] loses its negative half (nothing is
         rescaled here).  The loss key is then 'nmi' instead of 'ncc'.  similarity='mind': MIND_Loss(mind_radius,
         mind_dilation)(warped real_A, real_B), the local multi-modal similarity (build-defined: see MIND_Loss), for 2-D and
-        3-D shapes; the loss key is 'mind'.
+        3-D shapes; the loss key is 'mind'.  similarity='gradfield': GradField_Loss(gradfield_eps, gradfield_eta,
+        dim=len(shape), spacing=spacing)(warped real_A, real_B), the normalised-gradient-field distance (build-defined: see
+        GradField_Loss; eps 'auto', a positive float or a pair), the purely local multi-modal term for fine alignment and
+        for pairs with inverted contrast, for 2-D and 3-D shapes; the loss key is 'gradfield'.
         seg_labels (a list of 1..64 label values in [0, 255]; None = no segmentation term): `set_input` then also takes
         data['A_seg'] and data['B_seg'], integer label maps [B,1,*shape] of the moving and the fixed image, and the step
         adds seg_weight * LabelDice(seg_labels).loss(B_seg, A_seg, flow); `get_current_losses()` gains 'dice'.
         regularizer: 'diffusion' (default: Grad_Loss(penalty='l2'), loss key 'grad') or 'bending': lam *
         BendingEnergy_Loss(dim=len(shape), spacing=spacing)(flow), the second-order penalty that charges nothing for an
         affine motion (build-defined: see BendingEnergy_Loss), for 2-D and 3-D shapes; `spacing` is the voxel spacing in
-        the order (z,) y, x (None = 1) and is read by the bending energy and by the landmark term.  The loss key is then
+        the order (z,) y, x (None = 1) and is read by the bending energy, by the landmark term and by similarity='gradfield'.  The loss key is then
         'bending' instead of 'grad'.
         symmetric (build-defined, VoxelMorph's own bidirectional training; default False = the one-directional step): the
         target branch of the bidir network is computed and the similarity becomes 0.5 * (sim(y_source, real_B) +
@@ -83,8 +88,8 @@ class Registration3DModel(object):
                              "backward field")
         self.netR.skip_unused_target = not self.symmetric      # the one-directional step reads (y_source, flow) only
         self.optimizer_R = FlatAdam(self.netR.parameters(), lr=lr, betas=betas)
-        if similarity not in ('ncc', 'nmi', 'mind'):
-            raise ValueError("similarity must be 'ncc', 'nmi' or 'mind', got %r" % (similarity,))
+        if similarity not in ('ncc', 'nmi', 'mind', 'gradfield'):
+            raise ValueError("similarity must be 'ncc', 'nmi' or 'mind', or 'gradfield', got %r" % (similarity,))
         if ncc_kernel not in ('mean', 'gaussian'):
             raise ValueError("ncc_kernel must be 'mean' or 'gaussian', got %r" % (ncc_kernel,))
         self.similarity = similarity
@@ -100,6 +105,10 @@ class Registration3DModel(object):
         elif similarity == 'mind':
             mind = self.criterionMIND = MIND_Loss(radius=mind_radius, dilation=mind_dilation)
             sim = lambda s: sym(mind(s.y_source, s.real_B), lambda: mind(s.y_target, s.real_A))
+        elif similarity == 'gradfield':
+            gf = self.criterionGradField = GradField_Loss(eps=gradfield_eps, eta=gradfield_eta, dim=len(shape),
+                                                          spacing=spacing)
+            sim = lambda s: sym(gf(s.y_source, s.real_B), lambda: gf(s.y_target, s.real_A))
         else:
             bins = np.linspace(0.0, nmi_max_clip, 32) if nmi_bins is None else nmi_bins
             nmi = self.criterionNMI = NMI_Loss(bins, device=self.device, max_clip=nmi_max_clip)

@@ -848,6 +848,43 @@ int dfmir_mind_fwd(const float* a, const float* b, const float* mask, int nd, in
                    int dilation, float* ws, float* out, void* stream);
 int dfmir_mind_bwd(const float* a, const float* b, const float* mask, int nd, int B, int D, int H, int W, int radius,
                    int dilation, const float* ws, float* tmp, const float* gout, float* da, float* db, void* stream);
+/* Normalised-gradient-field similarity (Haber & Modersitzki, MICCAI 2006), build-defined: it rewards image edges that are
+ * parallel or anti-parallel, whatever the contrast.  a, b: [B][D][H][W] fp32 single-channel images, nd = 2 (D = 1) or 3
+ * (nd = 3 with D = 1 keeps three axes); axes in the order (z,) y, x of extent n_a >= 1 with spacing h_a (hz is not read for
+ * nd = 2).  Per sample and axis, with replicate clamping:
+ *   g_a(I)(x) = ( I(min(x_a + 1, n_a - 1)) - I(max(x_a - 1, 0)) ) / (2 h_a)      (half a one-sided difference on the border,
+ *                                                                               0 on an axis of extent 1)
+ *   dot = <g(A), g(B)>,   D_A = |g(A)|^2 + eps_A^2,   D_B = |g(B)|^2 + eps_B^2
+ *   s(x) = dot^2 / (D_A D_B) in [0, 1);  s = 0 with no gradient where D_A D_B == 0
+ *   loss = mean over (B, voxels) of (1 - s), or with mask ([B][D][H][W] float weights) sum mask (1 - s) / sum mask; an empty
+ *          mask gives 0 and zero gradients.
+ * eps: auto_eps == 0: the given eps_a, eps_b > 0 (eta is not read).  auto_eps != 0: eps_I = eta * mean over the whole
+ * tensor (batch included) of |g(I)|_2, eta > 0 (eps_a, eps_b are not read), formed on the device in double in a fixed
+ * order and A CONSTANT IN THE BACKWARD; the loss is then invariant under I -> alpha I + beta, alpha != 0; a constant image
+ * has eps = 0, hence s = 0, loss 1 and a zero gradient -- no NaN.
+ * dfmir_gradfield_fwd: out[0] = loss.  dfmir_gradfield_bwd: da / db (either may be NULL, not both) = gout[0] * dL/d(a / b):
+ * with w(x) = mask(x) / sum mask (1 / N without a mask)
+ *   G^A(x) = dL/dg(A)(x) = -2 w dot / (D_A D_B) * ( g(B) - (dot / D_A) g(A) ),   G^B the mirror expression
+ *   dI(y)  = sum_a (1 / 2 h_a) ( [y_a >= 1] G_a(y - e_a) + [y_a == n_a - 1] G_a(y) - [y_a <= n_a - 2] G_a(y + e_a)
+ *                                - [y_a == 0] G_a(y) )
+ * the exact adjoint of the clamped difference, in gather form: no atomics, no G volume in memory, every output written once.
+ * dfmir_gradfield_field: out[B][nd][D][H][W] = n(I) = g(I) / sqrt(|g(I)|^2 + eps^2) (0 where the root is 0), channels in
+ * the order (z,) y, x; one eps (or eta).
+ * ws: dfmir_gradfield_ws_floats() floats, 8-byte aligned, need not be zeroed: per-workgroup sums in double, added in a
+ * fixed order, and at its head eps_A, eps_B and sum mask, which the main kernels and the backward read on the device --
+ * keep it between fwd and bwd.  Loss, gradients and field are bit-identical from run to run; nothing syncs with the host,
+ * allocates or keeps state (gout is read on the device), so the calls capture into a hipGraph.  Refused ("invalid
+ * argument", nothing is launched): nd outside {2, 3}, nd = 2 with D != 1, an extent < 1, 2^31 or more voxels, a spacing,
+ * eps or eta that is not positive and finite, a NULL pointer other than mask and one of da / db.  The size query returns -1
+ * for a geometry the other entry points refuse. */
+long long dfmir_gradfield_ws_floats(int nd, int B, int D, int H, int W);
+int dfmir_gradfield_fwd(const float* a, const float* b, const float* mask, int nd, int B, int D, int H, int W, float hz,
+                        float hy, float hx, int auto_eps, double eta, double eps_a, double eps_b, float* ws, float* out,
+                        void* stream);
+int dfmir_gradfield_bwd(const float* a, const float* b, const float* mask, const float* gout, const float* ws, float* da,
+                        float* db, int nd, int B, int D, int H, int W, float hz, float hy, float hx, void* stream);
+int dfmir_gradfield_field(const float* I, int nd, int B, int D, int H, int W, float hz, float hy, float hx, int auto_eps,
+                          double eta, double eps, float* ws, float* out, void* stream);
 /* Label-map Dice under a flow: vxm `Dice().loss(one_hot(fix)[:, labels], SpatialTransformer(one_hot(mov)[:, labels], flow))`
  * (models/voxelmorph/torchvoxelmorph/losses.py:79-90 after layers.py:36-48; mode 1 = the nearest-neighbour label warp of
  * test.py:80-81, forward only) without the one-hot tensors.  nd = 2 ([B,1,H,W], D = 1) or 3.  mov / fix: 8-bit label maps
