@@ -169,6 +169,11 @@ _SIGS = {
     "dfmir_warp_ssd_fwd": [c_int] + [P] * 9 + [c_int] * 5 + [P],
     "dfmir_warp_ssd_fwd_grad": [c_int] + [P] * 10 + [c_int] * 5 + [P],
     "dfmir_warp_ssd_bwd": [P, P, P, P, c_longlong, P],
+    "dfmir_affine_ws_floats": [c_int] * 5,
+    "dfmir_affine_flow": [c_int, P, P] + [c_int] * 4 + [P],
+    "dfmir_affine_flow_bwd": [c_int, P, P, P] + [c_int] * 4 + [P],
+    "dfmir_affine_system": [c_int] + [P] * 6 + [c_int] * 6 + [P],
+    "dfmir_affine_lm_step": [c_int] + [P] * 7 + [c_int] * 3 + [c_double] * 2 + [P],
     "dfmir_landmark_ws_floats": [c_int] * 6,
     "dfmir_landmark_fwd": [c_int] + [P] * 10 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
     "dfmir_landmark_bwd": [c_int] + [P] * 8 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
@@ -254,6 +259,7 @@ def lib():
         h.dfmir_compose_bwd_ws_floats.restype = c_longlong
         h.dfmir_flow_invert_ws_floats.restype = c_longlong
         h.dfmir_warp_ssd_ws_floats.restype = c_longlong
+        h.dfmir_affine_ws_floats.restype = c_longlong
         h.dfmir_landmark_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong

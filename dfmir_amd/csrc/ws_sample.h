@@ -1,0 +1,126 @@
+// The cell and corner gather of the warped-feature SSD (warpssd.hip), shared with the affine system kernels (affine.hip):
+// the geometry of a feature volume, the cell floor() selects for a sample point with its guards, the gather of four channels
+// of its corners from the voxel-major packed copy (or the channel-major tensor), and the interpolant with its derivative.
+// Everything sits in an anonymous namespace: each file that includes this keeps its own copy of the host helpers.
+#pragma once
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int WS_T = 256;                    // threads per workgroup: 4 waves x 64 lanes
+constexpr int WS_MAXC = 16;
+
+struct WsGeom {
+  int D, H, W;                               // D == 1 for 2-D features
+  int S;                                     // voxels per sample
+  int nblk;                                  // workgroups per sample
+  int C, Cp;                                 // channels, and rounded up to 4
+};
+
+// The cell of one voxel: upper weights, offset of the lower corner in voxels (may be negative: only corners whose bit of
+// `ok` is set are addressed) and, per axis a, bits 2a (lower corner inside) and 2a + 1 (upper corner inside).
+template <int ND>
+struct WsCell {
+  float w1[ND];
+  int base;
+  unsigned ok;
+};
+
+template <int ND>
+__device__ __forceinline__ void ws_cell(const WsGeom& g, const int (&p)[ND], const float (&u)[ND], WsCell<ND>& q) {
+  int n[ND], st[ND];
+  if (ND == 3) { n[0] = g.D; n[1] = g.H; n[2] = g.W; st[0] = g.H * g.W; st[1] = g.W; st[2] = 1; }
+  else { n[0] = g.H; n[ND - 1] = g.W; st[0] = g.W; st[ND - 1] = 1; }
+  q.base = 0;
+  q.ok = 0u;
+#pragma unroll
+  for (int a = 0; a < ND; ++a) {
+    const float f = (float)p[a] + u[a];
+    const bool nearby = f >= -1.f && f < (float)n[a];             // false for NaN and for points past the padding cells:
+    const float fl = floorf(f);                                 // no corner is read then, and no float goes to int
+    const int i0 = nearby ? (int)fl : -2;
+    q.w1[a] = f - fl;
+    q.base += i0 * st[a];
+    if ((unsigned)i0 < (unsigned)n[a]) q.ok |= 1u << (2 * a);
+    if ((unsigned)(i0 + 1) < (unsigned)n[a]) q.ok |= 2u << (2 * a);
+  }
+}
+
+// Four channels 4 gi .. 4 gi + 3 of the 2^ND corners of a cell (x is bit 0, axis a bit ND - 1 - a); 0 outside the volume
+// and for channels >= C.  Every address formed lies inside the sample: a corner outside reads voxel 0 and is discarded.
+template <int ND, bool PACKED>
+__device__ __forceinline__ void ws_corners(const float* __restrict__ mb, const WsGeom& g, const WsCell<ND>& q, int gi,
+                                           float4 (&val)[1 << ND]) {
+  constexpr int NC = 1 << ND;
+  int st[ND];
+  if (ND == 3) { st[0] = g.H * g.W; st[1] = g.W; st[2] = 1; }
+  else { st[0] = g.W; st[ND - 1] = 1; }
+#pragma unroll
+  for (int m = 0; m < NC; ++m) {
+    bool in = true;
+    int o = q.base;
+#pragma unroll
+    for (int a = 0; a < ND; ++a) {
+      const int bit = (m >> (ND - 1 - a)) & 1;
+      in = in && ((q.ok >> (2 * a + bit)) & 1u);
+      o += bit * st[a];
+    }
+    o = in ? o : 0;
+    float4 t;
+    if (PACKED) {
+      t = *reinterpret_cast<const float4*>(mb + (long long)o * g.Cp + 4 * gi);
+    } else {
+      const int c0 = 4 * gi;                                    // c0 < C always; the others fall back to channel c0
+      const float* r = mb + (long long)c0 * g.S + o;
+      t.x = r[0];
+      t.y = r[c0 + 1 < g.C ? (long long)g.S : 0];
+      t.z = r[c0 + 2 < g.C ? 2LL * g.S : 0];
+      t.w = r[c0 + 3 < g.C ? 3LL * g.S : 0];
+      if (c0 + 1 >= g.C) t.y = 0.f;
+      if (c0 + 2 >= g.C) t.z = 0.f;
+      if (c0 + 3 >= g.C) t.w = 0.f;
+    }
+    val[m] = in ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// One channel: the interpolated value and the derivative of the interpolant along each axis (x innermost, then y, then z:
+// the order of the warp kernels)
+template <int ND>
+__device__ __forceinline__ float ws_interp(const float (&v)[1 << ND], const WsCell<ND>& q, float (&d)[ND]) {
+  const float x1 = q.w1[ND - 1], x0 = 1.f - x1, y1 = q.w1[ND - 2], y0 = 1.f - y1;
+  const float a00 = x0 * v[0] + x1 * v[1], a01 = x0 * v[2] + x1 * v[3];
+  const float d00 = v[1] - v[0], d01 = v[3] - v[2];
+  if (ND == 2) {
+    d[ND - 1] = y0 * d00 + y1 * d01;
+    d[ND - 2] = a01 - a00;
+    return y0 * a00 + y1 * a01;
+  }
+  constexpr int U = ND == 3 ? 4 : 0;                            // (keeps the 2-D instantiation inside v)
+  const float z1 = q.w1[0], z0 = 1.f - z1;
+  const float a10 = x0 * v[U] + x1 * v[U + 1], a11 = x0 * v[U + 2] + x1 * v[U + 3];
+  const float d10 = v[U + 1] - v[U], d11 = v[U + 3] - v[U + 2];
+  const float b0 = y0 * a00 + y1 * a01, b1 = y0 * a10 + y1 * a11;
+  d[ND - 1] = z0 * (y0 * d00 + y1 * d01) + z1 * (y0 * d10 + y1 * d11);
+  d[ND - 2] = z0 * (a01 - a00) + z1 * (a11 - a10);
+  d[0] = b1 - b0;
+  return z0 * b0 + z1 * b1;
+}
+
+// false for arguments the entry points refuse: nd outside {2, 3}, B < 1, C outside [1, 16], an extent < 2 (D is not read
+// when nd == 2), or 2^31 and more elements in the packed features or the flow
+bool ws_geom(int nd, int B, int C, int D, int H, int W, int vpt, WsGeom* g) {
+  if ((nd != 2 && nd != 3) || B < 1 || C < 1 || C > WS_MAXC || H < 2 || W < 2 || (nd == 3 && D < 2)) return false;
+  if (nd == 2) D = 1;
+  const long long S = (long long)D * H * W;
+  const int Cp = (C + 3) & ~3;
+  if (S * Cp * B >= (1LL << 31) || S * nd * B >= (1LL << 31)) return false;
+  g->D = D; g->H = H; g->W = W; g->S = (int)S; g->C = C; g->Cp = Cp;
+  g->nblk = (int)((S + (long long)WS_T * vpt - 1) / ((long long)WS_T * vpt));
+  return true;
+}
+
+inline bool ws_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace

@@ -231,6 +231,123 @@ def convex_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=
     return dict(flow=ops.resize_linear(soft, vol, mult=float(grid_sp)), coarse=soft, idx=idx)
 
 
+def _finite_number(x):
+    return not isinstance(x, bool) and isinstance(x, (int, float)) and float('-inf') < x < float('inf')
+
+
+@torch.no_grad()
+def affine_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=2, mask=None, theta=None, dof='affine',
+                levels=(4, 2, 1), iters=10, mu0=1e-3, mu_up=10.0, mu_down=0.1):
+    """Affine pre-alignment (build-defined): a multi-level Levenberg-Marquardt fit of one affine transform per sample to the
+    SSD of features, the global stage in front of convex_init and refine_flow, which only look as far as a search window or
+    a descent from the start reaches.  Returns dict(theta, flow, warped, history).
+
+    moving, fixed: [B,1,*vol] fp32 images, 2-D or 3-D; features as in refine_flow: 'mind' = ops.mind_descriptor(.,
+    mind_radius, mind_dilation) of both images, 'intensity' = the images themselves, or a pair (moving features, fixed
+    features) of [B,C,*vol] tensors, 1 <= C <= 16.  mask: float weights that broadcast to [B,1,*vol], or None.  theta: the
+    start, [B,nd,nd+1] fp32 in ops.affine_flow's convention ([A | t], centred voxel coordinates), None = identity.  dof:
+    'affine' (all P = nd (nd + 1) parameters are free) or 'translation' (only the t column; A keeps its starting value bit for
+    bit).  levels: pooling strides, integers >= 1, applied in order; iters: evaluations per level, an int or one per level.
+
+    A level of stride s works on ops.pool_features(., s) of both feature sets (and of the mask, as a 1-channel feature; s = 1
+    takes them as they are), the moving side packed once.  Its theta is [A | t / s] and its result goes back as [A | s t]; the
+    centres are the level's own (n_l - 1) / 2.  When s does not divide an extent the pooled grid's centre sits (n mod s) / 2
+    fine voxels from the fine centre: an approximation the later levels absorb.  The loop of one level, per sample and all on
+    the device (ops.affine_ssd_system, ops.affine_lm_step), starts from theta_acc = trial = the level's start, L_acc = +inf,
+    mu = mu0 (both reset at each level: the similarity changes):
+
+        for k in 0 .. iters - 1:
+            (L, g, H) = ops.affine_ssd_system at trial
+            L finite and L <= L_acc:  accept -- theta_acc = trial, L_acc = L, (g_acc, H_acc) = (g, H); k > 0: mu = max(mu mu_down, 1e-12)
+            otherwise:                reject -- mu = min(mu mu_up, 1e12)
+            solve (H_acc[f,f] + mu diag(H_acc[f,f])) d = -g_acc[f] over the free parameters f, Cholesky in fp64;
+                  a pivot <= 0 or not finite: d = 0 and the row's 'singular' flag is set
+            trial = theta_acc + d
+            history[row + k, b] = (L, L_acc, mu, accepted, singular)
+        the level's result: theta_acc
+
+    history: a float64 device tensor [sum iters, B, 5].  flow = ops.affine_flow(theta, vol) and warped = ops.warp(moving,
+    flow); with iters = 0 everywhere theta is the start bit for bit.  Nothing syncs with the host.  The staged pipeline this
+    opens: aff = affine_init(mov, fix); cv = convex_init(aff['warped'], fix); flow0 = ops.compose_flows(cv['flow'],
+    aff['flow']); refine_flow(mov, fix, flow0, update='compose', ...).
+
+    ValueError before any launch on images that are not two [B,1,*vol] tensors of one shape (any channel count with a feature
+    pair), an unknown `features` or `dof`, a theta of the wrong shape or dtype, levels that are not integers >= 1 or leave an
+    extent < 2, iters that are not integers >= 0 or disagree with levels in length, and mu0 <= 0, mu_up <= 1 or mu_down outside
+    (0, 1] (or any of them not finite)."""
+    what = "affine_init"
+    if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
+            or tuple(moving.shape) != tuple(fixed.shape):
+        raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
+    nd = moving.dim() - 2
+    B, vol = int(moving.shape[0]), tuple(int(n) for n in moving.shape[2:])
+    if dof not in ('affine', 'translation'):
+        raise ValueError("%s: dof must be 'affine' or 'translation', got %r" % (what, dof))
+    try:
+        levels = tuple(levels)
+    except TypeError:
+        raise ValueError("%s: levels must be a sequence of integers >= 1, got %r" % (what, levels)) from None
+    if not levels or any(isinstance(s, bool) or not isinstance(s, int) or s < 1 for s in levels):
+        raise ValueError("%s: levels must be a non-empty sequence of integers >= 1, got %r" % (what, levels))
+    for s in levels:
+        if min(n // s for n in vol) < 2:
+            raise ValueError("%s: every extent of a level must be >= 2, got %s // %d" % (what, vol, s))
+    if isinstance(iters, int) and not isinstance(iters, bool):
+        iters = (iters,) * len(levels)
+    try:
+        iters = tuple(iters)
+    except TypeError:
+        raise ValueError("%s: iters must be an integer >= 0 or one per level, got %r" % (what, iters)) from None
+    if len(iters) != len(levels) or any(isinstance(n, bool) or not isinstance(n, int) or n < 0 for n in iters):
+        raise ValueError("%s: iters must be an integer >= 0 or one per level (%d), got %r" % (what, len(levels), iters))
+    if not (_finite_number(mu0) and _finite_number(mu_up) and _finite_number(mu_down)) \
+            or not (mu0 > 0 and mu_up > 1 and 0 < mu_down <= 1):
+        raise ValueError("%s: mu0 must be > 0, mu_up > 1 and mu_down in (0, 1], all finite; got %r, %r, %r"
+                         % (what, mu0, mu_up, mu_down))
+    if theta is not None:
+        if not torch.is_tensor(theta) or tuple(theta.shape) != (B, nd, nd + 1) or theta.dtype != torch.float32:
+            raise ValueError("%s: theta must be an fp32 tensor [B,%d,%d] = %s" % (what, nd, nd + 1, (B, nd, nd + 1)))
+    _check_features(what, features, moving, nd, B, vol)
+    if mask is not None:
+        if not torch.is_tensor(mask):
+            raise ValueError("%s: mask must be a tensor" % what)
+        try:
+            mask = mask.expand((B, 1) + vol)
+        except RuntimeError:
+            raise ValueError("%s: mask %s does not broadcast to %s" % (what, tuple(mask.shape), (B, 1) + vol)) from None
+    Mm, Mf = _resolve_features(features, moving, fixed, mind_radius, mind_dilation)
+    dev = Mm.device
+    if mask is not None:
+        mask = mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+    th = ops.affine_identity(B, nd, dev) if theta is None else theta.detach().to(dev).clone(memory_format=torch.contiguous_format)
+    P = nd * (nd + 1)
+    history = torch.empty((sum(iters), B, 5), device=dev, dtype=torch.float64)
+    row = 0
+    for s, n in zip(levels, iters):
+        if n == 0:
+            continue
+        if s == 1:
+            Lm, Lf, Lk = Mm, Mf, mask
+        else:
+            Lm, Lf = ops.pool_features(Mm, s), ops.pool_features(Mf, s)
+            Lk = None if mask is None else ops.pool_features(mask, s)
+        geom, h, Lf, _, Lk = ops._affine_ssd_args(Lm, Lf, th, Lk, what)
+        acc = th.clone()
+        acc[:, :, nd] /= float(s)
+        trial = acc.clone()
+        state = ops.affine_lm_state(B, nd, mu0, dev)
+        for k in range(n):
+            out = ops._affine_system_launch(geom, h, Lf, trial, Lk, True)
+            o = 1 + B + B * P
+            ops.affine_lm_step(out[1:1 + B], out[o:o + B * P].view(B, P), out[o + B * P:].view(B, P, P), acc, trial, state,
+                               history[row + k], k, dof, mu_up, mu_down)
+        row += n
+        th = acc
+        th[:, :, nd] *= float(s)
+    flow = ops.affine_flow(th, vol)
+    return dict(theta=th, flow=flow, warped=ops.warp(moving, flow), history=history)
+
+
 def _refine_kwargs(refine, what):
     if not isinstance(refine, dict):
         raise ValueError("%s: refine must be None or a dict of refine_flow keywords, got %s" % (what, type(refine).__name__))

@@ -404,6 +404,33 @@ class WarpedSSD_Loss(_Loss):
         return loss
 
 
+class AffineSSD_Loss(_Loss):
+    """Build-defined (the reference has no affine stage): the SSD between fixed-image features and moving-image features
+    under an affine transform, the data term of affine pre-alignment (infer.affine_init), value and gradient to the
+    transform's parameters in one fused pass.  `AffineSSD_Loss(dim)(moving_features, fixed_features, theta, mask=None)`.
+
+    M, F [B,C,*vol] as for WarpedSSD_Loss (M may be the handle of ops.pack_features(M)); theta [B,nd,nd+1] fp32 = [A | t] in
+    centred voxel coordinates, axis order (z,) y, x (ops.affine_flow): with c_a = (n_a - 1) / 2,
+
+        y(x) = c + A (x - c) + t          L = WarpedSSD_Loss(dim)(M, F, phi, mask)  at  phi(x) = y(x) - x  by definition
+
+    -- the same sampling, mean, masked form and 0 for an empty mask -- without the flow tensor or a per-voxel gradient:
+    dL/dtheta[b,a,j] = sum_x dL/dphi_a(x) q_j(x), q = (x - c, 1), is added in double inside the pass.  Gradients go to theta
+    ONLY: features or a mask that require grad raise a ValueError.  Bit-identical from run to run (ops.affine_ssd;
+    dfmir_amd/csrc/affine.hip)."""
+
+    def __init__(self, dim=3, name=None, *args, **kwargs):
+        super().__init__(name=name or 'affine_ssd')
+        if dim not in (2, 3):
+            raise ValueError("AffineSSD_Loss: dim must be 2 or 3, got %r" % (dim,))
+        self.dim = dim
+
+    def forward(self, moving_features, fixed_features, theta, mask=None, *args, **kwargs):
+        if not torch.is_tensor(theta) or theta.dim() != 3 or theta.shape[1] != self.dim:
+            raise ValueError("AffineSSD_Loss(dim=%d) needs a theta [B,%d,%d]" % (self.dim, self.dim, self.dim + 1))
+        return ops.affine_ssd(moving_features, fixed_features, theta, mask=mask)
+
+
 class Landmark_Loss(_Loss):
     """Build-defined (the reference has no landmark code): the registration error of corresponding landmarks carried
     through a displacement field, the keypoint supervision of multi-modal registration.

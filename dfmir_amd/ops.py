@@ -2921,9 +2921,9 @@ def pack_features(M):
     return PackedFeatures(packed, M, tuple(M.shape))
 
 
-def _warp_ssd_args(mov, fix, flow, mask, what):
-    """(geom, handle, fix, flow, mask [B,1,*vol] or None) of a warp_ssd call after the argument checks; a [B,C,*vol] `mov`
-    is packed here.  Everything a CPU tensor can get wrong raises ValueError before the device is asked for."""
+def _ssd_features_args(mov, fix, what):
+    """(packed, shape, geom) of the feature pair of a warp_ssd / affine_ssd call after its checks (ValueError: nothing is
+    launched): `mov` a [B,C,*vol] tensor or a handle of ops.pack_features, `fix` a tensor of the same shape."""
     packed = isinstance(mov, PackedFeatures)
     if packed:
         shape = tuple(mov.shape)
@@ -2933,15 +2933,29 @@ def _warp_ssd_args(mov, fix, flow, mask, what):
     else:
         geom = _features_geom(mov, what)
         shape = tuple(mov.shape)
-    nd, B, C, D, H, W = geom
     if not torch.is_tensor(fix) or tuple(fix.shape) != shape:
         raise ValueError("%s: mov %s / fix %s differ in shape" % (what, shape, tuple(fix.shape) if torch.is_tensor(fix) else fix))
     _features_geom(fix, what, "fix")
+    return packed, shape, geom
+
+
+def _warp_ssd_args(mov, fix, flow, mask, what):
+    """(geom, handle, fix, flow, mask [B,1,*vol] or None) of a warp_ssd call after the argument checks; a [B,C,*vol] `mov`
+    is packed here.  Everything a CPU tensor can get wrong raises ValueError before the device is asked for."""
+    packed, shape, geom = _ssd_features_args(mov, fix, what)
+    nd, B = geom[0], geom[1]
     if not torch.is_tensor(flow) or tuple(flow.shape) != (B, nd) + shape[2:]:
         raise ValueError("%s: the flow of %s features is [B,%d,*vol] = %s, got %s"
                          % (what, shape, nd, (B, nd) + shape[2:], tuple(flow.shape) if torch.is_tensor(flow) else flow))
     if flow.dtype != torch.float32:
         raise ValueError("%s: fp32 tensors only (flow is %s)" % (what, flow.dtype))
+    return _ssd_pair_args(mov, packed, fix, flow, mask, shape, geom, what)
+
+
+def _ssd_pair_args(mov, packed, fix, flow, mask, shape, geom, what):
+    """The part of _warp_ssd_args that does not look at the flow beyond its device; `flow` may be any device tensor that says
+    where the call runs (ops.affine_ssd passes its theta)."""
+    B = geom[1]
     if mask is not None:
         if not torch.is_tensor(mask):
             raise ValueError("%s: mask must be a tensor" % what)
@@ -3012,7 +3026,205 @@ def warp_ssd_per_sample(mov, fix, flow, mask=None):
     return _warp_ssd_launch(geom, h, fix, flow_c, mask, None)[:geom[1]].clone()
 
 
-DSEARCH_MAX_RADIUS = {2: 8, 3: 4}              # dfmir_amd/csrc/dsearch.hip: what the cost kernel's staged window is sized for
+def affine_identity(B, nd, device):
+    """The identity transform [B,nd,nd+1] fp32 = [I | 0] on `device` (the convention: ops.affine_flow)."""
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1 or nd not in (2, 3):
+        raise ValueError("affine_identity: B must be an integer >= 1 and nd 2 or 3, got B = %r, nd = %r" % (B, nd))
+    return torch.eye(nd, nd + 1, dtype=torch.float32, device=device).repeat(B, 1, 1)
+
+
+def _affine_theta(theta, B, nd, what):
+    """theta [B,nd,nd+1] fp32 of an affine op after the argument checks (ValueError: nothing is launched)."""
+    if not torch.is_tensor(theta) or tuple(theta.shape) != (B, nd, nd + 1):
+        raise ValueError("%s: theta must be [B,%d,%d] = %s, got %s"
+                         % (what, nd, nd + 1, (B, nd, nd + 1), tuple(theta.shape) if torch.is_tensor(theta) else theta))
+    if theta.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (theta is %s)" % (what, theta.dtype))
+
+
+def _affine_vol(vol, B, what):
+    """(nd, D, H, W) of the volume an affine flow is made for."""
+    try:
+        vol = tuple(vol)
+    except TypeError:
+        raise ValueError("%s: vol must be 2 or 3 extents, got %r" % (what, vol)) from None
+    if len(vol) not in (2, 3) or any(isinstance(n, bool) or not isinstance(n, int) or n < 2 for n in vol):
+        raise ValueError("%s: vol must be 2 or 3 integer extents >= 2, got %r" % (what, vol))
+    nd = len(vol)
+    D, H, W = vol if nd == 3 else (1,) + vol
+    if B * 4 * D * H * W >= 2 ** 31:
+        raise ValueError("%s: a flow [%d,%d,*%s] is too large (2^31 or more elements with four channels)" % (what, B, nd, vol))
+    return nd, D, H, W
+
+
+class AffineFlowFn(Function):
+    """dfmir_affine_flow / _flow_bwd."""
+
+    @staticmethod
+    def forward(ctx, theta, geom):
+        nd, B, D, H, W = geom
+        flow = torch.empty((B, nd) + ((D, H, W) if nd == 3 else (H, W)), device=theta.device, dtype=torch.float32)
+        check(lib().dfmir_affine_flow(nd, _p(theta), _p(flow), B, D, H, W, _st()))
+        ctx.geom = geom
+        return flow
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dflow):
+        nd, B, D, H, W = ctx.geom
+        dflow = _c(dflow)
+        ws = torch.empty(int(lib().dfmir_affine_ws_floats(nd, B, D, H, W)), device=dflow.device, dtype=torch.float32)
+        dtheta = torch.empty((B, nd, nd + 1), device=dflow.device, dtype=torch.float32)
+        check(lib().dfmir_affine_flow_bwd(nd, _p(dflow), _p(ws), _p(dtheta), B, D, H, W, _st()))
+        return dtheta, None
+
+
+def affine_flow(theta, vol):
+    """The dense displacement field of an affine transform (build-defined): theta [B,nd,nd+1] fp32 = [A | t] in CENTRED voxel
+    coordinates, axis order (z,) y, x; vol = the nd extents.  With c_a = (n_a - 1) / 2 and q(x) = (x - c, 1):
+
+        y(x) = c + A (x - c) + t         flow[b,a,x] = y_a(x) - x_a = sum_j (A - I)_aj (x - c)_j + t_a        [B,nd,*vol]
+
+    in ops.warp's convention, so ops.warp(moving, flow), ops.compose_flows, ops.warp_dice and the landmark ops take it as it
+    is.  Identity is [I | 0] (ops.affine_identity).  Centring makes A the same matrix on every pooled level of a volume (only
+    t scales) and keeps the normal matrix of a fit conditioned.  Differentiable in theta: dtheta[b,a,j] = sum_x dflow[b,a,x]
+    q_j(x), added in double in two fixed-order stages without atomics -- bit-identical from run to run.  ValueError before any
+    launch on a theta that is not [B,nd,nd+1] fp32, extents that are not integers >= 2 and 2^31 or more elements; a CPU tensor
+    raises the usual "no CPU fallback" error."""
+    what = "affine_flow"
+    if not torch.is_tensor(theta) or theta.dim() != 3 or int(theta.shape[0]) < 1:
+        raise ValueError("%s: theta must be a [B,nd,nd+1] tensor, got %s"
+                         % (what, tuple(theta.shape) if torch.is_tensor(theta) else type(theta).__name__))
+    B = int(theta.shape[0])
+    nd, D, H, W = _affine_vol(vol, B, what)
+    _affine_theta(theta, B, nd, what)
+    _need(theta)
+    return AffineFlowFn.apply(_c(theta), (nd, B, D, H, W))
+
+
+def _affine_ssd_args(mov, fix, theta, mask, what):
+    """(geom, handle, fix, theta, mask) of an affine_ssd / affine_ssd_system call after the argument checks: warp_ssd's own
+    for the features and the mask, and theta's, which stands where warp_ssd's flow does."""
+    if not isinstance(mov, PackedFeatures) and not torch.is_tensor(mov):
+        raise ValueError("%s: mov must be a [B,C,*vol] tensor or a handle of ops.pack_features" % what)
+    packed, shape, geom = _ssd_features_args(mov, fix, what)
+    _affine_theta(theta, geom[1], geom[0], what)
+    return _ssd_pair_args(mov, packed, fix, theta, mask, shape, geom, what)
+
+
+def _affine_system_launch(geom, h, fix, theta, mask, full):
+    """dfmir_affine_system: the double buffer [L, L_b [B], gb [B,P], g [B,P] (, H [B,P,P])]."""
+    nd, B, C, D, H, W = geom
+    P = nd * (nd + 1)
+    ws = torch.empty(int(lib().dfmir_affine_ws_floats(nd, B, D, H, W)), device=theta.device, dtype=torch.float32)
+    out = torch.empty(1 + B + 2 * B * P + (B * P * P if full else 0), device=theta.device, dtype=torch.float64)
+    check(lib().dfmir_affine_system(nd, _p(h.packed), _p(fix), _p(theta), _p(mask), _p(ws), _p(out), 1 if full else 0,
+                                    B, C, D, H, W, _st()))
+    return out
+
+
+class AffineSSDFn(Function):
+    """dfmir_affine_system in gradient-only mode: the forward's one pass leaves dL/dtheta, the backward scales it by gout."""
+
+    @staticmethod
+    def forward(ctx, theta, geom, h, fix, mask):
+        nd, B = geom[0], geom[1]
+        out = _affine_system_launch(geom, h, fix, theta, mask, False)
+        ctx.save_for_backward(out[1 + B:1 + B + B * nd * (nd + 1)])
+        ctx.shape = (B, nd, nd + 1)
+        return out[0].to(torch.float32)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (gb,) = ctx.saved_tensors
+        return (gb * g.to(torch.float64)).to(torch.float32).reshape(ctx.shape), None, None, None, None
+
+
+def affine_ssd(mov, fix, theta, mask=None):
+    """The SSD between fixed-image features and moving-image features under an affine transform (build-defined; the
+    definition: losses.AffineSSD_Loss): by definition ops.warp_ssd(mov, fix, ops.affine_flow(theta, vol), mask) -- the same
+    mean over (B, C, voxels), the same masked form sum m mean_c e^2 / sum m, 0 for an empty mask -- as a device scalar, from
+    ONE fused pass that reads no flow and writes no per-voxel gradient (dfmir_amd/csrc/affine.hip: the moving features are
+    sampled in the cell warp_ssd selects, with its guards).  mov: [B,C,*vol] (packed per call) or the handle of
+    ops.pack_features(mov), 1 <= C <= 16; fix: [B,C,*vol]; theta: [B,nd,nd+1] fp32, ops.affine_flow's convention.  The
+    gradient goes to theta ONLY (sums in double, a fixed order: bit-identical from run to run); a `mov`, `fix` or `mask`
+    that requires grad raises.  ValueError before any launch on what ops.warp_ssd refuses and on a theta of the wrong shape
+    or dtype; a CPU tensor raises the usual "no CPU fallback" error."""
+    geom, h, fix, theta_c, mask = _affine_ssd_args(mov, fix, theta, mask, "affine_ssd")
+    return AffineSSDFn.apply(theta_c, geom, h, fix, mask)
+
+
+@torch.no_grad()
+def affine_ssd_system(mov, fix, theta, mask=None):
+    """The affine SSD per sample with its gradient and Gauss-Newton matrix (build-defined), arguments as ops.affine_ssd:
+    (L_b [B], g [B,P], H [B,P,P]) as float64 device tensors without gradient, P = nd (nd + 1) parameters flattened row-major
+    (a, j).  Per voxel, with y = y_theta(x) and q = (x - c, 1) (ops.affine_flow):
+
+        e_c = M_c(y) - F_c      r = sum_c e_c dM_c(y)  (nd)      G = sum_c dM_c dM_c^T  (nd x nd)      N_b = sum_x m  (S unmasked)
+        L_b = sum_x m mean_c e^2 / N_b
+        g_b = (2 / (C N_b)) sum_x m r (x) q          = dL_b / dtheta_b exactly
+        H_b = (2 / (C N_b)) sum_x m G (x) (q q^T)    the Gauss-Newton matrix of L_b, symmetric positive semi-definite
+
+    all 0 for N_b = 0.  dM is the derivative of the interpolant in the cell floor() selects: corner differences, zero-padded
+    corners taking part as zeros (warp_ssd's).  One pass over the voxels, sums in double in a fixed order."""
+    geom, h, fix, theta_c, mask = _affine_ssd_args(mov, fix, theta, mask, "affine_ssd_system")
+    nd, B = geom[0], geom[1]
+    P = nd * (nd + 1)
+    out = _affine_system_launch(geom, h, fix, theta_c, mask, True)
+    o = 1 + B + B * P
+    return out[1:1 + B].clone(), out[o:o + B * P].reshape(B, P).clone(), out[o + B * P:].reshape(B, P, P).clone()
+
+
+def affine_lm_state(B, nd, mu0, device):
+    """The state of ops.affine_lm_step at the start of a level: [B, 2 + P + P P] float64 = (L_acc = +inf, mu = mu0, g_acc = 0,
+    H_acc = 0) per sample."""
+    P = nd * (nd + 1)
+    state = torch.empty((B, 2 + P + P * P), dtype=torch.float64, device=device)
+    state[:, 0] = float('inf')
+    state[:, 1] = float(mu0)
+    state[:, 2:] = 0.0
+    return state
+
+
+@torch.no_grad()
+def affine_lm_step(L, g, H, theta_acc, trial, state, hist, k, dof='affine', mu_up=10.0, mu_down=0.1):
+    """One Levenberg-Marquardt step of infer.affine_init per sample, on the device and in place (dfmir_affine_lm_step): (L
+    [B], g [B,P], H [B,P,P]) float64 = the system AT `trial`; theta_acc, trial [B,nd,nd+1] fp32; state from
+    ops.affine_lm_state; hist [B,5] float64 receives (L, L_acc, mu, accepted, singular); k = the evaluation's index within
+    its level.  L finite and L <= L_acc accepts the trial (and for k > 0 mu = max(mu mu_down, 1e-12)), anything else rejects it
+    (mu = min(mu mu_up, 1e12)); then (H_acc[f,f] + mu diag H_acc[f,f]) d = -g_acc[f] over the free parameters (dof 'affine':
+    all; 'translation': the t column) by Cholesky in fp64 -- a pivot <= 0 or not finite gives d = 0 and the singular flag --
+    and trial = theta_acc + d.  Nothing syncs with the host."""
+    what = "affine_lm_step"
+    if dof not in ('affine', 'translation'):
+        raise ValueError("%s: dof must be 'affine' or 'translation', got %r" % (what, dof))
+    if not torch.is_tensor(theta_acc) or theta_acc.dim() != 3:
+        raise ValueError("%s: theta_acc must be [B,nd,nd+1]" % what)
+    B, nd = int(theta_acc.shape[0]), int(theta_acc.shape[1])
+    if nd not in (2, 3):
+        raise ValueError("%s: theta_acc must be [B,nd,nd+1] with nd 2 or 3, got %s" % (what, tuple(theta_acc.shape)))
+    P = nd * (nd + 1)
+    _affine_theta(theta_acc, B, nd, what)
+    _affine_theta(trial, B, nd, what)
+    for t, shape, name in ((L, (B,), "L"), (g, (B, P), "g"), (H, (B, P, P), "H"), (state, (B, 2 + P + P * P), "state"),
+                           (hist, (B, 5), "hist")):
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float64:
+            raise ValueError("%s: %s must be a float64 tensor %s" % (what, name, shape))
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError("%s: k must be an integer >= 0, got %r" % (what, k))
+    if not (mu_up > 1.0 and 0.0 < mu_down <= 1.0 and mu_up < float('inf')):
+        raise ValueError("%s: mu_up must be finite and > 1, mu_down in (0, 1], got %r, %r" % (what, mu_up, mu_down))
+    for t in (L, g, H, theta_acc, trial, state, hist):
+        if not t.is_cuda:
+            raise DfmirHipError("dfmir_amd ops run only on the HIP device (got a %s tensor); there is no CPU fallback" % t.device)
+        if not t.is_contiguous():
+            raise ValueError("%s: contiguous tensors only (the step works in place)" % what)
+    check(lib().dfmir_affine_lm_step(nd, _p(L), _p(g), _p(H), _p(theta_acc), _p(trial), _p(state), _p(hist), B, k,
+                                     1 if dof == 'translation' else 0, float(mu_up), float(mu_down), _st()))
+
+
+DSEARCH_MAX_RADIUS = {2: 8, 3: 4}           # dfmir_amd/csrc/dsearch.hip: what the cost kernel's staged window is sized for
 
 
 def _dsearch_radius(radius, nd, what):

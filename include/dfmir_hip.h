@@ -771,6 +771,40 @@ int dfmir_warp_ssd_fwd_grad(int nd, const float* Mp, const float* M, const float
                             float* ws, float* per_sample, float* loss, float* scale, float* unit, int B, int C, int D, int H,
                             int W, void* stream);
 int dfmir_warp_ssd_bwd(const float* unit, const float* gout, const float* scale, float* dflow, long long n, void* stream);
+/* Affine pre-alignment (build-defined: the reference has no affine stage).  theta: [B][nd][nd + 1] fp32 = [A | t] in CENTRED
+ * voxel coordinates, axis order (z,) y, x; nd = 2 or 3 (D is not read when nd == 2).  With c_a = (n_a - 1) / 2 and
+ * q(x) = (x - c, 1):   y(x) = c + A (x - c) + t,   flow_a(x) = y_a(x) - x_a = sum_j (A - I)_aj (x - c)_j + t_a  (formed like
+ * that, in fp32, j ascending, t last).  Identity is [I | 0].  P = nd (nd + 1) parameters, flattened row-major (a, j).
+ * dfmir_affine_flow: flow [B][nd][S] (the warp kernels' convention); 16-byte stores where W % 4 == 0 and flow is aligned.
+ * dfmir_affine_flow_bwd: dtheta[b][a][j] = sum_x dflow[b][a][x] q_j(x), fp32 [B][P]: sums in double, two stages in a fixed
+ * order, no atomics.
+ * dfmir_affine_system: the affine SSD of packed moving features Mp (dfmir_warp_ssd_pack's layout, 1 <= C <= 16) against F
+ * [B][C][S] under an optional mask m [B][S], in ONE pass over the voxels.  M is sampled at x + flow(x) exactly as
+ * dfmir_warp_ssd_fwd samples it (the same cell, guards and corner differences, the flow in dfmir_affine_flow's arithmetic).
+ *   e_c = M_c(y) - F_c,  r = sum_c e_c dM_c(y)  (nd),  G = sum_c dM_c dM_c^T  (nd x nd),  N_b = sum_x m  (S without a mask)
+ *   L_b = sum_x m mean_c e^2 / N_b      g_b = (2 / (C N_b)) sum_x m r (x) q  = dL_b / dtheta_b
+ *   H_b = (2 / (C N_b)) sum_x m G (x) (q q^T)     the Gauss-Newton matrix of L_b, symmetric positive semi-definite
+ *   L   = sum_b sum_x m mean_c e^2 / sum_b N_b,   gb_b = dL / dtheta_b = g_b N_b / sum_b N_b;   all 0 where the weights sum to 0
+ * out (doubles, 8-byte aligned): [0] L, [1 .. B] L_b, gb [B][P], g [B][P] and -- full != 0 only -- H [B][P][P]:
+ * 1 + B + 2 B P (+ B P P) doubles.  Per-workgroup sums in double, added in a fixed order: bit-identical from run to run.
+ * dfmir_affine_lm_step: one Levenberg-Marquardt step per sample b on the device (infer.affine_init states the loop).
+ * state[b] = (L_acc, mu, g_acc [P], H_acc [P][P]) doubles; with L = Lb[b]:  L finite and L <= L_acc accepts (theta_acc =
+ * trial, L_acc = L, (g_acc, H_acc) = (g, H), and for k > 0 mu = max(mu mu_down, 1e-12)), otherwise mu = min(mu mu_up, 1e12);
+ * then (H_acc[f,f] + mu diag H_acc[f,f]) d = -g_acc[f] over the free parameters f (all, or with translation != 0 the t
+ * column) by Cholesky in fp64 -- a pivot <= 0 or not finite: d = 0 and the row is flagged singular -- and trial =
+ * fp32(theta_acc + d) on f, theta_acc elsewhere; hist[b] = (L, L_acc, mu, accepted, singular), 5 doubles.
+ * ws: dfmir_affine_ws_floats floats (-1 for a refused shape), 8-byte aligned, need not be zeroed; it serves _flow_bwd and
+ * _system.  Refused ("invalid argument", nothing is launched): nd outside {2, 3}, B < 1, an extent < 2, C outside [1, 16], 2^31
+ * or more elements in the flow or the packed features, a NULL pointer other than mask, a misaligned buffer, k < 0, mu_up <= 1,
+ * mu_down outside (0, 1].  Nothing syncs, allocates or keeps state. */
+long long dfmir_affine_ws_floats(int nd, int B, int D, int H, int W);
+int dfmir_affine_flow(int nd, const float* theta, float* flow, int B, int D, int H, int W, void* stream);
+int dfmir_affine_flow_bwd(int nd, const float* dflow, float* ws, float* dtheta, int B, int D, int H, int W, void* stream);
+int dfmir_affine_system(int nd, const float* Mp, const float* F, const float* theta, const float* mask, float* ws, double* out,
+                        int full, int B, int C, int D, int H, int W, void* stream);
+int dfmir_affine_lm_step(int nd, const double* Lb, const double* g, const double* H, float* theta_acc, float* trial,
+                         double* state, double* hist, int B, int k, int translation, double mu_up, double mu_down,
+                         void* stream);
 /* Landmark (keypoint) registration error of a displacement field (build-defined: the reference has no landmark code).
  * flow u: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when nd == 2); channel a displaces axis a in voxels, in the
  * order (z,) y, x, exactly as the warp kernels read a flow: warped(x) = moving(x + u(x)) with x in the fixed image's grid,
