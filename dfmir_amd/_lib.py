@@ -174,6 +174,9 @@ _SIGS = {
     "dfmir_affine_flow_bwd": [c_int, P, P, P] + [c_int] * 4 + [P],
     "dfmir_affine_system": [c_int] + [P] * 6 + [c_int] * 6 + [P],
     "dfmir_affine_lm_step": [c_int] + [P] * 7 + [c_int] * 3 + [c_double] * 2 + [P],
+    "dfmir_gauss_smooth": [c_int, P, P, P, c_longlong] + [c_int] * 3 + [c_double] * 4 + [P],
+    "dfmir_demons_ws_floats": [c_int] * 6,
+    "dfmir_demons_force": [c_int] + [P] * 8 + [c_float] + [c_int] * 5 + [P],
     "dfmir_landmark_ws_floats": [c_int] * 6,
     "dfmir_landmark_fwd": [c_int] + [P] * 10 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
     "dfmir_landmark_bwd": [c_int] + [P] * 8 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
@@ -260,6 +263,7 @@ def lib():
         h.dfmir_flow_invert_ws_floats.restype = c_longlong
         h.dfmir_warp_ssd_ws_floats.restype = c_longlong
         h.dfmir_affine_ws_floats.restype = c_longlong
+        h.dfmir_demons_ws_floats.restype = c_longlong
         h.dfmir_landmark_ws_floats.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong

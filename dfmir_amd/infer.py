@@ -348,6 +348,138 @@ def affine_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=
     return dict(theta=th, flow=flow, warped=ops.warp(moving, flow), history=history)
 
 
+@torch.no_grad()
+def demons_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
+                levels=(4, 2, 1), iters=10, max_step=2.0, sigma_fluid=1.0, sigma_diffusion=1.0,
+                update='compose', diffeomorphic=False, exp_steps=4):
+    """The demons iteration (build-defined): a second-order dense solver on the feature SSD, coarse to fine -- a per-voxel
+    Gauss-Newton step (ops.demons_force) regularised by Gaussian smoothing of the update (fluid) and of the field
+    (diffusion), with no backward pass, no optimiser state and no learning rate.  Returns dict(flow, warped, history, energy0,
+    energy).
+
+    moving, fixed: [B,1,*vol] fp32 images, 2-D or 3-D; flow: the starting field [B,nd,*vol] in voxels (ops.warp's
+    convention), None = zeros.  features as in refine_flow: 'mind' = ops.mind_descriptor(., mind_radius, mind_dilation) of
+    both images, 'intensity' = the images themselves, or a pair (moving features, fixed features) of [B,C,*vol] tensors,
+    1 <= C <= 16.  mask: float weights that broadcast to [B,1,*vol], or None.  levels: pooling strides, integers >= 1, applied
+    in order; iters: iterations per level, an int or one per level (a level with 0 iterations is skipped).
+
+    A level of stride s works on ops.pool_features(., s) of both feature sets (and of the mask, as a 1-channel feature; s = 1
+    takes them as they are), the moving side packed once.  Its field is u = ops.resize_linear(previous, vol // s,
+    mult=s_prev / s) -- the first level starts from `flow` with s_prev = 1; a field that already has the level's shape and
+    stride is taken as it is -- and each iteration is
+
+        d, L, _ = ops.demons_force(h, Lf, u, Lk, max_step)        history[row] = L   (the energy at the u the force saw)
+        d = ops.gaussian_smooth(d, sigma_fluid)                    skipped when sigma_fluid == 0
+        diffeomorphic:  d = d * 2^-exp_steps, then exp_steps times d = ops.vecint_step(d)      (d <- exp(d))
+        u = ops.compose_flows(d, u)     'compose': u <- d + u(x + d), the correction applied in the fixed image's frame
+            or u + d                    'add'
+        u = ops.gaussian_smooth(u, sigma_diffusion)                skipped when sigma_diffusion == 0
+
+    The sigmas and max_step are in the level's own voxels.  After the last level the field goes to `vol` with
+    ops.resize_linear(u, vol, mult=s_last), skipped when s_last == 1.  history: a device tensor [sum iters]; energy0 and
+    energy: ops.warp_ssd on the full-resolution features (and the mask) at the input flow and at the result, as device
+    scalars; warped = ops.warp(moving, flow).  With iters = 0 everywhere `flow` is the input bit for bit (or zeros).  Nothing
+    syncs with the host and nothing records a gradient.
+
+    Where the field lands: when s does not divide an extent the pooled grid's centre sits (n mod s) / 2 fine voxels from the
+    fine centre, and the stride-s pooling puts coarse sample i at fine coordinate s i + (s - 1) / 2 while ops.resize_linear
+    aligns corners: an approximation the later levels absorb (affine_init's and convex_init's).
+
+    Where the stage sits: after affine_init and convex_init, composed as refine_flow's docstring shows -- aff =
+    affine_init(mov, fix); cv = convex_init(aff['warped'], fix); flow0 = ops.compose_flows(cv['flow'], aff['flow']);
+    demons_flow(mov, fix, flow0) -- or on a network's flow with levels=(1,).
+
+    Out of scope: symmetric (ESM) forces that average in the gradient of the fixed features, a gradient of
+    ops.gaussian_smooth, and the wiring into register_volume / register_pair_refined.
+
+    ValueError before any launch on everything affine_init refuses for its images, features, mask, levels and iters, a flow
+    that is not [B,nd,*vol] fp32, an unknown `update`, a `diffeomorphic` that is not a bool, an exp_steps that is not an
+    integer in 0..8, a max_step that is not finite and > 0, a sigma that is negative or not finite and a sigma whose radius
+    ceil(3 sigma) exceeds ops.GAUSS_MAX_RADIUS."""
+    what = "demons_flow"
+    if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
+            or tuple(moving.shape) != tuple(fixed.shape):
+        raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
+    nd = moving.dim() - 2
+    B, vol = int(moving.shape[0]), tuple(int(n) for n in moving.shape[2:])
+    if update not in ('add', 'compose'):
+        raise ValueError("%s: update must be 'add' or 'compose', got %r" % (what, update))
+    if not isinstance(diffeomorphic, bool):
+        raise ValueError("%s: diffeomorphic must be a bool, got %r" % (what, diffeomorphic))
+    if isinstance(exp_steps, bool) or not isinstance(exp_steps, int) or not 0 <= exp_steps <= 8:
+        raise ValueError("%s: exp_steps must be an integer in 0..8, got %r" % (what, exp_steps))
+    if not _finite_number(max_step) or not max_step > 0:
+        raise ValueError("%s: max_step must be a finite number > 0, got %r" % (what, max_step))
+    for name, sg in (("sigma_fluid", sigma_fluid), ("sigma_diffusion", sigma_diffusion)):
+        if not _finite_number(sg) or sg < 0:
+            raise ValueError("%s: %s must be a finite number >= 0, got %r" % (what, name, sg))
+        ops.gauss_radii(sg, 3.0, nd, "%s: %s" % (what, name))
+    try:
+        levels = tuple(levels)
+    except TypeError:
+        raise ValueError("%s: levels must be a sequence of integers >= 1, got %r" % (what, levels)) from None
+    if not levels or any(isinstance(s, bool) or not isinstance(s, int) or s < 1 for s in levels):
+        raise ValueError("%s: levels must be a non-empty sequence of integers >= 1, got %r" % (what, levels))
+    for s in levels:
+        if min(n // s for n in vol) < 2:
+            raise ValueError("%s: every extent of a level must be >= 2, got %s // %d" % (what, vol, s))
+    if isinstance(iters, int) and not isinstance(iters, bool):
+        iters = (iters,) * len(levels)
+    try:
+        iters = tuple(iters)
+    except TypeError:
+        raise ValueError("%s: iters must be an integer >= 0 or one per level, got %r" % (what, iters)) from None
+    if len(iters) != len(levels) or any(isinstance(n, bool) or not isinstance(n, int) or n < 0 for n in iters):
+        raise ValueError("%s: iters must be an integer >= 0 or one per level (%d), got %r" % (what, len(levels), iters))
+    if flow is not None and (not torch.is_tensor(flow) or tuple(flow.shape) != (B, nd) + vol or flow.dtype != torch.float32):
+        raise ValueError("%s: flow must be an fp32 tensor [B,%d,*vol] = %s" % (what, nd, (B, nd) + vol))
+    _check_features(what, features, moving, nd, B, vol)
+    if mask is not None:
+        if not torch.is_tensor(mask):
+            raise ValueError("%s: mask must be a tensor" % what)
+        try:
+            mask = mask.expand((B, 1) + vol)
+        except RuntimeError:
+            raise ValueError("%s: mask %s does not broadcast to %s" % (what, tuple(mask.shape), (B, 1) + vol)) from None
+    Mm, Mf = _resolve_features(features, moving, fixed, mind_radius, mind_dilation)
+    full = ops.pack_features(Mm)
+    dev = full.packed.device
+    if mask is not None:
+        mask = mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+    flow0 = ops.zeros((B, nd) + vol, dev) if flow is None else flow.detach().to(dev).clone(memory_format=torch.contiguous_format)
+    history = torch.empty((sum(iters),), device=dev, dtype=torch.float32)
+    energy0 = ops.warp_ssd(full, Mf, flow0, mask)
+    u, s_prev, row = flow0, 1, 0
+    for s, n in zip(levels, iters):
+        if n == 0:
+            continue
+        if s == 1:
+            h, Lf, Lk = full, Mf, mask
+        else:
+            h, Lf = ops.pack_features(ops.pool_features(Mm, s)), ops.pool_features(Mf, s)
+            Lk = None if mask is None else ops.pool_features(mask, s)
+        lvol = tuple(m // s for m in vol)
+        if s != s_prev or tuple(u.shape[2:]) != lvol:
+            u = ops.resize_linear(u, lvol, mult=float(s_prev) / float(s))
+        for k in range(n):
+            d, L, _ = ops.demons_force(h, Lf, u, Lk, max_step)
+            history[row + k] = L
+            if sigma_fluid > 0:
+                d = ops.gaussian_smooth(d, sigma_fluid)
+            if diffeomorphic:
+                d = d * (2.0 ** -exp_steps)
+                for _ in range(exp_steps):
+                    d = ops.vecint_step(d)
+            u = ops.compose_flows(d, u) if update == 'compose' else u + d
+            if sigma_diffusion > 0:
+                u = ops.gaussian_smooth(u, sigma_diffusion)
+        row += n
+        s_prev = s
+    if s_prev != 1:
+        u = ops.resize_linear(u, vol, mult=float(s_prev))
+    return dict(flow=u, warped=ops.warp(moving, u), history=history, energy0=energy0, energy=ops.warp_ssd(full, Mf, u, mask))
+
+
 def _refine_kwargs(refine, what):
     if not isinstance(refine, dict):
         raise ValueError("%s: refine must be None or a dict of refine_flow keywords, got %s" % (what, type(refine).__name__))

@@ -7,6 +7,7 @@ eager-PyTorch fallback: a non-CUDA tensor raises.
 import collections
 import ctypes
 import functools
+import math
 import os
 
 import numpy as np
@@ -3376,6 +3377,114 @@ def box_smooth_flow(disp):
     out = torch.empty_like(disp)
     check(lib().dfmir_dsearch_smooth(nd, _p(disp), _p(out), B, D, H, W, _st()))
     return out
+
+
+GAUSS_MAX_RADIUS = 16      # DFMIR_GAUSS_MAX_RADIUS (include/dfmir_hip.h): the halo dfmir_amd/csrc/gauss.hip sizes its LDS tile for
+
+
+def gauss_radii(sigma, truncate, nd, what):
+    """((sigma_a) per axis as floats, (r_a) per axis) of a gaussian_smooth call after the checks on `sigma` and `truncate`
+    (ValueError: nothing is launched): r_a = ceil(truncate * sigma_a) <= GAUSS_MAX_RADIUS."""
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float)) and 0.0 <= v < float('inf')
+    if number(sigma):
+        sig = (float(sigma),) * nd
+    else:
+        try:
+            sig = tuple(sigma)
+        except TypeError:
+            sig = None
+        if sig is None or len(sig) != nd or not all(number(v) for v in sig):
+            raise ValueError("%s: sigma must be a finite number >= 0 or %d of them, got %r" % (what, nd, sigma))
+        sig = tuple(float(v) for v in sig)
+    if isinstance(truncate, bool) or not isinstance(truncate, (int, float)) or not 0.0 < truncate < float('inf'):
+        raise ValueError("%s: truncate must be a finite number > 0, got %r" % (what, truncate))
+    radii = tuple(int(min(math.ceil(float(truncate) * s), GAUSS_MAX_RADIUS + 1)) for s in sig)
+    if max(radii) > GAUSS_MAX_RADIUS:
+        raise ValueError("%s: the radius ceil(truncate * sigma) must be <= GAUSS_MAX_RADIUS = %d, got sigma %r, truncate %r"
+                         % (what, GAUSS_MAX_RADIUS, sigma, truncate))
+    return sig, radii
+
+
+@torch.no_grad()
+def gaussian_smooth(x, sigma, truncate=3.0):
+    """Gaussian smoothing of a field or a feature volume (build-defined): x [B,C,*vol] fp32, 2-D or 3-D, any C >= 1; sigma: a
+    finite float >= 0 in voxels, or nd of them in axis order (z,) y, x; truncate: finite and > 0.  Per axis a,
+    r_a = ceil(truncate * sigma_a) and w_a[k] = exp(-k^2 / (2 sigma_a^2)) for |k| <= r_a (formed in double, rounded to fp32);
+    the filter is separable and RENORMALISED AT THE FACES,
+
+        out(i) = sum_k w[k] in(i + k) [i + k inside] / sum_k w[k] [i + k inside]                  along each axis
+
+    so a constant comes back constant -- ops.box_smooth_flow's convention, and the reason the filter is not zero padding.
+    sigma_a == 0 leaves that axis alone, and with every sigma 0 the result equals the input bit for bit.  An extent smaller
+    than the window is legal (the whole axis then lies inside every window); r_a <= GAUSS_MAX_RADIUS = 16, what the kernel's
+    LDS tile is sized for.  2-D is one launch (tile and halo in LDS, both axes filtered there); 3-D is the (y, x) pass per
+    plane and a z pass, two reads and two writes of the tensor (dfmir_amd/csrc/gauss.hip).  Bit-identical from run to run;
+    nothing syncs with the host.  No gradient, in the manner of ops.box_smooth_flow: an input that requires grad raises.
+    ValueError before any launch on a rank other than 4 or 5, C < 1, an extent < 2, a dtype other than fp32, 2^31 or more
+    elements, a tensor that requires grad, a sigma that is negative, not finite or not 1 or nd numbers, a truncate that is
+    not finite and > 0 and a radius above GAUSS_MAX_RADIUS; a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "gaussian_smooth"
+    if not torch.is_tensor(x) or x.dim() not in (4, 5):
+        raise ValueError("%s: x must be a [B,C,H,W] or [B,C,D,H,W] tensor, got %s"
+                         % (what, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+    nd = x.dim() - 2
+    if x.shape[0] < 1 or x.shape[1] < 1 or min(x.shape[2:]) < 2:
+        raise ValueError("%s: x needs B >= 1, C >= 1 and every extent >= 2, got %s" % (what, tuple(x.shape)))
+    if x.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (x is %s)" % (what, x.dtype))
+    if x.numel() >= 2 ** 31:
+        raise ValueError("%s: x %s has 2^31 or more elements" % (what, tuple(x.shape)))
+    if x.requires_grad:
+        raise ValueError("%s: x requires grad, but the op has no gradient (detach it)" % what)
+    sig, radii = gauss_radii(sigma, truncate, nd, what)
+    _need(x)
+    x = _c(x)
+    D, H, W = (int(n) for n in (x.shape[2:] if nd == 3 else (1,) + tuple(x.shape[2:])))
+    sz, sy, sx = sig if nd == 3 else (0.0,) + sig
+    out = torch.empty_like(x)
+    two = nd == 3 and radii[0] > 0 and max(radii[1:]) > 0
+    tmp = torch.empty_like(x) if two else None
+    check(lib().dfmir_gauss_smooth(nd, _p(x), _p(out), _p(tmp), int(x.shape[0]) * int(x.shape[1]), D, H, W, sz, sy, sx,
+                                   float(truncate), _st()))
+    return out
+
+
+@torch.no_grad()
+def demons_force(mov, fix, flow, mask=None, max_step=2.0):
+    """The demons force (build-defined): a per-voxel Gauss-Newton step on the feature SSD that ops.warp_ssd and
+    ops.affine_ssd_system use.  mov: a [B,C,*vol] feature tensor (packed per call) or the handle of ops.pack_features(mov);
+    fix, flow, mask: exactly as ops.warp_ssd takes them (1 <= C <= 16, 2-D or 3-D, flow [B,nd,*vol] in voxels, mask float
+    weights that broadcast to [B,1,*vol]); max_step: finite and > 0, in voxels.  Per voxel x, with p = x + flow(x):
+
+        m_c = M_c(p)        J_c = the derivative of the interpolant in the cell floor() selects: corner differences, padded
+                            corners as zeros (warp_ssd's)                   e_c = m_c - F_c(x)
+        s = (1/C) sum_c e_c^2          g = (1/C) sum_c e_c J_c  (nd)          H = (1/C) sum_c J_c J_c^T  (nd x nd)
+        d(x) = -(H + (s / max_step^2) I)^-1 g
+
+    With C = 1 this is Thirion's force with Vercauteren's step bound, -e J / (|J|^2 + e^2 / max_step^2); for any C
+    |d(x)| <= max_step / 2.  Where g is exactly zero (that includes points with no corner inside the volume) d = +0 without a
+    division; elsewhere the system is solved in closed form, and if a component is not finite the vector is 0.  A mask weight
+    <= 0 gives d(x) = 0; a positive weight leaves d as it is and weights only the energy.  Returns (d [B,nd,*vol], L, L_b [B]):
+    L and L_b are the (masked) mean of s with warp_ssd's reduction, as device tensors.  One fused gather pass, no warped
+    tensor; everything is bit-identical from run to run; nothing syncs with the host.  No gradient: a `mov`, `fix`, `flow` or
+    `mask` that requires grad raises.  ValueError before any launch on what ops.warp_ssd refuses and on a max_step that is
+    not finite and > 0; a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "demons_force"
+    if isinstance(max_step, bool) or not isinstance(max_step, (int, float)) or not 0.0 < max_step < float('inf'):
+        raise ValueError("%s: max_step must be a finite number > 0, got %r" % (what, max_step))
+    if not isinstance(mov, PackedFeatures) and not torch.is_tensor(mov):
+        raise ValueError("%s: mov must be a [B,C,*vol] tensor or a handle of ops.pack_features" % what)
+    if torch.is_tensor(flow) and flow.requires_grad:
+        raise ValueError("%s: flow requires grad, but the op has no gradient (detach it)" % what)
+    geom, h, fix, flow_c, mask = _warp_ssd_args(mov, fix, flow, mask, what)
+    nd, B, C, D, H, W = geom
+    ws = torch.empty(int(lib().dfmir_demons_ws_floats(nd, B, C, D, H, W)), device=flow_c.device, dtype=torch.float32)
+    out = torch.empty(B + 1, device=flow_c.device, dtype=torch.float32)
+    d = torch.empty_like(flow_c)
+    check(lib().dfmir_demons_force(nd, _p(h.packed), _p(fix), _p(flow_c), _p(mask), _p(ws), _p(out), _p(out[B:]), _p(d),
+                                   float(max_step), B, C, D, H, W, _st()))
+    return d, out[B].clone(), out[:B].clone()
 
 
 LANDMARK_PENALTIES = {'l2': 0, 'tre': 1}

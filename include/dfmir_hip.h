@@ -805,6 +805,50 @@ int dfmir_affine_system(int nd, const float* Mp, const float* F, const float* th
 int dfmir_affine_lm_step(int nd, const double* Lb, const double* g, const double* H, float* theta_acc, float* trial,
                          double* state, double* hist, int B, int k, int translation, double mu_up, double mu_down,
                          void* stream);
+/* Gaussian smoothing of fields and feature volumes (build-defined: the reference has no such filter).  in, out: [planes][(D)]
+ * [H][W] fp32, planes = B * C, nd = 2 or 3 (D and sz are not read when nd == 2); sigma (sz, sy, sx) in voxels, finite and >= 0;
+ * truncate finite and > 0.  Per axis a:  r_a = ceil(truncate * sigma_a) <= DFMIR_GAUSS_MAX_RADIUS,  w_a[k] = exp(-k^2 / (2
+ * sigma_a^2)) for |k| <= r_a, formed in double and rounded to fp32.  The filter is separable and RENORMALISED AT THE FACES:
+ *   out(i) = sum_k w[k] in(i + k) [i + k inside] / sum_k w[k] [i + k inside]        along each axis in turn (x, y, then z)
+ * so a constant comes back constant (dfmir_dsearch_smooth's convention; not zero padding).  A sum starts from its centre
+ * term and adds the pairs w[k] (in(i - k) + in(i + k)), k = 1 .. r_a; the divisor is formed in the kernel.  sigma_a == 0 leaves
+ * axis a alone bit for bit, and with every sigma 0 out is a copy of in.  An extent smaller than the window is legal: the whole
+ * axis then lies inside every window.  2-D: ONE launch, the tile and its halo filtered along both axes in LDS.  3-D: the (y, x)
+ * pass per plane into tmp, then the z pass as the same kernel on the view [planes][D][H W]: two reads and two writes of the
+ * tensor (one of each when sz == 0 or sy == sx == 0).  tmp: planes * D * H * W floats, read only when both passes run (may be
+ * NULL otherwise); in, out and tmp must not alias.  16-byte accesses where the row length (W; for the z pass H W) is a
+ * multiple of 4 and the pointers are aligned.  Every output is written once from sums in a fixed order: bit-identical from
+ * run to run.  Refused ("invalid argument", nothing is launched): nd outside {2, 3}, planes < 1, an extent < 2, 2^31 or more
+ * elements, a sigma that is negative or not finite, a truncate that is not finite and > 0, a radius above
+ * DFMIR_GAUSS_MAX_RADIUS, a NULL or aliased pointer.  Nothing syncs, allocates or keeps state. */
+#define DFMIR_GAUSS_MAX_RADIUS 16     /* a 32 x 64 tile with a halo of 16 on every side: 24 KiB of LDS, and 16 KiB for the x pass */
+int dfmir_gauss_smooth(int nd, const float* in, float* out, float* tmp, long long planes, int D, int H, int W, double sz,
+                       double sy, double sx, double truncate, void* stream);
+/* The demons force: a per-voxel Gauss-Newton step on the warped-feature SSD (build-defined: the reference has no such
+ * solver).  Mp, F, phi and mask are dfmir_warp_ssd_fwd's: Mp the packed moving features (dfmir_warp_ssd_pack), F [B][C][S], 1 <=
+ * C <= 16, phi [B][nd][S] in voxels, mask [B][S] or NULL.  Per voxel x, with p = x + phi(x), sampled exactly as
+ * dfmir_warp_ssd_fwd samples (the same cell, guards and corner differences):
+ *   m_c = M_c(p),  J_c = the derivative of the interpolant in the cell floor() selects (nd),  e_c = m_c - F_c(x)
+ *   s = (1/C) sum_c e_c^2        g = (1/C) sum_c e_c J_c  (nd)        H = (1/C) sum_c J_c J_c^T  (nd x nd)
+ *   d(x) = -(H + (s / max_step^2) I)^-1 g          [B][nd][S], the update in voxels, channel order (z,) y, x
+ * With C = 1 this is Thirion's force with Vercauteren's step bound, -e J / (|J|^2 + e^2 / max_step^2); for any C |d(x)| <=
+ * max_step / 2 (H = K^T K, g = K^T e' with K = J / sqrt C, e' = e / sqrt C, and ||(K^T K + a I)^-1 K^T|| <= 1 / (2 sqrt a)).
+ * Where g is exactly 0 -- that includes points with no corner inside the volume -- d = +0 without a division; elsewhere s > 0
+ * and the matrix is positive definite: the three sums are added in double (each product of two floats is exact there) and the system is solved in closed form by
+ * its L D L^T factors in double -- near convergence s / max_step^2 falls below eps32 |J|^2, where fp32 sums or the adjugate are off by
+ * the order of |d| --, and if a component of
+ * the result is not finite the vector is 0.  A mask weight <= 0 gives d(x) = 0; a positive weight leaves d as it is and weights
+ * only the energy.  per_sample[b] = L_b and loss[0] = L: the (masked) mean of s with dfmir_warp_ssd_fwd's reduction (double
+ * slots per workgroup, added by one workgroup in a fixed order; 0 for an empty mask).  ONE gather pass: the cell is formed once
+ * per voxel, the channels pass in groups of four from the packed copy; no warped tensor, no e tensor, no atomics; every output
+ * is bit-identical from run to run.  16-byte accesses of phi, F and d where W % 4 == 0 and the three are 16-byte aligned.
+ * Refused ("invalid argument", nothing is launched): what dfmir_warp_ssd_fwd refuses, a NULL pointer other than mask, d == phi,
+ * a max_step that is not finite and > 0.  ws: dfmir_demons_ws_floats floats (-1 for a refused shape), 8-byte aligned, need not
+ * be zeroed.  Nothing syncs, allocates or keeps state. */
+long long dfmir_demons_ws_floats(int nd, int B, int C, int D, int H, int W);
+int dfmir_demons_force(int nd, const float* Mp, const float* F, const float* phi, const float* mask, float* ws,
+                       float* per_sample, float* loss, float* d, float max_step, int B, int C, int D, int H, int W,
+                       void* stream);
 /* Landmark (keypoint) registration error of a displacement field (build-defined: the reference has no landmark code).
  * flow u: [B][nd][(D)][H][W] fp32, nd = 2 or 3 (D is not read when nd == 2); channel a displaces axis a in voxels, in the
  * order (z,) y, x, exactly as the warp kernels read a flow: warped(x) = moving(x + u(x)) with x in the fixed image's grid,
