@@ -11,10 +11,8 @@
 //                      + 2 sum_{a<b} (U_ab(p-e_a-e_b) - U_ab(p-e_a+e_b) - U_ab(p+e_a-e_b) + U_ab(p+e_a+e_b)) / (4 h_a h_b) ]
 //   with U = the derivative value extended by 0 outside Omega (the exact adjoint).
 //
-// One workgroup = one BEND_TY x BEND_TX tile of (y, x) of one plane (b, c) and, in 3-D, one chunk of BEND_ZC planes along z
-// that it marches through; wave w owns two rows of the tile, its lanes run along x (every LDS access is stride 1 over the
-// lanes).  The next plane of u travels global -> registers -> LDS while the current one is computed (BendStage: 16-byte
-// loads of the 64 interior columns when W % 4 == 0, scalars otherwise; zeros outside the volume).
+// Tiles, z chunks and the staging of a plane of u are those of stencil_tile.h, one (b, c) plane per workgroup and zeros
+// outside the volume.
 //   bend_fwd_k<ND3, VEC>  u with a halo of 1, three open planes; e per voxel (0 outside Omega) added in double per thread,
 //                         one double slot per workgroup.  df_slot_mean_k (one workgroup) adds the slots in a fixed order.
 //   bend_bwd_k<ND3, VEC>  gather form, no atomics, no derivative volume in HBM: u with a halo of 2 (three open planes); the
@@ -23,15 +21,11 @@
 //                         voxel, border or interior, collects its adjoint stencil from them with the one expression.
 // bend_dz / bend_dp are the ONE place the second differences are formed, for both directions.  Nothing syncs with the
 // host (gout is read on the device), allocates or keeps state; loss and gradient are bit-identical from run to run.
-#include "common.h"
+#include "stencil_tile.h"
+
+using namespace stencil;
 
 namespace {
-
-constexpr int BEND_T = 256;                  // threads per workgroup: 4 waves x 64 lanes
-constexpr int BEND_TY = 8, BEND_TX = 64;     // tile of (y, x): two rows per wave, one column per lane
-constexpr int BEND_ZC = 16;                  // planes of a z chunk (3-D)
-constexpr int BEND_RS = 72;                  // floats per LDS row of u: column x0 sits at BEND_X0 (16-byte aligned)
-constexpr int BEND_X0 = 4;
 
 struct BendGeom {
   int D, H, W;                               // D == 1: a 2-D field
@@ -39,133 +33,64 @@ struct BendGeom {
   float czz, cyy, cxx, czy, czx, cyx;        // 1 / h_a^2 and 1 / (4 h_a h_b)
 };
 
-// One plane of u around a tile, with HALO voxels per side: fetch() brings it into registers (zeros outside the volume),
-// commit() stores it to an LDS plane of (BEND_TY + 2 HALO) rows of BEND_RS floats.
-template <int HALO, bool VEC>
-struct BendStage {
-  static constexpr int ROWS = BEND_TY + 2 * HALO, COLS = BEND_TX + 2 * HALO, QPR = BEND_TX / 4;
-  static constexpr int NS = VEC ? 1 : (ROWS * COLS + BEND_T - 1) / BEND_T;
-  static_assert(ROWS * QPR <= BEND_T && ROWS * 2 * HALO <= BEND_T, "one quad and one halo value per thread");
-  static_assert(BEND_X0 >= HALO && BEND_X0 + BEND_TX + HALO <= BEND_RS, "LDS row too short");
-  float4 q;
-  float s[NS];
-
-  __device__ __forceinline__ void fetch(const float* __restrict__ up, const BendGeom& g, int gz, int y0, int x0) {
-    const int tid = threadIdx.x;
-    const bool zin = gz >= 0 && gz < g.D;
-    const float* pl = up + (zin ? (long long)gz * g.H * g.W : 0LL);
-    if (VEC) {
-      q = make_float4(0.f, 0.f, 0.f, 0.f);
-      s[0] = 0.f;
-      if (tid < ROWS * QPR) {                      // the interior columns: x0 and W are multiples of 4
-        const int r = tid / QPR, gy = y0 - HALO + r, gx = x0 + 4 * (tid % QPR);
-        if (zin && gy >= 0 && gy < g.H && gx < g.W) q = *reinterpret_cast<const float4*>(pl + (long long)gy * g.W + gx);
-      }
-      if (tid < ROWS * 2 * HALO) {                 // the halo columns
-        const int r = tid / (2 * HALO), j = tid % (2 * HALO), gy = y0 - HALO + r;
-        const int gx = j < HALO ? x0 - HALO + j : x0 + BEND_TX + j - HALO;
-        if (zin && gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) s[0] = pl[(long long)gy * g.W + gx];
-      }
-    } else {
-#pragma unroll
-      for (int n = 0; n < NS; ++n) {
-        const int i = tid + n * BEND_T, r = i / COLS, gy = y0 - HALO + r, gx = x0 - HALO + i - r * COLS;
-        s[n] = 0.f;
-        if (i < ROWS * COLS && zin && gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) s[n] = pl[(long long)gy * g.W + gx];
-      }
-    }
-  }
-
-  __device__ __forceinline__ void commit(float* __restrict__ dst) const {
-    const int tid = threadIdx.x;
-    if (VEC) {
-      if (tid < ROWS * QPR)
-        *reinterpret_cast<float4*>(dst + (tid / QPR) * BEND_RS + BEND_X0 + 4 * (tid % QPR)) = q;
-      if (tid < ROWS * 2 * HALO) {
-        const int r = tid / (2 * HALO), j = tid % (2 * HALO);
-        dst[r * BEND_RS + (j < HALO ? BEND_X0 - HALO + j : BEND_X0 + BEND_TX + j - HALO)] = s[0];
-      }
-    } else {
-#pragma unroll
-      for (int n = 0; n < NS; ++n) {
-        const int i = tid + n * BEND_T, r = i / COLS;
-        if (i < ROWS * COLS) dst[r * BEND_RS + BEND_X0 - HALO + i - r * COLS] = s[n];
-      }
-    }
-  }
-};
-
-// The second differences at one voxel.  A, B, C point at the voxel in the staged planes z - 1, z, z + 1 (rows of BEND_RS).
+// The second differences at one voxel.  A, B, C point at the voxel in the staged planes z - 1, z, z + 1 (rows of RS).
 struct BendDz { float zz, zy, zx; };
 struct BendDp { float yy, xx, yx; };
 __device__ __forceinline__ BendDz bend_dz(const float* A, const float* B, const float* C, const BendGeom& g) {
   BendDz d;
   d.zz = (C[0] - 2.f * B[0] + A[0]) * g.czz;
-  d.zy = (C[BEND_RS] - C[-BEND_RS] - A[BEND_RS] + A[-BEND_RS]) * g.czy;
+  d.zy = (C[RS] - C[-RS] - A[RS] + A[-RS]) * g.czy;
   d.zx = (C[1] - C[-1] - A[1] + A[-1]) * g.czx;
   return d;
 }
 __device__ __forceinline__ BendDp bend_dp(const float* B, const BendGeom& g) {
   BendDp d;
-  d.yy = (B[BEND_RS] - 2.f * B[0] + B[-BEND_RS]) * g.cyy;
+  d.yy = (B[RS] - 2.f * B[0] + B[-RS]) * g.cyy;
   d.xx = (B[1] - 2.f * B[0] + B[-1]) * g.cxx;
-  d.yx = (B[BEND_RS + 1] - B[BEND_RS - 1] - B[-BEND_RS + 1] + B[-BEND_RS - 1]) * g.cyx;
+  d.yx = (B[RS + 1] - B[RS - 1] - B[-RS + 1] + B[-RS - 1]) * g.cyx;
   return d;
-}
-
-// (plane, z chunk, tile origin) of a workgroup
-struct BendTile { long long plane; int z0, z1, y0, x0; };
-__device__ __forceinline__ BendTile bend_tile(const BendGeom& g) {
-  BendTile t;
-  unsigned b = blockIdx.x;
-  t.x0 = (int)(b % (unsigned)g.ntx) * BEND_TX; b /= (unsigned)g.ntx;
-  t.y0 = (int)(b % (unsigned)g.nty) * BEND_TY; b /= (unsigned)g.nty;
-  t.z0 = (int)(b % (unsigned)g.nzc) * BEND_ZC;
-  t.z1 = t.z0 + BEND_ZC < g.D ? t.z0 + BEND_ZC : g.D;
-  t.plane = b / (unsigned)g.nzc;
-  return t;
 }
 
 // ------------------------------------------------------------------------------------------------ forward
 template <bool ND3, bool VEC>
-__global__ __launch_bounds__(BEND_T) void bend_fwd_k(const float* __restrict__ u, BendGeom g, double* __restrict__ part) {
-  constexpr int ROWS = BEND_TY + 2;
-  __shared__ __attribute__((aligned(16))) float su[ND3 ? 3 : 1][ROWS * BEND_RS];
-  __shared__ double red[BEND_T / 64];
-  const BendTile t = bend_tile(g);
+__global__ __launch_bounds__(NT) void bend_fwd_k(const float* __restrict__ u, BendGeom g, double* __restrict__ part) {
+  constexpr int ROWS = TY + 2;
+  __shared__ __attribute__((aligned(16))) float su[ND3 ? 3 : 1][ROWS * RS];
+  __shared__ double red[NT / 64];
+  const Tile t = tile_of(g, ZC);
   const float* up = u + t.plane * ((long long)g.D * g.H * g.W);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int x = t.x0 + lane;
   const bool xin = x >= 1 && x <= g.W - 2;
-  const int c0 = (2 * w + 1) * BEND_RS + BEND_X0 + lane;        // the thread's first voxel in a staged plane
-  BendStage<1, VEC> st;
+  const int c0 = (2 * w + 1) * RS + X0 + lane;                     // the thread's first voxel in a staged plane
+  Stage<1, 1, VEC> st;
   double acc = 0.0;
   if constexpr (!ND3) {
-    st.fetch(up, g, 0, t.y0, t.x0);
+    st.fetch(up, g, 0, 0, t.y0, t.x0);
     st.commit(su[0]);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int y = t.y0 + 2 * w + j;
-      const BendDp p = bend_dp(su[0] + c0 + j * BEND_RS, g);
+      const BendDp p = bend_dp(su[0] + c0 + j * RS, g);
       const float e = p.yy * p.yy + p.xx * p.xx + 2.f * (p.yx * p.yx);
       acc += (double)((xin && y >= 1 && y <= g.H - 2) ? e : 0.f);
     }
   } else {
     int ia = 0, ib = 1, ic = 2;                                  // slots of the planes z - 1, z, z + 1
-    st.fetch(up, g, t.z0 - 1, t.y0, t.x0);
+    st.fetch(up, g, 0, t.z0 - 1, t.y0, t.x0);
     st.commit(su[ia]);
-    st.fetch(up, g, t.z0, t.y0, t.x0);
+    st.fetch(up, g, 0, t.z0, t.y0, t.x0);
     st.commit(su[ib]);
-    st.fetch(up, g, t.z0 + 1, t.y0, t.x0);
+    st.fetch(up, g, 0, t.z0 + 1, t.y0, t.x0);
     for (int z = t.z0; z < t.z1; ++z) {
       st.commit(su[ic]);
       __syncthreads();
-      if (z + 1 < t.z1) st.fetch(up, g, z + 2, t.y0, t.x0);     // in flight while this plane is computed
+      if (z + 1 < t.z1) st.fetch(up, g, 0, z + 2, t.y0, t.x0);     // in flight while this plane is computed
       const bool zin = z >= 1 && z <= g.D - 2;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int y = t.y0 + 2 * w + j, c = c0 + j * BEND_RS;
+        const int y = t.y0 + 2 * w + j, c = c0 + j * RS;
         const BendDz q = bend_dz(su[ia] + c, su[ib] + c, su[ic] + c, g);
         const BendDp p = bend_dp(su[ib] + c, g);
         const float e = q.zz * q.zz + p.yy * p.yy + p.xx * p.xx + 2.f * (q.zy * q.zy + q.zx * q.zx + p.yx * p.yx);
@@ -175,35 +100,35 @@ __global__ __launch_bounds__(BEND_T) void bend_fwd_k(const float* __restrict__ u
       const int o = ia; ia = ib; ib = ic; ic = o;
     }
   }
-  acc = block_sum_ordered<BEND_T>(acc, red);
+  acc = block_sum_ordered<NT>(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 // ------------------------------------------------------------------------------------------------ backward
 // du = gout * k * [ sum_a c_aa (U_aa(-) - 2 U_aa + U_aa(+)) + 2 sum_{a<b} c_ab (U_ab(--) - U_ab(-+) - U_ab(+-) + U_ab(++)) ],
-// k = 2 / N.  The derivative planes hold (BEND_TY + 2) x (BEND_TX + 2) values (tile + 1), rows of DC floats.
+// k = 2 / N.  The derivative planes hold (TY + 2) x (TX + 2) values (tile + 1), rows of DC floats.
 template <bool ND3, bool VEC>
-__global__ __launch_bounds__(BEND_T) void bend_bwd_k(const float* __restrict__ u, const float* __restrict__ gout, float k,
-                                                     BendGeom g, float* __restrict__ du) {
-  constexpr int UR = BEND_TY + 4, DR = BEND_TY + 2, DC = BEND_TX + 2, DN = DR * DC;
-  __shared__ __attribute__((aligned(16))) float su[ND3 ? 3 : 1][UR * BEND_RS];
+__global__ __launch_bounds__(NT) void bend_bwd_k(const float* __restrict__ u, const float* __restrict__ gout, float k,
+                                                 BendGeom g, float* __restrict__ du) {
+  constexpr int UR = TY + 4, DR = TY + 2, DC = TX + 2, DN = DR * DC;
+  __shared__ __attribute__((aligned(16))) float su[ND3 ? 3 : 1][UR * RS];
   __shared__ float sz[ND3 ? 3 : 1][ND3 ? 3 : 1][ND3 ? DN : 1];   // u_zz, u_zy, u_zx of three planes (3-D)
   __shared__ float sp[3][DN];                                    // u_yy, u_xx, u_yx of the output plane
-  const BendTile t = bend_tile(g);
+  const Tile t = tile_of(g, ZC);
   const long long vol = (long long)g.D * g.H * g.W;
   const float* up = u + t.plane * vol;
   float* dp = du + t.plane * vol;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int x = t.x0 + lane;
   const float s = gout[0] * k;
-  BendStage<2, VEC> st;
+  Stage<1, 2, VEC> st;
 
   // u_yy, u_xx, u_yx of plane z (staged in `pl`) over tile + 1, times the Omega indicator
   auto in_plane = [&](const float* pl, bool zin) {
-    for (int i = tid; i < DN; i += BEND_T) {
+    for (int i = tid; i < DN; i += NT) {
       const int ly = i / DC, lx = i - ly * DC, gy = t.y0 - 1 + ly, gx = t.x0 - 1 + lx;
       const bool in = zin && gy >= 1 && gy <= g.H - 2 && gx >= 1 && gx <= g.W - 2;
-      const BendDp p = bend_dp(pl + (ly + 1) * BEND_RS + BEND_X0 - 1 + lx, g);
+      const BendDp p = bend_dp(pl + (ly + 1) * RS + X0 - 1 + lx, g);
       sp[0][i] = in ? p.yy : 0.f;
       sp[1][i] = in ? p.xx : 0.f;
       sp[2][i] = in ? p.yx : 0.f;
@@ -216,7 +141,7 @@ __global__ __launch_bounds__(BEND_T) void bend_bwd_k(const float* __restrict__ u
   };
 
   if constexpr (!ND3) {
-    st.fetch(up, g, 0, t.y0, t.x0);
+    st.fetch(up, g, 0, 0, t.y0, t.x0);
     st.commit(su[0]);
     __syncthreads();
     in_plane(su[0], true);
@@ -231,21 +156,21 @@ __global__ __launch_bounds__(BEND_T) void bend_bwd_k(const float* __restrict__ u
   } else {
     int ua = 0, ub = 1, uc = 2;              // u slots of the planes q - 1, q, q + 1
     int da = 0, db = 1, dc = 2;              // derivative slots of the planes q - 2, q - 1, q
-    st.fetch(up, g, t.z0 - 2, t.y0, t.x0);
+    st.fetch(up, g, 0, t.z0 - 2, t.y0, t.x0);
     st.commit(su[ua]);
-    st.fetch(up, g, t.z0 - 1, t.y0, t.x0);
+    st.fetch(up, g, 0, t.z0 - 1, t.y0, t.x0);
     st.commit(su[ub]);
-    st.fetch(up, g, t.z0, t.y0, t.x0);
+    st.fetch(up, g, 0, t.z0, t.y0, t.x0);
     for (int q = t.z0 - 1; q <= t.z1; ++q) {         // q: the derivative plane formed; the output plane is z = q - 1
       st.commit(su[uc]);
       __syncthreads();
-      if (q < t.z1) st.fetch(up, g, q + 2, t.y0, t.x0);
+      if (q < t.z1) st.fetch(up, g, 0, q + 2, t.y0, t.x0);
       const bool emit = q - 1 >= t.z0;
       const bool qin = q >= 1 && q <= g.D - 2;
-      for (int i = tid; i < DN; i += BEND_T) {
+      for (int i = tid; i < DN; i += NT) {
         const int ly = i / DC, lx = i - ly * DC, gy = t.y0 - 1 + ly, gx = t.x0 - 1 + lx;
         const bool in = qin && gy >= 1 && gy <= g.H - 2 && gx >= 1 && gx <= g.W - 2;
-        const int c = (ly + 1) * BEND_RS + BEND_X0 - 1 + lx;
+        const int c = (ly + 1) * RS + X0 - 1 + lx;
         const BendDz d = bend_dz(su[ua] + c, su[ub] + c, su[uc] + c, g);
         sz[dc][0][i] = in ? d.zz : 0.f;
         sz[dc][1][i] = in ? d.zy : 0.f;
@@ -283,7 +208,7 @@ bool bend_geom(int B, int C, int D, int H, int W, float hz, float hy, float hx, 
   if ((D > 1 && !bend_finite_pos(hz)) || !bend_finite_pos(hy) || !bend_finite_pos(hx)) return false;
   if ((long long)B * C * D * H * W >= (1LL << 31)) return false;
   g->D = D; g->H = H; g->W = W;
-  g->nzc = (D + BEND_ZC - 1) / BEND_ZC; g->nty = (H + BEND_TY - 1) / BEND_TY; g->ntx = (W + BEND_TX - 1) / BEND_TX;
+  set_tile_counts(g, ZC);
   const double z = D > 1 ? hz : 1.0, y = hy, x = hx;
   g->czz = (float)(1.0 / (z * z)); g->cyy = (float)(1.0 / (y * y)); g->cxx = (float)(1.0 / (x * x));
   g->czy = (float)(1.0 / (4.0 * z * y)); g->czx = (float)(1.0 / (4.0 * z * x)); g->cyx = (float)(1.0 / (4.0 * y * x));
@@ -291,8 +216,6 @@ bool bend_geom(int B, int C, int D, int H, int W, float hz, float hy, float hx, 
   *count = (double)*planes * (D > 1 ? D - 2 : 1) * (H - 2) * (W - 2);
   return true;
 }
-inline long long bend_nwg(const BendGeom& g, long long planes) { return planes * g.nzc * g.nty * g.ntx; }   // < 2^31
-inline bool bend_vec(const BendGeom& g, const void* p) { return g.W % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -301,7 +224,7 @@ extern "C" long long dfmir_bend_ws_floats(int B, int C, int D, int H, int W) {
   long long planes;
   double count;
   if (!bend_geom(B, C, D, H, W, 1.f, 1.f, 1.f, &g, &planes, &count)) return -1;
-  return 2 * bend_nwg(g, planes);
+  return 2 * planes * wg_per_plane(g);
 }
 
 extern "C" int dfmir_bend_fwd(const float* flow, float* ws, float* out, int B, int C, int D, int H, int W, float hz,
@@ -312,18 +235,18 @@ extern "C" int dfmir_bend_fwd(const float* flow, float* ws, float* out, int B, i
   DF_ARG_CHECK(flow && ws && out && (reinterpret_cast<uintptr_t>(ws) & 7) == 0 &&
                bend_geom(B, C, D, H, W, hz, hy, hx, &g, &planes, &count));
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nwg = (unsigned)bend_nwg(g, planes);
+  const unsigned nwg = (unsigned)(planes * wg_per_plane(g));      // < 2^31
   double* part = reinterpret_cast<double*>(ws);
-  const bool vec = bend_vec(g, flow);
+  const bool vec = vec_ok(g.W, flow);
   if (D > 1) {
-    if (vec) bend_fwd_k<true, true><<<nwg, BEND_T, 0, st>>>(flow, g, part);
-    else bend_fwd_k<true, false><<<nwg, BEND_T, 0, st>>>(flow, g, part);
+    if (vec) bend_fwd_k<true, true><<<nwg, NT, 0, st>>>(flow, g, part);
+    else bend_fwd_k<true, false><<<nwg, NT, 0, st>>>(flow, g, part);
   } else {
-    if (vec) bend_fwd_k<false, true><<<nwg, BEND_T, 0, st>>>(flow, g, part);
-    else bend_fwd_k<false, false><<<nwg, BEND_T, 0, st>>>(flow, g, part);
+    if (vec) bend_fwd_k<false, true><<<nwg, NT, 0, st>>>(flow, g, part);
+    else bend_fwd_k<false, false><<<nwg, NT, 0, st>>>(flow, g, part);
   }
   DF_LAUNCH_CHECK();
-  df_slot_mean_k<BEND_T><<<1, BEND_T, 0, st>>>(part, (int)nwg, count, out);      // loss = (the slots, in a fixed order) / N
+  df_slot_mean_k<NT><<<1, NT, 0, st>>>(part, (int)nwg, count, out);      // loss = (the slots, in a fixed order) / N
   DF_LAUNCH_CHECK();
   return 0;
 }
@@ -335,15 +258,15 @@ extern "C" int dfmir_bend_bwd(const float* flow, const float* gout, float* dflow
   double count;
   DF_ARG_CHECK(flow && gout && dflow && bend_geom(B, C, D, H, W, hz, hy, hx, &g, &planes, &count));
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nwg = (unsigned)bend_nwg(g, planes);
+  const unsigned nwg = (unsigned)(planes * wg_per_plane(g));      // < 2^31
   const float k = (float)(2.0 / count);
-  const bool vec = bend_vec(g, flow);
+  const bool vec = vec_ok(g.W, flow);
   if (D > 1) {
-    if (vec) bend_bwd_k<true, true><<<nwg, BEND_T, 0, st>>>(flow, gout, k, g, dflow);
-    else bend_bwd_k<true, false><<<nwg, BEND_T, 0, st>>>(flow, gout, k, g, dflow);
+    if (vec) bend_bwd_k<true, true><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
+    else bend_bwd_k<true, false><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
   } else {
-    if (vec) bend_bwd_k<false, true><<<nwg, BEND_T, 0, st>>>(flow, gout, k, g, dflow);
-    else bend_bwd_k<false, false><<<nwg, BEND_T, 0, st>>>(flow, gout, k, g, dflow);
+    if (vec) bend_bwd_k<false, true><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
+    else bend_bwd_k<false, false><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
   }
   DF_LAUNCH_CHECK();
   return 0;

@@ -13,11 +13,9 @@
 //     dI(y)  = sum_a (1 / 2 h_a) ( [y_a >= 1] G_a(y - e_a) + [y_a == n_a - 1] G_a(y) - [y_a <= n_a - 2] G_a(y + e_a) - [y_a == 0] G_a(y) )
 //   the exact adjoint of the clamped difference.
 //
-// One workgroup = one GF_TY x GF_TX tile of (y, x) of one sample and one chunk of g.zc planes along z that it marches
-// through; wave w owns two rows of the tile, its lanes run along x (every LDS access is stride 1 over the lanes).  The next
-// plane travels global -> registers -> LDS while the current one is computed (GfStage: 16-byte loads of the 64 interior
-// columns when W % 4 == 0, scalars otherwise).  A staged plane holds I at the CLAMPED coordinates, so a difference of two
-// staged neighbours is the clamped difference, on the border as in the interior, and every address is inside the volume.
+// Tiles, z chunks (of g.zc planes) and the layout of a staged plane are those of stencil_tile.h, one sample per workgroup.
+// A staged plane holds I at the CLAMPED coordinates (GfStage::fetch), so a difference of two staged neighbours is the
+// clamped difference, on the border as in the interior, and every address is inside the volume.
 //   gf_pass_k<MODE, VEC>  halo 1, three open planes.  GF_STATS: sum |g(A)|, sum |g(B)|; GF_LOSS: sum m (1 - s), sum m;
 //                         in double per thread, one double slot per workgroup and sum, added in a fixed order by the
 //                         one-workgroup gf_eps_k / gf_loss_k, which leave eps_A, eps_B and sum m in the workspace (the
@@ -30,16 +28,14 @@
 // arithmetic is fp32 (in double the division and the square root made every kernel compute-bound at about 1.2 TB/s of
 // its traffic); the sums and eps are double.  Nothing allocates or keeps state; loss, gradients and field are
 // bit-identical from run to run.
-#include "common.h"
+#include "stencil_tile.h"
+
+using namespace stencil;
 
 namespace {
 
-constexpr int GF_T = 256;                  // threads per workgroup: 4 waves x 64 lanes
-constexpr int GF_TY = 8, GF_TX = 64;       // tile of (y, x): two rows per wave, one column per lane
-constexpr int GF_ZC = 16, GF_ZC_MIN = 4;   // planes of a z chunk: halved down to GF_ZC_MIN while the grid stays below
+constexpr int GF_ZC_MIN = 4;               // planes of a z chunk: halved from ZC down to GF_ZC_MIN while the grid stays below
 constexpr long long GF_WG_TARGET = 768;    //   GF_WG_TARGET workgroups (three per compute unit; profiles/gradfield_timing.txt)
-constexpr int GF_RS = 72;                  // floats per LDS row: column x0 sits at GF_X0 (16-byte aligned)
-constexpr int GF_X0 = 4;
 constexpr int GF_HEAD = 4;                 // doubles at the head of the workspace: eps_A, eps_B, sum m, (unused)
 
 enum { GF_STATS = 0, GF_LOSS = 1, GF_FIELD = 2 };
@@ -52,71 +48,47 @@ struct GfGeom {
 
 __device__ __forceinline__ int gf_clamp(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-// One plane of an image around a tile, with HALO voxels per side, at the clamped coordinates: fetch() brings it into
-// registers, commit() stores it to an LDS plane of (GF_TY + 2 HALO) rows of GF_RS floats.
+// One plane of an image around a tile in the layout of stencil::Stage, which stores it to LDS (commit()); fetch() brings
+// it into registers at the clamped coordinates.  A tile that ends past W replicates the last column in its quads.
 template <int HALO, bool VEC>
-struct GfStage {
-  static constexpr int ROWS = GF_TY + 2 * HALO, COLS = GF_TX + 2 * HALO, QPR = GF_TX / 4;
-  static constexpr int NS = VEC ? 1 : (ROWS * COLS + GF_T - 1) / GF_T;
-  static_assert(ROWS * QPR <= GF_T && ROWS * 2 * HALO <= GF_T, "one quad and one halo value per thread");
-  static_assert(GF_X0 >= HALO && GF_X0 + GF_TX + HALO <= GF_RS, "LDS row too short");
-  float4 q;
-  float s[NS];
-
+struct GfStage : Stage<1, HALO, VEC> {
+  using S = Stage<1, HALO, VEC>;
   __device__ __forceinline__ void fetch(const float* __restrict__ ip, const GfGeom& g, int gz, int y0, int x0) {
     const int tid = threadIdx.x;
     const float* pl = ip + (long long)gf_clamp(gz, g.D) * g.H * g.W;
     if (VEC) {
-      if (tid < ROWS * QPR) {                      // the interior columns: x0 and W are multiples of 4
-        const int r = tid / QPR, gx = x0 + 4 * (tid % QPR);
+      if (tid < S::ROWS * S::QPR) {                // the interior columns
+        const int r = tid / S::QPR, gx = x0 + 4 * (tid % S::QPR);
         const float* row = pl + (long long)gf_clamp(y0 - HALO + r, g.H) * g.W;
         if (gx < g.W) {
-          q = *reinterpret_cast<const float4*>(row + gx);
+          this->q[0] = *reinterpret_cast<const float4*>(row + gx);
         } else {
           const float v = row[g.W - 1];
-          q = make_float4(v, v, v, v);
+          this->q[0] = make_float4(v, v, v, v);
         }
       }
-      if (tid < ROWS * 2 * HALO) {                 // the halo columns
+      if (tid < S::ROWS * 2 * HALO) {              // the halo columns
         const int r = tid / (2 * HALO), j = tid % (2 * HALO);
-        const int gx = j < HALO ? x0 - HALO + j : x0 + GF_TX + j - HALO;
-        s[0] = pl[(long long)gf_clamp(y0 - HALO + r, g.H) * g.W + gf_clamp(gx, g.W)];
+        const int gx = j < HALO ? x0 - HALO + j : x0 + TX + j - HALO;
+        this->s[0][0] = pl[(long long)gf_clamp(y0 - HALO + r, g.H) * g.W + gf_clamp(gx, g.W)];
       }
     } else {
 #pragma unroll
-      for (int n = 0; n < NS; ++n) {
-        const int i = tid + n * GF_T, r = i / COLS;
-        if (i < ROWS * COLS)
-          s[n] = pl[(long long)gf_clamp(y0 - HALO + r, g.H) * g.W + gf_clamp(x0 - HALO + i - r * COLS, g.W)];
-      }
-    }
-  }
-
-  __device__ __forceinline__ void commit(float* __restrict__ dst) const {
-    const int tid = threadIdx.x;
-    if (VEC) {
-      if (tid < ROWS * QPR)
-        *reinterpret_cast<float4*>(dst + (tid / QPR) * GF_RS + GF_X0 + 4 * (tid % QPR)) = q;
-      if (tid < ROWS * 2 * HALO) {
-        const int r = tid / (2 * HALO), j = tid % (2 * HALO);
-        dst[r * GF_RS + (j < HALO ? GF_X0 - HALO + j : GF_X0 + GF_TX + j - HALO)] = s[0];
-      }
-    } else {
-#pragma unroll
-      for (int n = 0; n < NS; ++n) {
-        const int i = tid + n * GF_T, r = i / COLS;
-        if (i < ROWS * COLS) dst[r * GF_RS + GF_X0 - HALO + i - r * COLS] = s[n];
+      for (int n = 0; n < S::NS; ++n) {
+        const int i = tid + n * NT, r = i / S::COLS;
+        if (i < S::ROWS * S::COLS)
+          this->s[0][n] = pl[(long long)gf_clamp(y0 - HALO + r, g.H) * g.W + gf_clamp(x0 - HALO + i - r * S::COLS, g.W)];
       }
     }
   }
 };
 
-// The first differences at one voxel.  A, B, C point at the voxel in the staged planes z - 1, z, z + 1 (rows of GF_RS).
+// The first differences at one voxel.  A, B, C point at the voxel in the staged planes z - 1, z, z + 1 (rows of RS).
 struct GfVec { float z, y, x; };
 __device__ __forceinline__ GfVec gf_grad(const float* A, const float* B, const float* C, const GfGeom& g) {
   GfVec v;
   v.z = (C[0] - A[0]) * g.cz;
-  v.y = (B[GF_RS] - B[-GF_RS]) * g.cy;
+  v.y = (B[RS] - B[-RS]) * g.cy;
   v.x = (B[1] - B[-1]) * g.cx;
   return v;
 }
@@ -136,39 +108,26 @@ __device__ __forceinline__ GfSim gf_sim(const GfVec& ga, const GfVec& gb, float 
   return s;
 }
 
-// (sample, z chunk, tile origin) of a workgroup
-struct GfTile { long long plane; int z0, z1, y0, x0; };
-__device__ __forceinline__ GfTile gf_tile(const GfGeom& g) {
-  GfTile t;
-  unsigned b = blockIdx.x;
-  t.x0 = (int)(b % (unsigned)g.ntx) * GF_TX; b /= (unsigned)g.ntx;
-  t.y0 = (int)(b % (unsigned)g.nty) * GF_TY; b /= (unsigned)g.nty;
-  t.z0 = (int)(b % (unsigned)g.nzc) * g.zc;
-  t.z1 = t.z0 + g.zc < g.D ? t.z0 + g.zc : g.D;
-  t.plane = b / (unsigned)g.nzc;
-  return t;
-}
-
 // ------------------------------------------------------------------------------------------------ statistics, loss, field
 // a: the image (GF_FIELD) or the first image; b: the second image (GF_STATS: may be NULL, its sum is then 0).
 // wsd: the head of the workspace (eps_A, eps_B; read by GF_LOSS and GF_FIELD).  part: 2 gridDim.x double slots.
 // out (GF_FIELD): [B][nch][D][H][W], channel nch - 3 + (0: z, 1: y, 2: x), so that nch = 2 drops z.
 template <int MODE, bool VEC>
-__global__ __launch_bounds__(GF_T) void gf_pass_k(const float* __restrict__ a, const float* __restrict__ b,
-                                                  const float* __restrict__ mask, const double* __restrict__ wsd, GfGeom g,
-                                                  double* __restrict__ part, float* __restrict__ out, int nch) {
-  constexpr int ROWS = GF_TY + 2;
-  __shared__ __attribute__((aligned(16))) float sa[3][ROWS * GF_RS];
-  __shared__ __attribute__((aligned(16))) float sb[3][MODE == GF_FIELD ? 4 : ROWS * GF_RS]   /* (no second image for the field) */;
-  __shared__ double red[GF_T / 64];
-  const GfTile t = gf_tile(g);
+__global__ __launch_bounds__(NT) void gf_pass_k(const float* __restrict__ a, const float* __restrict__ b,
+                                                const float* __restrict__ mask, const double* __restrict__ wsd, GfGeom g,
+                                                double* __restrict__ part, float* __restrict__ out, int nch) {
+  constexpr int ROWS = TY + 2;
+  __shared__ __attribute__((aligned(16))) float sa[3][ROWS * RS];
+  __shared__ __attribute__((aligned(16))) float sb[3][MODE == GF_FIELD ? 4 : ROWS * RS]   /* (no second image for the field) */;
+  __shared__ double red[NT / 64];
+  const Tile t = tile_of(g, g.zc);
   const long long vol = (long long)g.D * g.H * g.W;
   const float* ap = a + t.plane * vol;
   const bool two = MODE != GF_FIELD && b != nullptr;
   const float* bp = two ? b + t.plane * vol : ap;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int x = t.x0 + lane;
-  const int c0 = (2 * w + 1) * GF_RS + GF_X0 + lane;            // the thread's first voxel in a staged plane
+  const int c0 = (2 * w + 1) * RS + X0 + lane;                     // the thread's first voxel in a staged plane
   const bool one = g.D == 1;                                    // one plane: staged once, it is its own neighbour in z
   float ea2 = 0.f, eb2 = 0.f;
   if (MODE != GF_STATS) { ea2 = (float)(wsd[0] * wsd[0]); eb2 = (float)(wsd[1] * wsd[1]); }
@@ -197,7 +156,7 @@ __global__ __launch_bounds__(GF_T) void gf_pass_k(const float* __restrict__ a, c
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int y = t.y0 + 2 * w + j, c = c0 + j * GF_RS;
+      const int y = t.y0 + 2 * w + j, c = c0 + j * RS;
       const bool in = y < g.H && x < g.W;
       const long long o = ((long long)z * g.H + y) * g.W + x;
       const GfVec ga = gf_grad(sa[ia] + c, sa[ib] + c, sa[ic] + c, g);
@@ -228,9 +187,9 @@ __global__ __launch_bounds__(GF_T) void gf_pass_k(const float* __restrict__ a, c
     if (!one) { const int o = ia; ia = ib; ib = ic; ic = o; }
   }
   if (MODE != GF_FIELD) {
-    acc0 = block_sum_ordered<GF_T>(acc0, red);
+    acc0 = block_sum_ordered<NT>(acc0, red);
     if (threadIdx.x == 0) part[blockIdx.x] = acc0;
-    acc1 = block_sum_ordered<GF_T>(acc1, red);
+    acc1 = block_sum_ordered<NT>(acc1, red);
     if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = acc1;
   }
 }
@@ -238,14 +197,14 @@ __global__ __launch_bounds__(GF_T) void gf_pass_k(const float* __restrict__ a, c
 // (the two sums of the slots, in a fixed order; valid in thread 0)  ONE workgroup.
 __device__ __forceinline__ void gf_slot_sums(const double* __restrict__ part, int nslots, double* red, double& s0, double& s1) {
   s0 = s1 = 0.0;
-  for (int i = threadIdx.x; i < nslots; i += GF_T) { s0 += part[i]; s1 += part[nslots + i]; }
-  s0 = block_sum_ordered<GF_T>(s0, red);
-  s1 = block_sum_ordered<GF_T>(s1, red);
+  for (int i = threadIdx.x; i < nslots; i += NT) { s0 += part[i]; s1 += part[nslots + i]; }
+  s0 = block_sum_ordered<NT>(s0, red);
+  s1 = block_sum_ordered<NT>(s1, red);
 }
 // eps_A, eps_B into the head of the workspace: eta * (the slots' sums) / count, or the given values when part == NULL.
-__global__ __launch_bounds__(GF_T) void gf_eps_k(const double* __restrict__ part, int nslots, double count, double eta,
-                                                 double ea, double eb, double* __restrict__ wsd) {
-  __shared__ double red[GF_T / 64];
+__global__ __launch_bounds__(NT) void gf_eps_k(const double* __restrict__ part, int nslots, double count, double eta,
+                                               double ea, double eb, double* __restrict__ wsd) {
+  __shared__ double red[NT / 64];
   if (part) {
     gf_slot_sums(part, nslots, red, ea, eb);
     ea = eta * (ea / count);
@@ -254,9 +213,9 @@ __global__ __launch_bounds__(GF_T) void gf_eps_k(const double* __restrict__ part
   if (threadIdx.x == 0) { wsd[0] = ea; wsd[1] = eb; }
 }
 // out[0] = sum m (1 - s) / sum m (0 for an empty mask); sum m stays in the head of the workspace for the backward.
-__global__ __launch_bounds__(GF_T) void gf_loss_k(const double* __restrict__ part, int nslots, double* __restrict__ wsd,
-                                                  float* __restrict__ out) {
-  __shared__ double red[GF_T / 64];
+__global__ __launch_bounds__(NT) void gf_loss_k(const double* __restrict__ part, int nslots, double* __restrict__ wsd,
+                                                float* __restrict__ out) {
+  __shared__ double red[NT / 64];
   double l, m;
   gf_slot_sums(part, nslots, red, l, m);
   if (threadIdx.x == 0) {
@@ -267,18 +226,18 @@ __global__ __launch_bounds__(GF_T) void gf_loss_k(const double* __restrict__ par
 
 // ------------------------------------------------------------------------------------------------ backward
 // dI(y) = sum_a c_a ( G_a(y - e_a) - G_a(y + e_a) + ([y_a == n_a - 1] - [y_a == 0]) G_a(y) ) with G = 0 outside the volume.
-// The G plane holds (GF_TY + 2) x (GF_TX + 2) values (tile + 1), rows of DC floats; sg[3 i + (0: z, 1: y, 2: x)] of image i.
+// The G plane holds (TY + 2) x (TX + 2) values (tile + 1), rows of DC floats; sg[3 i + (0: z, 1: y, 2: x)] of image i.
 template <bool VEC>
-__global__ __launch_bounds__(GF_T) void gf_bwd_k(const float* __restrict__ a, const float* __restrict__ b,
-                                                 const float* __restrict__ mask, const float* __restrict__ gout,
-                                                 const double* __restrict__ wsd, GfGeom g, float* __restrict__ da,
-                                                 float* __restrict__ db) {
-  constexpr int UR = GF_TY + 4, MR = GF_TY + 2, DC = GF_TX + 2, DN = MR * DC;
-  __shared__ __attribute__((aligned(16))) float sa[3][UR * GF_RS];
-  __shared__ __attribute__((aligned(16))) float sb[3][UR * GF_RS];
-  __shared__ __attribute__((aligned(16))) float sm[MR * GF_RS];
+__global__ __launch_bounds__(NT) void gf_bwd_k(const float* __restrict__ a, const float* __restrict__ b,
+                                               const float* __restrict__ mask, const float* __restrict__ gout,
+                                               const double* __restrict__ wsd, GfGeom g, float* __restrict__ da,
+                                               float* __restrict__ db) {
+  constexpr int UR = TY + 4, MR = TY + 2, DC = TX + 2, DN = MR * DC;
+  __shared__ __attribute__((aligned(16))) float sa[3][UR * RS];
+  __shared__ __attribute__((aligned(16))) float sb[3][UR * RS];
+  __shared__ __attribute__((aligned(16))) float sm[MR * RS];
   __shared__ float sg[6][DN];
-  const GfTile t = gf_tile(g);
+  const Tile t = tile_of(g, g.zc);
   const long long vol = (long long)g.D * g.H * g.W;
   const float* ap = a + t.plane * vol;
   const float* bp = b + t.plane * vol;
@@ -325,15 +284,15 @@ __global__ __launch_bounds__(GF_T) void gf_bwd_k(const float* __restrict__ a, co
       if (mp) fm.fetch(mp, g, q + 1, t.y0, t.x0);
     }
     const bool qin = q >= 0 && q < g.D;
-    for (int i = tid; i < DN; i += GF_T) {
+    for (int i = tid; i < DN; i += NT) {
       const int ly = i / DC, lx = i - ly * DC, gy = t.y0 - 1 + ly, gx = t.x0 - 1 + lx;
       GfVec GA = {0.f, 0.f, 0.f}, GB = {0.f, 0.f, 0.f};
       if (qin && gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
-        const int c = (ly + 1) * GF_RS + GF_X0 - 1 + lx;
+        const int c = (ly + 1) * RS + X0 - 1 + lx;
         const GfVec ga = gf_grad(sa[s0] + c, sa[s1] + c, sa[s2] + c, g);
         const GfVec gb = gf_grad(sb[s0] + c, sb[s1] + c, sb[s2] + c, g);
         const GfSim s = gf_sim(ga, gb, ea2, eb2);
-        const float m = mp ? sm[ly * GF_RS + GF_X0 - 1 + lx] : 1.f;
+        const float m = mp ? sm[ly * RS + X0 - 1 + lx] : 1.f;
         const float coef = -2.f * (k * m) * s.dot * s.ri;
         GA.z = coef * (gb.z - s.ra * ga.z); GA.y = coef * (gb.y - s.ra * ga.y); GA.x = coef * (gb.x - s.ra * ga.x);
         GB.z = coef * (ga.z - s.rb * gb.z); GB.y = coef * (ga.y - s.rb * gb.y); GB.x = coef * (ga.x - s.rb * gb.x);
@@ -377,23 +336,23 @@ bool gf_geom(int nd, int B, int D, int H, int W, float hz, float hy, float hx, G
   if ((nd == 3 && !gf_finite_pos(hz)) || !gf_finite_pos(hy) || !gf_finite_pos(hx)) return false;
   if ((long long)B * D * H * W >= (1LL << 31)) return false;
   g->D = D; g->H = H; g->W = W;
-  g->nty = (H + GF_TY - 1) / GF_TY; g->ntx = (W + GF_TX - 1) / GF_TX;
-  g->zc = GF_ZC;                           // (a function of the geometry alone: the size query and the calls agree)
-  while (g->zc > GF_ZC_MIN && (long long)B * ((D + g->zc - 1) / g->zc) * g->nty * g->ntx < GF_WG_TARGET) g->zc /= 2;
-  g->nzc = (D + g->zc - 1) / g->zc;
+  g->zc = ZC;                              // (a function of the geometry alone: the size query and the calls agree)
+  set_tile_counts(g, g->zc);
+  while (g->zc > GF_ZC_MIN && B * wg_per_plane(*g) < GF_WG_TARGET) {
+    g->zc /= 2;
+    set_tile_counts(g, g->zc);
+  }
   g->cz = nd == 3 ? (float)(1.0 / (2.0 * (double)hz)) : 0.f;
   g->cy = (float)(1.0 / (2.0 * (double)hy)); g->cx = (float)(1.0 / (2.0 * (double)hx));
   *count = (double)B * D * H * W;
   return true;
 }
-inline long long gf_nwg(const GfGeom& g, int B) { return (long long)B * g.nzc * g.nty * g.ntx; }          // < 2^31
-inline bool gf_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int MODE>
 void gf_pass(bool vec, unsigned nwg, hipStream_t st, const float* a, const float* b, const float* mask, const double* wsd,
              const GfGeom& g, double* part, float* out, int nch) {
-  if (vec) gf_pass_k<MODE, true><<<nwg, GF_T, 0, st>>>(a, b, mask, wsd, g, part, out, nch);
-  else gf_pass_k<MODE, false><<<nwg, GF_T, 0, st>>>(a, b, mask, wsd, g, part, out, nch);
+  if (vec) gf_pass_k<MODE, true><<<nwg, NT, 0, st>>>(a, b, mask, wsd, g, part, out, nch);
+  else gf_pass_k<MODE, false><<<nwg, NT, 0, st>>>(a, b, mask, wsd, g, part, out, nch);
 }
 
 // eps_A, eps_B into the head of the workspace: the statistics pass and its reduction ("auto"), or the given values
@@ -404,7 +363,7 @@ int gf_set_eps(bool vec, unsigned nwg, hipStream_t st, const float* a, const flo
     gf_pass<GF_STATS>(vec, nwg, st, a, b, nullptr, wsd, g, part, nullptr, 0);
     DF_LAUNCH_CHECK();
   }
-  gf_eps_k<<<1, GF_T, 0, st>>>(auto_eps ? part : nullptr, (int)nwg, count, eta, ea, eb, wsd);
+  gf_eps_k<<<1, NT, 0, st>>>(auto_eps ? part : nullptr, (int)nwg, count, eta, ea, eb, wsd);
   DF_LAUNCH_CHECK();
   return 0;
 }
@@ -418,7 +377,7 @@ extern "C" long long dfmir_gradfield_ws_floats(int nd, int B, int D, int H, int 
   GfGeom g;
   double count;
   if (!gf_geom(nd, B, D, H, W, 1.f, 1.f, 1.f, &g, &count)) return -1;
-  return 2 * (GF_HEAD + 2 * gf_nwg(g, B));
+  return 2 * (GF_HEAD + 2 * B * wg_per_plane(g));
 }
 
 extern "C" int dfmir_gradfield_fwd(const float* a, const float* b, const float* mask, int nd, int B, int D, int H, int W,
@@ -429,13 +388,13 @@ extern "C" int dfmir_gradfield_fwd(const float* a, const float* b, const float* 
   DF_ARG_CHECK(a && b && ws && out && (reinterpret_cast<uintptr_t>(ws) & 7) == 0 && gf_eps_ok(auto_eps, eta, eps_a, eps_b) &&
                gf_geom(nd, B, D, H, W, hz, hy, hx, &g, &count));
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nwg = (unsigned)gf_nwg(g, B);
+  const unsigned nwg = (unsigned)(B * wg_per_plane(g));      // < 2^31
   double* wsd = reinterpret_cast<double*>(ws);
-  const bool vec = W % 4 == 0 && gf_al16(a) && gf_al16(b);
+  const bool vec = vec_ok(W, a, b);
   if (int rc = gf_set_eps(vec, nwg, st, a, b, g, count, auto_eps, eta, eps_a, eps_b, wsd)) return rc;
   gf_pass<GF_LOSS>(vec, nwg, st, a, b, mask, wsd, g, wsd + GF_HEAD, nullptr, 0);
   DF_LAUNCH_CHECK();
-  gf_loss_k<<<1, GF_T, 0, st>>>(wsd + GF_HEAD, (int)nwg, wsd, out);
+  gf_loss_k<<<1, NT, 0, st>>>(wsd + GF_HEAD, (int)nwg, wsd, out);
   DF_LAUNCH_CHECK();
   return 0;
 }
@@ -448,11 +407,11 @@ extern "C" int dfmir_gradfield_bwd(const float* a, const float* b, const float* 
   DF_ARG_CHECK(a && b && gout && ws && (da || db) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0 &&
                gf_geom(nd, B, D, H, W, hz, hy, hx, &g, &count));
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nwg = (unsigned)gf_nwg(g, B);
+  const unsigned nwg = (unsigned)(B * wg_per_plane(g));      // < 2^31
   const double* wsd = reinterpret_cast<const double*>(ws);
-  const bool vec = W % 4 == 0 && gf_al16(a) && gf_al16(b) && (!mask || gf_al16(mask));
-  if (vec) gf_bwd_k<true><<<nwg, GF_T, 0, st>>>(a, b, mask, gout, wsd, g, da, db);
-  else gf_bwd_k<false><<<nwg, GF_T, 0, st>>>(a, b, mask, gout, wsd, g, da, db);
+  const bool vec = vec_ok(W, a, b, mask);
+  if (vec) gf_bwd_k<true><<<nwg, NT, 0, st>>>(a, b, mask, gout, wsd, g, da, db);
+  else gf_bwd_k<false><<<nwg, NT, 0, st>>>(a, b, mask, gout, wsd, g, da, db);
   DF_LAUNCH_CHECK();
   return 0;
 }
@@ -464,9 +423,9 @@ extern "C" int dfmir_gradfield_field(const float* I, int nd, int B, int D, int H
   DF_ARG_CHECK(I && ws && out && (reinterpret_cast<uintptr_t>(ws) & 7) == 0 && gf_eps_ok(auto_eps, eta, eps, eps) &&
                gf_geom(nd, B, D, H, W, hz, hy, hx, &g, &count));
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nwg = (unsigned)gf_nwg(g, B);
+  const unsigned nwg = (unsigned)(B * wg_per_plane(g));      // < 2^31
   double* wsd = reinterpret_cast<double*>(ws);
-  const bool vec = W % 4 == 0 && gf_al16(I);
+  const bool vec = vec_ok(W, I);
   if (int rc = gf_set_eps(vec, nwg, st, I, nullptr, g, count, auto_eps, eta, eps, eps, wsd)) return rc;
   gf_pass<GF_FIELD>(vec, nwg, st, I, nullptr, nullptr, wsd, g, nullptr, out, nd);
   DF_LAUNCH_CHECK();

@@ -14,11 +14,8 @@
 //   stats    per sample over Omega_m: count of d <= 0, min d, max d, mean d, mean l, std l (population),
 //            l = log(max(d + log_offset, log_floor))
 //
-// One workgroup = one JAC_TY x JAC_TX tile of (y, x) of one sample and, in 3-D, one chunk of JAC_ZC planes along z that it
-// marches through; wave w owns two rows of the tile, its lanes run along x (every LDS access is stride 1 over the lanes).
-// A voxel needs all nd channels at once, so a staged plane is nd channel planes; the next one travels global -> registers
-// -> LDS while the current one is computed (JacStage: 16-byte loads of the 64 interior columns when W % 4 == 0, scalars
-// otherwise; zeros outside the volume).
+// Tiles, z chunks and the staging of a plane of u are those of stencil_tile.h, with zeros outside the volume.  A voxel
+// needs all nd channels at once, so a staged plane is nd channel planes.
 //   jac_fwd_k<ND3, VEC, MODE>  u with a halo of 1, three open planes.  JAC_PENALTY: psi added in double per thread, one
 //                              double slot per workgroup, df_slot_mean_k adds the slots.  JAC_MAP: d or 1.0f stored.
 //                              JAC_STATS: count, min, max and three double sums per workgroup; jac_stats_fin_k (one
@@ -31,16 +28,13 @@
 //                              voxel, border or interior, collects its 2 nd terms with the one expression.
 // jac_det2 / jac_det3 are the ONE place the determinant and the cofactors are formed, jac_at the one place J is.  Nothing
 // syncs with the host (gout is read on the device), allocates or keeps state; every output is bit-identical from run to run.
-#include "common.h"
+#include "stencil_tile.h"
 #include <math.h>
+
+using namespace stencil;
 
 namespace {
 
-constexpr int JAC_T = 256;                   // threads per workgroup: 4 waves x 64 lanes
-constexpr int JAC_TY = 8, JAC_TX = 64;       // tile of (y, x): two rows per wave, one column per lane
-constexpr int JAC_ZC = 16;                   // planes of a z chunk (3-D)
-constexpr int JAC_RS = 72;                   // floats per LDS row of u: column x0 sits at JAC_X0 (16-byte aligned)
-constexpr int JAC_X0 = 4;
 constexpr int JAC_PENALTY = 0, JAC_MAP = 1, JAC_STATS = 2;
 constexpr int JAC_SLOT = 7;                  // doubles per workgroup of JAC_STATS: count, min, max, sum d, S1, S2, pivot
 
@@ -50,71 +44,6 @@ struct JacGeom {
   int power;
   float eps;
   double off, lfloor;                        // log_offset, log_floor
-};
-
-// One plane of all NC channels of u around a tile, with HALO voxels per side: fetch() brings it into registers (zeros
-// outside the volume), commit() stores it to NC LDS planes of (JAC_TY + 2 HALO) rows of JAC_RS floats.
-template <int NC, int HALO, bool VEC>
-struct JacStage {
-  static constexpr int ROWS = JAC_TY + 2 * HALO, COLS = JAC_TX + 2 * HALO, QPR = JAC_TX / 4, CH = ROWS * JAC_RS;
-  static constexpr int NS = VEC ? 1 : (ROWS * COLS + JAC_T - 1) / JAC_T;
-  static_assert(ROWS * QPR <= JAC_T && ROWS * 2 * HALO <= JAC_T, "one quad and one halo value per thread and channel");
-  static_assert(JAC_X0 >= HALO && JAC_X0 + JAC_TX + HALO <= JAC_RS, "LDS row too short");
-  float4 q[NC];
-  float s[NC][NS];
-
-  // ub: the sample's first channel; vol = D H W, the channel stride
-  __device__ __forceinline__ void fetch(const float* __restrict__ ub, const JacGeom& g, long long vol, int gz, int y0, int x0) {
-    const int tid = threadIdx.x;
-    const bool zin = gz >= 0 && gz < g.D;
-    const long long zo = zin ? (long long)gz * g.H * g.W : 0LL;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const float* pl = ub + c * vol + zo;
-      if (VEC) {
-        q[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        s[c][0] = 0.f;
-        if (tid < ROWS * QPR) {                      // the interior columns: x0 and W are multiples of 4
-          const int r = tid / QPR, gy = y0 - HALO + r, gx = x0 + 4 * (tid % QPR);
-          if (zin && gy >= 0 && gy < g.H && gx < g.W) q[c] = *reinterpret_cast<const float4*>(pl + (long long)gy * g.W + gx);
-        }
-        if (tid < ROWS * 2 * HALO) {                 // the halo columns
-          const int r = tid / (2 * HALO), j = tid % (2 * HALO), gy = y0 - HALO + r;
-          const int gx = j < HALO ? x0 - HALO + j : x0 + JAC_TX + j - HALO;
-          if (zin && gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) s[c][0] = pl[(long long)gy * g.W + gx];
-        }
-      } else {
-#pragma unroll
-        for (int n = 0; n < NS; ++n) {
-          const int i = tid + n * JAC_T, r = i / COLS, gy = y0 - HALO + r, gx = x0 - HALO + i - r * COLS;
-          s[c][n] = 0.f;
-          if (i < ROWS * COLS && zin && gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) s[c][n] = pl[(long long)gy * g.W + gx];
-        }
-      }
-    }
-  }
-
-  __device__ __forceinline__ void commit(float* __restrict__ dst) const {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      float* d = dst + c * CH;
-      if (VEC) {
-        if (tid < ROWS * QPR)
-          *reinterpret_cast<float4*>(d + (tid / QPR) * JAC_RS + JAC_X0 + 4 * (tid % QPR)) = q[c];
-        if (tid < ROWS * 2 * HALO) {
-          const int r = tid / (2 * HALO), j = tid % (2 * HALO);
-          d[r * JAC_RS + (j < HALO ? JAC_X0 - HALO + j : JAC_X0 + JAC_TX + j - HALO)] = s[c][0];
-        }
-      } else {
-#pragma unroll
-        for (int n = 0; n < NS; ++n) {
-          const int i = tid + n * JAC_T, r = i / COLS;
-          if (i < ROWS * COLS) d[r * JAC_RS + JAC_X0 - HALO + i - r * COLS] = s[c][n];
-        }
-      }
-    }
-  }
 };
 
 // The determinant d and the cofactors c[a][b] = dd/dJ_ab of one J.
@@ -162,49 +91,37 @@ __device__ __forceinline__ JacM<ND3> jac_at(const float* A, const float* B, cons
   else return jac_det2(J);
 }
 
-// (sample, z chunk, tile origin) of a workgroup
-struct JacTile { long long b; int z0, z1, y0, x0; };
-__device__ __forceinline__ JacTile jac_tile(const JacGeom& g) {
-  JacTile t;
-  unsigned b = blockIdx.x;
-  t.x0 = (int)(b % (unsigned)g.ntx) * JAC_TX; b /= (unsigned)g.ntx;
-  t.y0 = (int)(b % (unsigned)g.nty) * JAC_TY; b /= (unsigned)g.nty;
-  t.z0 = (int)(b % (unsigned)g.nzc) * JAC_ZC;
-  t.z1 = t.z0 + JAC_ZC < g.D ? t.z0 + JAC_ZC : g.D;
-  t.b = b / (unsigned)g.nzc;
-  return t;
-}
 __device__ __forceinline__ bool jac_in(const JacGeom& g, int n, int p) { return p >= g.m && p <= n - 1 - g.m; }
 
 // Maximum over a workgroup, valid in thread 0 only (the contract of block_sum_ordered).
-__device__ __forceinline__ float jac_block_max(float v, float* sm /* JAC_T / 64 */) {
+__device__ __forceinline__ float jac_block_max(float v, float* sm /* NT / 64 */) {
   v = wave_max(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
   __syncthreads();
   float t = -HUGE_VALF;
   if (threadIdx.x == 0)
-    for (int w = 0; w < JAC_T / 64; ++w) t = fmaxf(t, sm[w]);
+    for (int w = 0; w < NT / 64; ++w) t = fmaxf(t, sm[w]);
   return t;
 }
 
 // ------------------------------------------------------------------------------------------------ forward
 template <bool ND3, bool VEC, int MODE>
-__global__ __launch_bounds__(JAC_T) void jac_fwd_k(const float* __restrict__ u, JacGeom g, double* __restrict__ part,
-                                                   float* __restrict__ detmap) {
+__global__ __launch_bounds__(NT) void jac_fwd_k(const float* __restrict__ u, JacGeom g, double* __restrict__ part,
+                                                float* __restrict__ detmap) {
   constexpr int NC = ND3 ? 3 : 2;
-  using Stage = JacStage<NC, 1, VEC>;
+  using Stage = stencil::Stage<NC, 1, VEC>;
   constexpr int CH = Stage::CH;
   __shared__ __attribute__((aligned(16))) float su[ND3 ? 3 : 1][NC * CH];
-  __shared__ double red[JAC_T / 64];
-  __shared__ float redf[JAC_T / 64];
-  const JacTile t = jac_tile(g);
+  __shared__ double red[NT / 64];
+  __shared__ float redf[NT / 64];
+  const Tile t = tile_of(g, ZC);
   const long long vol = (long long)g.D * g.H * g.W;
-  const float* ub = u + t.b * NC * vol;
+  const float* ub = u + t.plane * NC * vol;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int x = t.x0 + lane;
   const bool xin = jac_in(g, g.W, x);
-  const int c0 = (2 * w + 1) * JAC_RS + JAC_X0 + lane;          // the thread's first voxel in a staged plane
+  const int c0 = (2 * w + 1) * RS + X0 + lane;                     // the thread's first voxel in a staged plane
   Stage st;
   double acc = 0.0, s1 = 0.0, s2 = 0.0, cnt = 0.0, piv = 0.0;   // acc: the sum of psi (penalty) or of d (statistics)
   float mn = HUGE_VALF, mx = -HUGE_VALF;
@@ -221,7 +138,7 @@ __global__ __launch_bounds__(JAC_T) void jac_fwd_k(const float* __restrict__ u, 
       const float p = e > 0.f ? (g.power == 2 ? e * e : e) : 0.f;
       acc += (double)(in ? p : 0.f);
     } else if constexpr (MODE == JAC_MAP) {
-      if (y < g.H && x < g.W) detmap[t.b * vol + ((long long)z * g.H + y) * g.W + x] = in ? d : 1.f;
+      if (y < g.H && x < g.W) detmap[t.plane * vol + ((long long)z * g.H + y) * g.W + x] = in ? d : 1.f;
     } else if (in) {
       cnt += d <= 0.f ? 1.0 : 0.0;
       mn = fminf(mn, d);
@@ -239,8 +156,8 @@ __global__ __launch_bounds__(JAC_T) void jac_fwd_k(const float* __restrict__ u, 
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int y = t.y0 + 2 * w + j;
-      const float* B = su[0] + c0 + j * JAC_RS;
-      visit(jac_at<false>(B, B, B, CH, JAC_RS).d, xin && jac_in(g, g.H, y), 0, y);
+      const float* B = su[0] + c0 + j * RS;
+      visit(jac_at<false>(B, B, B, CH, RS).d, xin && jac_in(g, g.H, y), 0, y);
     }
   } else {
     int ia = 0, ib = 1, ic = 2;                                  // slots of the planes z - 1, z, z + 1
@@ -256,21 +173,21 @@ __global__ __launch_bounds__(JAC_T) void jac_fwd_k(const float* __restrict__ u, 
       const bool zin = jac_in(g, g.D, z);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int y = t.y0 + 2 * w + j, c = c0 + j * JAC_RS;
-        visit(jac_at<true>(su[ia] + c, su[ib] + c, su[ic] + c, CH, JAC_RS).d, zin && xin && jac_in(g, g.H, y), z, y);
+        const int y = t.y0 + 2 * w + j, c = c0 + j * RS;
+        visit(jac_at<true>(su[ia] + c, su[ib] + c, su[ic] + c, CH, RS).d, zin && xin && jac_in(g, g.H, y), z, y);
       }
       __syncthreads();
       const int o = ia; ia = ib; ib = ic; ic = o;
     }
   }
   if constexpr (MODE == JAC_PENALTY) {
-    acc = block_sum_ordered<JAC_T>(acc, red);
+    acc = block_sum_ordered<NT>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
   } else if constexpr (MODE == JAC_STATS) {
-    cnt = block_sum_ordered<JAC_T>(cnt, red);
-    acc = block_sum_ordered<JAC_T>(acc, red);
-    s1 = block_sum_ordered<JAC_T>(s1, red);
-    s2 = block_sum_ordered<JAC_T>(s2, red);
+    cnt = block_sum_ordered<NT>(cnt, red);
+    acc = block_sum_ordered<NT>(acc, red);
+    s1 = block_sum_ordered<NT>(s1, red);
+    s2 = block_sum_ordered<NT>(s2, red);
     mn = -jac_block_max(-mn, redf);
     mx = jac_block_max(mx, redf);
     if (threadIdx.x == 0) {
@@ -282,14 +199,14 @@ __global__ __launch_bounds__(JAC_T) void jac_fwd_k(const float* __restrict__ u, 
 
 // stats[b][0..5] = count of d <= 0, min d, max d, mean d, mean l, std l from the `per` slot sets of sample b, added in a
 // fixed order; n = |Omega_m|.  One workgroup per sample.
-__global__ __launch_bounds__(JAC_T) void jac_stats_fin_k(const double* __restrict__ part, int per, double n,
-                                                         double* __restrict__ stats) {
-  __shared__ double red[JAC_T / 64];
-  __shared__ float redf[JAC_T / 64];
+__global__ __launch_bounds__(NT) void jac_stats_fin_k(const double* __restrict__ part, int per, double n,
+                                                      double* __restrict__ stats) {
+  __shared__ double red[NT / 64];
+  __shared__ float redf[NT / 64];
   const double* p = part + (long long)blockIdx.x * per * JAC_SLOT;
   double cnt = 0.0, sd = 0.0, s1 = 0.0, s2 = 0.0;
   float mn = HUGE_VALF, mx = -HUGE_VALF;
-  for (int i = threadIdx.x; i < per; i += JAC_T) {
+  for (int i = threadIdx.x; i < per; i += NT) {
     const double* q = p + (long long)i * JAC_SLOT;
     cnt += q[0];
     mn = fminf(mn, (float)q[1]);
@@ -298,10 +215,10 @@ __global__ __launch_bounds__(JAC_T) void jac_stats_fin_k(const double* __restric
     s1 += q[4];
     s2 += q[5];
   }
-  cnt = block_sum_ordered<JAC_T>(cnt, red);
-  sd = block_sum_ordered<JAC_T>(sd, red);
-  s1 = block_sum_ordered<JAC_T>(s1, red);
-  s2 = block_sum_ordered<JAC_T>(s2, red);
+  cnt = block_sum_ordered<NT>(cnt, red);
+  sd = block_sum_ordered<NT>(sd, red);
+  s1 = block_sum_ordered<NT>(s1, red);
+  s2 = block_sum_ordered<NT>(s2, red);
   mn = -jac_block_max(-mn, redf);
   mx = jac_block_max(mx, redf);
   if (threadIdx.x == 0) {
@@ -315,20 +232,20 @@ __global__ __launch_bounds__(JAC_T) void jac_stats_fin_k(const double* __restric
 
 // ------------------------------------------------------------------------------------------------ backward
 // du_a(q) = gout * k * sum_b [ W_ab(q - e_b) - W_ab(q + e_b) ], k = 1 / 2N.  The y and x columns of W of one plane hold
-// (JAC_TY + 2) x (JAC_TX + 2) values (tile + 1; its corners are never read and never written), rows of DC floats.
+// (TY + 2) x (TX + 2) values (tile + 1; its corners are never read and never written), rows of DC floats.
 template <bool ND3, bool VEC>
-__global__ __launch_bounds__(JAC_T) void jac_bwd_k(const float* __restrict__ u, const float* __restrict__ gout, float k,
-                                                   JacGeom g, float* __restrict__ du) {
+__global__ __launch_bounds__(NT) void jac_bwd_k(const float* __restrict__ u, const float* __restrict__ gout, float k,
+                                                JacGeom g, float* __restrict__ du) {
   constexpr int NC = ND3 ? 3 : 2;
-  using Stage = JacStage<NC, 2, VEC>;
-  constexpr int CH = Stage::CH, DR = JAC_TY + 2, DC = JAC_TX + 2, DN = DR * DC, RING = 2 * JAC_TX + 2 * JAC_TY;
-  static_assert(RING <= JAC_T, "one ring voxel per thread");
+  using Stage = stencil::Stage<NC, 2, VEC>;
+  constexpr int CH = Stage::CH, DR = TY + 2, DC = TX + 2, DN = DR * DC, RING = 2 * TX + 2 * TY;
+  static_assert(RING <= NT, "one ring voxel per thread");
   __shared__ __attribute__((aligned(16))) float su[ND3 ? 3 : 1][NC * CH];
   __shared__ float sw[2][NC][DN];                                // W_ay and W_ax of the plane
-  const JacTile t = jac_tile(g);
+  const Tile t = tile_of(g, ZC);
   const long long vol = (long long)g.D * g.H * g.W;
-  const float* ub = u + t.b * NC * vol;
-  float* dp = du + t.b * NC * vol;
+  const float* ub = u + t.plane * NC * vol;
+  float* dp = du + t.plane * NC * vol;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int x = t.x0 + lane;
   const float s = gout[0] * k;
@@ -336,8 +253,8 @@ __global__ __launch_bounds__(JAC_T) void jac_bwd_k(const float* __restrict__ u, 
 
   // W at the tile-relative voxel (ly, lx) of the plane staged in B (A, C: its neighbours along z), times the Omega_m indicator
   auto weights = [&](const float* A, const float* B, const float* C, int ly, int lx, bool zin) {
-    const int c = (ly + 2) * JAC_RS + JAC_X0 + lx;
-    JacM<ND3> r = jac_at<ND3>(A + c, B + c, C + c, CH, JAC_RS);
+    const int c = (ly + 2) * RS + X0 + lx;
+    JacM<ND3> r = jac_at<ND3>(A + c, B + c, C + c, CH, RS);
     const float e = g.eps - r.d;
     const bool on = zin && jac_in(g, g.H, t.y0 + ly) && jac_in(g, g.W, t.x0 + lx) && e > 0.f;
     const float f = g.power == 2 ? -2.f * e : -1.f;             // psi'(d) where it is not 0
@@ -366,8 +283,8 @@ __global__ __launch_bounds__(JAC_T) void jac_bwd_k(const float* __restrict__ u, 
     }
     if (tid < RING) {
       int ly, lx;
-      if (tid < 2 * JAC_TX) { ly = tid < JAC_TX ? -1 : JAC_TY; lx = tid & (JAC_TX - 1); }
-      else { const int i = tid - 2 * JAC_TX; ly = i < JAC_TY ? i : i - JAC_TY; lx = i < JAC_TY ? -1 : JAC_TX; }
+      if (tid < 2 * TX) { ly = tid < TX ? -1 : TY; lx = tid & (TX - 1); }
+      else { const int i = tid - 2 * TX; ly = i < TY ? i : i - TY; lx = i < TY ? -1 : TX; }
       put(weights(A, B, C, ly, lx, zin), ly, lx);
     }
   };
@@ -447,24 +364,22 @@ bool jac_geom(int nd, int B, int D, int H, int W, int m, JacGeom* g, double* ome
   if ((nd == 3 && D < need) || H < need || W < need) return false;
   if ((long long)B * nd * D * H * W >= (1LL << 31)) return false;
   g->D = D; g->H = H; g->W = W; g->m = m;
-  g->nzc = (D + JAC_ZC - 1) / JAC_ZC; g->nty = (H + JAC_TY - 1) / JAC_TY; g->ntx = (W + JAC_TX - 1) / JAC_TX;
+  set_tile_counts(g, ZC);
   g->power = 2; g->eps = 0.f; g->off = 0.0; g->lfloor = 1.0;
   *omega = (double)(nd == 3 ? D - 2 * m : 1) * (H - 2 * m) * (W - 2 * m);
   return true;
 }
-inline long long jac_per(const JacGeom& g) { return (long long)g.nzc * g.nty * g.ntx; }     // workgroups per sample
-inline bool jac_vec(const JacGeom& g, const void* p) { return g.W % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool jac_penalty_ok(float eps, int power) { return (power == 1 || power == 2) && eps >= 0.f && eps <= 3.0e38f; }
 
 template <int MODE>
 void jac_launch_fwd(int nd, const float* flow, const JacGeom& g, unsigned nwg, double* part, float* detmap, hipStream_t st) {
-  const bool vec = jac_vec(g, flow);
+  const bool vec = vec_ok(g.W, flow);
   if (nd == 3) {
-    if (vec) jac_fwd_k<true, true, MODE><<<nwg, JAC_T, 0, st>>>(flow, g, part, detmap);
-    else jac_fwd_k<true, false, MODE><<<nwg, JAC_T, 0, st>>>(flow, g, part, detmap);
+    if (vec) jac_fwd_k<true, true, MODE><<<nwg, NT, 0, st>>>(flow, g, part, detmap);
+    else jac_fwd_k<true, false, MODE><<<nwg, NT, 0, st>>>(flow, g, part, detmap);
   } else {
-    if (vec) jac_fwd_k<false, true, MODE><<<nwg, JAC_T, 0, st>>>(flow, g, part, detmap);
-    else jac_fwd_k<false, false, MODE><<<nwg, JAC_T, 0, st>>>(flow, g, part, detmap);
+    if (vec) jac_fwd_k<false, true, MODE><<<nwg, NT, 0, st>>>(flow, g, part, detmap);
+    else jac_fwd_k<false, false, MODE><<<nwg, NT, 0, st>>>(flow, g, part, detmap);
   }
 }
 
@@ -474,7 +389,7 @@ extern "C" long long dfmir_jacdet_ws_floats(int nd, int B, int D, int H, int W) 
   JacGeom g;
   double omega;
   if (!jac_geom(nd, B, D, H, W, 1, &g, &omega)) return -1;
-  return 2 * JAC_SLOT * B * jac_per(g);
+  return 2 * JAC_SLOT * B * wg_per_plane(g);
 }
 
 extern "C" int dfmir_jacdet_fwd(int nd, const float* flow, float* ws, float* out, int B, int D, int H, int W, int border,
@@ -485,11 +400,11 @@ extern "C" int dfmir_jacdet_fwd(int nd, const float* flow, float* ws, float* out
                jac_geom(nd, B, D, H, W, border, &g, &omega));
   g.eps = eps; g.power = power;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nwg = (unsigned)(B * jac_per(g));
+  const unsigned nwg = (unsigned)(B * wg_per_plane(g));
   double* part = reinterpret_cast<double*>(ws);
   jac_launch_fwd<JAC_PENALTY>(nd, flow, g, nwg, part, nullptr, st);
   DF_LAUNCH_CHECK();
-  df_slot_mean_k<JAC_T><<<1, JAC_T, 0, st>>>(part, (int)nwg, omega * B, out);    // loss = (the slots, in a fixed order) / N
+  df_slot_mean_k<NT><<<1, NT, 0, st>>>(part, (int)nwg, omega * B, out);    // loss = (the slots, in a fixed order) / N
   DF_LAUNCH_CHECK();
   return 0;
 }
@@ -501,15 +416,15 @@ extern "C" int dfmir_jacdet_bwd(int nd, const float* flow, const float* gout, fl
   DF_ARG_CHECK(flow && gout && dflow && jac_penalty_ok(eps, power) && jac_geom(nd, B, D, H, W, border, &g, &omega));
   g.eps = eps; g.power = power;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nwg = (unsigned)(B * jac_per(g));
+  const unsigned nwg = (unsigned)(B * wg_per_plane(g));
   const float k = (float)(0.5 / (omega * B));
-  const bool vec = jac_vec(g, flow);
+  const bool vec = vec_ok(g.W, flow);
   if (nd == 3) {
-    if (vec) jac_bwd_k<true, true><<<nwg, JAC_T, 0, st>>>(flow, gout, k, g, dflow);
-    else jac_bwd_k<true, false><<<nwg, JAC_T, 0, st>>>(flow, gout, k, g, dflow);
+    if (vec) jac_bwd_k<true, true><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
+    else jac_bwd_k<true, false><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
   } else {
-    if (vec) jac_bwd_k<false, true><<<nwg, JAC_T, 0, st>>>(flow, gout, k, g, dflow);
-    else jac_bwd_k<false, false><<<nwg, JAC_T, 0, st>>>(flow, gout, k, g, dflow);
+    if (vec) jac_bwd_k<false, true><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
+    else jac_bwd_k<false, false><<<nwg, NT, 0, st>>>(flow, gout, k, g, dflow);
   }
   DF_LAUNCH_CHECK();
   return 0;
@@ -520,7 +435,7 @@ extern "C" int dfmir_jacdet_map(int nd, const float* flow, float* detmap, int B,
   JacGeom g;
   double omega;
   DF_ARG_CHECK(flow && detmap && jac_geom(nd, B, D, H, W, border, &g, &omega));
-  jac_launch_fwd<JAC_MAP>(nd, flow, g, (unsigned)(B * jac_per(g)), nullptr, detmap, (hipStream_t)stream);
+  jac_launch_fwd<JAC_MAP>(nd, flow, g, (unsigned)(B * wg_per_plane(g)), nullptr, detmap, (hipStream_t)stream);
   DF_LAUNCH_CHECK();
   return 0;
 }
@@ -535,9 +450,9 @@ extern "C" int dfmir_jacdet_stats(int nd, const float* flow, float* ws, double* 
   g.off = log_offset; g.lfloor = log_floor;
   hipStream_t st = (hipStream_t)stream;
   double* part = reinterpret_cast<double*>(ws);
-  jac_launch_fwd<JAC_STATS>(nd, flow, g, (unsigned)(B * jac_per(g)), part, nullptr, st);
+  jac_launch_fwd<JAC_STATS>(nd, flow, g, (unsigned)(B * wg_per_plane(g)), part, nullptr, st);
   DF_LAUNCH_CHECK();
-  jac_stats_fin_k<<<(unsigned)B, JAC_T, 0, st>>>(part, (int)jac_per(g), omega, stats);
+  jac_stats_fin_k<<<(unsigned)B, NT, 0, st>>>(part, (int)wg_per_plane(g), omega, stats);
   DF_LAUNCH_CHECK();
   return 0;
 }

@@ -41,7 +41,7 @@ FAMILIES = ("noise", "smooth")
 
 SHAPES_3D = [(2, 3, 3, 3, 3), (1, 3, 5, 6, 7), (2, 3, 13, 17, 19), (1, 3, 1, 20, 33), (1, 2, 4, 9, 70), (1, 1, 3, 3, 260)]
 SHAPES_2D = [(2, 2, 3, 3), (2, 2, 9, 11), (1, 2, 37, 41), (1, 2, 5, 300)]
-TILE_Y, TILE_X, CHUNK_Z = 8, 64, 16          # BEND_TY, BEND_TX, BEND_ZC of bend.hip
+TILE_Y, TILE_X, CHUNK_Z = 8, 64, 16          # TY, TX, ZC of csrc/stencil_tile.h
 SHAPES_TILE = ([(1, 1, d, 5, 8) for d in (CHUNK_Z - 1, CHUNK_Z, CHUNK_Z + 1)] +
                [(1, 1, 4, h, 6) for h in (TILE_Y - 1, TILE_Y, TILE_Y + 1)] +
                [(1, 1, 4, 4, w) for w in (TILE_X - 1, TILE_X, TILE_X + 1)] +

@@ -58,7 +58,7 @@ AMPLITUDE = {"fold": 3.0, "mild": 0.5}
 LOG_OFFSET = {"fold": 3.0, "mild": 0.0}
 COMBOS = ((2, 0.0), (2, 0.5), (1, 0.0))          # (power, eps)
 
-TILE_Y, TILE_X, CHUNK_Z = 8, 64, 16          # JAC_TY, JAC_TX, JAC_ZC of jacdet.hip
+TILE_Y, TILE_X, CHUNK_Z = 8, 64, 16          # TY, TX, ZC of csrc/stencil_tile.h
 SHAPES_3D = ([(2, 3, 3, 3, 3), (1, 3, 5, 6, 7), (2, 3, 13, 17, 19), (1, 3, 4, 9, 70), (1, 3, 3, 3, 260)] +
              [(1, 3, d, 5, 8) for d in (CHUNK_Z - 1, CHUNK_Z, CHUNK_Z + 1)] +
              [(1, 3, 4, h, 6) for h in (TILE_Y - 1, TILE_Y, TILE_Y + 1)] +
