@@ -201,7 +201,11 @@ __global__ __launch_bounds__(256) void patchnce_fwd_k(const float* __restrict__ 
 }
 
 // dq[c][r] = (g_r/T) * ( sum_{j != i} probs[r][1+j] k[c][j] + (probs[r][0]-1) k[c][r] )
+// LDS: key tile [JT][C+1] + dls [TI][JT] + os [C][TI] floats within 64 KB, i.e. C <= NCE_BWD_CMAX = 330 (two channels per
+// thread at the most); wider rows are refused by the launcher and, ahead of the forward, by ops.PatchNCEFn / NCETermsFn
 #define NCE_JT 32
+#define NCE_BWD_CMAX 330
+#define NCE_BWD_NCP ((NCE_BWD_CMAX + 255) / 256)
 __global__ __launch_bounds__(256) void patchnce_bwd_k(const float* __restrict__ dloss,
                                                       const float* __restrict__ probs,
                                                       const float* __restrict__ k, float* __restrict__ dq,
@@ -216,10 +220,10 @@ __global__ __launch_bounds__(256) void patchnce_bwd_k(const float* __restrict__ 
   const long long g0 = (r0 / R) * R;
   const int i0 = (int)(r0 - g0);
   const long long ld = (long long)R + 1;
-  const int ncp = (C + 255) / 256;  // channels per thread (<= 4)
-  float acc[4][NCE_TI];
+  const int ncp = (C + 255) / 256;  // channels per thread (<= NCE_BWD_NCP)
+  float acc[NCE_BWD_NCP][NCE_TI];
 #pragma unroll
-  for (int u = 0; u < 4; ++u)
+  for (int u = 0; u < NCE_BWD_NCP; ++u)
 #pragma unroll
     for (int ii = 0; ii < NCE_TI; ++ii) acc[u][ii] = 0.f;
 
@@ -239,7 +243,7 @@ __global__ __launch_bounds__(256) void patchnce_bwd_k(const float* __restrict__ 
     }
     __syncthreads();
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < NCE_BWD_NCP; ++u) {
       const int c = tid + 256 * u;
       if (u < ncp && c < C) {
         for (int jj = 0; jj < NCE_JT; ++jj) {
@@ -252,7 +256,7 @@ __global__ __launch_bounds__(256) void patchnce_bwd_k(const float* __restrict__ 
   }
   __syncthreads();
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
+  for (int u = 0; u < NCE_BWD_NCP; ++u) {
     const int c = tid + 256 * u;
     if (u < ncp && c < C) {
 #pragma unroll
@@ -501,14 +505,16 @@ extern "C" int dfmir_patchnce_bwd(const float* dloss, const float* probs, const 
   DF_ARG_CHECK(dloss && probs && k && dq && rows > 0 && C > 0 && G > 0 && T > 0.f);
   DF_ARG_CHECK(rows % G == 0);
   const int R = (int)(rows / G);
-  DF_ARG_CHECK(R % NCE_TI == 0 && C <= 1024);
+  DF_ARG_CHECK(R % NCE_TI == 0);
   if (R == 256 && C <= 256 && (C & 15) == 0) {
     patchnce_bwd_mfma_k<<<(unsigned)(rows / NCE_TI), 256, 0, (hipStream_t)stream>>>(dloss, probs, k, dq, rows, C, 1.f / T);
     DF_LAUNCH_CHECK();
     return 0;
   }
+  DF_ARG_CHECK(C <= NCE_BWD_CMAX);
   const size_t sh = ((size_t)NCE_JT * (C + 1) + NCE_TI * NCE_JT + (size_t)C * NCE_TI) * sizeof(float);
-  DF_ARG_CHECK(sh <= 64 * 1024);
+  static_assert(((size_t)NCE_JT * (NCE_BWD_CMAX + 1) + NCE_TI * NCE_JT + (size_t)NCE_BWD_CMAX * NCE_TI) * sizeof(float) <= 64 * 1024,
+                "NCE_BWD_CMAX must fit the kernel's LDS");
   patchnce_bwd_k<<<(unsigned)(rows / NCE_TI), 256, sh, (hipStream_t)stream>>>(dloss, probs, k, dq, rows, C, R,
                                                                          1.f / T);
   DF_LAUNCH_CHECK();

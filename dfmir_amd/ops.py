@@ -2017,10 +2017,10 @@ class PatchGatherFn(Function):
 
     @staticmethod
     def forward(ctx, feat, ids, groups=1, distinct=True):
+        ids = _c(ids.to(torch.int64))            # (int32 ids are welcome: widened before the dtype check)
         _need(feat, ids)
         ctx.stash = getattr(feat, "_df_tap_stash", None) if feat.is_contiguous() else None
         feat = _c(feat)
-        ids = _c(ids.to(torch.int64))
         B, C = feat.shape[0], feat.shape[1]
         S = feat.numel() // (B * C)
         G = int(groups)
@@ -2070,7 +2070,7 @@ def ids_distinct(ids, groups=1):
     seen = getattr(ids, "_df_distinct_checked", None)
     if seen is not None and seen[0] == key:
         return seen[1]
-    if torch.cuda.is_current_stream_capturing():
+    if ids.is_cuda and torch.cuda.is_current_stream_capturing():    # (a host tensor: no device to ask, nothing captured)
         return False                          # no host round trip inside a capture: take the safe (atomic) form
     srt = torch.sort(ids.reshape(int(groups), -1), dim=1).values
     hit = bool((srt[:, 1:] != srt[:, :-1]).all()) if srt.shape[1] > 1 else True
@@ -2112,6 +2112,18 @@ def l2norm_rows(x, eps=1e-7):
     return L2NormFn.apply(x, eps)
 
 
+PATCHNCE_BWD_MAX_C = 330     # NCE_BWD_CMAX of csrc/patchnce.hip: the scalar backward's key tile in 64 KB of LDS
+
+
+def _patchnce_need_bwd(C, what):
+    """The forward takes rows of up to 1019 channels, dfmir_patchnce_bwd only C <= 330 (its matrix-core form C <= 256).
+    Refuse BEFORE the forward when q wants a gradient the library cannot compute, instead of raising in the middle of
+    autograd."""
+    if C > PATCHNCE_BWD_MAX_C:
+        raise DfmirHipError("%s: no gradient kernel for %d channels (the backward takes C <= %d); detach q for the "
+                            "loss value alone" % (what, C, PATCHNCE_BWD_MAX_C))
+
+
 class PatchNCEFn(Function):
     """q, k [C, rows] -> per-row InfoNCE loss [rows]; gradient flows to q only (k is detached,
     patchnce.py:17)."""
@@ -2124,6 +2136,8 @@ class PatchNCEFn(Function):
         if rows % groups != 0:
             raise DfmirHipError("patchnce: rows %d not divisible by groups %d" % (rows, groups))
         R = rows // groups
+        if ctx.needs_input_grad[0]:
+            _patchnce_need_bwd(C, "patchnce")
         loss = torch.empty(rows, device=q.device, dtype=torch.float32)
         probs = torch.empty((rows, R + 1), device=q.device, dtype=torch.float32)
         check(lib().dfmir_patchnce_fwd(_p(q), _p(k), _p(loss), _p(probs), rows, C, groups, float(T), _st()))
@@ -2158,6 +2172,9 @@ class NCETermsFn(Function):
         ks = [_c(t) for t in qk[L:]]
         _need(*qs)
         _need(*ks)
+        for l in range(L):
+            if ctx.needs_input_grad[4 + l]:
+                _patchnce_need_bwd(qs[l].shape[0], "nce_terms")
         rows = qs[0].shape[1]
         if rows % n_terms or rows % groups:
             raise DfmirHipError("nce_terms: %d rows, %d terms, %d groups" % (rows, n_terms, groups))
@@ -2274,6 +2291,7 @@ def draw_patch_ids(sizes, n_sets, P, device):
 def patch_gather_multi(srcs, ids):
     """srcs: G tensors [Bper, C, *sp] (no gradient: the detached key side); ids [G, P] -> [C, G*Bper*P]."""
     _need(*srcs)
+    ids = _c(ids.to(torch.int64))
     _need(ids)
     G = len(srcs)
     srcs = [_c(s) for s in srcs]
@@ -2282,7 +2300,6 @@ def patch_gather_multi(srcs, ids):
     for s_ in srcs:
         if tuple(s_.shape) != tuple(srcs[0].shape):
             raise DfmirHipError("patch_gather_multi: sources differ in shape")
-    ids = _c(ids.to(torch.int64))
     if ids.dim() != 2 or ids.shape[0] != G:
         raise DfmirHipError("patch_gather_multi: ids must be [G, P]")
     Pn = ids.shape[1]
@@ -2318,6 +2335,7 @@ def nce_head_multi(srcs, ids, mlp0, mlp2, eps=1e-7):
     Bper, C = srcs[0].shape[0], srcs[0].shape[1]
     S = srcs[0].numel() // (Bper * C)
     ids = _c(ids.to(torch.int64))
+    _need(ids)
     out, _, _, _, _ = _nce_head_launch([s_.data_ptr() for s_ in srcs], len(srcs), ids, mlp0, mlp2, Bper, C, S, ids.shape[1], eps,
                                        srcs[0].device, False)
     return out
@@ -2330,10 +2348,10 @@ class NceHeadFn(Function):
 
     @staticmethod
     def forward(ctx, feat, ids, w1, b1, w2, b2, mlp0, mlp2, eps, distinct):
+        ids = _c(ids.to(torch.int64))
         _need(feat, ids)
         ctx.stash = getattr(feat, "_df_tap_stash", None) if feat.is_contiguous() else None
         feat = _c(feat)
-        ids = _c(ids.to(torch.int64))
         G, Pn = ids.shape
         B, C = feat.shape[0], feat.shape[1]
         if B % G:

@@ -1,8 +1,9 @@
 """Plain float64 references (torch, CPU) of the operations around the convolutions: masked L1, flow smoothness
-(Grad_Loss), windowed NCC, InstanceNorm (+ReLU, +residual), Adam, the displacement-field warp, the VecInt step and the linear
-resize.  TEST infrastructure, written from the formulas in the docstrings of oracle/dfmir_oracle.py; tests/test_ref64.py checks
-each one against the fp32 oracle on small inputs, the GPU tests (tests/test_gpu_pointwise_fp64.py, tests/test_gpu_warp_fp64.py)
-compare the HIP kernels with them.
+(Grad_Loss), windowed NCC, InstanceNorm (+ReLU, +residual), Adam, the displacement-field warp, the VecInt step, the linear
+resize and the PatchNCE path (patch gather, L2 normalisation, the MLP head, InfoNCE rows, the loss algebra).  TEST
+infrastructure, written from the formulas in the docstrings of oracle/dfmir_oracle.py and the kernels' comments;
+tests/test_ref64.py checks each one against the fp32 oracle on small inputs, the GPU tests (tests/test_gpu_pointwise_fp64.py,
+tests/test_gpu_warp_fp64.py, tests/test_gpu_patchnce_fp64.py) compare the HIP kernels with them.
 
 Every function takes tensors of any float dtype and computes in `dtype` (float64 by default); gradients come from
 autograd on the returned value.  `dtype=torch.float32` turns a function into a plain fp32 restatement (another valid
@@ -212,3 +213,98 @@ def resize_linear(x, out_sp, mult=1.0, dtype=torch.float64):
         i1 = (i0 + 1).clamp(max=n_in - 1)
         y = (1.0 - l) * y.index_select(ax, i0) + l * y.index_select(ax, i1)
     return y * mult
+
+
+# ------------------------------------------------------------------------------------------------- PatchNCE
+def l2_normalize_grad(x, dy, eps=1e-7, dtype=torch.float64):
+    """dx of y = x / (n + eps), n = sqrt(sum_c x^2), rows [rows, C]:  dx = dy / (n + eps) - x (dy . x) / (n (n + eps)^2),
+    the second term 0 where n == 0 (a zero row: y = 0, dx = dy / eps).  Autograd through sqrt gives NaN there, so the
+    zero row is DEFINED here, as l2norm_bwd_k defines it."""
+    x, dy = _t(x, dtype), _t(dy, dtype)
+    n = x.pow(2).sum(1, keepdim=True).sqrt()
+    dot = (dy * x).sum(1, keepdim=True)
+    safe = torch.where(n > 0, n, torch.ones_like(n))
+    k2 = torch.where(n > 0, dot / (n + eps) / (n + eps) / safe, torch.zeros_like(n))     # (this order: no n^3 to overflow in fp32)
+    return dy / (n + eps) - x * k2
+
+
+class _L2Normalize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, eps):
+        ctx.save_for_backward(x)
+        ctx.eps = eps
+        return x / (x.pow(2).sum(1, keepdim=True).sqrt() + eps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return l2_normalize_grad(x, dy, ctx.eps, x.dtype), None
+
+
+def l2_normalize(x, eps=1e-7, dtype=torch.float64):
+    """x / (sqrt(sum_c x^2) + eps) on [rows, C]; the gradient is l2_normalize_grad (written out, not autograd's)."""
+    return _L2Normalize.apply(_t(x, dtype), float(eps))
+
+
+def patchnce_rows(q, k, groups, T, dtype=torch.float64):
+    """Per-row InfoNCE loss of q, k [rows, C]; consecutive groups of R = rows / groups rows share negatives.  Logits
+    q . k^T within a group, the diagonal replaced by -10, the positive logit q_i . k_i prepended, all divided by T;
+    loss_i = logsumexp(row i) - positive_i, with an explicit max shift.  k is detached: the gradient flows to q only."""
+    q, k = _t(q, dtype), _t(k, dtype).detach()
+    rows, Cn = q.shape
+    R = rows // groups
+    assert R * groups == rows
+    qg, kg = q.reshape(groups, R, Cn), k.reshape(groups, R, Cn)
+    pos = (qg * kg).sum(2, keepdim=True)
+    neg = torch.matmul(qg, kg.transpose(1, 2)).masked_fill(torch.eye(R, dtype=torch.bool)[None], -10.0)
+    z = torch.cat([pos, neg], 2) / T
+    m = z.detach().max(2, keepdim=True).values
+    lse = m[..., 0] + torch.log(torch.exp(z - m).sum(2))
+    return (lse - z[..., 0]).reshape(rows)
+
+
+def _ids2(ids, groups):
+    return ids.reshape(int(groups), -1).long()
+
+
+def patch_gather(feat, ids, groups=1, dtype=torch.float64):
+    """feat [B, C, *sp], ids [G, P] (or [P], G = 1) -> rows [B * P, C]: row b * P + p is feat[b, :, ids[b // (B / G), p]]
+    over the flattened spatial positions."""
+    f = _t(feat, dtype)
+    B, Cn = f.shape[:2]
+    ids = _ids2(ids, groups)
+    bpg = B // ids.shape[0]
+    ff = f.reshape(B, Cn, -1)
+    return torch.cat([ff[b][:, ids[b // bpg]].t() for b in range(B)], 0)
+
+
+def patch_gather_adjoint(drows, ids, groups, shape, dtype=torch.float64):
+    """The adjoint of patch_gather: drows [B * P, C] scattered into zeros of `shape` by index_add_; repeated ids accumulate."""
+    d = _t(drows, dtype)
+    B, Cn = shape[:2]
+    ids = _ids2(ids, groups)
+    P, bpg = ids.shape[1], B // ids.shape[0]
+    out = torch.zeros(B, Cn, math.prod(shape[2:]), dtype=dtype)
+    for b in range(B):
+        out[b].index_add_(1, ids[b // bpg], d[b * P:(b + 1) * P].t())
+    return out.reshape(shape)
+
+
+def nce_head(feat, ids, w1, b1, w2, b2, eps=1e-7, groups=1, dtype=torch.float64):
+    """gather -> relu(x W1^T + b1) -> W2^T + b2 -> l2_normalize: rows [B * P, nc]; w1 [nc, C], w2 [nc, nc] (Linear layout)."""
+    x = patch_gather(feat, ids, groups, dtype)
+    h = torch.relu(x @ _t(w1, dtype).t() + _t(b1, dtype))
+    return l2_normalize(h @ _t(w2, dtype).t() + _t(b2, dtype), eps, dtype)
+
+
+def segment_means(rows, n_terms, scale, dtype=torch.float64):
+    """out[t] = scale * sum_l mean(rows[l, t * seg : (t + 1) * seg]) for rows [L, T * seg]."""
+    r = _t(rows, dtype)
+    L = r.shape[0]
+    return scale * r.reshape(L, int(n_terms), -1).mean(2).sum(0)
+
+
+def scalar_combine(M, xs, dtype=torch.float64):
+    """out[j] = sum_i M[j][i] x_i for one-element tensors x_i."""
+    Mt = torch.as_tensor(M, dtype=torch.float32).to(dtype)         # the coefficients reach the kernel as fp32
+    return Mt @ torch.stack([_t(x, dtype).reshape(()) for x in xs])

@@ -166,3 +166,45 @@ def test_checkpoint_keys_equal_the_reference_written_files():
         # the MLPs are created from the five tapped features' channel counts (networks.py:587-595): 1, 2*ngf, 4*ngf x 3
         f.create_mlp([torch.zeros(1, c, 1, 1) for c in (1, 2 * ngf, 4 * ngf, 4 * ngf, 4 * ngf)])
         assert sig(f) == want["F"]
+
+
+def test_ids_distinct_tags_cache_and_groups():
+    """ops.ids_distinct decides between the plain-store scatter (a data race on repeated ids) and the accumulating one.  On
+    host tensors: a tagged tensor is trusted only while the tag is fresh; an in-place write makes it stale and the content
+    decides again; the verdict is cached ON the tensor per (version, address, groups), so a second tensor at the same address
+    is judged by its own content; ids are distinct per GROUP; a single id per group is distinct."""
+    ids = torch.tensor([4, 9, 2, 7, 0, 5])
+    assert not hasattr(ids, "_df_distinct_checked")
+    assert ops.ids_distinct(ids) is True and ids._df_distinct_checked[1] is True
+    rep = torch.tensor([4, 9, 4, 7, 0, 5])
+    assert ops.ids_distinct(rep) is False
+    assert ops.ids_distinct(rep, 2) is False                       # [4 9 4] / [7 0 5]: the repeat sits inside group 0
+    assert ops.ids_distinct(rep, 3) is True                        # [4 9] / [4 7] / [0 5]: now in two groups
+    assert ops.ids_distinct(torch.tensor([4, 4, 9, 7, 0, 5]), 3) is False
+    assert ops.ids_distinct(torch.tensor([[1, 2, 3], [3, 2, 1]]), 2) is True       # the same id in two groups
+    assert ops.ids_distinct(torch.tensor([[1, 2, 3], [3, 2, 1]]).reshape(-1), 1) is False
+    # a tag is believed without looking (that is its point) -- and only while version and address still match
+    tagged = ops.mark_distinct(torch.tensor([1, 1, 2]))
+    assert ops.ids_distinct(tagged) is True
+    tagged[2] = 5                                                   # in-place write: the tag is stale, the content decides
+    assert ops.ids_distinct(tagged) is False
+    tagged[1] = 7
+    assert ops.ids_distinct(tagged) is True
+    # the cached verdict: same tensor state -> no second look; after a write -> a fresh look
+    t = torch.tensor([3, 1, 2])
+    assert ops.ids_distinct(t) is True
+    key = t._df_distinct_checked[0]
+    t._df_distinct_checked = (key, False)                           # plant a verdict: it must be returned as it stands
+    assert ops.ids_distinct(t) is False
+    assert ops.ids_distinct(t, 3) is True                           # another group count is another key
+    t[0] = 1
+    assert ops.ids_distinct(t) is False and t._df_distinct_checked[0] != key
+    # a second tensor at the same address (a view shares it, and the version) carries no verdict of its own
+    base = torch.tensor([6, 6, 8, 9])
+    assert ops.ids_distinct(base) is False
+    alias = base.view(4)
+    assert alias.data_ptr() == base.data_ptr() and not hasattr(alias, "_df_distinct_checked")
+    assert ops.ids_distinct(alias[2:]) is True and ops.ids_distinct(alias) is False
+    # P == 1: one id per group
+    assert ops.ids_distinct(torch.tensor([5])) is True and ops.ids_distinct(torch.tensor([5, 5, 5]), 3) is True
+    assert ops.ids_distinct(torch.tensor([5, 5, 5], dtype=torch.int32), 1) is False

@@ -345,3 +345,158 @@ def test_warp_and_resize_size_functions_at_their_boundaries():
             args = [2, 3, 4, 5, 6, 7, 8]
             args[hole] = v
             assert ws(*args) == 0, args
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# PatchNCE path
+def _nce_module():
+    from tests import test_gpu_patchnce_fp64 as G
+    return G
+
+
+@pytest.mark.parametrize("shape", [(37, 1), (50, 3), (20, 24), (5, 300)], ids=lambda s: "rows%d-C%d" % s)
+def test_l2_normalize(shape):
+    x, dy = C.randn(901, *shape), C.randn(902, *shape)
+    ref = val_and_grads(lambda t: (O.l2_normalize(t) * dy).sum(), x)
+    got = val_and_grads(lambda t: (R.l2_normalize(t) * dy.double()).sum(), x, dtype=torch.float64)
+    assert rel(R.l2_normalize(x), O.l2_normalize(x)) <= 2e-5
+    if shape[1] > 1:                                                 # (C = 1: dx is a pure cancellation, the fp32 oracle 1e-2 off)
+        assert rel(got[1], ref[1]) <= 1e-4
+    # the written-out gradient is autograd's wherever autograd has one, at any eps
+    for eps in (1e-7, 1e-3):
+        xd = x.double().requires_grad_()
+        ((xd / (xd.pow(2).sum(1, keepdim=True).sqrt() + eps)) * dy.double()).sum().backward()
+        # (C = 1: two terms of size |dy| / n cancel to |dy| eps / n^2, a factor n / eps ~ 1e7 that float64 round-off rides on)
+        assert rel(R.l2_normalize_grad(x, dy, eps), xd.grad) <= (1e-12 if shape[1] > 1 else 1e-8)
+    # a zero row: y = 0, dx = dy / eps (defined, where autograd through sqrt has NaN)
+    x[2] = 0.0
+    xd = x.double().requires_grad_()
+    y = R.l2_normalize(xd, 1e-3)
+    (y * dy.double()).sum().backward()
+    assert bool((y[2] == 0).all()) and torch.equal(xd.grad[2], dy[2].double() / 1e-3) and bool(torch.isfinite(xd.grad).all())
+    assert R.l2_normalize(x, dtype=torch.float32).dtype == torch.float32
+
+
+@pytest.mark.parametrize("cfg", [(32, 24, 2, 0.07), (16, 3, 3, 1.0), (48, 64, 1, 0.07), (16, 1, 2, 0.01)],
+                         ids=lambda c: "R%d-C%d-G%d-T%g" % c)
+def test_patchnce_rows(cfg):
+    Rr, Cn, G, T = cfg
+    q, k = O.l2_normalize(C.randn(903, Rr * G, Cn)), O.l2_normalize(C.randn(904, Rr * G, Cn))
+    cot = C.randn(905, Rr * G)
+    ref = val_and_grads(lambda t: (O.patchnce_loss(t, k, G, T) * cot).sum(), q)
+    got = val_and_grads(lambda t: (R.patchnce_rows(t, k, G, T) * cot.double()).sum(), q, dtype=torch.float64)
+    assert rel(R.patchnce_rows(q, k, G, T), O.patchnce_loss(q, k, G, T)) <= 2e-5
+    assert rel(got[1], ref[1]) <= 1e-4
+    assert rel(R.patchnce_rows(q, k, 1, T), O.patchnce_loss(q, k, G, T, all_negatives=True)) <= 2e-5
+    # the oracle itself evaluated in float64: the same function to round-off
+    assert rel(R.patchnce_rows(q, k, G, T), O.patchnce_loss(q.double(), k.double(), G, T)) <= 1e-12
+    kd = k.double().requires_grad_()                                  # no gradient reaches k
+    assert torch.autograd.grad(R.patchnce_rows(q.double().requires_grad_(), kd, G, T).sum(), kd, allow_unused=True)[0] is None
+
+
+def test_patch_gather_and_head_against_the_patch_sampler():
+    B, Cn, H, W, P, nc = 2, 5, 6, 7, 9, 8
+    feat = C.randn(906, B, Cn, H, W)
+    ids = C.patch_ids(3, 0, H * W, P)
+    plain = O.PatchSampler(nc, False)
+    assert rel(R.l2_normalize(R.patch_gather(feat, ids)), plain([feat], P, [ids])[0][0]) <= 2e-5
+    smp = O.PatchSampler(nc, True)
+    smp.create_mlp([feat])
+    with torch.no_grad():
+        for i, p_ in enumerate(smp.mlp_0.parameters()):
+            p_.copy_(C.randn(907 + i, *p_.shape) * 0.5)
+    cot = C.randn(911, B * P, nc)
+    fo = feat.clone().requires_grad_()
+    (smp([fo], P, [ids])[0][0] * cot).sum().backward()
+    leaves = [t.detach().double().requires_grad_() for t in [feat] + list(smp.mlp_0.parameters())]
+    y = R.nce_head(leaves[0], ids, *leaves[1:])
+    (y * cot.double()).sum().backward()
+    assert rel(y, smp([feat], P, [ids])[0][0]) <= 2e-5
+    for a, b in zip([t.grad for t in leaves], [fo.grad] + [p_.grad for p_ in smp.mlp_0.parameters()]):
+        assert rel(a, b) <= 1e-4
+    # grouped ids and the adjoint: <gather(f), d> == <f, adjoint(d)>, repeated ids accumulate
+    G, Bper = 3, 2
+    f = C.randn(912, G * Bper, Cn, H, W).double()
+    gids = torch.stack([C.patch_ids(4 + g, 0, H * W, P) for g in range(G)])
+    gids[1, 4] = gids[1, 0]
+    rows = R.patch_gather(f, gids, G)
+    for b in range(G * Bper):
+        assert torch.equal(rows[b * P:(b + 1) * P], f[b].reshape(Cn, -1)[:, gids[b // Bper]].t())
+    d = C.randn(913, G * Bper * P, Cn).double()
+    adj = R.patch_gather_adjoint(d, gids, G, f.shape)
+    assert abs(float((rows * d).sum() - (f * adj).sum())) <= 1e-12 * float(d.abs().sum())
+    pos = int(gids[1, 0])
+    assert torch.equal(adj[2, :, pos // W, pos % W], d[2 * P + 0] + d[2 * P + 4])
+
+
+def test_segment_means_and_scalar_combine():
+    rows = C.randn(914, 5, 3 * 257).double()
+    ref = sum(rows[l].reshape(3, 257).mean(1) for l in range(5)) * -0.3
+    assert rel(R.segment_means(rows, 3, -0.3), ref) <= 1e-14
+    M, xs = C.randn(915, 4, 3), [C.randn(916 + i, 1).double() for i in range(3)]
+    assert rel(R.scalar_combine(M.tolist(), xs), M.double() @ torch.cat(xs)) <= 1e-14
+
+
+def _nce_variants(G):
+    for case in G.VARIANT_SHAPES:
+        for variant in ("plain", "correlated", "ties", "unnormalised", "zero-row"):
+            for T in ((1.0, 0.01, G.T0) if variant == "plain" else (G.T0,)):
+                yield case, variant, T
+
+
+def test_patchnce_gpu_inputs_are_testable():
+    """Every shape of the GPU module's table and every well-conditioned variant: the fp32 oracle sits a factor 10 inside the bars
+    in the sharp metrics (so the bars stand on their own there); the correlated keys give float64 row losses in [0.05, 1]; the
+    unnormalised input, compared through bounded(oracle=...), stays under the 10 x bar cap."""
+    G = _nce_module()
+    worst = [0.0, 0.0]
+    cases = [(c, "plain", G.T0, 700) for c in G.NCE_CASES] + [v + (720,) for v in _nce_variants(G)]    # the GPU tests' seeds
+    for (name, Rr, Cn, Gr), variant, T, seed in cases:
+        q, k, cot = G.nce_inputs(Rr, Cn, Gr, variant, seed=seed)
+        lr, dqr = G.nce_reference(q, k, cot, Gr, T)
+        lo, dqo = G.nce_oracle(q, k, cot, Gr, T)
+        if variant == "correlated":
+            assert 0.05 <= float(lr.min()) and float(lr.max()) <= 1.0, (name, float(lr.min()), float(lr.max()))
+        if variant in G.ILL_VARIANTS:
+            assert G.oracle_bound(lr, lo, G.BAR)[0] <= 10 * G.BAR, name
+            assert G.oracle_bound(dqr, dqo, G.BAR_DQ)[0] <= 10 * G.BAR_DQ, name
+        else:
+            worst[0], worst[1] = max(worst[0], G.rows_err(lo, lr)), max(worst[1], G.per_row_err(dqo, dqr))
+            assert G.rows_err(lo, lr) <= G.BAR / 10 and G.per_row_err(dqo, dqr) <= G.BAR_DQ / 10, (name, variant, T)
+        assert bool((dqr[cot == 0] == 0).all())
+    assert worst[0] > 0.0 and worst[1] > 0.0
+
+
+@pytest.mark.parametrize("route,P,all_neg", _nce_module().ROUTES,
+                         ids=["%s-P%d-%s" % (r, P, "allneg" if a else "perimage") for r, P, a in _nce_module().ROUTES])
+def test_host_route_inputs_are_testable(route, P, all_neg):
+    """The end-to-end routes compare their gradients through bounded(oracle=...): the oracle in fp32 against itself in float64,
+    on the GPU test's inputs and a seeded id draw of the same size, stays under the cap."""
+    G = _nce_module()
+    fq, fk, params, nc = G.route_inputs(route)
+    Pn = min(P, 256)
+    ids = C.patch_ids(7, 0, 256, Pn)
+    cot = G.route_cot(2 * Pn)
+    ref = G.route_oracle(route, fq, fk, params, nc, ids, all_neg, cot, torch.float64)
+    o32 = G.route_oracle(route, fq, fk, params, nc, ids, all_neg, cot, torch.float32)
+    assert G.rows_err(o32[0], ref[0]) <= G.BAR / 10
+    for r, o, bar in zip(ref[1:], o32[1:], (G.BAR_DFEAT, G.BAR_DQ, G.BAR_DQ, G.BAR_DQ, G.BAR_DQ)):
+        assert G.oracle_bound(r, o, bar)[0] <= 10 * bar
+
+
+def test_l2norm_gpu_inputs_are_testable():
+    """ops.l2norm_rows' cases: plain fp32 torch stays far inside the bar in the per-row metric at every shape, scale and eps
+    with C > 1; at C = 1 against the scale the GPU test uses."""
+    G = _nce_module()
+    for (Cn, rows) in G.L2_SHAPES:
+        for scale in (1.0, 1e-6, 1e15):
+            for eps in (1e-7, 1e-3):
+                x, dy = G.l2_inputs(Cn, rows, scale)
+                yr, dxr = R.l2_normalize(x, eps), R.l2_normalize_grad(x, dy, eps)
+                yo, dxo = R.l2_normalize(x, eps, dtype=torch.float32), R.l2_normalize_grad(x, dy, eps, dtype=torch.float32)
+                assert G.per_row_err(yo, yr) <= G.BAR / 10
+                if Cn == 1:
+                    floor = float(dy.abs().max()) / (float(x.abs().min()) + eps)
+                    assert G.oracle_bound(dxr, dxo, G.BAR, floor=floor)[1] <= G.BAR / 10
+                else:
+                    assert G.per_row_err(dxo, dxr) <= G.BAR / 10, (Cn, rows, scale, eps)
