@@ -82,7 +82,8 @@ static inline int df_cu_count() {
 // FIXED-POINT integers into the scratch the caller handed over: integer addition is associative, so the result does not
 // depend on the order in which workgroups finish (fp32 atomics make every weight gradient run-to-run different in its
 // last bits).  fx = device pointer to {scale, 1 / scale} (a power of two such that the bound count * max|x| * max|dy| maps
-// below 2^61), nullptr outside a begin / end pair -- the kernels then add floats as before.
+// below 2^61; the bias pass gets the pair of its own bound count * max|dy|: losses.hip det_scale_k), nullptr outside a
+// begin / end pair -- the kernels then add floats as before.
 const float* df_det_fx();
 __device__ __forceinline__ void df_acc(float* base, long long idx, float v, const float* fx) {
   if (fx) atomicAdd(reinterpret_cast<unsigned long long*>(base) + idx, (unsigned long long)__float2ll_rn(v * fx[0]));

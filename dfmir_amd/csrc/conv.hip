@@ -999,7 +999,8 @@ static int bias_grad_launch(const float* dy, float* db, int N, int C, long long 
   if (nsplit > 64) nsplit = 64;
   if (nsplit < 1) nsplit = 1;
   DF_ARG_CHECK(N <= 65535);
-  bias_grad_k<<<dim3(C, N, nsplit), S >= 4096 ? 256 : 64, 0, st>>>(dy, db, N, C, S, nsplit, df_det_fx());
+  const float* fx = df_det_fx();                // deterministic mode: the db slots have the scale pair fx[2..3] (losses.hip)
+  bias_grad_k<<<dim3(C, N, nsplit), S >= 4096 ? 256 : 64, 0, st>>>(dy, db, N, C, S, nsplit, fx ? fx + 2 : nullptr);
   DF_LAUNCH_CHECK();
   return 0;
 }

@@ -1249,8 +1249,9 @@ extern "C" int dfmir_mul(const float* a, const float* b, float* out, long long n
   return 0;
 }
 // ---------------------------------------------------------------------------------------------
-// Deterministic weight gradients (include/dfmir_hip.h).  fx lives at the head of the caller's scratch; the 8-byte sum
-// slots follow at float offset DF_DET_HEAD.
+// Deterministic weight gradients (include/dfmir_hip.h).  fx lives at the head of the caller's scratch -- [0..1] the
+// {scale, 1 / scale} of the dW slots, [2..3] that of the db slots (only the bias pass, conv.hip bias_grad_launch, writes
+// those), [4..5] the operands' maxima where no probe came -- and the 8-byte sum slots follow at float offset DF_DET_HEAD.
 static thread_local const float* tl_det_fx = nullptr;
 const float* df_det_fx() { return tl_det_fx; }
 constexpr int DF_DET_HEAD = 8;
@@ -1261,14 +1262,23 @@ __global__ __launch_bounds__(256) void det_scale_k(const float* __restrict__ x_a
   __syncthreads();
   const float ay = reduce_absmax(dy_amax, dyn, sm);
   if (threadIdx.x) return;
-  // every sum the kernels form -- dW[.] = sum x * dy over `count` positions, db[.] = sum dy -- is bounded by B
-  const float B = count * fmaxf(ax, 1.f) * ay;
-  int e = 0;
-  if (B > 0.f && B < 3.0e38f) frexpf(B, &e);               // B < 2^e
-  int sh = 61 - e;
-  sh = sh > 120 ? 120 : (sh < -120 ? -120 : sh);
-  fx[0] = ldexpf(1.f, sh);
-  fx[1] = ldexpf(1.f, -sh);
+  // dW[.] = sum x * dy over `count` positions is bounded by count * max|x| * max|dy|, db[.] = sum dy by count * max|dy|:
+  // one {scale, 1 / scale} pair each (fx[0..1]: dW slots, fx[2..3]: db slots).  The exponent of a bound is the SUM of the
+  // frexpf exponents of its factors (f < 2^e each, so the product < 2^(sum)): integers, so a bound beyond the fp32 range
+  // cannot overflow while it is formed, and a small max|x| shrinks the dW quantum with it.  A zero factor (all sums are
+  // exact zeros) keeps the shift of a bound of 1; the shift is clamped so that both powers of two stay normal floats.
+  int ec = 0, ex = 0, ey = 0;
+  frexpf(count, &ec);
+  if (ax > 0.f && ax <= 3.4028235e38f) frexpf(ax, &ex);
+  if (ay > 0.f && ay <= 3.4028235e38f) frexpf(ay, &ey);
+  const bool zw = !(ax > 0.f) || !(ay > 0.f), zb = !(ay > 0.f);
+  int sw = zw ? 61 : 61 - (ec + ex + ey), sb = zb ? 61 : 61 - (ec + ey);
+  sw = sw > 126 ? 126 : (sw < -126 ? -126 : sw);
+  sb = sb > 126 ? 126 : (sb < -126 ? -126 : sb);
+  fx[0] = ldexpf(1.f, sw);
+  fx[1] = ldexpf(1.f, -sw);
+  fx[2] = ldexpf(1.f, sb);
+  fx[3] = ldexpf(1.f, -sb);
 }
 __global__ __launch_bounds__(256) void det_final_k(const long long* __restrict__ slots, const float* __restrict__ fx,
                                                    float* __restrict__ out, long long n) {
@@ -1308,7 +1318,7 @@ extern "C" int dfmir_det_end(const float* scratch, float* dw_out, long long n_dw
   hipStream_t st = (hipStream_t)stream;
   const long long* slots = reinterpret_cast<const long long*>(scratch + DF_DET_HEAD);
   if (n_dw) det_final_k<<<df_grid(n_dw, 256, 2048), 256, 0, st>>>(slots, scratch, dw_out, n_dw);
-  if (n_db) det_final_k<<<df_grid(n_db, 256, 64), 256, 0, st>>>(slots + n_dw, scratch, db_out, n_db);
+  if (n_db) det_final_k<<<df_grid(n_db, 256, 64), 256, 0, st>>>(slots + n_dw, scratch + 2, db_out, n_db);   // the db pair
   DF_LAUNCH_CHECK();
   return 0;
 }

@@ -1093,9 +1093,16 @@ int dfmir_fill_from_scalar(const float* gout, float* dx, long long n, float scal
  *     scratch + dfmir_det_head_floats() as the entry point's dw_tcc (8 bytes per element: element i of the gradient is
  *     slot i) and NULL as its db; a bias gradient is taken with dfmir_bias_grad into slots n_dw .. n_dw + n_db - 1
  *     (pointer scratch + head + 2 * n_dw).
- *   scale: a power of two chosen on the device such that count * max(max|x|, 1) * max|dy| -- a bound of every sum formed --
- *     maps below 2^61.  x_amax / dy_amax: range probes as for the split kernels, or NULL with x / dy given (measured here).
- *   dfmir_det_end: dw_out[i] += slot[i] / scale (i < n_dw), db_out[j] += slot[n_dw + j] / scale, and ends the mode.
+ *   scale: two powers of two chosen on the device, one for the dW slots and one for the db slots (which only
+ *     dfmir_bias_grad writes).  With frexp exponents e(f) (f < 2^e(f)): scale_dw = 2^(61 - e(count) - e(max|x|) - e(max|dy|)),
+ *     scale_db = 2^(61 - e(count) - e(max|dy|)), so that the bounds count * max|x| * max|dy| of every dW sum and
+ *     count * max|dy| of every db sum map below 2^61.  The exponents are added as integers: a bound beyond the fp32 range
+ *     is handled like any other (the gradient itself must fit fp32), and the quantum 1 / scale_dw shrinks with max|x|, so
+ *     inputs far below 1 keep a resolution of at most 2^-58 of the bound.  A zero max|x| or max|dy| (every sum is an exact
+ *     zero) takes the scale 2^61; the shift is clamped to [-126, 126] (both powers stay normal floats), which only coarsens
+ *     the grid for bounds below 2^-65.  x_amax / dy_amax: range probes as for the split kernels, or NULL with x / dy given
+ *     (measured here).
+ *   dfmir_det_end: dw_out[i] += slot[i] / scale_dw (i < n_dw), db_out[j] += slot[n_dw + j] / scale_db, and ends the mode.
  * ---------------------------------------------------------------------------------------- */
 int dfmir_det_head_floats(void);
 int dfmir_det_begin(float* scratch, long long slots, const float* x, long long nx, const float* x_amax, int x_amax_n,

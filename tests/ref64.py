@@ -1,9 +1,10 @@
 """Plain float64 references (torch, CPU) of the operations around the convolutions: masked L1, flow smoothness
 (Grad_Loss), windowed NCC, InstanceNorm (+ReLU, +residual), Adam, the displacement-field warp, the VecInt step, the linear
-resize and the PatchNCE path (patch gather, L2 normalisation, the MLP head, InfoNCE rows, the loss algebra).  TEST
+resize, the PatchNCE path (patch gather, L2 normalisation, the MLP head, InfoNCE rows, the loss algebra) and the weight and
+bias gradients of a convolution.  TEST
 infrastructure, written from the formulas in the docstrings of oracle/dfmir_oracle.py and the kernels' comments;
 tests/test_ref64.py checks each one against the fp32 oracle on small inputs, the GPU tests (tests/test_gpu_pointwise_fp64.py,
-tests/test_gpu_warp_fp64.py, tests/test_gpu_patchnce_fp64.py) compare the HIP kernels with them.
+tests/test_gpu_warp_fp64.py, tests/test_gpu_patchnce_fp64.py, tests/test_gpu_wgrad_fp64.py) compare the HIP kernels with them.
 
 Every function takes tensors of any float dtype and computes in `dtype` (float64 by default); gradients come from
 autograd on the returned value.  `dtype=torch.float32` turns a function into a plain fp32 restatement (another valid
@@ -308,3 +309,103 @@ def scalar_combine(M, xs, dtype=torch.float64):
     """out[j] = sum_i M[j][i] x_i for one-element tensors x_i."""
     Mt = torch.as_tensor(M, dtype=torch.float32).to(dtype)         # the coefficients reach the kernel as fp32
     return Mt @ torch.stack([_t(x, dtype).reshape(()) for x in xs])
+
+
+# ----------------------------------------------------------------------- convolution weight / bias gradients
+def nearest_up2(a):
+    """Every voxel of [N, C, *sp] repeated twice along every spatial axis (nearest-neighbour up-sampling by 2)."""
+    for ax in range(2, a.dim()):
+        a = a.repeat_interleave(2, dim=ax)
+    return a
+
+
+def upcat(a, b):
+    """cat(nearest_up2(a), b) over the channels, built explicitly (the operand ops.upcat_conv3d never builds)."""
+    return torch.cat([nearest_up2(a), b], 1)
+
+
+def _per_axis(v, nd):
+    v = tuple(int(e) for e in v) if isinstance(v, (tuple, list)) else (int(v),) * nd
+    assert len(v) == nd, (v, nd)
+    return v
+
+
+def pad_by_index(x, pad, pad_mode):
+    """x [N, C, *sp] padded by pad[a] on both sides of spatial axis a: pad_mode 0 = zeros, 1 = reflect without the edge
+    (index -i reads i, index n - 1 + i reads n - 1 - i).  Explicit index arithmetic, not F.pad."""
+    for a, p in enumerate(pad):
+        if p == 0:
+            continue
+        ax, n = 2 + a, x.shape[2 + a]
+        if pad_mode == 0:
+            shp = list(x.shape)
+            shp[ax] = n + 2 * p
+            xp = torch.zeros(shp, dtype=x.dtype)
+            xp.narrow(ax, p, n).copy_(x)
+            x = xp
+        else:
+            assert p <= n - 1, "reflect padding needs pad < extent"
+            i = torch.arange(-p, n + p).abs()
+            i = torch.where(i > n - 1, 2 * (n - 1) - i, i)
+            x = x.index_select(ax, i)
+    return x
+
+
+def _contract(A, Bm, order):
+    """A [Cin, P], Bm [Cout, P] -> [Cout, Cin] = sum over P.  'matmul': one matrix product; 'chunk64': a running sum over
+    chunks of 64 positions (every chunk a product of its own, added to the accumulator in position order)."""
+    if order == "matmul":
+        return Bm @ A.t()
+    assert order == "chunk64", order
+    P = A.shape[1]
+    acc = torch.zeros(Bm.shape[0], A.shape[0], dtype=A.dtype)
+    nfull = P // 64
+    if nfull:
+        part = torch.bmm(Bm[:, :nfull * 64].reshape(Bm.shape[0], nfull, 64).transpose(0, 1),
+                         A[:, :nfull * 64].reshape(A.shape[0], nfull, 64).permute(1, 2, 0))
+        for i in range(nfull):
+            acc = acc + part[i]
+    if P > nfull * 64:
+        acc = acc + Bm[:, nfull * 64:] @ A[:, nfull * 64:].t()
+    return acc
+
+
+def conv_weight_grad(x, dy, K, stride, pad, pad_mode, dtype=torch.float64, order="matmul"):
+    """dW [Cout, Cin, *K] of y = conv(x, W), stride `stride`, padding `pad` (zeros: pad_mode 0, reflect: 1), from the
+    definition:  dW[co, ci, t] = sum over (n, o) of xp[n, ci, stride * o + t] * dy[n, co, o]  with xp the padded input and o
+    the output positions -- for every tap t the strided slice of xp contracted with dy over batch and positions.  x, dy
+    [N, C, *sp] with 2 or 3 spatial axes (a 2-D layer may come as [N, C, 1, H, W] with K = (1, k, k), pad = (0, p, p)); K
+    and pad an int or one per axis.  x = (a, b): the operand is cat(nearest_up2(a), b), built here.  `order`: how the fp32
+    restatement (dtype=torch.float32) sums -- 'matmul' or 'chunk64', see _contract; two valid orders, so that neither
+    flatters the yardstick."""
+    if isinstance(x, (tuple, list)):
+        x = upcat(_t(x[0], dtype), _t(x[1], dtype))
+    x, dy = _t(x, dtype), _t(dy, dtype)
+    nd = x.dim() - 2
+    K, pad = _per_axis(K, nd), _per_axis(pad, nd)
+    out_sp = tuple(dy.shape[2:])
+    for a in range(nd):
+        assert out_sp[a] == (x.shape[2 + a] + 2 * pad[a] - K[a]) // stride + 1, (a, out_sp, tuple(x.shape), K, pad, stride)
+    xp = pad_by_index(x, pad, pad_mode)
+    Cin, Cout = x.shape[1], dy.shape[1]
+    Bm = dy.transpose(0, 1).reshape(Cout, -1)
+    dw = torch.zeros((Cout, Cin) + K, dtype=dtype)
+    taps = [()]
+    for k in K:
+        taps = [t + (i,) for t in taps for i in range(k)]
+    for t in taps:
+        sl = xp
+        for a in range(nd):
+            sl = sl.narrow(2 + a, t[a], stride * (out_sp[a] - 1) + 1)
+            if stride > 1:
+                sl = sl.index_select(2 + a, torch.arange(0, sl.shape[2 + a], stride))
+        dw[(slice(None), slice(None)) + t] = _contract(sl.transpose(0, 1).reshape(Cin, -1), Bm, order)
+    return dw
+
+
+def conv_bias_grad(dy, dtype=torch.float64, order="matmul"):
+    """db [Cout] = sum of dy [N, Cout, *sp] over batch and positions; order as in conv_weight_grad ('matmul': torch's sum)."""
+    Bm = _t(dy, dtype).transpose(0, 1).reshape(dy.shape[1], -1)
+    if order == "matmul":
+        return Bm.sum(1)
+    return _contract(torch.ones(1, Bm.shape[1], dtype=dtype), Bm, order)[:, 0]

@@ -7,6 +7,9 @@ The warp, VecInt and resize restatements are compared with the oracle's function
 round trip through normalised coordinates), with the documented adjoint formulas and with F.interpolate; the two host-only
 size functions that choose the warp and resize backward forms are checked at their boundaries through ctypes.
 
+conv_weight_grad / conv_bias_grad (the tap-by-tap contraction, both evaluation orders, the up-cat operand) are compared with
+float64 autograd through F.conv2d / F.conv3d.
+
 The tests after those evaluate, with the oracle alone, the ill-conditioned inputs of tests/test_gpu_pointwise_fp64.py: the bound
 `max(bar, 2 x oracle error)` they lead to must stay within 10 x the bar, else the input tests nothing."""
 import ctypes
@@ -500,3 +503,74 @@ def test_l2norm_gpu_inputs_are_testable():
                     assert G.oracle_bound(dxr, dxo, G.BAR, floor=floor)[1] <= G.BAR / 10
                 else:
                     assert G.per_row_err(dxo, dxr) <= G.BAR / 10, (Cn, rows, scale, eps)
+
+
+# ------------------------------------------------------------------- convolution weight / bias gradients
+def _conv_autograd(x, dy, Cout, K, stride, pad, reflect):
+    """dW, db of float64 autograd through F.conv2d / F.conv3d with a bias (the weights' values play no part)."""
+    nd = x.dim() - 2
+    conv = F.conv2d if nd == 2 else F.conv3d
+    w = torch.zeros((Cout, x.shape[1]) + (K,) * nd, dtype=torch.float64, requires_grad=True)
+    b = torch.zeros(Cout, dtype=torch.float64, requires_grad=True)
+    xd = x.double()
+    if reflect:
+        y = conv(F.pad(xd, (pad,) * (2 * nd), mode="reflect"), w, b, stride=stride)
+    else:
+        y = conv(xd, w, b, stride=stride, padding=pad)
+    (y * dy.double()).sum().backward()
+    return w.grad, b.grad
+
+
+WG_CASES = [  # nd, Cin, Cout, K, stride, pad, reflect, N, spatial
+    (2, 3, 5, 1, 1, 0, False, 2, (7, 9)), (2, 3, 5, 1, 2, 0, False, 2, (7, 9)),
+    (2, 4, 3, 3, 1, 1, False, 2, (9, 13)), (2, 4, 3, 3, 1, 1, True, 2, (9, 13)),
+    (2, 4, 3, 3, 2, 1, False, 1, (15, 17)), (2, 4, 3, 3, 2, 1, True, 1, (16, 10)),
+    (2, 1, 6, 7, 1, 3, True, 2, (11, 12)), (2, 2, 3, 7, 1, 3, False, 1, (9, 20)), (2, 2, 3, 7, 2, 3, True, 1, (13, 12)),
+    (3, 3, 4, 3, 1, 1, False, 2, (5, 7, 9)), (3, 3, 4, 3, 1, 1, True, 1, (5, 7, 9)),
+    (3, 2, 5, 3, 2, 1, False, 1, (9, 11, 13)), (3, 2, 5, 3, 2, 1, True, 1, (8, 6, 10)),
+    (3, 3, 2, 1, 1, 0, False, 1, (4, 5, 6)), (3, 2, 2, 7, 1, 3, False, 1, (7, 8, 9)), (3, 1, 2, 7, 2, 3, True, 1, (8, 9, 7)),
+]
+
+
+@pytest.mark.parametrize("cfg", WG_CASES, ids=[str(c) for c in WG_CASES])
+@pytest.mark.parametrize("order", ["matmul", "chunk64"])
+def test_conv_weight_and_bias_grad(cfg, order):
+    nd, Cin, Cout, K, stride, pad, reflect, N, sp = cfg
+    x = C.randn(501, N, Cin, *sp)
+    out = tuple((n + 2 * pad - K) // stride + 1 for n in sp)
+    dy = C.randn(502, N, Cout, *out)
+    dw_ref, db_ref = _conv_autograd(x, dy, Cout, K, stride, pad, reflect)
+    dw = R.conv_weight_grad(x, dy, K, stride, pad, 1 if reflect else 0, order=order)
+    assert dw.dtype == torch.float64 and rel(dw, dw_ref) <= 1e-13
+    assert rel(R.conv_bias_grad(dy, order=order), db_ref) <= 1e-13
+    # the fp32 restatement is the same sum at fp32 round-off
+    assert rel(R.conv_weight_grad(x, dy, K, stride, pad, 1 if reflect else 0, torch.float32, order), dw_ref) <= 2e-5
+    assert rel(R.conv_bias_grad(dy, torch.float32, order), db_ref) <= 2e-5
+
+
+def test_conv_weight_grad_of_a_2d_layer_given_as_5d():
+    """[N, C, 1, H, W] with K = (1, 3, 3), pad = (0, 1, 1): the form the GPU tests hand to ops.conv_wgrad_raw."""
+    x, dy = C.randn(503, 2, 3, 8, 10), C.randn(504, 2, 4, 8, 10)
+    for mode in (0, 1):
+        a = R.conv_weight_grad(x, dy, 3, 1, 1, mode)
+        b = R.conv_weight_grad(x.unsqueeze(2), dy.unsqueeze(2), (1, 3, 3), 1, (0, 1, 1), mode)
+        assert torch.equal(a, b[:, :, 0])
+
+
+@pytest.mark.parametrize("order", ["matmul", "chunk64"])
+def test_conv_weight_grad_upcat_form(order):
+    a, b = C.randn(505, 2, 8, 3, 4, 4), C.randn(506, 2, 3, 6, 8, 8)
+    dy = C.randn(507, 2, 5, 6, 8, 8)
+    xcat = torch.cat([F.interpolate(a, scale_factor=2, mode="nearest"), b], 1)
+    assert torch.equal(R.upcat(a, b), xcat)
+    dw_ref, _ = _conv_autograd(xcat, dy, 5, 3, 1, 1, False)
+    assert rel(R.conv_weight_grad((a, b), dy, 3, 1, 1, 0, order=order), dw_ref) <= 1e-13
+
+
+def test_conv_weight_grad_orders_differ_in_fp32_only():
+    """The two evaluation orders are the same numbers in float64 (to its round-off) and two different roundings in fp32."""
+    x, dy = C.randn(508, 2, 6, 24, 40), C.randn(509, 2, 7, 24, 40)
+    d64 = [R.conv_weight_grad(x, dy, 3, 1, 1, 0, order=o) for o in ("matmul", "chunk64")]
+    d32 = [R.conv_weight_grad(x, dy, 3, 1, 1, 0, torch.float32, o) for o in ("matmul", "chunk64")]
+    assert rel(d64[0], d64[1]) <= 1e-13
+    assert not torch.equal(d32[0], d32[1]) and rel(d32[0], d32[1]) <= 1e-5
