@@ -175,6 +175,9 @@ _SIGS = {
     "dfmir_affine_system": [c_int] + [P] * 6 + [c_int] * 6 + [P],
     "dfmir_affine_lm_step": [c_int] + [P] * 7 + [c_int] * 3 + [c_double] * 2 + [P],
     "dfmir_gauss_smooth": [c_int, P, P, P, c_longlong] + [c_int] * 3 + [c_double] * 4 + [P],
+    "dfmir_spline_prefilter": [c_int, P, P, P, c_longlong] + [c_int] * 3 + [P],
+    "dfmir_warp_cubic_fwd": [c_int, P, P, P] + [c_int] * 5 + [P],
+    "dfmir_warp_cubic_bwd_flow": [c_int, P, P, P, P] + [c_int] * 5 + [P],
     "dfmir_demons_ws_floats": [c_int] * 6,
     "dfmir_demons_force": [c_int] + [P] * 8 + [c_float] + [c_int] * 5 + [P],
     "dfmir_landmark_ws_floats": [c_int] * 6,

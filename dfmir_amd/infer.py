@@ -35,9 +35,34 @@ def _resolve_features(features, moving, fixed, mind_radius, mind_dilation):
     return Mm.detach(), Mf.detach()
 
 
+INTERPS = ('linear', 'cubic')
+
+
+def _check_interp(what, interp):
+    if not isinstance(interp, str) or interp not in INTERPS:
+        raise ValueError("%s: interp must be 'linear' or 'cubic', got %r" % (what, interp))
+
+
+def _final_warp(moving, flow, interp):
+    """The `warped` a solver returns: ops.warp (bi-/trilinear, zero padding) or ops.warp_cubic (cubic B-spline, mirror)."""
+    return ops.warp_cubic(moving, flow) if interp == 'cubic' else ops.warp(moving, flow)
+
+
+@torch.no_grad()
+def resample(moving, flow, interp='cubic'):
+    """The moving image through a flow that a solver found, in one call: interp 'cubic' = ops.warp_cubic(moving, flow) --
+    third-order B-spline interpolation with mirror extension, which may overshoot the range of `moving` at edges -- or
+    'linear' = ops.warp(moving, flow), bi-/trilinear with zero padding.  moving [B,C,*vol] fp32, flow [B,nd,*vol] in voxels;
+    no gradient is recorded.  ValueError on any other interp and on what the op refuses."""
+    _check_interp("resample", interp)
+    if not torch.is_tensor(moving) or not torch.is_tensor(flow):
+        raise ValueError("resample: moving and flow must be tensors")
+    return _final_warp(moving.detach(), flow.detach(), interp)
+
+
 def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
                 regularizer='diffusion', lam, spacing=None, grid_downsize=2, iters=50, lr, betas=(0.9, 0.999),
-                update='add', parametrisation='linear', fold_weight=0.0, fold_eps=0.0, fold_power=2):
+                update='add', parametrisation='linear', fold_weight=0.0, fold_eps=0.0, fold_power=2, interp='linear'):
     """Instance optimisation: `iters` Adam iterations on the displacement field of ONE pair (build-defined), the step
     between a network's flow and the reported number.  Returns dict(flow, warped, history).
 
@@ -74,8 +99,13 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
     nothing more and the result is bit-identical to a call without the keyword.  With fold_weight > 0, J_k gains
     fold_weight * ops.jacobian_penalty(flow_k, fold_eps, fold_power) and the returned dict gains 'fold_history', a device
     tensor [iters + 1] of that penalty (unweighted) at flow_0 .. flow_iters; `history` keeps its two columns.  ValueError on
-    a negative or non-finite weight and on a fold_eps / fold_power that ops.jacobian_penalty refuses."""
+    a negative or non-finite weight and on a fold_eps / fold_power that ops.jacobian_penalty refuses.
+
+    interp: how the returned `warped` is sampled, and nothing else: 'linear' (the default) = ops.warp(moving, flow), 'cubic'
+    = ops.warp_cubic(moving, flow) (mirror extension, may overshoot).  The loop's SSD kernel samples linearly either way, so
+    flow and history do not depend on it.  ValueError on any other value."""
     what = "refine_flow"
+    _check_interp(what, interp)
     if isinstance(fold_weight, bool) or not isinstance(fold_weight, (int, float)) or not 0.0 <= fold_weight < float('inf'):
         raise ValueError("%s: fold_weight must be a finite weight >= 0, got %r" % (what, fold_weight))
     fold = float(fold_weight) > 0.0
@@ -153,7 +183,7 @@ def refine_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         history[iters, 1] = reg(out)
         if fold:
             fold_history[iters] = jd(out)
-        warped = ops.warp(moving, out)
+        warped = _final_warp(moving, out, interp)
     res = dict(flow=out, warped=warped, history=history)
     if fold:
         res['fold_history'] = fold_history
@@ -237,7 +267,7 @@ def _finite_number(x):
 
 @torch.no_grad()
 def affine_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=2, mask=None, theta=None, dof='affine',
-                levels=(4, 2, 1), iters=10, mu0=1e-3, mu_up=10.0, mu_down=0.1):
+                levels=(4, 2, 1), iters=10, mu0=1e-3, mu_up=10.0, mu_down=0.1, interp='linear'):
     """Affine pre-alignment (build-defined): a multi-level Levenberg-Marquardt fit of one affine transform per sample to the
     SSD of features, the global stage in front of convex_init and refine_flow, which only look as far as a search window or
     a descent from the start reaches.  Returns dict(theta, flow, warped, history).
@@ -274,8 +304,12 @@ def affine_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=
     ValueError before any launch on images that are not two [B,1,*vol] tensors of one shape (any channel count with a feature
     pair), an unknown `features` or `dof`, a theta of the wrong shape or dtype, levels that are not integers >= 1 or leave an
     extent < 2, iters that are not integers >= 0 or disagree with levels in length, and mu0 <= 0, mu_up <= 1 or mu_down outside
-    (0, 1] (or any of them not finite)."""
+    (0, 1] (or any of them not finite), and an interp other than 'linear' or 'cubic'.
+
+    interp: how the returned `warped` is sampled, and nothing else: 'linear' (the default) = ops.warp(moving, flow), 'cubic'
+    = ops.warp_cubic(moving, flow) (mirror extension, may overshoot); theta, flow and history do not depend on it."""
     what = "affine_init"
+    _check_interp(what, interp)
     if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
             or tuple(moving.shape) != tuple(fixed.shape):
         raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
@@ -345,13 +379,13 @@ def affine_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=
         th = acc
         th[:, :, nd] *= float(s)
     flow = ops.affine_flow(th, vol)
-    return dict(theta=th, flow=flow, warped=ops.warp(moving, flow), history=history)
+    return dict(theta=th, flow=flow, warped=_final_warp(moving, flow, interp), history=history)
 
 
 @torch.no_grad()
 def demons_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, mind_dilation=2, mask=None,
                 levels=(4, 2, 1), iters=10, max_step=2.0, sigma_fluid=1.0, sigma_diffusion=1.0,
-                update='compose', diffeomorphic=False, exp_steps=4):
+                update='compose', diffeomorphic=False, exp_steps=4, interp='linear'):
     """The demons iteration (build-defined): a second-order dense solver on the feature SSD, coarse to fine -- a per-voxel
     Gauss-Newton step (ops.demons_force) regularised by Gaussian smoothing of the update (fluid) and of the field
     (diffusion), with no backward pass, no optimiser state and no learning rate.  Returns dict(flow, warped, history, energy0,
@@ -395,8 +429,12 @@ def demons_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
     ValueError before any launch on everything affine_init refuses for its images, features, mask, levels and iters, a flow
     that is not [B,nd,*vol] fp32, an unknown `update`, a `diffeomorphic` that is not a bool, an exp_steps that is not an
     integer in 0..8, a max_step that is not finite and > 0, a sigma that is negative or not finite and a sigma whose radius
-    ceil(3 sigma) exceeds ops.GAUSS_MAX_RADIUS."""
+    ceil(3 sigma) exceeds ops.GAUSS_MAX_RADIUS, and an interp other than 'linear' or 'cubic'.
+
+    interp: how the returned `warped` is sampled, and nothing else: 'linear' (the default) = ops.warp(moving, flow), 'cubic'
+    = ops.warp_cubic(moving, flow) (mirror extension, may overshoot); flow, history and the energies do not depend on it."""
     what = "demons_flow"
+    _check_interp(what, interp)
     if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
             or tuple(moving.shape) != tuple(fixed.shape):
         raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
@@ -477,7 +515,8 @@ def demons_flow(moving, fixed, flow=None, *, features='mind', mind_radius=2, min
         s_prev = s
     if s_prev != 1:
         u = ops.resize_linear(u, vol, mult=float(s_prev))
-    return dict(flow=u, warped=ops.warp(moving, u), history=history, energy0=energy0, energy=ops.warp_ssd(full, Mf, u, mask))
+    return dict(flow=u, warped=_final_warp(moving, u, interp), history=history, energy0=energy0,
+                energy=ops.warp_ssd(full, Mf, u, mask))
 
 
 def _refine_kwargs(refine, what):

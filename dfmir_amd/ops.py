@@ -1792,7 +1792,127 @@ class WarpFn(Function):
 
 
 def warp(src, flow, mode="bilinear"):
+    """src(x + flow(x)): mode 'nearest' for labels, 'cubic' = ops.warp_cubic (third-order B-spline, MIRROR extension where
+    the linear mode pads with zeros), any other string the bi-/trilinear warp."""
+    if mode == "cubic":
+        return warp_cubic(src, flow)
     return WarpFn.apply(src, flow, 1 if mode == "nearest" else 0)
+
+
+def _cubic_image(x, what, name):
+    """(nd, D, H, W) of a [B,C,*vol] fp32 image of the cubic ops after its checks (ValueError: nothing is launched)."""
+    if not torch.is_tensor(x) or x.dim() not in (4, 5):
+        raise ValueError("%s: %s must be a [B,C,H,W] or [B,C,D,H,W] tensor, got %s"
+                         % (what, name, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+    if min(x.shape) < 1:
+        raise ValueError("%s: %s needs B >= 1, C >= 1 and every extent >= 1, got %s" % (what, name, tuple(x.shape)))
+    if x.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (%s is %s)" % (what, name, x.dtype))
+    if x.numel() >= 2 ** 31:
+        raise ValueError("%s: %s %s has 2^31 or more elements" % (what, name, tuple(x.shape)))
+    nd = x.dim() - 2
+    D, H, W = (int(n) for n in (x.shape[2:] if nd == 3 else (1,) + tuple(x.shape[2:])))
+    return nd, D, H, W
+
+
+def _spline_prefilter(x, nd, D, H, W):
+    out = torch.empty_like(x)
+    tmp = torch.empty_like(x) if nd == 3 and D > 1 and (H > 1 or W > 1) else None
+    check(lib().dfmir_spline_prefilter(nd, _p(x), _p(out), _p(tmp), int(x.shape[0]) * int(x.shape[1]), D, H, W, _st()))
+    return out
+
+
+@torch.no_grad()
+def spline_prefilter(x):
+    """The coefficients of the interpolating cubic B-spline of an image (build-defined): x [B,C,*vol] fp32, 2-D or 3-D,
+    every extent >= 1; returns c of the same shape.  With refl the whole-sample mirror d c b | a b c d | c b a -- for an
+    axis of extent n > 1, j = i mod (2 n - 2), refl(i) = j if j < n else 2 n - 2 - j; refl(i) = 0 for n == 1 -- c solves,
+    along every axis in turn (the axes commute),
+
+        (c[refl(i - 1)] + 4 c[i] + c[refl(i + 1)]) / 6 = s[i]
+
+    which is scipy.ndimage.spline_filter(order=3, mode='mirror').  The kernel evaluates the exact inverse as the FIR
+    c[i] = sum_{|k| <= 16} sqrt(3) z^|k| s[refl(i + k)], z = sqrt(3) - 2 (the tail is below 8e-10 max |s|); an axis of extent 1 is
+    left alone bit for bit.  max |c| is about 2.3 max |s| for noise.  2-D is one launch, 3-D the (y, x) pass and a z pass
+    (dfmir_amd/csrc/cubic.hip).  Bit-identical from run to run; nothing syncs with the host.  No gradient: an input that
+    requires grad raises.  ValueError before any launch on a rank other than 4 or 5, an empty axis, a dtype other than fp32,
+    2^31 or more elements and a tensor that requires grad; a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "spline_prefilter"
+    nd, D, H, W = _cubic_image(x, what, "x")
+    if x.requires_grad:
+        raise ValueError("%s: x requires grad, but the op has no gradient (detach it)" % what)
+    _need(x)
+    return _spline_prefilter(_c(x), nd, D, H, W)
+
+
+class WarpCubicFn(Function):
+    """dfmir_warp_cubic_fwd / _bwd_flow on the prefiltered coefficients; the gradient goes to the flow only."""
+
+    @staticmethod
+    def forward(ctx, src, flow, prefiltered, geom):
+        nd, D, H, W = geom
+        src, flow = _c(src.detach()), _c(flow.detach())
+        coef = src if prefiltered else _spline_prefilter(src, nd, D, H, W)
+        B, C = int(src.shape[0]), int(src.shape[1])
+        out = torch.empty_like(coef)
+        check(lib().dfmir_warp_cubic_fwd(nd, _p(coef), _p(flow), _p(out), B, C, D, H, W, _st()))
+        ctx.save_for_backward(coef, flow)
+        ctx.geom = geom
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        if ctx.needs_input_grad[0]:
+            raise DfmirHipError("warp_cubic: the gradient to src is not implemented (d(flow) only; detach src)")
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        coef, flow = ctx.saved_tensors
+        nd, D, H, W = ctx.geom
+        dflow = torch.empty_like(flow)
+        check(lib().dfmir_warp_cubic_bwd_flow(nd, _p(_c(dout)), _p(coef), _p(flow), _p(dflow), int(coef.shape[0]),
+                                              int(coef.shape[1]), D, H, W, _st()))
+        return None, dflow, None, None
+
+
+def warp_cubic(src, flow, prefiltered=False):
+    """src(x + flow(x)) by third-order (cubic) B-spline interpolation (build-defined): src [B,C,*vol] fp32, 2-D or 3-D; flow
+    [B,nd,*vol] in voxels, ops.warp's convention (channel a displaces axis a, p = x + flow(x)).  The image is first turned
+    into spline coefficients c = ops.spline_prefilter(src) -- pass them yourself with prefiltered=True to warp one image
+    many times -- and then, per axis, i = floor(p), t = p - i,
+
+        w0 = (1 - t)^3 / 6    w1 = (3 t^3 - 6 t^2 + 4) / 6    w2 = (-3 t^3 + 3 t^2 + 3 t + 1) / 6    w3 = t^3 / 6
+        out(x) = sum over the 4^nd taps of  prod_a w_ka(t_a) * c[refl(i_a - 1 + k_a)]
+
+    with refl the whole-sample mirror of ops.spline_prefilter, applied at ANY distance outside the volume: exactly
+    scipy.ndimage.map_coordinates(src, p, order=3, mode='mirror').  This DIVERGES ON PURPOSE from the linear and nearest
+    modes of ops.warp, which pad with zeros: a point far outside reads a mirrored copy of the image, not 0.  The spline
+    interpolates (zero flow returns src up to rounding) but is not confined to the range of src: it OVERSHOOTS at edges,
+    and nothing clamps.  A position that is not finite, or has |p| >= 2^24 on any axis, gives out = 0 and a zero gradient.
+    Gradient: to the flow only, dflow[b,a,x] = sum_c dout[b,c,x] d out[b,c,x] / d p_a with the derivative weights
+    w0' = -(1 - t)^2 / 2, w1' = (3 t^2 - 4 t) / 2, w2' = (-3 t^2 + 2 t + 1) / 2, w3' = t^2 / 2 on axis a -- continuous across cell
+    faces, unlike the linear warp's.  A src that requires grad raises DfmirHipError in the backward, as the nearest mode
+    does.  One thread per voxel, no atomics: value and gradient are bit-identical from run to run; nothing syncs with the
+    host.  ValueError before any launch on a rank other than 4 or 5, an empty axis, a flow that is not [B,nd,*vol], a dtype
+    other than fp32, tensors on different devices, 2^31 or more elements and a prefiltered that is not a bool; a CPU tensor
+    raises the usual "no CPU fallback" error."""
+    what = "warp_cubic"
+    if not isinstance(prefiltered, bool):
+        raise ValueError("%s: prefiltered must be a bool, got %r" % (what, prefiltered))
+    geom = _cubic_image(src, what, "src")
+    nd = geom[0]
+    want = (int(src.shape[0]), nd) + tuple(src.shape[2:])
+    if not torch.is_tensor(flow) or tuple(flow.shape) != want:
+        raise ValueError("%s: the flow of a %s image is [B,%d,*vol] = %s, got %s"
+                         % (what, tuple(src.shape), nd, want, tuple(flow.shape) if torch.is_tensor(flow) else type(flow).__name__))
+    if flow.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (flow is %s)" % (what, flow.dtype))
+    if flow.numel() >= 2 ** 31:
+        raise ValueError("%s: flow %s has 2^31 or more elements" % (what, tuple(flow.shape)))
+    if flow.device != src.device:
+        raise ValueError("%s: src is on %s, flow on %s" % (what, src.device, flow.device))
+    _need(src, flow)
+    return WarpCubicFn.apply(src, flow, prefiltered, geom)
 
 
 class VecIntStepFn(Function):

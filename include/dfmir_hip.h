@@ -824,6 +824,42 @@ int dfmir_affine_lm_step(int nd, const double* Lb, const double* g, const double
 #define DFMIR_GAUSS_MAX_RADIUS 16     /* a 32 x 64 tile with a halo of 16 on every side: 24 KiB of LDS, and 16 KiB for the x pass */
 int dfmir_gauss_smooth(int nd, const float* in, float* out, float* tmp, long long planes, int D, int H, int W, double sz,
                        double sy, double sx, double truncate, void* stream);
+/* Cubic B-spline image resampling (build-defined: the reference has nothing above first order).  Images and coefficients:
+ * [planes][(D)][H][W] fp32, planes = B * C, nd = 2 or 3 (D is not read when nd == 2), every extent >= 1.
+ *   Index reflection, an axis of extent n:  n == 1: refl(i) = 0;  n > 1: j = i mod (2 n - 2) taken non-negative, refl(i) = j if
+ *   j < n, else 2 n - 2 - j: the whole-sample mirror  d c b | a b c d | c b a, at ANY distance from the volume.
+ *   Prefilter c = P s, per axis (the axes commute): along one axis c solves  (c[refl(i - 1)] + 4 c[i] + c[refl(i + 1)]) / 6 =
+ *   s[i]  (scipy.ndimage.spline_filter1d(order=3, mode='mirror')); for n == 1, c = s.  Evaluated as the FIR form
+ *     c[i] = sum_{|k| <= 16} sqrt(3) z^|k| s[refl(i + k)],   z = sqrt(3) - 2,
+ *   the exact inverse truncated where the tail is below 8e-10 max |s|; the weights are formed in double and rounded to fp32, a
+ *   sum adds the pairs w[k] (s[i - k] + s[i + k]) from k = 16 down to 1 and the centre term last.
+ *   Sampling at p (per axis i = floor(p), t = p - i):
+ *     w0 = (1 - t)^3 / 6,  w1 = (3 t^3 - 6 t^2 + 4) / 6,  w2 = (-3 t^3 + 3 t^2 + 3 t + 1) / 6,  w3 = t^3 / 6
+ *     w0' = -(1 - t)^2 / 2,  w1' = (3 t^2 - 4 t) / 2,  w2' = (-3 t^2 + 2 t + 1) / 2,  w3' = t^2 / 2
+ *     out = sum over the 4^nd taps of  prod_a w_ka(t_a) * c[refl(i_a - 1 + k_a)]
+ *   which is scipy.ndimage.map_coordinates(order=3, mode='mirror'): mirror extension at any distance, NOT the zero padding of
+ *   the linear warp kernels.  The result is not confined to the range of s (the spline overshoots at edges; nothing clamps).
+ * dfmir_spline_prefilter: in -> out, out of place.  2-D: ONE launch, the tile and a halo of 16 reflected cells filtered along both
+ * axes in LDS.  3-D: the (y, x) pass per plane into tmp, then the z pass as the same kernel on the view [planes][D][H W].  tmp:
+ * planes * D * H * W floats, read only when both passes run (nd == 3, D > 1 and H > 1 or W > 1; may be NULL otherwise); in, out
+ * and tmp must not alias.  An axis of extent 1 is left alone bit for bit.  16-byte accesses where the row length (W; for the z
+ * pass H W) is a multiple of 4 and the pointers are aligned.
+ * dfmir_warp_cubic_fwd: out[b][c][x] = the spline of coef[b][c] (PREFILTERED coefficients) at p = x + flow[b][:][x]; flow
+ * [B][nd][S] in voxels, channel a displaces axis a, order (z,) y, x -- the warp kernels' convention.  floor and t are taken
+ * from the flow (floor(p) = x + floor(flow), t = flow - floor(flow)).  A position that is not finite, or whose fp32 sum x + flow
+ * has magnitude >= 2^24 on any axis, gives out = 0 and a zero gradient.
+ * dfmir_warp_cubic_bwd_flow: dflow[b][a][x] = sum_c dout[b][c][x] * d out[b][c][x] / d p_a  (w' on axis a, w on the others),
+ * continuous in p; the channels are added in channel order and every element is written once: no atomics.  There is no
+ * gradient to coef here.
+ * One thread per voxel; the 4 reflected indices and weights per axis are formed once per voxel, without reflection when every
+ * tap is inside.  Every output of the three calls is bit-identical from run to run.  Refused ("invalid argument", nothing is
+ * launched): nd outside {2, 3}, planes, B or C < 1, an extent < 1 (warp: > 2^24), 2^31 or more elements, a NULL or aliased
+ * pointer.  Nothing syncs, allocates or keeps state. */
+int dfmir_spline_prefilter(int nd, const float* in, float* out, float* tmp, long long planes, int D, int H, int W, void* stream);
+int dfmir_warp_cubic_fwd(int nd, const float* coef, const float* flow, float* out, int B, int C, int D, int H, int W,
+                         void* stream);
+int dfmir_warp_cubic_bwd_flow(int nd, const float* dout, const float* coef, const float* flow, float* dflow, int B, int C,
+                              int D, int H, int W, void* stream);
 /* The demons force: a per-voxel Gauss-Newton step on the warped-feature SSD (build-defined: the reference has no such
  * solver).  Mp, F, phi and mask are dfmir_warp_ssd_fwd's: Mp the packed moving features (dfmir_warp_ssd_pack), F [B][C][S], 1 <=
  * C <= 16, phi [B][nd][S] in voxels, mask [B][S] or NULL.  Per voxel x, with p = x + phi(x), sampled exactly as
