@@ -12,7 +12,7 @@
 //             voxel stops updating once max_c |r_k,c| <= tol (it keeps its w and its r from then on).  Per sample and k:
 //             rms_k = sqrt(sum over voxels and channels of r_k^2 / S), max_k = max |r_k,c|.
 //
-// The sampling is that of the inverse-consistency kernels (flow_sample.h: ic_voxel with its `nearby` guard, the 8-byte
+// The sampling is that of the inverse-consistency kernels (flow_sample.h: ic_voxel on lin_cell.h's guarded cell, the 8-byte
 // corner-pair loads, IcThread's voxel ownership): a workgroup owns IC_T * VPT consecutive voxels of ONE sample, VPT = 4 with
 // 16-byte loads / stores through LDS when W % 4 == 0 and the streamed pointers are 16-byte aligned, else 1.
 //   compose_fwd_k   ic_fwd_k's body storing r instead of reducing it.

@@ -19,7 +19,7 @@
 //
 // dfmir_dice_* / dfmir_mse_*: the dense vxm Dice and MSE of float tensors; per-workgroup partial sums in a fixed tree,
 // added in index order by a finaliser (bit-reproducible), element-wise backward.
-#include "common.h"
+#include "lin_cell.h"
 
 namespace {
 
@@ -46,23 +46,21 @@ struct WdGeom {
 
 __device__ __forceinline__ u64 wd_fx(float w) { return (u64)__float2ull_rn(w * WD_FX); }
 
-// One output voxel (z, y, x) of batch element b: the slots and weights of its corners.  mode 1: the rounded corner alone.
+// One output voxel p = (z, y, x) of batch element b, displaced by u: the slots and upper weights of its corners.  (Mode 1
+// of the forward does not come here: it takes the rounded corner alone.)
 struct WdCorners {
   int c[8];        // slot of corner k (255: out of the volume or not scored); k = 4 dz + 2 dy + dx
-  float wz1, wy1, wx1;
+  float w1[3];
 };
-__device__ __forceinline__ void wd_corners(const uint8_t* __restrict__ mb, const uint8_t* slot, const WdGeom& g, float fz,
-                                           float fy, float fx, WdCorners& o) {
-  const float z0f = floorf(fz), y0f = floorf(fy), x0f = floorf(fx);
-  const int z0 = (int)z0f, y0 = (int)y0f, x0 = (int)x0f;
-  o.wz1 = fz - z0f; o.wy1 = fy - y0f; o.wx1 = fx - x0f;
-  const long long HW = (long long)g.H * g.W;
+__device__ __forceinline__ void wd_corners(const uint8_t* __restrict__ mb, const uint8_t* slot, const WdGeom& g,
+                                           const int (&p)[3], const float (&u)[3], WdCorners& o) {
+  const int n[3] = {g.D, g.H, g.W};
+  LinCell<3> q;
+  lin_cell<3, int>(p, u, n, q);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int zz = z0 + (k >> 2), yy = y0 + ((k >> 1) & 1), xx = x0 + (k & 1);
-    const bool v = (unsigned)zz < (unsigned)g.D && (unsigned)yy < (unsigned)g.H && (unsigned)xx < (unsigned)g.W;
-    o.c[k] = v ? (int)slot[mb[(long long)zz * HW + (long long)yy * g.W + xx]] : 255;
-  }
+  for (int a = 0; a < 3; ++a) o.w1[a] = q.w1[a];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o.c[k] = q.in(k) ? (int)slot[mb[q.off(k)]] : 255;
 }
 
 template <int VEC>
@@ -123,11 +121,10 @@ __global__ __launch_bounds__(WD_THREADS) void warp_dice_fwd_k(const uint8_t* __r
         continue;
       }
       WdCorners o;
-      wd_corners(mb, slot, g, fz, fy, fx, o);
-      const float wz[2] = {1.f - o.wz1, o.wz1}, wy[2] = {1.f - o.wy1, o.wy1}, wx[2] = {1.f - o.wx1, o.wx1};
+      wd_corners(mb, slot, g, {z, y, x0 + e}, {dz[e], dy[e], dx[e]}, o);
       float w[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) w[k] = wz[k >> 2] * wy[(k >> 1) & 1] * wx[k & 1];
+      for (int k = 0; k < 8; ++k) w[k] = lin_cw<3>(o.w1, k);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         if (o.c[k] == 255) continue;
@@ -240,22 +237,20 @@ __global__ __launch_bounds__(WD_THREADS) void warp_dice_bwd_k(const uint8_t* __r
     }
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      const float fz = (float)z + dz[e], fy = (float)y + dy[e], fx = (float)(x0 + e) + dx[e];
       const int sf = slot[fl_lab[e]];
       WdCorners o;
-      wd_corners(mb, slot, g, fz, fy, fx, o);
+      wd_corners(mb, slot, g, {z, y, x0 + e}, {dz[e], dy[e], dx[e]}, o);
       float v[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int c = o.c[k];
         v[k] = c == 255 ? 0.f : (c == sf ? sgT[c] : 0.f) + sgS[c];
       }
-      const float wz1 = o.wz1, wy1 = o.wy1, wx1 = o.wx1, wz0 = 1.f - wz1, wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-      const float p0 = wy0 * (wx0 * v[0] + wx1 * v[1]) + wy1 * (wx0 * v[2] + wx1 * v[3]);
-      const float p1 = wy0 * (wx0 * v[4] + wx1 * v[5]) + wy1 * (wx0 * v[6] + wx1 * v[7]);
-      gz[e] = go * (p1 - p0);
-      gy[e] = go * (wz0 * (wx0 * (v[2] - v[0]) + wx1 * (v[3] - v[1])) + wz1 * (wx0 * (v[6] - v[4]) + wx1 * (v[7] - v[5])));
-      gx[e] = go * (wz0 * (wy0 * (v[1] - v[0]) + wy1 * (v[3] - v[2])) + wz1 * (wy0 * (v[5] - v[4]) + wy1 * (v[7] - v[6])));
+      float d[3];
+      lin_flow_grad<3>(v, o.w1, d);
+      gz[e] = go * d[0];
+      gy[e] = go * d[1];
+      gx[e] = go * d[2];
     }
     if (VEC == 4) {
       if (g.nd == 3)

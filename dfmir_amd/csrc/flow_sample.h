@@ -1,14 +1,13 @@
 // What the kernels that sample one displacement field at the points another one names have in common (invcons.hip: the
 // inverse-consistency loss; compose.hip: composition and fixed-point inversion of flows).  Fields are [B][ND][(D)][H][W]
 // fp32, channel i displaces axis i in voxels, order (z,) y, x, as the warp kernels read a flow; sampling is (bi/tri)linear
-// and corners outside the volume read as 0.  ic_voxel is the ONE place r(x) = u(x) + v(x + u(x)) and the corner terms are
-// formed; IcThread says which voxels a thread owns (VPT = 4: 16-byte loads / stores through LDS when W % 4 == 0 and the
-// pointers are aligned, else 1); ic_block_reduce adds a double and takes a maximum over the workgroup in a fixed order;
-// ic_bwd_voxels is the adjoint of the sampling for a gradient that either file supplies.  Everything here has internal
-// linkage: each file compiles its own copy.
+// and corners outside the volume read as 0: the cell, the value and the corner weights are lin_cell.h's.  ic_voxel is the
+// ONE place r(x) = u(x) + v(x + u(x)) and the corner terms are formed; IcThread says which voxels a thread owns (VPT = 4:
+// 16-byte loads / stores through LDS when W % 4 == 0 and the pointers are aligned, else 1); ic_block_reduce adds a double
+// and takes a maximum over the workgroup in a fixed order; ic_bwd_voxels is the adjoint of the sampling for a gradient that
+// either file supplies.  Everything here has internal linkage: each file compiles its own copy.
 #pragma once
-#include "common.h"
-#include <math.h>
+#include "lin_cell.h"
 
 namespace {
 
@@ -44,12 +43,12 @@ __device__ __forceinline__ void ic_block_reduce(double& s, unsigned& m, double* 
 
 struct __attribute__((packed, aligned(4))) IcPair { float a, b; };      // two neighbours along x, 4-byte aligned
 
-// One voxel: the sample point p + u, its corners and r.  Bit ND - 1 - a of corner m is set when it is the upper one along
-// axis a (x is bit 0).
+// One voxel: the cell of the sample point p + u (lin_cell.h), its corners and r.  Bit ND - 1 - a of corner m is set when it
+// is the upper one along axis a (x is bit 0).
 template <int ND>
 struct IcVox {
   static constexpr int NC = 1 << ND;
-  float w[ND][2];                            // interpolation weights along each axis: lower, upper corner
+  LinCell<ND> cell;
   int off[NC];                               // offset of corner m in a channel of v, -1 when it lies outside
   float val[ND][NC];                         // v_c at the corners (0 outside)
   float r[ND];
@@ -59,37 +58,14 @@ template <int ND>
 __device__ __forceinline__ void ic_voxel(const float* __restrict__ vb, const IcGeom& g, const int (&p)[ND],
                                          const float (&u)[ND], IcVox<ND>& q) {
   constexpr int NC = 1 << ND;
-  int n[ND], st[ND], i0[ND];
-  if (ND == 3) { n[0] = g.D; n[1] = g.H; n[2] = g.W; st[0] = g.H * g.W; st[1] = g.W; st[2] = 1; }
-  else { n[0] = g.H; n[ND - 1] = g.W; st[0] = g.W; st[ND - 1] = 1; }
-  bool ok[ND][2];
+  int n[ND];
+  lin_extents<ND>(g.D, g.H, g.W, n);
+  lin_cell<ND, int>(p, u, n, q.cell);
 #pragma unroll
-  for (int a = 0; a < ND; ++a) {
-    const float f = (float)p[a] + u[a];
-    const bool nearby = f >= -1.f && f < (float)n[a];             // false for NaN and for points past the padding cells:
-    const float fl = floorf(f);                                 // no corner is read then, and no float goes to int
-    i0[a] = nearby ? (int)fl : -2;
-    q.w[a][1] = f - fl;
-    q.w[a][0] = 1.f - q.w[a][1];
-    ok[a][0] = (unsigned)i0[a] < (unsigned)n[a];
-    ok[a][1] = (unsigned)(i0[a] + 1) < (unsigned)n[a];
-  }
-#pragma unroll
-  for (int m = 0; m < NC; ++m) {
-    bool in = true;
-    int o = 0;
-#pragma unroll
-    for (int a = 0; a < ND; ++a) {
-      const int bit = (m >> (ND - 1 - a)) & 1;                  // x is bit 0
-      in = in && ok[a][bit];
-      o += (i0[a] + bit) * st[a];
-    }
-    q.off[m] = in ? o : -1;
-  }
+  for (int m = 0; m < NC; ++m) q.off[m] = q.cell.in(m) ? q.cell.off(m) : -1;
 #pragma unroll
   for (int c = 0; c < ND; ++c) {
     const float* vc = vb + (long long)c * g.S;
-    float acc = 0.f;
     // the two x corners of a row of the cell travel as ONE 8-byte load (the gather is bound by the number of load
     // instructions, not by bytes): at the pair when both lie inside, else at the neighbouring pair that holds the one inside
     // -- every address is inside the channel, no branch
@@ -100,28 +76,8 @@ __device__ __forceinline__ void ic_voxel(const float* __restrict__ vb, const IcG
       q.val[c][m] = o0 >= 0 ? (o1 >= 0 ? t.a : t.b) : 0.f;
       q.val[c][m + 1] = o1 >= 0 ? (o0 >= 0 ? t.b : t.a) : 0.f;
     }
-    // x innermost, then y, then z: the order of the warp kernels
-    if (ND == 3) {
-      const float a0 = q.w[1][0] * (q.w[2][0] * q.val[c][0] + q.w[2][1] * q.val[c][1]) +
-                       q.w[1][1] * (q.w[2][0] * q.val[c][2] + q.w[2][1] * q.val[c][3]);
-      const float a1 = q.w[1][0] * (q.w[2][0] * q.val[c][4] + q.w[2][1] * q.val[c][5]) +
-                       q.w[1][1] * (q.w[2][0] * q.val[c][6] + q.w[2][1] * q.val[c][NC - 1]);
-      acc = q.w[0][0] * a0 + q.w[0][1] * a1;
-    } else {
-      acc = q.w[0][0] * (q.w[ND - 1][0] * q.val[c][0] + q.w[ND - 1][1] * q.val[c][1]) +
-            q.w[0][1] * (q.w[ND - 1][0] * q.val[c][2] + q.w[ND - 1][1] * q.val[c][3]);
-    }
-    q.r[c] = u[c] + acc;
+    q.r[c] = u[c] + lin_value<ND>(q.val[c], q.cell.w1);
   }
-}
-// weight of corner m with x as bit 0 (axis a is bit ND - 1 - a)
-template <int ND>
-__device__ __forceinline__ float ic_cw(const IcVox<ND>& q, int m, int skip /* axis left out, -1 for none */) {
-  float t = 1.f;
-#pragma unroll
-  for (int a = 0; a < ND; ++a)
-    if (a != skip) t *= q.w[a][(m >> (ND - 1 - a)) & 1];
-  return t;
 }
 
 // Which voxels a thread owns.  VPT == 1: one, workgroup base + thread.  VPT == 4: a wave owns 256 consecutive voxels; in
@@ -237,7 +193,7 @@ __device__ __forceinline__ void ic_bwd_voxels(const float* __restrict__ u, const
           float dvc = 0.f;
 #pragma unroll
           for (int m = 0; m < NC; ++m) {
-            const float wv = ic_cw<ND>(q, m, a) * q.val[c][m];
+            const float wv = lin_cw<ND>(q.cell.w1, m, 1.f, a) * q.val[c][m];
             dvc += ((m >> (ND - 1 - a)) & 1) ? wv : -wv;
           }
           t += cf[c] * dvc;
@@ -256,7 +212,7 @@ __device__ __forceinline__ void ic_bwd_voxels(const float* __restrict__ u, const
 #pragma unroll
         for (int m = 0; m < NC; ++m) {
           if (q.off[m] < 0) continue;
-          const float wm = ic_cw<ND>(q, m, -1);
+          const float wm = lin_cw<ND>(q.cell.w1, m);
 #pragma unroll
           for (int c = 0; c < ND; ++c)
             atomicAdd(ab + (long long)c * g.S + q.off[m], (unsigned long long)__float2ll_rn(ldexpf(s * cf[c] * wm, ex)));

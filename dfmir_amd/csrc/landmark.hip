@@ -34,8 +34,7 @@
 //              Chosen over a sort by cell (more launches and scratch for nothing at K <= 4096) and over 64-bit fixed-point
 //              atomics on dflow (would need a volume-sized integer accumulator).
 // Nothing syncs with the host, allocates or keeps state.
-#include "common.h"
-#include <math.h>
+#include "lin_cell.h"
 
 namespace {
 
@@ -84,15 +83,6 @@ struct LmPoint {
   float d;                                   // |r|
 };
 
-// weight of corner c of a cell: axis a is bit ND - 1 - a (x is bit 0), the product taken in the order (z,) y, x
-template <int ND>
-__device__ __forceinline__ float lm_cw(const float (&w1)[ND], int c) {
-  float t = ((c >> (ND - 1)) & 1) ? w1[0] : 1.f - w1[0];
-#pragma unroll
-  for (int a = 1; a < ND; ++a) t *= ((c >> (ND - 1 - a)) & 1) ? w1[a] : 1.f - w1[a];
-  return t;
-}
-
 // One landmark.  q, p: its ND coordinates (p == nullptr: map only, validity is that of q and the weight alone).  No float
 // that failed the range test is converted to int; every corner read lies inside the channel: 0 <= i0_a <= n_a - 2.
 template <int ND>
@@ -132,7 +122,7 @@ __device__ __forceinline__ void lm_point(const float* __restrict__ fb, const flo
     int off = base;
 #pragma unroll
     for (int a = 0; a < ND; ++a) off += ((cn >> (ND - 1 - a)) & 1) * g.st[a];
-    const float cw = lm_cw<ND>(o.w1, cn);
+    const float cw = lin_cw<ND>(o.w1, cn);
 #pragma unroll
     for (int c = 0; c < ND; ++c) u[c] += cw * fb[(long long)c * g.S + off];
   }
@@ -361,7 +351,7 @@ __global__ __launch_bounds__(LM_T) void lm_bwd_k(const float* __restrict__ ws, l
             cj |= (bp & 1) << (ND - 1 - a);
           }
           if (hit) {
-            const float cw = lm_cw<ND>(w1, cj);
+            const float cw = lin_cw<ND>(w1, cj);
 #pragma unroll
             for (int c = 0; c < ND; ++c) acc[cn][c] += gj[c] * cw;
             if (below) lower |= 1u << cn;

@@ -5,233 +5,67 @@
 // directly -- the reference's normalise-to-[-1,1] / permute / grid_sample round trip
 // (torchvoxelmorph/layers.py:36-48) is never materialised.
 #include "common.h"
+#include "lin_cell.h"
 
-// ------------------------------------------------------------------------------------------ 2-D
-__global__ __launch_bounds__(256) void warp2d_fwd_k(const float* __restrict__ src,
-                                                    const float* __restrict__ flow,
-                                                    float* __restrict__ out, int B, int C, int H, int W,
-                                                    int mode, int add_identity) {
-  const long long HW = (long long)H * W;
-  const long long total = (long long)B * HW;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int x = (int)(i % W);
-  const long long r = i / W;
-  const int y = (int)(r % H);
-  const long long b = r / H;
-  const long long sp = (long long)y * W + x;
-  const float fy = (float)y + flow[(b * 2 + 0) * HW + sp];
-  const float fx = (float)x + flow[(b * 2 + 1) * HW + sp];
-  const float* sb = src + b * C * HW;
-  float* ob = out + b * C * HW + sp;
+// ------------------------------------------------------------------------- one voxel per thread
+// The arithmetic is lin_cell.h's per-voxel routines, the ones the windowed kernels fall back to.  2-D runs with D = 1.
+template <int ND>
+struct WarpVoxel {
+  int p[ND], n[ND];
+  long long b, S, sp;
+  __device__ __forceinline__ bool decode(int B, int D, int H, int W) {
+    S = (long long)D * H * W;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * S) return false;
+    long long r = i / W;
+    p[ND - 1] = (int)(i % W);
+    p[ND - 2] = (int)(r % H); r /= H;
+    if (ND == 3) { p[0] = (int)(r % D); r /= D; }
+    lin_extents<ND>(D, H, W, n);
+    b = r;
+    sp = i - b * S;
+    return true;
+  }
+};
+
+template <int ND>
+__global__ __launch_bounds__(256) void warp_fwd_k(const float* __restrict__ src, const float* __restrict__ flow,
+                                                  float* __restrict__ out, int B, int C, int D, int H, int W, int mode,
+                                                  int add_identity) {
+  WarpVoxel<ND> t;
+  if (!t.decode(B, D, H, W)) return;
+  const float* sb = src + t.b * C * t.S;
+  const float* fb = flow + t.b * ND * t.S;
+  float* ob = out + t.b * C * t.S;
   if (mode == 1) {
-    const int yy = (int)nearbyintf(fy), xx = (int)nearbyintf(fx);
-    const bool v = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
+    bool v = true;
+    long long o = 0;
+#pragma unroll
+    for (int a = 0; a < ND; ++a) {
+      const int i = (int)nearbyintf((float)t.p[a] + fb[a * t.S + t.sp]);
+      v = v && (unsigned)i < (unsigned)t.n[a];
+      o = o * t.n[a] + i;
+    }
     for (int c = 0; c < C; ++c) {
-      float val = v ? sb[c * HW + (long long)yy * W + xx] : 0.f;
-      if (add_identity) val += sb[c * HW + sp];
-      ob[c * HW] = val;
+      float val = v ? sb[c * t.S + o] : 0.f;
+      if (add_identity) val += sb[c * t.S + t.sp];
+      ob[c * t.S + t.sp] = val;
     }
     return;
   }
-  const float y0f = floorf(fy), x0f = floorf(fx);
-  const int y0 = (int)y0f, x0 = (int)x0f;
-  const float wy1 = fy - y0f, wx1 = fx - x0f, wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-  const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)(y0 + 1) < (unsigned)H;
-  const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)(x0 + 1) < (unsigned)W;
-  const long long o00 = (long long)y0 * W + x0;
-  for (int c = 0; c < C; ++c) {
-    const float* sc = sb + c * HW;
-    const float v00 = (vy0 && vx0) ? sc[o00] : 0.f;
-    const float v01 = (vy0 && vx1) ? sc[o00 + 1] : 0.f;
-    const float v10 = (vy1 && vx0) ? sc[o00 + W] : 0.f;
-    const float v11 = (vy1 && vx1) ? sc[o00 + W + 1] : 0.f;
-    float val = wy0 * (wx0 * v00 + wx1 * v01) + wy1 * (wx0 * v10 + wx1 * v11);
-    if (add_identity) val += sc[sp];
-    ob[c * HW] = val;
-  }
+  lin_voxel_fwd<ND, long long>(sb, fb, ob, C, t.n, t.S, t.sp, t.p, add_identity);
 }
 
-__global__ __launch_bounds__(256) void warp2d_bwd_k(const float* __restrict__ dout,
-                                                    const float* __restrict__ src,
-                                                    const float* __restrict__ flow,
-                                                    float* __restrict__ dsrc, float* __restrict__ dflow,
-                                                    int B, int C, int H, int W, int add_identity,
-                                                    int flow_into_src) {
-  const long long HW = (long long)H * W;
-  const long long total = (long long)B * HW;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int x = (int)(i % W);
-  const long long r = i / W;
-  const int y = (int)(r % H);
-  const long long b = r / H;
-  const long long sp = (long long)y * W + x;
-  const float fy = (float)y + flow[(b * 2 + 0) * HW + sp];
-  const float fx = (float)x + flow[(b * 2 + 1) * HW + sp];
-  const float y0f = floorf(fy), x0f = floorf(fx);
-  const int y0 = (int)y0f, x0 = (int)x0f;
-  const float wy1 = fy - y0f, wx1 = fx - x0f, wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-  const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)(y0 + 1) < (unsigned)H;
-  const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)(x0 + 1) < (unsigned)W;
-  const long long o00 = (long long)y0 * W + x0;
-  const float* sb = src + b * C * HW;
-  float* db = dsrc ? dsrc + b * C * HW : nullptr;
-  const float* gb = dout + b * C * HW + sp;
-  float gy = 0.f, gx = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float g = gb[c * HW];
-    const float* sc = sb + c * HW;
-    const float v00 = (vy0 && vx0) ? sc[o00] : 0.f;
-    const float v01 = (vy0 && vx1) ? sc[o00 + 1] : 0.f;
-    const float v10 = (vy1 && vx0) ? sc[o00 + W] : 0.f;
-    const float v11 = (vy1 && vx1) ? sc[o00 + W + 1] : 0.f;
-    gy += g * (wx0 * (v10 - v00) + wx1 * (v11 - v01));
-    gx += g * (wy0 * (v01 - v00) + wy1 * (v11 - v10));
-    if (db) {
-      float* dc = db + c * HW;
-      if (vy0 && vx0) atomicAdd(dc + o00, g * wy0 * wx0);
-      if (vy0 && vx1) atomicAdd(dc + o00 + 1, g * wy0 * wx1);
-      if (vy1 && vx0) atomicAdd(dc + o00 + W, g * wy1 * wx0);
-      if (vy1 && vx1) atomicAdd(dc + o00 + W + 1, g * wy1 * wx1);
-      if (add_identity) atomicAdd(dc + sp, g);
-    }
-  }
-  if (flow_into_src) {
-    atomicAdd(db + 0 * HW + sp, gy);
-    atomicAdd(db + 1 * HW + sp, gx);
-  } else if (dflow) {
-    dflow[(b * 2 + 0) * HW + sp] = gy;
-    dflow[(b * 2 + 1) * HW + sp] = gx;
-  }
-}
-
-// ------------------------------------------------------------------------------------------ 3-D
-__global__ __launch_bounds__(256) void warp3d_fwd_k(const float* __restrict__ src,
-                                                    const float* __restrict__ flow,
-                                                    float* __restrict__ out, int B, int C, int D, int H,
-                                                    int W, int mode, int add_identity) {
-  const long long HW = (long long)H * W, S = HW * D;
-  const long long total = (long long)B * S;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int x = (int)(i % W);
-  long long r = i / W;
-  const int y = (int)(r % H); r /= H;
-  const int z = (int)(r % D);
-  const long long b = r / D;
-  const long long sp = ((long long)z * H + y) * W + x;
-  const float fz = (float)z + flow[(b * 3 + 0) * S + sp];
-  const float fy = (float)y + flow[(b * 3 + 1) * S + sp];
-  const float fx = (float)x + flow[(b * 3 + 2) * S + sp];
-  const float* sb = src + b * C * S;
-  float* ob = out + b * C * S + sp;
-  if (mode == 1) {
-    const int zz = (int)nearbyintf(fz), yy = (int)nearbyintf(fy), xx = (int)nearbyintf(fx);
-    const bool v = (unsigned)zz < (unsigned)D && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-    for (int c = 0; c < C; ++c) {
-      float val = v ? sb[c * S + ((long long)zz * H + yy) * W + xx] : 0.f;
-      if (add_identity) val += sb[c * S + sp];
-      ob[c * S] = val;
-    }
-    return;
-  }
-  const float z0f = floorf(fz), y0f = floorf(fy), x0f = floorf(fx);
-  const int z0 = (int)z0f, y0 = (int)y0f, x0 = (int)x0f;
-  const float wz1 = fz - z0f, wy1 = fy - y0f, wx1 = fx - x0f;
-  const float wz0 = 1.f - wz1, wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-  const bool vz0 = (unsigned)z0 < (unsigned)D, vz1 = (unsigned)(z0 + 1) < (unsigned)D;
-  const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)(y0 + 1) < (unsigned)H;
-  const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)(x0 + 1) < (unsigned)W;
-  const long long o000 = ((long long)z0 * H + y0) * W + x0;
-  for (int c = 0; c < C; ++c) {
-    const float* sc = sb + c * S;
-    const float v000 = (vz0 && vy0 && vx0) ? sc[o000] : 0.f;
-    const float v001 = (vz0 && vy0 && vx1) ? sc[o000 + 1] : 0.f;
-    const float v010 = (vz0 && vy1 && vx0) ? sc[o000 + W] : 0.f;
-    const float v011 = (vz0 && vy1 && vx1) ? sc[o000 + W + 1] : 0.f;
-    const float v100 = (vz1 && vy0 && vx0) ? sc[o000 + HW] : 0.f;
-    const float v101 = (vz1 && vy0 && vx1) ? sc[o000 + HW + 1] : 0.f;
-    const float v110 = (vz1 && vy1 && vx0) ? sc[o000 + HW + W] : 0.f;
-    const float v111 = (vz1 && vy1 && vx1) ? sc[o000 + HW + W + 1] : 0.f;
-    float val = wz0 * (wy0 * (wx0 * v000 + wx1 * v001) + wy1 * (wx0 * v010 + wx1 * v011)) +
-                wz1 * (wy0 * (wx0 * v100 + wx1 * v101) + wy1 * (wx0 * v110 + wx1 * v111));
-    if (add_identity) val += sc[sp];
-    ob[c * S] = val;
-  }
-}
-
-__global__ __launch_bounds__(256) void warp3d_bwd_k(const float* __restrict__ dout,
-                                                    const float* __restrict__ src,
-                                                    const float* __restrict__ flow,
-                                                    float* __restrict__ dsrc, float* __restrict__ dflow,
-                                                    int B, int C, int D, int H, int W, int add_identity,
-                                                    int flow_into_src) {
-  const long long HW = (long long)H * W, S = HW * D;
-  const long long total = (long long)B * S;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int x = (int)(i % W);
-  long long r = i / W;
-  const int y = (int)(r % H); r /= H;
-  const int z = (int)(r % D);
-  const long long b = r / D;
-  const long long sp = ((long long)z * H + y) * W + x;
-  const float fz = (float)z + flow[(b * 3 + 0) * S + sp];
-  const float fy = (float)y + flow[(b * 3 + 1) * S + sp];
-  const float fx = (float)x + flow[(b * 3 + 2) * S + sp];
-  const float z0f = floorf(fz), y0f = floorf(fy), x0f = floorf(fx);
-  const int z0 = (int)z0f, y0 = (int)y0f, x0 = (int)x0f;
-  const float wz1 = fz - z0f, wy1 = fy - y0f, wx1 = fx - x0f;
-  const float wz0 = 1.f - wz1, wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-  const bool vz0 = (unsigned)z0 < (unsigned)D, vz1 = (unsigned)(z0 + 1) < (unsigned)D;
-  const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)(y0 + 1) < (unsigned)H;
-  const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)(x0 + 1) < (unsigned)W;
-  const long long o000 = ((long long)z0 * H + y0) * W + x0;
-  const float* sb = src + b * C * S;
-  float* db = dsrc ? dsrc + b * C * S : nullptr;
-  const float* gb = dout + b * C * S + sp;
-  float gz = 0.f, gy = 0.f, gx = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float g = gb[c * S];
-    const float* sc = sb + c * S;
-    const float v000 = (vz0 && vy0 && vx0) ? sc[o000] : 0.f;
-    const float v001 = (vz0 && vy0 && vx1) ? sc[o000 + 1] : 0.f;
-    const float v010 = (vz0 && vy1 && vx0) ? sc[o000 + W] : 0.f;
-    const float v011 = (vz0 && vy1 && vx1) ? sc[o000 + W + 1] : 0.f;
-    const float v100 = (vz1 && vy0 && vx0) ? sc[o000 + HW] : 0.f;
-    const float v101 = (vz1 && vy0 && vx1) ? sc[o000 + HW + 1] : 0.f;
-    const float v110 = (vz1 && vy1 && vx0) ? sc[o000 + HW + W] : 0.f;
-    const float v111 = (vz1 && vy1 && vx1) ? sc[o000 + HW + W + 1] : 0.f;
-    const float p0 = wy0 * (wx0 * v000 + wx1 * v001) + wy1 * (wx0 * v010 + wx1 * v011);
-    const float p1 = wy0 * (wx0 * v100 + wx1 * v101) + wy1 * (wx0 * v110 + wx1 * v111);
-    gz += g * (p1 - p0);
-    gy += g * (wz0 * (wx0 * (v010 - v000) + wx1 * (v011 - v001)) +
-               wz1 * (wx0 * (v110 - v100) + wx1 * (v111 - v101)));
-    gx += g * (wz0 * (wy0 * (v001 - v000) + wy1 * (v011 - v010)) +
-               wz1 * (wy0 * (v101 - v100) + wy1 * (v111 - v110)));
-    if (db) {
-      float* dc = db + c * S;
-      if (vz0 && vy0 && vx0) atomicAdd(dc + o000, g * wz0 * wy0 * wx0);
-      if (vz0 && vy0 && vx1) atomicAdd(dc + o000 + 1, g * wz0 * wy0 * wx1);
-      if (vz0 && vy1 && vx0) atomicAdd(dc + o000 + W, g * wz0 * wy1 * wx0);
-      if (vz0 && vy1 && vx1) atomicAdd(dc + o000 + W + 1, g * wz0 * wy1 * wx1);
-      if (vz1 && vy0 && vx0) atomicAdd(dc + o000 + HW, g * wz1 * wy0 * wx0);
-      if (vz1 && vy0 && vx1) atomicAdd(dc + o000 + HW + 1, g * wz1 * wy0 * wx1);
-      if (vz1 && vy1 && vx0) atomicAdd(dc + o000 + HW + W, g * wz1 * wy1 * wx0);
-      if (vz1 && vy1 && vx1) atomicAdd(dc + o000 + HW + W + 1, g * wz1 * wy1 * wx1);
-      if (add_identity) atomicAdd(dc + sp, g);
-    }
-  }
-  if (flow_into_src) {
-    atomicAdd(db + 0 * S + sp, gz);
-    atomicAdd(db + 1 * S + sp, gy);
-    atomicAdd(db + 2 * S + sp, gx);
-  } else if (dflow) {
-    dflow[(b * 3 + 0) * S + sp] = gz;
-    dflow[(b * 3 + 1) * S + sp] = gy;
-    dflow[(b * 3 + 2) * S + sp] = gx;
-  }
+template <int ND>
+__global__ __launch_bounds__(256) void warp_bwd_k(const float* __restrict__ dout, const float* __restrict__ src,
+                                                  const float* __restrict__ flow, float* __restrict__ dsrc,
+                                                  float* __restrict__ dflow, int B, int C, int D, int H, int W,
+                                                  int add_identity, int flow_into_src) {
+  WarpVoxel<ND> t;
+  if (!t.decode(B, D, H, W)) return;
+  lin_voxel_bwd<ND, long long>(dout + t.b * C * t.S, src + t.b * C * t.S, flow + t.b * ND * t.S,
+                               dsrc ? dsrc + t.b * C * t.S : nullptr, dflow ? dflow + t.b * ND * t.S : nullptr, C, t.n, t.S,
+                               t.sp, t.p, add_identity, flow_into_src);
 }
 
 // --------------------------------------------------------------------------------- resize
@@ -591,63 +425,50 @@ int df_warp_win_fwd_try(int nd, const float* src, const float* flow, float* out,
 int df_warp_win_bwd_try(int nd, const float* dout, const float* src, const float* flow, float* dsrc, float* dflow,
                         int B, int C, int D, int H, int W, int add_identity, int flow_into_src, hipStream_t st);
 
-extern "C" int dfmir_warp2d_fwd(const float* src, const float* flow, float* out, int B, int C, int H,
-                                int W, int mode, int add_identity, void* stream) {
-  DF_ARG_CHECK(src && flow && out && B > 0 && C > 0 && H > 0 && W > 0);
-  DF_ARG_CHECK(!add_identity || C == 2);
-  const long long total = (long long)B * H * W;
-  if (mode == 0 && df_warp_win_fwd_try(2, src, flow, out, B, C, 1, H, W, add_identity, (hipStream_t)stream)) {
-    DF_LAUNCH_CHECK();
-    return 0;
+// nd = 2 passes D = 1
+static int warp_fwd_launch(int nd, const float* src, const float* flow, float* out, int B, int C, int D, int H, int W,
+                           int mode, int add_identity, void* stream) {
+  DF_ARG_CHECK(src && flow && out && B > 0 && C > 0 && D > 0 && H > 0 && W > 0);
+  DF_ARG_CHECK(!add_identity || C == nd);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)(((long long)B * D * H * W + 255) / 256);
+  if (mode != 0 || !df_warp_win_fwd_try(nd, src, flow, out, B, C, D, H, W, add_identity, st)) {
+    if (nd == 3) warp_fwd_k<3><<<grid, 256, 0, st>>>(src, flow, out, B, C, D, H, W, mode, add_identity);
+    else warp_fwd_k<2><<<grid, 256, 0, st>>>(src, flow, out, B, C, 1, H, W, mode, add_identity);
   }
-  warp2d_fwd_k<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, flow, out, B, C, H,
-                                                                                W, mode, add_identity);
   DF_LAUNCH_CHECK();
   return 0;
+}
+static int warp_bwd_launch(int nd, const float* dout, const float* src, const float* flow, float* dsrc, float* dflow, int B,
+                           int C, int D, int H, int W, int add_identity, int flow_into_src, void* stream) {
+  DF_ARG_CHECK(dout && src && flow && B > 0 && C > 0 && D > 0 && H > 0 && W > 0);
+  DF_ARG_CHECK(!flow_into_src || (dsrc && C == nd));
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)(((long long)B * D * H * W + 255) / 256);
+  if (!df_warp_win_bwd_try(nd, dout, src, flow, dsrc, dflow, B, C, D, H, W, add_identity, flow_into_src, st)) {
+    if (nd == 3) warp_bwd_k<3><<<grid, 256, 0, st>>>(dout, src, flow, dsrc, dflow, B, C, D, H, W, add_identity, flow_into_src);
+    else warp_bwd_k<2><<<grid, 256, 0, st>>>(dout, src, flow, dsrc, dflow, B, C, 1, H, W, add_identity, flow_into_src);
+  }
+  DF_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int dfmir_warp2d_fwd(const float* src, const float* flow, float* out, int B, int C, int H,
+                                int W, int mode, int add_identity, void* stream) {
+  return warp_fwd_launch(2, src, flow, out, B, C, 1, H, W, mode, add_identity, stream);
 }
 extern "C" int dfmir_warp2d_bwd(const float* dout, const float* src, const float* flow, float* dsrc,
                                 float* dflow, int B, int C, int H, int W, int add_identity,
                                 int flow_into_src, void* stream) {
-  DF_ARG_CHECK(dout && src && flow && B > 0 && C > 0 && H > 0 && W > 0);
-  DF_ARG_CHECK(!flow_into_src || (dsrc && C == 2));
-  const long long total = (long long)B * H * W;
-  if (df_warp_win_bwd_try(2, dout, src, flow, dsrc, dflow, B, C, 1, H, W, add_identity, flow_into_src, (hipStream_t)stream)) {
-    DF_LAUNCH_CHECK();
-    return 0;
-  }
-  warp2d_bwd_k<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      dout, src, flow, dsrc, dflow, B, C, H, W, add_identity, flow_into_src);
-  DF_LAUNCH_CHECK();
-  return 0;
+  return warp_bwd_launch(2, dout, src, flow, dsrc, dflow, B, C, 1, H, W, add_identity, flow_into_src, stream);
 }
 extern "C" int dfmir_warp3d_fwd(const float* src, const float* flow, float* out, int B, int C, int D,
                                 int H, int W, int mode, int add_identity, void* stream) {
-  DF_ARG_CHECK(src && flow && out && B > 0 && C > 0 && D > 0 && H > 0 && W > 0);
-  DF_ARG_CHECK(!add_identity || C == 3);
-  const long long total = (long long)B * D * H * W;
-  if (mode == 0 && df_warp_win_fwd_try(3, src, flow, out, B, C, D, H, W, add_identity, (hipStream_t)stream)) {
-    DF_LAUNCH_CHECK();
-    return 0;
-  }
-  warp3d_fwd_k<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      src, flow, out, B, C, D, H, W, mode, add_identity);
-  DF_LAUNCH_CHECK();
-  return 0;
+  return warp_fwd_launch(3, src, flow, out, B, C, D, H, W, mode, add_identity, stream);
 }
 extern "C" int dfmir_warp3d_bwd(const float* dout, const float* src, const float* flow, float* dsrc,
                                 float* dflow, int B, int C, int D, int H, int W, int add_identity,
                                 int flow_into_src, void* stream) {
-  DF_ARG_CHECK(dout && src && flow && B > 0 && C > 0 && D > 0 && H > 0 && W > 0);
-  DF_ARG_CHECK(!flow_into_src || (dsrc && C == 3));
-  const long long total = (long long)B * D * H * W;
-  if (df_warp_win_bwd_try(3, dout, src, flow, dsrc, dflow, B, C, D, H, W, add_identity, flow_into_src, (hipStream_t)stream)) {
-    DF_LAUNCH_CHECK();
-    return 0;
-  }
-  warp3d_bwd_k<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      dout, src, flow, dsrc, dflow, B, C, D, H, W, add_identity, flow_into_src);
-  DF_LAUNCH_CHECK();
-  return 0;
+  return warp_bwd_launch(3, dout, src, flow, dsrc, dflow, B, C, D, H, W, add_identity, flow_into_src, stream);
 }
 long long df_warp_win_bwd_own_ws(int nd, int B, int C, int D, int H, int W);
 int df_warp_win_bwd_own_try(int nd, const float* dout, const float* src, const float* flow, float* dsrc, float* dflow,

@@ -19,13 +19,13 @@
 // LDS layout: natural x order, row stride 41 words (== 9 mod 32).  A half-wave is 8 x-quads x 4 rows;
 // its lanes read words 4*xq + 41*row + shift, i.e. banks {4i + 9r}: all 32 distinct.
 #include "common.h"
+#include "lin_cell.h"
 
 typedef unsigned wu32x4 __attribute__((ext_vector_type(4)));
 
 template <int ND> struct WinGeom;
 template <> struct WinGeom<3> { static constexpr int TZ = 8, TY = 8, EZ = 12, EY = 12; };
 template <> struct WinGeom<2> { static constexpr int TZ = 1, TY = 64, EZ = 1, EY = 68; };
-typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
 static constexpr int WTX = 32;        // tile width (8 lanes x 4 voxels)
 static constexpr int WEX = 40;        // window width
 static constexpr int WRS = 41;        // LDS row stride (== 9 mod 32: see the bank note above)
@@ -44,7 +44,7 @@ __device__ __forceinline__ int wave_min_i(int v) {
 template <int ND>
 struct WinThread {
   int base[4];                 // LDS index of corner (z0,y0,x0)
-  float wz1[4], wy1[4], wx1[4];
+  float w1[4][ND];             // upper weights along (z,) y, x
   unsigned fast;
 };
 
@@ -61,6 +61,17 @@ __device__ __forceinline__ bool win_tile(int ntx, int nty, int ntz, int B, int& 
   tzb = L % ntz;
   b = L / ntz;
   return true;
+}
+
+// floorf(f) as an int for the window test, defined for NaN (-> -WFAR), inf and |f| >= 2^31: an index at +-2^30 minus any
+// window origin neither wraps nor lies in a window, and it bounds the window minimum as every index outside [-1, n) does.
+// For every finite f this is what the unguarded (int)floorf(f) gave on the hardware (which saturates), so windows and
+// fast / slow voxels are as before.  NaN is a deliberate departure: the hardware's convert gave 0, so a NaN voxel could be
+// a fast voxel of cell 0 and its NaN weights went into the LDS d(src) window; now it is always a slow voxel, lin_cell
+// gives it no corner, it adds nothing to d(src), and it pulls the window minimum of its tile to -1.
+__device__ __forceinline__ int win_index(float fl) {
+  constexpr float WFAR = 1073741824.f;
+  return (int)fminf(fmaxf(fl, -WFAR), WFAR);
 }
 
 template <int ND>
@@ -83,13 +94,17 @@ __device__ __forceinline__ void win_prologue(const float* __restrict__ flow, int
     const float fz = (ND == 3) ? (float)z + __uint_as_float(f[0][e]) : 0.f;
     const float fy = (float)y + __uint_as_float(f[ND - 2][e]);
     const float fx = (float)(x + e) + __uint_as_float(f[ND - 1][e]);
+    // Not lin_cell: its guard turns every point outside [-1, n) into index -2, but the window reaches past the frame (it
+    // reads zeros there), so such a point may still be a fast voxel, and one past the upper end bounds the window minimum
+    // by n - 1: which voxels are fast decides the window origin and the fixed-point scale of the owner-gather backward,
+    // i.e. bits of d(src).  The true index is kept; win_index only makes the conversion defined.
     const float z0f = floorf(fz), y0f = floorf(fy), x0f = floorf(fx);
-    z0[e] = (ND == 3) ? (int)z0f : 0;
-    y0[e] = (int)y0f;
-    x0[e] = (int)x0f;
-    th.wz1[e] = (ND == 3) ? fz - z0f : 0.f;
-    th.wy1[e] = fy - y0f;
-    th.wx1[e] = fx - x0f;
+    z0[e] = (ND == 3) ? win_index(z0f) : 0;
+    y0[e] = win_index(y0f);
+    x0[e] = win_index(x0f);
+    if (ND == 3) th.w1[e][0] = fz - z0f;
+    th.w1[e][ND - 2] = fy - y0f;
+    th.w1[e][ND - 1] = fx - x0f;
     if (active) {   // corners below -1 / above size-1 only ever read zeros: clamp them out of the minimum
       if (ND == 3) mz = min(mz, max(-1, min(z0[e], D - 1)));
       my = min(my, max(-1, min(y0[e], H - 1)));
@@ -160,108 +175,42 @@ __device__ __forceinline__ void win_load(const __amdgpu_buffer_rsrc_t rs, float*
   }
 }
 
-// ---- scalar per-voxel routines for the (rare) voxels whose taps leave the window; same arithmetic as
-// the one-voxel-per-thread kernels in warp.hip
+// LDS corners of a cell whose lower corner is at p, in lin_cell.h's order (x is bit 0)
 template <int ND>
-struct VoxelTaps {
-  int z0, y0, x0;
-  float wz1, wy1, wx1;
-  bool zv[2], yv[2], xv[2];
+__device__ __forceinline__ int win_corner(int m) {
+  return (ND == 3 ? (m >> 2) * WinGeom<ND>::EY * WRS : 0) + ((m >> 1) & 1) * WRS + (m & 1);
+}
+template <int ND>
+__device__ __forceinline__ void win_gather(const float* p, float (&v)[1 << ND]) {
+#pragma unroll
+  for (int m = 0; m < (1 << ND); ++m) v[m] = p[win_corner<ND>(m)];
+}
+// the eight (four) corner weights of g, added into the LDS window at p by `add`: a float atomic, or fixed point
+template <int ND, typename T, class ADD>
+__device__ __forceinline__ void win_scatter(T* p, const float (&w1)[ND], float g, ADD add) {
+#pragma unroll
+  for (int m = 0; m < (1 << ND); ++m) add(p + win_corner<ND>(m), lin_cw<ND>(w1, m, g));
+}
+// channel c of the flow gradient of a quad's voxel e (the VecInt own term: channel c of d(src) is axis c)
+template <int ND>
+__device__ __forceinline__ float win_axis(const float (&gf)[ND][4], int c, int e) {
+  float r = gf[ND - 1][e];
+#pragma unroll
+  for (int a = ND - 2; a >= 0; --a) r = c == a ? gf[a][e] : r;
+  return r;
+}
+
+// The (rare) voxels whose taps leave the window are redone start to finish by lin_cell.h's per-voxel routines, the
+// arithmetic of the one-voxel-per-thread kernels in warp.hip.
+template <int ND>
+struct WinVoxel {
+  int n[ND], p[ND];
+  __device__ __forceinline__ WinVoxel(int D, int H, int W, int z, int y, int x) {
+    lin_extents<ND>(D, H, W, n);
+    if (ND == 3) p[0] = z;
+    p[ND - 2] = y; p[ND - 1] = x;
+  }
 };
-template <int ND>
-__device__ __forceinline__ VoxelTaps<ND> voxel_taps(const float* __restrict__ fb, int S, int sp, int z, int y, int x,
-                                                    int D, int H, int W) {
-  VoxelTaps<ND> v;
-  const float fz = (ND == 3) ? (float)z + fb[sp] : 0.f;
-  const float fy = (float)y + fb[(long long)(ND - 2) * S + sp];
-  const float fx = (float)x + fb[(long long)(ND - 1) * S + sp];
-  const float z0f = floorf(fz), y0f = floorf(fy), x0f = floorf(fx);
-  v.z0 = (ND == 3) ? (int)z0f : 0; v.y0 = (int)y0f; v.x0 = (int)x0f;
-  v.wz1 = (ND == 3) ? fz - z0f : 0.f; v.wy1 = fy - y0f; v.wx1 = fx - x0f;
-  v.zv[0] = (ND == 2) || (unsigned)v.z0 < (unsigned)D; v.zv[1] = (ND == 3) && (unsigned)(v.z0 + 1) < (unsigned)D;
-  v.yv[0] = (unsigned)v.y0 < (unsigned)H; v.yv[1] = (unsigned)(v.y0 + 1) < (unsigned)H;
-  v.xv[0] = (unsigned)v.x0 < (unsigned)W; v.xv[1] = (unsigned)(v.x0 + 1) < (unsigned)W;
-  return v;
-}
-
-template <int ND>
-__device__ void voxel_fwd_slow(const float* __restrict__ src_b, const float* __restrict__ flow_b,
-                               float* __restrict__ out_b, int C, int D, int H, int W, int S, int z, int y, int x,
-                               int add_identity) {
-  const int sp = (z * H + y) * W + x;
-  const VoxelTaps<ND> v = voxel_taps<ND>(flow_b, S, sp, z, y, x, D, H, W);
-  const int o = (v.z0 * H + v.y0) * W + v.x0, HW = H * W;
-  for (int c = 0; c < C; ++c) {
-    const float* sc = src_b + (long long)c * S;
-    float acc = 0.f;
-#pragma unroll
-    for (int kz = ND - 2; kz >= 0; --kz) {
-      float pl = 0.f;
-#pragma unroll
-      for (int ky = 1; ky >= 0; --ky) {
-        const bool rv = v.zv[kz] && v.yv[ky];
-        const float a0 = (rv && v.xv[0]) ? sc[o + kz * HW + ky * W] : 0.f;
-        const float a1 = (rv && v.xv[1]) ? sc[o + kz * HW + ky * W + 1] : 0.f;
-        const float row = (1.f - v.wx1) * a0 + v.wx1 * a1;
-        pl = ky ? v.wy1 * row : (1.f - v.wy1) * row + pl;
-      }
-      acc = (ND == 3) ? (kz ? v.wz1 * pl : (1.f - v.wz1) * pl + acc) : pl;
-    }
-    if (add_identity) acc += sc[sp];
-    out_b[(long long)c * S + sp] = acc;
-  }
-}
-
-template <int ND>
-__device__ void voxel_bwd_slow(const float* __restrict__ dout_b, const float* __restrict__ src_b,
-                               const float* __restrict__ flow_b, float* __restrict__ dsrc_b,
-                               float* __restrict__ dflow_b, int C, int D, int H, int W, int S, int z, int y, int x,
-                               int add_identity, int flow_into_src) {
-  const int sp = (z * H + y) * W + x;
-  const VoxelTaps<ND> v = voxel_taps<ND>(flow_b, S, sp, z, y, x, D, H, W);
-  const int o = (v.z0 * H + v.y0) * W + v.x0, HW = H * W;
-  const float wz[2] = {1.f - v.wz1, v.wz1}, wy[2] = {1.f - v.wy1, v.wy1}, wx[2] = {1.f - v.wx1, v.wx1};
-  float gz = 0.f, gy = 0.f, gx = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float g = dout_b[(long long)c * S + sp];
-    const float* sc = src_b + (long long)c * S;
-    float* dc = dsrc_b ? dsrc_b + (long long)c * S : nullptr;
-    float cv[2][2][2];
-#pragma unroll
-    for (int kz = 0; kz < ND - 1; ++kz)
-#pragma unroll
-      for (int ky = 0; ky < 2; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 2; ++kx) {
-          const bool ok = v.zv[kz] && v.yv[ky] && v.xv[kx];
-          const int off = o + kz * HW + ky * W + kx;
-          cv[kz][ky][kx] = ok ? sc[off] : 0.f;
-          if (dc && ok) atomicAdd(dc + off, (ND == 3) ? g * wz[kz] * wy[ky] * wx[kx] : g * wy[ky] * wx[kx]);
-        }
-    if (ND == 3) {
-      const float p0 = wy[0] * (wx[0] * cv[0][0][0] + wx[1] * cv[0][0][1]) + wy[1] * (wx[0] * cv[0][1][0] + wx[1] * cv[0][1][1]);
-      const float p1 = wy[0] * (wx[0] * cv[1][0][0] + wx[1] * cv[1][0][1]) + wy[1] * (wx[0] * cv[1][1][0] + wx[1] * cv[1][1][1]);
-      gz += g * (p1 - p0);
-      gy += g * (wz[0] * (wx[0] * (cv[0][1][0] - cv[0][0][0]) + wx[1] * (cv[0][1][1] - cv[0][0][1])) +
-                 wz[1] * (wx[0] * (cv[1][1][0] - cv[1][0][0]) + wx[1] * (cv[1][1][1] - cv[1][0][1])));
-      gx += g * (wz[0] * (wy[0] * (cv[0][0][1] - cv[0][0][0]) + wy[1] * (cv[0][1][1] - cv[0][1][0])) +
-                 wz[1] * (wy[0] * (cv[1][0][1] - cv[1][0][0]) + wy[1] * (cv[1][1][1] - cv[1][1][0])));
-    } else {
-      gy += g * (wx[0] * (cv[0][1][0] - cv[0][0][0]) + wx[1] * (cv[0][1][1] - cv[0][0][1]));
-      gx += g * (wy[0] * (cv[0][0][1] - cv[0][0][0]) + wy[1] * (cv[0][1][1] - cv[0][1][0]));
-    }
-    if (dc && add_identity) atomicAdd(dc + sp, g);
-  }
-  if (flow_into_src) {
-    if (ND == 3) atomicAdd(dsrc_b + sp, gz);
-    atomicAdd(dsrc_b + (long long)(ND - 2) * S + sp, gy);
-    atomicAdd(dsrc_b + (long long)(ND - 1) * S + sp, gx);
-  } else if (dflow_b) {
-    if (ND == 3) dflow_b[sp] = gz;
-    dflow_b[(long long)(ND - 2) * S + sp] = gy;
-    dflow_b[(long long)(ND - 1) * S + sp] = gx;
-  }
-}
 
 #define WIN_THREAD_COORDS()                                                            \
   using G = WinGeom<ND>;                                                               \
@@ -273,6 +222,47 @@ __device__ void voxel_bwd_slow(const float* __restrict__ dout_b, const float* __
   const bool active = x < W && y < H && z < D;                                         \
   const int S = D * H * W;                                                             \
   const int sp = (z * H + y) * W + x
+
+// Phase A of both backward kernels: d(flow) = sum_c dout_c * d(interp)/d(position) of the quad, corner values from the src
+// window, stored unless it goes into d(src) (flow_into_src) or nobody asked (dflow == NULL).  Fast voxels only -- a slow
+// voxel's gradient stays 0 here and is written start to finish by lin_voxel_bwd later (the float4 store covers both).
+// `run` is workgroup-uniform; the caller's window is free again after the next barrier.
+template <int ND>
+__device__ __forceinline__ void win_dflow(const float* __restrict__ dout, const float* __restrict__ src,
+                                          float* __restrict__ dflow, float* win, const WinThread<ND>& th, int b, int C,
+                                          int D, int H, int W, int S, int sp, int oz, int oy, int ox, bool active, bool run,
+                                          int flow_into_src, float (&gf)[ND][4]) {
+#pragma unroll
+  for (int a = 0; a < ND; ++a)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gf[a][e] = 0.f;
+  if (!run) return;
+  for (int c = 0; c < C; ++c) {
+    const float* sc = src + ((long long)b * C + c) * S;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sc), 0, (unsigned)S * 4u, 0x00020000);
+    if (c) __syncthreads();
+    win_load<ND>(rs, win, D, H, W, oz, oy, ox);
+    __syncthreads();
+    if (!active) continue;
+    const float4 g4 = *reinterpret_cast<const float4*>(dout + ((long long)b * C + c) * S + sp);
+    const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float g = gg[e] * (((th.fast >> e) & 1u) ? 1.f : 0.f);
+      float v[1 << ND], d[ND];
+      win_gather<ND>(win + th.base[e], v);
+      lin_flow_grad<ND>(v, th.w1[e], d);
+#pragma unroll
+      for (int a = 0; a < ND; ++a) gf[a][e] += g * d[a];
+    }
+  }
+  if (active && !flow_into_src && dflow) {
+    float* fb = dflow + (long long)b * ND * S + sp;
+#pragma unroll
+    for (int a = 0; a < ND; ++a)
+      *reinterpret_cast<float4*>(fb + (long long)a * S) = make_float4(gf[a][0], gf[a][1], gf[a][2], gf[a][3]);
+  }
+}
 
 // WW_OCC (A/B build switch, scripts/build_ko.sh warp_win WW_OCC 1 2 3): bit 0 = the forward kernel at 8 waves per SIMD
 // (64 VGPRs: 4 instead of 3 workgroups per CU), bit 1 = pass 1 of the owner-gather backward at 6 waves per SIMD
@@ -312,15 +302,9 @@ __global__ __launch_bounds__(WNT) WW_FWD_ATTR void warp_win_fwd_k(const float* _
     float r[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float* p = win + th.base[e];
-      const float wx1 = th.wx1[e], wy1 = th.wy1[e], wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-      float val = wy0 * (wx0 * p[0] + wx1 * p[1]) + wy1 * (wx0 * p[WRS] + wx1 * p[WRS + 1]);
-      if (ND == 3) {
-        const float* q = p + G::EY * WRS;
-        const float p1 = wy0 * (wx0 * q[0] + wx1 * q[1]) + wy1 * (wx0 * q[WRS] + wx1 * q[WRS + 1]);
-        val = (1.f - th.wz1[e]) * val + th.wz1[e] * p1;
-      }
-      r[e] = val;
+      float v[1 << ND];
+      win_gather<ND>(win + th.base[e], v);
+      r[e] = lin_value<ND>(v, th.w1[e]);
     }
     if (add_identity) {
       const float4 id = *reinterpret_cast<const float4*>(sc + sp);
@@ -332,9 +316,11 @@ __global__ __launch_bounds__(WNT) WW_FWD_ATTR void warp_win_fwd_k(const float* _
     const unsigned slow = ~th.fast & 15u;
 #pragma unroll 1
     for (int e = 0; e < 4; ++e)
-      if ((slow >> e) & 1u)
-        voxel_fwd_slow<ND>(src + (long long)b * C * S, flow + (long long)b * ND * S, out + (long long)b * C * S, C, D,
-                           H, W, S, z, y, x + e, add_identity);
+      if ((slow >> e) & 1u) {
+        const WinVoxel<ND> vx(D, H, W, z, y, x + e);
+        lin_voxel_fwd<ND, int>(src + (long long)b * C * S, flow + (long long)b * ND * S, out + (long long)b * C * S, C, vx.n,
+                               S, sp + e, vx.p, add_identity);
+      }
   }
 }
 
@@ -350,50 +336,9 @@ __global__ __launch_bounds__(WNT) void warp_win_bwd_k(const float* __restrict__ 
   int oz, oy, ox;
   const bool need_own = dsrc && (add_identity || flow_into_src);
   win_prologue<ND>(flow, b, S, H, W, D, z, y, x, active, need_own, th, red, oz, oy, ox);
-  // fast voxels only: a slow voxel is handled start to finish by voxel_bwd_slow at the end
-  float fm[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) fm[e] = ((th.fast >> e) & 1u) ? 1.f : 0.f;
-  // ---- phase A: d(flow) = sum_c dout_c * d(interp)/d(position), corner values from the src window
-  float gz[4] = {0.f, 0.f, 0.f, 0.f}, gy[4] = {0.f, 0.f, 0.f, 0.f}, gx[4] = {0.f, 0.f, 0.f, 0.f};
-  if ((dflow || flow_into_src) && !(WW_KO & 4)) {
-    for (int c = 0; c < C; ++c) {
-      const float* sc = src + ((long long)b * C + c) * S;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sc), 0, (unsigned)S * 4u, 0x00020000);
-      if (c) __syncthreads();
-      win_load<ND>(rs, win, D, H, W, oz, oy, ox);
-      __syncthreads();
-      if (!active) continue;
-      const float4 g4 = *reinterpret_cast<const float4*>(dout + ((long long)b * C + c) * S + sp);
-      const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float* p = win + th.base[e];
-        const float g = gg[e] * fm[e];
-        const float wx1 = th.wx1[e], wy1 = th.wy1[e], wz1 = th.wz1[e];
-        const float wx0 = 1.f - wx1, wy0 = 1.f - wy1, wz0 = 1.f - wz1;
-        const float c0 = p[0], c1 = p[1], c2 = p[WRS], c3 = p[WRS + 1];
-        if (ND == 3) {
-          const float* q = p + G::EY * WRS;
-          const float c4 = q[0], c5 = q[1], c6 = q[WRS], c7 = q[WRS + 1];
-          const float p0 = wy0 * (wx0 * c0 + wx1 * c1) + wy1 * (wx0 * c2 + wx1 * c3);
-          const float p1 = wy0 * (wx0 * c4 + wx1 * c5) + wy1 * (wx0 * c6 + wx1 * c7);
-          gz[e] += g * (p1 - p0);
-          gy[e] += g * (wz0 * (wx0 * (c2 - c0) + wx1 * (c3 - c1)) + wz1 * (wx0 * (c6 - c4) + wx1 * (c7 - c5)));
-          gx[e] += g * (wz0 * (wy0 * (c1 - c0) + wy1 * (c3 - c2)) + wz1 * (wy0 * (c5 - c4) + wy1 * (c7 - c6)));
-        } else {
-          gy[e] += g * (wx0 * (c2 - c0) + wx1 * (c3 - c1));
-          gx[e] += g * (wy0 * (c1 - c0) + wy1 * (c3 - c2));
-        }
-      }
-    }
-    if (active && !flow_into_src) {
-      float* fb = dflow + (long long)b * ND * S + sp;
-      if (ND == 3) *reinterpret_cast<float4*>(fb) = make_float4(gz[0], gz[1], gz[2], gz[3]);
-      *reinterpret_cast<float4*>(fb + (long long)(ND - 2) * S) = make_float4(gy[0], gy[1], gy[2], gy[3]);
-      *reinterpret_cast<float4*>(fb + (long long)(ND - 1) * S) = make_float4(gx[0], gx[1], gx[2], gx[3]);
-    }
-  }
+  float gf[ND][4];
+  win_dflow<ND>(dout, src, dflow, win, th, b, C, D, H, W, S, sp, oz, oy, ox, active,
+                (dflow || flow_into_src) && !(WW_KO & 4), flow_into_src, gf);
   // ---- phase B: d(src): scatter into a zeroed LDS window, then flush the touched cells
   if (dsrc) {
     constexpr int NW = G::EZ * G::EY * WRS;
@@ -409,29 +354,11 @@ __global__ __launch_bounds__(WNT) void warp_win_bwd_k(const float* __restrict__ 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if (!((th.fast >> e) & 1u)) continue;
-          float* p = win + th.base[e];
           const float g = gg[e];
-          const float wx1 = th.wx1[e], wy1 = th.wy1[e], wz1 = th.wz1[e];
-          const float wx0 = 1.f - wx1, wy0 = 1.f - wy1, wz0 = 1.f - wz1;
-          if (ND == 3) {
-            float* q = p + G::EY * WRS;
-            atomicAdd(p, g * wz0 * wy0 * wx0);
-            atomicAdd(p + 1, g * wz0 * wy0 * wx1);
-            atomicAdd(p + WRS, g * wz0 * wy1 * wx0);
-            atomicAdd(p + WRS + 1, g * wz0 * wy1 * wx1);
-            atomicAdd(q, g * wz1 * wy0 * wx0);
-            atomicAdd(q + 1, g * wz1 * wy0 * wx1);
-            atomicAdd(q + WRS, g * wz1 * wy1 * wx0);
-            atomicAdd(q + WRS + 1, g * wz1 * wy1 * wx1);
-          } else {
-            atomicAdd(p, g * wy0 * wx0);
-            atomicAdd(p + 1, g * wy0 * wx1);
-            atomicAdd(p + WRS, g * wy1 * wx0);
-            atomicAdd(p + WRS + 1, g * wy1 * wx1);
-          }
+          win_scatter<ND>(win + th.base[e], th.w1[e], g, [](float* q, float v) { atomicAdd(q, v); });
           if (need_own) {
             float ov = add_identity ? g : 0.f;
-            if (flow_into_src) ov += (ND == 3) ? (c == 0 ? gz[e] : (c == 1 ? gy[e] : gx[e])) : (c == 0 ? gy[e] : gx[e]);
+            if (flow_into_src) ov += win_axis<ND>(gf, c, e);
             atomicAdd(win + own + e, ov);
           }
         }
@@ -451,11 +378,13 @@ __global__ __launch_bounds__(WNT) void warp_win_bwd_k(const float* __restrict__ 
     const unsigned slow = ~th.fast & 15u;
 #pragma unroll 1
     for (int e = 0; e < 4; ++e)
-      if ((slow >> e) & 1u)
-        voxel_bwd_slow<ND>(dout + (long long)b * C * S, src + (long long)b * C * S, flow + (long long)b * ND * S,
-                           dsrc ? dsrc + (long long)b * C * S : nullptr,
-                           dflow ? dflow + (long long)b * ND * S : nullptr, C, D, H, W, S, z, y, x + e, add_identity,
-                           flow_into_src);
+      if ((slow >> e) & 1u) {
+        const WinVoxel<ND> vx(D, H, W, z, y, x + e);
+        lin_voxel_bwd<ND, int>(dout + (long long)b * C * S, src + (long long)b * C * S, flow + (long long)b * ND * S,
+                               dsrc ? dsrc + (long long)b * C * S : nullptr,
+                               dflow ? dflow + (long long)b * ND * S : nullptr, C, vx.n, S, sp + e, vx.p, add_identity,
+                               flow_into_src);
+      }
   }
 }
 
@@ -521,9 +450,6 @@ __global__ __launch_bounds__(WNT) WW_OWN_ATTR void warp_win_bwd_own_k(const floa
   // CU bounds pass 1, not its arithmetic)
   win_prologue<ND>(flow, b, S, H, W, D, z, y, x, active, need_own, th, red, oz, oy, ox, true, tzb_ * G::TZ, tyb_ * G::TY,
                    tx_ * WTX);
-  float fm[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) fm[e] = ((th.fast >> e) & 1u) ? 1.f : 0.f;
   // touched sub-box of the window: upper corner of every fast voxel's taps (and its own cell), workgroup maximum
   {
     int uz = -1, uy = -1, ux = -1;
@@ -540,47 +466,8 @@ __global__ __launch_bounds__(WNT) WW_OWN_ATTR void warp_win_bwd_own_k(const floa
     uz = wave_max_i(uz); uy = wave_max_i(uy); ux = wave_max_i(ux);
     if ((t & 63) == 0 && ux >= 0) { atomicMax(&s_ext[0], uz + 1); atomicMax(&s_ext[1], uy + 1); atomicMax(&s_ext[2], ux + 1); }
   }
-  // ---- phase A: d(flow) (identical to warp_win_bwd_k)
-  float gz[4] = {0.f, 0.f, 0.f, 0.f}, gy[4] = {0.f, 0.f, 0.f, 0.f}, gx[4] = {0.f, 0.f, 0.f, 0.f};
-  if (dflow || flow_into_src) {
-    for (int c = 0; c < C; ++c) {
-      const float* sc = src + ((long long)b * C + c) * S;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sc), 0, (unsigned)S * 4u, 0x00020000);
-      if (c) __syncthreads();
-      win_load<ND>(rs, win, D, H, W, oz, oy, ox);
-      __syncthreads();
-      if (!active) continue;
-      const float4 g4 = *reinterpret_cast<const float4*>(dout + ((long long)b * C + c) * S + sp);
-      const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float* p = win + th.base[e];
-        const float g = gg[e] * fm[e];
-        const float wx1 = th.wx1[e], wy1 = th.wy1[e], wz1 = th.wz1[e];
-        const float wx0 = 1.f - wx1, wy0 = 1.f - wy1, wz0 = 1.f - wz1;
-        const float c0 = p[0], c1 = p[1], c2 = p[WRS], c3 = p[WRS + 1];
-        if (ND == 3) {
-          const float* q = p + G::EY * WRS;
-          const float c4 = q[0], c5 = q[1], c6 = q[WRS], c7 = q[WRS + 1];
-          const float p0 = wy0 * (wx0 * c0 + wx1 * c1) + wy1 * (wx0 * c2 + wx1 * c3);
-          const float p1 = wy0 * (wx0 * c4 + wx1 * c5) + wy1 * (wx0 * c6 + wx1 * c7);
-          gz[e] += g * (p1 - p0);
-          gy[e] += g * (wz0 * (wx0 * (c2 - c0) + wx1 * (c3 - c1)) + wz1 * (wx0 * (c6 - c4) + wx1 * (c7 - c5)));
-          gx[e] += g * (wz0 * (wy0 * (c1 - c0) + wy1 * (c3 - c2)) + wz1 * (wy0 * (c5 - c4) + wy1 * (c7 - c6)));
-        } else {
-          gy[e] += g * (wx0 * (c2 - c0) + wx1 * (c3 - c1));
-          gx[e] += g * (wy0 * (c1 - c0) + wy1 * (c3 - c2));
-        }
-      }
-    }
-    if (active && !flow_into_src && dflow) {
-      float* fb = dflow + (long long)b * ND * S + sp;
-      // slow voxels: their d(flow) is written by pass 3; fast ones here (a float4 store covers both: pass 3 runs later)
-      if (ND == 3) *reinterpret_cast<float4*>(fb) = make_float4(gz[0], gz[1], gz[2], gz[3]);
-      *reinterpret_cast<float4*>(fb + (long long)(ND - 2) * S) = make_float4(gy[0], gy[1], gy[2], gy[3]);
-      *reinterpret_cast<float4*>(fb + (long long)(ND - 1) * S) = make_float4(gx[0], gx[1], gx[2], gx[3]);
-    }
-  }
+  float gf[ND][4];
+  win_dflow<ND>(dout, src, dflow, win, th, b, C, D, H, W, S, sp, oz, oy, ox, active, dflow || flow_into_src, flow_into_src, gf);
   // ---- phase B: d(src) of the fast voxels, fixed point in LDS, store of the touched sub-box
   const int own = ((z - oz) * G::EY + (y - oy)) * WRS + (x - ox);
   int ez = 0, ey = 0, ex4 = 0;
@@ -593,9 +480,10 @@ __global__ __launch_bounds__(WNT) WW_OWN_ATTR void warp_win_bwd_own_k(const floa
       gg[0] = g4.x; gg[1] = g4.y; gg[2] = g4.z; gg[3] = g4.w;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        gg[e] *= fm[e];
+        const float fm = ((th.fast >> e) & 1u) ? 1.f : 0.f;      // fast voxels only
+        gg[e] *= fm;
         ov[e] = add_identity ? gg[e] : 0.f;
-        if (flow_into_src) ov[e] += fm[e] * ((ND == 3) ? (c == 0 ? gz[e] : (c == 1 ? gy[e] : gx[e])) : (c == 0 ? gy[e] : gx[e]));
+        if (flow_into_src) ov[e] += fm * win_axis<ND>(gf, c, e);
         const float am = fabsf(gg[e]) + fabsf(ov[e]);
         bad = bad || !(am < 3.0e38f);                       // NaN or inf
         m += am;
@@ -620,29 +508,9 @@ __global__ __launch_bounds__(WNT) WW_OWN_ATTR void warp_win_bwd_own_k(const floa
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         if (!((th.fast >> e) & 1u)) continue;
-        int* p = wini + th.base[e];
-        const float g = gg[e] * up;
-        const float wx1 = th.wx1[e], wy1 = th.wy1[e], wz1 = th.wz1[e];
-        const float wx0 = 1.f - wx1, wy0 = 1.f - wy1, wz0 = 1.f - wz1;
-#define OWN_ADD(ptr_, val_) atomicAdd(reinterpret_cast<unsigned*>(ptr_), (unsigned)__float2int_rn(val_))
-        if (ND == 3) {
-          int* q = p + G::EY * WRS;
-          OWN_ADD(p, g * wz0 * wy0 * wx0);
-          OWN_ADD(p + 1, g * wz0 * wy0 * wx1);
-          OWN_ADD(p + WRS, g * wz0 * wy1 * wx0);
-          OWN_ADD(p + WRS + 1, g * wz0 * wy1 * wx1);
-          OWN_ADD(q, g * wz1 * wy0 * wx0);
-          OWN_ADD(q + 1, g * wz1 * wy0 * wx1);
-          OWN_ADD(q + WRS, g * wz1 * wy1 * wx0);
-          OWN_ADD(q + WRS + 1, g * wz1 * wy1 * wx1);
-        } else {
-          OWN_ADD(p, g * wy0 * wx0);
-          OWN_ADD(p + 1, g * wy0 * wx1);
-          OWN_ADD(p + WRS, g * wy1 * wx0);
-          OWN_ADD(p + WRS + 1, g * wy1 * wx1);
-        }
-        if (need_own) OWN_ADD(wini + own + e, ov[e] * up);
-#undef OWN_ADD
+        const auto own_add = [](int* q, float v) { atomicAdd(reinterpret_cast<unsigned*>(q), (unsigned)__float2int_rn(v)); };
+        win_scatter<ND>(wini + th.base[e], th.w1[e], gg[e] * up, own_add);
+        if (need_own) own_add(wini + own + e, ov[e] * up);
       }
     }
     __syncthreads();
@@ -733,7 +601,7 @@ __global__ __launch_bounds__(WNT) void warp_win_gather_k(const float* __restrict
         const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(scratch + ((long long)tl * C + c) * WinOwn<ND>::CELLS), 0,
             (unsigned)(WinOwn<ND>::CELLS * 4), 0x00020000);
-        const u32x4w q = __builtin_amdgcn_raw_buffer_load_b128(wsrc, off[g0 + i], 0, 0);
+        const wu32x4 q = __builtin_amdgcn_raw_buffer_load_b128(wsrc, off[g0 + i], 0, 0);
         v[i] = make_float4(__uint_as_float(q[0]), __uint_as_float(q[1]), __uint_as_float(q[2]), __uint_as_float(q[3]));
       }
 #pragma unroll
@@ -758,9 +626,10 @@ __global__ __launch_bounds__(256) void warp_win_slow_k(const float* __restrict__
     const unsigned v = slowlist[(long long)tile * WinOwn<ND>::TILE_VOX + i];
     const int b = (int)(v / (unsigned)S), sp = (int)(v - (unsigned)b * (unsigned)S);
     const int x = sp % W, y = (sp / W) % H, z = sp / (W * H);
-    voxel_bwd_slow<ND>(dout + (long long)b * C * S, src + (long long)b * C * S, flow + (long long)b * ND * S,
-                       dsrc + (long long)b * C * S, dflow ? dflow + (long long)b * ND * S : nullptr, C, D, H, W, S, z, y, x,
-                       add_identity, flow_into_src);
+    const WinVoxel<ND> vx(D, H, W, z, y, x);
+    lin_voxel_bwd<ND, int>(dout + (long long)b * C * S, src + (long long)b * C * S, flow + (long long)b * ND * S,
+                           dsrc + (long long)b * C * S, dflow ? dflow + (long long)b * ND * S : nullptr, C, vx.n, S, sp, vx.p,
+                           add_identity, flow_into_src);
   }
 }
 

@@ -1,10 +1,10 @@
 // The cell and corner gather of the warped-feature SSD (warpssd.hip), shared with the affine system kernels (affine.hip):
-// the geometry of a feature volume, the cell floor() selects for a sample point with its guards, the gather of four channels
-// of its corners from the voxel-major packed copy (or the channel-major tensor), and the interpolant with its derivative.
-// Everything sits in an anonymous namespace: each file that includes this keeps its own copy of the host helpers.
+// the geometry of a feature volume, the cell floor() selects for a sample point with its guards (lin_cell.h's), the
+// gather of four channels of its corners from the voxel-major packed copy (or the channel-major tensor), and the
+// interpolant with its derivative.  Everything sits in an anonymous namespace: each file that includes this keeps its own
+// copy of the host helpers.
 #pragma once
-#include "common.h"
-#include <math.h>
+#include "lin_cell.h"
 
 namespace {
 
@@ -18,33 +18,15 @@ struct WsGeom {
   int C, Cp;                                 // channels, and rounded up to 4
 };
 
-// The cell of one voxel: upper weights, offset of the lower corner in voxels (may be negative: only corners whose bit of
-// `ok` is set are addressed) and, per axis a, bits 2a (lower corner inside) and 2a + 1 (upper corner inside).
+// The cell of one voxel is lin_cell.h's, with its guards.
 template <int ND>
-struct WsCell {
-  float w1[ND];
-  int base;
-  unsigned ok;
-};
+using WsCell = LinCell<ND>;
 
 template <int ND>
 __device__ __forceinline__ void ws_cell(const WsGeom& g, const int (&p)[ND], const float (&u)[ND], WsCell<ND>& q) {
-  int n[ND], st[ND];
-  if (ND == 3) { n[0] = g.D; n[1] = g.H; n[2] = g.W; st[0] = g.H * g.W; st[1] = g.W; st[2] = 1; }
-  else { n[0] = g.H; n[ND - 1] = g.W; st[0] = g.W; st[ND - 1] = 1; }
-  q.base = 0;
-  q.ok = 0u;
-#pragma unroll
-  for (int a = 0; a < ND; ++a) {
-    const float f = (float)p[a] + u[a];
-    const bool nearby = f >= -1.f && f < (float)n[a];             // false for NaN and for points past the padding cells:
-    const float fl = floorf(f);                                 // no corner is read then, and no float goes to int
-    const int i0 = nearby ? (int)fl : -2;
-    q.w1[a] = f - fl;
-    q.base += i0 * st[a];
-    if ((unsigned)i0 < (unsigned)n[a]) q.ok |= 1u << (2 * a);
-    if ((unsigned)(i0 + 1) < (unsigned)n[a]) q.ok |= 2u << (2 * a);
-  }
+  int n[ND];
+  lin_extents<ND>(g.D, g.H, g.W, n);
+  lin_cell<ND, int>(p, u, n, q);
 }
 
 // Four channels 4 gi .. 4 gi + 3 of the 2^ND corners of a cell (x is bit 0, axis a bit ND - 1 - a); 0 outside the volume
@@ -53,20 +35,10 @@ template <int ND, bool PACKED>
 __device__ __forceinline__ void ws_corners(const float* __restrict__ mb, const WsGeom& g, const WsCell<ND>& q, int gi,
                                            float4 (&val)[1 << ND]) {
   constexpr int NC = 1 << ND;
-  int st[ND];
-  if (ND == 3) { st[0] = g.H * g.W; st[1] = g.W; st[2] = 1; }
-  else { st[0] = g.W; st[ND - 1] = 1; }
 #pragma unroll
   for (int m = 0; m < NC; ++m) {
-    bool in = true;
-    int o = q.base;
-#pragma unroll
-    for (int a = 0; a < ND; ++a) {
-      const int bit = (m >> (ND - 1 - a)) & 1;
-      in = in && ((q.ok >> (2 * a + bit)) & 1u);
-      o += bit * st[a];
-    }
-    o = in ? o : 0;
+    const bool in = q.in(m);
+    const int o = in ? q.off(m) : 0;
     float4 t;
     if (PACKED) {
       t = *reinterpret_cast<const float4*>(mb + (long long)o * g.Cp + 4 * gi);
@@ -85,8 +57,10 @@ __device__ __forceinline__ void ws_corners(const float* __restrict__ mb, const W
   }
 }
 
-// One channel: the interpolated value and the derivative of the interpolant along each axis (x innermost, then y, then z:
-// the order of the warp kernels)
+// One channel: the interpolated value and the derivative of the interpolant along each axis.  The value is lin_value's (x
+// innermost, then y, then z), but the derivatives along y and z are differences of the interpolated rows and planes,
+// a01 - a00 and b1 - b0, where lin_flow_grad weights differences of corners: x0 (v2 - v0) + x1 (v3 - v1) and
+// (x0 v2 + x1 v3) - (x0 v0 + x1 v1) are different fp32 numbers, so the two orders stay apart.
 template <int ND>
 __device__ __forceinline__ float ws_interp(const float (&v)[1 << ND], const WsCell<ND>& q, float (&d)[ND]) {
   const float x1 = q.w1[ND - 1], x0 = 1.f - x1, y1 = q.w1[ND - 2], y0 = 1.f - y1;

@@ -5,15 +5,17 @@ check the inputs (lattice distances, exclusion caps, the nearest ties, the chain
 builders and CPU evaluators live in tests/warp_cases.py, which the CPU module and scripts/warp_margins.py share.
 
 Launcher branch -> test id.  "windowed" = W % 4 == 0 (tiles 8 x 8 x 32 / 64 x 32, windows 12 x 12 x 40 / 68 x 40, the grid
-rounded up to 8 workgroups, win_tile's remap over the XCDs), "scalar" = the one-voxel-per-thread kernels.
+rounded up to 8 workgroups, win_tile's remap over the XCDs), "scalar" = the one-voxel-per-thread kernels.  Both are built on
+the cell of dfmir_amd/csrc/lin_cell.h (lin_cell, lin_value, lin_flow_grad, lin_cw, lin_voxel_fwd / lin_voxel_bwd).
+    lin_cell's guard / win_prologue's clamp   test_warp_far_and_non_finite_flow[*]: NaN, inf and +-1e30 displacements
   dfmir_warp3d_fwd / dfmir_warp2d_fwd
     warp_win_fwd_k<3|2>, mode 0               test_warp_vs_restatement[3d-win-* | 2d-win-*]: tile counts 1 (7 of 8 workgroups idle),
                                               4, 6 (3 z tiles), 8 ragged, 12 with a batch, 27; one voxel short / past per axis
-      voxel_fwd_slow inside it                ... the lattice and far families (far: almost every voxel)
+      lin_voxel_fwd<*, int> inside it         ... the lattice and far families (far: almost every voxel)
       add_identity = 1                        test_vecint_step_vs_restatement[*-win-*], test_vecint_seven_steps[*-win-*]
-    warp3d_fwd_k / warp2d_fwd_k, mode 0       test_warp_vs_restatement[3d-sca-* | 2d-sca-*] (255 / 256 / 258 voxels: one block)
+    warp_fwd_k<3|2>, mode 0                   test_warp_vs_restatement[3d-sca-* | 2d-sca-*] (255 / 256 / 258 voxels: one block)
       add_identity = 1                        test_vecint_step_vs_restatement[*-sca-*], test_vecint_seven_steps[*-sca-*]
-    warp3d_fwd_k / warp2d_fwd_k, mode 1       test_warp_nearest_vs_restatement[*] (every shape: mode 1 never takes the window),
+    warp_fwd_k<3|2>, mode 1                   test_warp_nearest_vs_restatement[*] (every shape: mode 1 never takes the window),
                                               test_warp_nearest_ties_go_to_the_even_voxel
       mode 1 with add_identity = 1            unreachable: ops passes add_identity only from VecIntStepFn, with mode 0
     win_eligible refusing a W % 4 == 0 shape  a volume of 2^31 bytes or 2^30 tiles: not run; test_ref64.py pins the host logic
@@ -21,9 +23,9 @@ rounded up to 8 workgroups, win_tile's remap over the XCDs), "scalar" = the one-
     warp_win_bwd_k<3|2>, dsrc == NULL         test_warp_vs_restatement[*-win-*] (the flow-only backward of WarpFn)
     warp_win_bwd_k, dsrc, LDS + atomics       test_warp_vs_restatement[*-win-*] (ops._warp_bwd into a zeroed buffer)
     warp_win_bwd_k, need_own                  test_vecint_step_vs_restatement[*-win-*] (ops._warp_bwd(dout, v, v, zeros, None, 1, 1))
-      voxel_bwd_slow inside it                ... the lattice / far families, vi-6
-    warp3d_bwd_k / warp2d_bwd_k, dsrc == NULL test_warp_vs_restatement[*-sca-*] (flow only)
-    warp3d_bwd_k / warp2d_bwd_k, dsrc, dflow  test_warp_vs_restatement[*-sca-*] (src and flow require gradients)
+      lin_voxel_bwd<*, int> inside it         ... the lattice / far families, vi-6
+    warp_bwd_k<3|2>, dsrc == NULL             test_warp_vs_restatement[*-sca-*] (flow only)
+    warp_bwd_k<3|2>, dsrc, dflow              test_warp_vs_restatement[*-sca-*] (src and flow require gradients)
     ..., dsrc, dflow == NULL                  test_warp_vs_restatement[*-sca-*] (src alone requires a gradient)
     ..., add_identity = flow_into_src = 1     test_vecint_step_vs_restatement[*-sca-*], test_vecint_seven_steps[*-sca-*]
   dfmir_warp_bwd_own
@@ -32,7 +34,7 @@ rounded up to 8 workgroups, win_tile's remap over the XCDs), "scalar" = the one-
     own term (add_identity, flow_into_src)    test_vecint_step_vs_restatement[*-win-*], test_vecint_seven_steps[*-win-*]
     warp_win_slow_k with the own term         ... the lattice family and vi-6 (the own cell leaves the window)
     dflow == NULL without flow_into_src       test_warp_vs_restatement[*-win-*] (src alone requires a gradient: phase A and the d(flow)
-                                              stores are skipped, warp_win_slow_k hands voxel_bwd_slow a null dflow)
+                                              stores are skipped, warp_win_slow_k hands lin_voxel_bwd a null dflow)
   dfmir_resize_fwd
     resize_rows_fwd_k                         test_resize_vs_restatement[6x10x12-12x20x24], [12x20x24-6x10x12], [1x8-1x16], [5x1x8-5x1x16]
       its second grid pass (> 20480 rows)     test_resize_vs_restatement[24x30x4-48x75x8]
@@ -464,6 +466,51 @@ def test_warp_exact_identities(shape):
                 out, dsrc, dflow = gpu_warp(src, flow, g, want_src=want_src)
                 assert float(out.abs().max()) == 0.0 and float(dflow.abs().max()) == 0.0, (far, axis)
                 assert dsrc is None or float(dsrc.abs().max()) == 0.0, (far, axis)
+
+
+FAR_VALUES = (float("nan"), float("inf"), 1e30, -1e30)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(1, 2, 8, 8, 32), (1, 2, 5, 6, 9), (1, 2, 64, 32), (1, 2, 7, 9)], ids=_id)
+def test_warp_far_and_non_finite_flow(shape):
+    """A smooth flow with twelve voxels overwritten, one component each, by NaN, +inf, +1e30 and -1e30: the displacements
+    that no int holds.  From the zero-padding definition: a NaN or infinite coordinate has NaN weights, so the output
+    there is NaN; at +-1e30 the weights are 0 and 1 and every corner lies outside, so the output is exactly 0; no other
+    output voxel reads the flow of these twelve, so the rest stays within the smooth bound of the float64 restatement of
+    the untouched flow; d(flow) is finite wherever the flow is.  d(src) is finite everywhere: a voxel with no corner inside
+    the volume scatters to no cell, and the guarded cell gives these twelve none (the unguarded convert took NaN to cell 0,
+    whose NaN weights then reached d(src); autograd through the restatement yields NaN there too, from 0 x NaN, so d(src)
+    is not compared with it).  Both backward forms run (with and without d(src)), and on the windowed shapes the LDS-atomic
+    kernel.  One windowed tile and one scalar block per dimension."""
+    nd = len(shape) - 2
+    seed = 9100 + sum(shape)
+    src, g, flow0 = noise(seed, shape, 2.0), noise(seed + 1, shape, 1.0), flow_field(shape, "smooth", seed + 2)
+    vox = flow0[0, 0].numel()
+    flow = flow0.clone()
+    touched = torch.zeros(shape[2:], dtype=torch.bool)
+    for i in range(12):
+        at = (i * 7919 + 3) % vox
+        assert not bool(touched.view(-1)[at])
+        touched.view(-1)[at] = True
+        flow[0, i % nd].view(-1)[at] = FAR_VALUES[i % 4]
+    bad = ~torch.isfinite(flow).all(1, keepdim=True)                   # NaN and inf voxels
+    far = touched[None, None] & ~bad                                   # +-1e30
+    assert int(bad.sum()) == 6 and int(far.sum()) == 6
+    ref = R.warp(src.double(), flow0.double())
+    rest = ~touched[None, None].expand_as(src)
+    for want_src in (True, False):
+        out, dsrc, dflow = gpu_warp(src, flow, g, want_src=want_src)
+        what = "far flow %s%s" % (_id(shape), "" if want_src else " flow only")
+        assert bool(torch.isnan(out[bad.expand_as(out)]).all()), what
+        assert bool((out[far.expand_as(out)] == 0).all()), what
+        _check(what, rel_errors(torch.where(rest, out, torch.zeros(())), ref, rest.double()), BOUND_WARP["smooth"][:2],
+               WARP_NAMES[:2])
+        assert bool(torch.isfinite(dflow[(~bad).expand_as(dflow)]).all()), what
+        assert dsrc is None or bool(torch.isfinite(dsrc).all()), what
+    if shape[-1] % 4 == 0:
+        dsrc, dflow = gpu_warp_atomic(src, flow, g)
+        assert bool(torch.isfinite(dsrc).all()) and bool(torch.isfinite(dflow[(~bad).expand_as(dflow)]).all()), shape
 
 
 @pytest.mark.gpu
