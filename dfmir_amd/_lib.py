@@ -183,6 +183,9 @@ _SIGS = {
     "dfmir_landmark_ws_floats": [c_int] * 6,
     "dfmir_landmark_fwd": [c_int] + [P] * 10 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
     "dfmir_landmark_bwd": [c_int] + [P] * 8 + [c_int] * 5 + [c_float] * 3 + [c_int, P],
+    "dfmir_tps_ws_bytes": [c_int] * 6,
+    "dfmir_tps_fwd": [c_int, P, P, P, P, c_int, c_int, c_longlong] + [c_int] * 3 + [c_double] * 3 + [P],
+    "dfmir_tps_bwd_coef": [c_int, P, P, P, P] + [c_int] * 5 + [c_double] * 3 + [P],
     "dfmir_nmi_ws_floats": [c_longlong, c_int],
     "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
     "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],
@@ -268,6 +271,7 @@ def lib():
         h.dfmir_affine_ws_floats.restype = c_longlong
         h.dfmir_demons_ws_floats.restype = c_longlong
         h.dfmir_landmark_ws_floats.restype = c_longlong
+        h.dfmir_tps_ws_bytes.restype = c_longlong
         h.dfmir_nmi_ws_floats.restype = c_longlong
         h.dfmir_mind_ws_floats.restype = c_longlong
         h.dfmir_gradfield_ws_floats.restype = c_longlong

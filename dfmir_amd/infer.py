@@ -683,3 +683,38 @@ def landmark_error(flow, fixed_pts, moving_pts, spacing=None, weight=None):
     initial = ((fixed_pts - moving_pts) * h).square().sum(2).sqrt()
     initial = torch.where(torch.isnan(tre), tre, initial)
     return dict(tre=tre, initial=initial, mean=mean)
+
+
+@torch.no_grad()
+def landmark_init(moving, fixed, fixed_pts, moving_pts, *, spacing=None, smoothing=0.0, weight=None, interp='linear'):
+    """Stage 0 of the inference pipeline for a pair with corresponding keypoints (annotated, detected or predicted): the
+    thin-plate-spline flow through them (build-defined; the definition: ops.tps_fit).  Returns dict(flow, warped, coef, tre).
+
+    moving, fixed: [B,C,*vol] fp32 images of one shape, 2-D or 3-D (`fixed` gives the grid; only `moving` is sampled);
+    fixed_pts q, moving_pts p: [B,K,nd] fp32 voxel coordinates, axis order (z,) y, x, nd + 1 <= K <= ops.LANDMARK_MAX_K;
+    spacing: nd positive numbers (None = 1); smoothing: lambda >= 0, 0 interpolates (flow(q_k) = p_k - q_k); weight: [B,K]
+    or None, 0 marks a padding entry, as does a non-finite coordinate.
+
+        flow   = ops.tps_flow(ops.tps_fit(q, p, vol, spacing, smoothing, weight))     [B,nd,*vol], ops.warp's convention
+        warped = ops.warp(moving, flow) (interp 'linear') or ops.warp_cubic(moving, flow) ('cubic')
+        coef   = the float64 coefficients [B,K+nd+1,nd] = [w; a_0; A] of the fit
+        tre    = ops.landmark_distances(flow, q, p, weight, spacing)[0]               [B,K], NaN for an invalid landmark
+
+    The flow feeds the solvers directly: refine_flow(moving, fixed, flow), demons_flow(moving, fixed, flow).  The fit syncs
+    with the host once.  No gradient is recorded (for a loss through the interpolant use ops.tps_fit and ops.tps_flow).
+    ValueError on an unknown interp, images that are not two tensors of one [B,C,*vol] shape, and whatever ops.tps_fit
+    refuses (a singular system included)."""
+    what = "landmark_init"
+    _check_interp(what, interp)
+    if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
+            or tuple(moving.shape) != tuple(fixed.shape):
+        raise ValueError("%s: moving and fixed must be two [B,C,*vol] tensors of one shape" % what)
+    vol = tuple(int(n) for n in moving.shape[2:])
+    if torch.is_tensor(fixed_pts) and fixed_pts.dim() == 3 and int(fixed_pts.shape[0]) != int(moving.shape[0]):
+        raise ValueError("%s: %d samples of images, %d of points" % (what, int(moving.shape[0]), int(fixed_pts.shape[0])))
+    fixed_pts = fixed_pts.detach() if torch.is_tensor(fixed_pts) else fixed_pts
+    moving_pts = moving_pts.detach() if torch.is_tensor(moving_pts) else moving_pts
+    handle = ops.tps_fit(fixed_pts, moving_pts, vol, spacing, smoothing, weight)
+    flow = ops.tps_flow(handle)
+    tre = ops.landmark_distances(flow, fixed_pts, moving_pts, weight, spacing)[0]
+    return dict(flow=flow, warped=_final_warp(moving.detach(), flow, interp), coef=handle.coef, tre=tre)

@@ -3744,6 +3744,230 @@ def warp_points(points, flow):
     return _landmark_fwd(_c(flow), _c(points), None, None, geom, 0, want_mapped=True)[3]
 
 
+class TPSHandle:
+    """What ops.tps_fit returns: coef [B,K+nd+1,nd] float64 = [w (K rows); a_0; A (nd rows)] (it carries the autograd graph to
+    moving_pts when those require grad), ctrl [B,K,nd] fp32 = the sanitised control positions in voxels (a padding entry is
+    0), scale = the nd factors h_a / L as Python floats, vol = the nd extents, nd."""
+    __slots__ = ("coef", "ctrl", "scale", "vol", "nd")
+
+    def __init__(self, coef, ctrl, scale, vol):
+        self.coef, self.ctrl, self.scale, self.vol, self.nd = coef, ctrl, tuple(scale), tuple(vol), len(vol)
+
+
+def tps_scale(vol, spacing=None, what="tps_scale"):
+    """The nd factors h_a / L, L = max_a h_a (S_a - 1), that take voxel coordinates of a volume `vol` to the normalised
+    coordinates of the thin-plate spline ops (part of their definition: ops.tps_fit)."""
+    try:
+        vol = tuple(vol)
+    except TypeError:
+        raise ValueError("%s: vol must be 2 or 3 extents, got %r" % (what, vol)) from None
+    if len(vol) not in (2, 3) or any(isinstance(n, bool) or not isinstance(n, int) or n < 2 for n in vol):
+        raise ValueError("%s: vol must be 2 or 3 integer extents >= 2, got %r" % (what, vol))
+    h = bending_spacing(spacing, (len(vol),), what)
+    L = max(ha * (n - 1) for ha, n in zip(h, vol))
+    return tuple(ha / L for ha in h)
+
+
+def tps_fit(fixed_pts, moving_pts, vol, spacing=None, smoothing=0.0, weight=None):
+    """Fit the thin-plate / polyharmonic spline through K pairs of corresponding points (build-defined) and return a
+    TPSHandle for ops.tps_flow / ops.tps_points.  fixed_pts q, moving_pts p: [B,K,nd] fp32 voxel coordinates, nd = 2 or 3,
+    axis order as a flow's channels ((z,) y, x), nd + 1 <= K <= LANDMARK_MAX_K; vol: the nd extents S_a >= 2; spacing: nd
+    positive numbers h (None = 1); smoothing: lambda >= 0; weight omega: [B,K] fp32 or None (= 1).
+
+    The target displacement is d_k = p_k - q_k in voxels, ops.warp's convention (warped(x) = moving(x + u(x)), so u(q_k) =
+    d_k).  Basis functions live in NORMALISED coordinates xh_a = h_a x_a / L, L = max_a h_a (S_a - 1) -- part of the
+    definition: analytically the interpolant is the same, but the float64 system of 1024 points in a 256^2 image has condition
+    number 2e14 in voxel coordinates and 1e8 in normalised ones.  The flow is
+
+        u(x) = a_0 + A^T xh + sum_k w_k phi(|xh - qh_k|)       phi(r) = -r (3-D),  r^2 log r with phi(0) = 0 (2-D)
+
+    and coef = [w; a_0; A] solves (Phi + diag(lambda / omega_k)) w + P a = d, P^T w = 0 with Phi_jk = phi(|qh_j - qh_k|), P =
+    [1, qh].  With weight=None that is scipy.interpolate.RBFInterpolator(qh, d, kernel='linear' | 'thin_plate_spline',
+    degree=1, smoothing=lambda).  lambda = 0 interpolates: u(q_k) = d_k; an affinely related point set gives w = 0.
+
+    An entry with omega = 0, or with a non-finite coordinate in q or p, is padding: its row and column of the system are the
+    identity's, its right-hand side and its row of P are zero, so its coefficient is exactly 0, and its position in `ctrl` is
+    0.  A NaN or negative weight raises.
+
+    The system is assembled and solved in float64 with torch on the points' device (pairwise squared distances axis by axis,
+    torch.linalg.solve_ex): no kernel of this library runs, so CPU tensors are served too (ops.tps_flow then refuses them).
+    One host sync reads the solver's `info` and a rank test of P (the smallest eigenvalue of P^T P above 1e-12 of the largest).  The right-hand side is p - q in differentiable torch ops with q detached: autograd reaches moving_pts
+    through the returned coef; no gradient is defined for the control positions q or for the weight.  ValueError on K
+    outside [nd + 1, LANDMARK_MAX_K], a bad vol, spacing, smoothing or weight, and when the solve fails (info != 0) or returns
+    a non-finite coefficient: coincident points with smoothing = 0, fewer than nd + 1 valid points, or valid points that lie
+    on one line (plane); DfmirHipError on shapes or dtypes that disagree."""
+    what = "tps_fit"
+    if not torch.is_tensor(fixed_pts) or not torch.is_tensor(moving_pts):
+        raise DfmirHipError("%s: fixed_pts and moving_pts must be [B,K,nd] tensors" % what)
+    scale = tps_scale(vol, spacing, what)
+    vol = tuple(vol)
+    nd = len(vol)
+    if fixed_pts.dim() != 3 or int(fixed_pts.shape[2]) != nd or int(fixed_pts.shape[0]) < 1 \
+            or tuple(moving_pts.shape) != tuple(fixed_pts.shape):
+        raise DfmirHipError("%s: points mismatch (expected two [B,K,%d] sets of one shape for a volume %s, got %s and %s)"
+                            % (what, nd, vol, tuple(fixed_pts.shape), tuple(moving_pts.shape)))
+    B, K = int(fixed_pts.shape[0]), int(fixed_pts.shape[1])
+    if weight is not None and (not torch.is_tensor(weight) or tuple(weight.shape) != (B, K)):
+        raise DfmirHipError("%s: weight mismatch (expected [B,K] = [%d,%d])" % (what, B, K))
+    for name, t in (("fixed_pts", fixed_pts), ("moving_pts", moving_pts), ("weight", weight)):
+        if t is not None and t.dtype != torch.float32:
+            raise DfmirHipError("%s: fp32 tensors only (%s is %s)" % (what, name, t.dtype))
+        if t is not None and t.device != fixed_pts.device:
+            raise DfmirHipError("%s: fixed_pts on %s, %s on %s" % (what, fixed_pts.device, name, t.device))
+    if not nd + 1 <= K <= LANDMARK_MAX_K:
+        raise ValueError("%s: K must lie in [%d, %d], got %d landmarks" % (what, nd + 1, LANDMARK_MAX_K, K))
+    if isinstance(smoothing, bool) or not isinstance(smoothing, (int, float)) or not 0.0 <= smoothing < float('inf'):
+        raise ValueError("%s: smoothing must be a finite number >= 0, got %r" % (what, smoothing))
+    dev, f64 = fixed_pts.device, torch.float64
+    with torch.no_grad():
+        q = fixed_pts.detach().to(f64)
+        valid = torch.isfinite(q).all(-1) & torch.isfinite(moving_pts.detach()).all(-1)
+        om = None
+        if weight is not None:
+            om = weight.detach().to(f64)
+            valid = valid & (om != 0)
+        v = valid.to(f64)
+        q = torch.where(valid[..., None], q, torch.zeros_like(q))
+        qh = q * torch.tensor(scale, dtype=f64, device=dev)
+        # squared distances axis by axis: exact zeros on the diagonal, none of the cancellation of the matmul form of
+        # torch.cdist (whose exact mode refuses K = 4096 on the device: its grid exceeds the launch limit)
+        s = torch.zeros((B, K, K), dtype=f64, device=dev)
+        for a in range(nd):
+            s += (qh[:, :, None, a] - qh[:, None, :, a]).square()
+        if nd == 3:
+            phi = -s.sqrt()
+        else:
+            phi = torch.where(s > 0, 0.5 * s * torch.log(torch.where(s > 0, s, torch.ones_like(s))), torch.zeros_like(s))
+        R = K + nd + 1
+        A = torch.zeros((B, R, R), dtype=f64, device=dev)
+        A[:, :K, :K] = phi * (v[:, :, None] * v[:, None, :])
+        diag = 1.0 - v                                                     # identity rows of the padding entries
+        if smoothing > 0.0:
+            diag = diag + float(smoothing) * v / (torch.where(valid, om, torch.ones_like(v)) if om is not None else 1.0)
+        A[:, :K, :K] += torch.diag_embed(diag)
+        Pm = torch.cat([torch.ones_like(qh[..., :1]), qh], -1) * v[..., None]
+        A[:, :K, K:] = Pm
+        A[:, K:, :K] = Pm.transpose(1, 2)
+    d = torch.where(valid[..., None], moving_pts.to(f64) - q, torch.zeros_like(q))
+    rhs = torch.cat([d, torch.zeros((B, nd + 1, nd), dtype=f64, device=dev)], 1)
+    coef, info = torch.linalg.solve_ex(A, rhs)
+    with torch.no_grad():
+        bad_w = torch.zeros((), dtype=torch.bool, device=dev) if om is None else ~(om >= 0).all()
+        # fewer than nd + 1 valid points, or all of them on one line (plane): P has no full column rank, which an LU in
+        # floating point need not notice -- the Gram matrix of P's columns shows it
+        ev = torch.linalg.eigvalsh(Pm.transpose(1, 2) @ Pm)
+        few = (valid.sum(1) < nd + 1).any() | ~(ev[:, 0] > 1e-12 * ev[:, -1]).all()
+        flags = torch.stack([(info != 0).any() | few, ~torch.isfinite(coef).all(), bad_w]).tolist()    # the one host sync
+    if flags[2]:
+        raise ValueError("%s: weight must hold numbers >= 0 (0 marks a padding entry)" % what)
+    if flags[0] or flags[1]:
+        raise ValueError("%s: the spline system is singular (coincident points with smoothing = 0, fewer than %d valid points, "
+                         "or valid points on one %s)" % (what, nd + 1, "line" if nd == 2 else "plane"))
+    return TPSHandle(coef, q.to(torch.float32).contiguous(), scale, vol)
+
+
+def _tps_args(handle_or_coef, handle, what):
+    """(coef, handle, B, K) of a tps_flow / tps_points call after the argument checks (nothing is launched on a bad one)."""
+    if isinstance(handle_or_coef, TPSHandle):
+        if handle is not None:
+            raise ValueError("%s: give either a handle, or a coef tensor and handle=" % what)
+        handle = handle_or_coef
+        coef = handle.coef
+    else:
+        coef = handle_or_coef
+        if not isinstance(handle, TPSHandle):
+            raise ValueError("%s: a coef tensor needs handle= the TPSHandle of ops.tps_fit whose control points it weights" % what)
+    ctrl = handle.ctrl
+    B, K, nd = (int(n) for n in ctrl.shape)
+    if not torch.is_tensor(coef) or tuple(coef.shape) != (B, K + nd + 1, nd):
+        raise DfmirHipError("%s: coef mismatch (expected [B,K+nd+1,nd] = %s, got %s)"
+                            % (what, (B, K + nd + 1, nd), tuple(coef.shape) if torch.is_tensor(coef) else type(coef).__name__))
+    if coef.dtype != torch.float64:
+        raise DfmirHipError("%s: coef must be float64 (got %s)" % (what, coef.dtype))
+    if coef.device != ctrl.device:
+        raise DfmirHipError("%s: coef on %s, control points on %s" % (what, coef.device, ctrl.device))
+    _need(ctrl)
+    return coef, handle, B, K
+
+
+def _tps_zyx(nd, vals, fill):
+    return tuple(vals) if nd == 3 else (fill,) + tuple(vals)
+
+
+class TpsFlowFn(Function):
+    """dfmir_tps_fwd / dfmir_tps_bwd_coef."""
+
+    @staticmethod
+    def forward(ctx, coef, ctrl, vol, scale):
+        nd = len(vol)
+        B, K = int(ctrl.shape[0]), int(ctrl.shape[1])
+        coef = _c(coef)
+        flow = torch.empty((B, nd) + vol, device=ctrl.device, dtype=torch.float32)
+        check(lib().dfmir_tps_fwd(nd, _p(coef), _p(ctrl), None, _p(flow), B, K, 0, *_tps_zyx(nd, vol, 1),
+                                  *_tps_zyx(nd, scale, 1.0), _st()))
+        ctx.save_for_backward(ctrl)
+        ctx.meta = (nd, B, K, vol, scale)
+        return flow
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        ctrl, = ctx.saved_tensors
+        nd, B, K, vol, scale = ctx.meta
+        g = _c(g)
+        dhw = _tps_zyx(nd, vol, 1)
+        ws = torch.empty(int(lib().dfmir_tps_ws_bytes(nd, B, K, *dhw)) // 8, device=g.device, dtype=torch.float64)
+        dcoef = torch.empty((B, K + nd + 1, nd), device=g.device, dtype=torch.float64)
+        check(lib().dfmir_tps_bwd_coef(nd, _p(ctrl), _p(g), _p(dcoef), _p(ws), B, K, *dhw, *_tps_zyx(nd, scale, 1.0), _st()))
+        return dcoef, None, None, None
+
+
+def tps_flow(handle_or_coef, handle=None):
+    """The dense flow [B,nd,*vol] fp32 of a thin-plate spline (build-defined; the definition: ops.tps_fit): u at every voxel
+    of the handle's volume, in ops.warp's convention.  tps_flow(handle) evaluates the handle's own coefficients; tps_flow(coef,
+    handle=handle) evaluates a float64 tensor coef [B,K+nd+1,nd] on the handle's control points, scale and volume.  Basis
+    values are fp32, their products with the coefficients and the sum over the control points float64, rounded once
+    (dfmir_amd/csrc/tps.hip).  Differentiable in coef (once): dcoef[k] = sum_x phi(|xh - qh_k|) g(x), da_0 = sum g, dA = sum
+    xh g^T in float64 without atomics -- through the handle's coef the gradient reaches the moving_pts of ops.tps_fit.  No
+    gradient is defined for the control positions.  Forward and backward are bit-identical from run to run.  Raises before
+    any launch on a coef that is not float64 [B,K+nd+1,nd] on the control points' device and on a volume of 2^31 or more flow
+    elements; a CPU handle raises the usual "no CPU fallback" error."""
+    what = "tps_flow"
+    coef, handle, B, K = _tps_args(handle_or_coef, handle, what)
+    if lib().dfmir_tps_ws_bytes(handle.nd, B, K, *_tps_zyx(handle.nd, handle.vol, 1)) < 0:
+        raise DfmirHipError("%s: needs B <= 65535 and fewer than 2^31 flow elements, got B = %d, vol %s" % (what, B, handle.vol))
+    return TpsFlowFn.apply(coef, handle.ctrl, handle.vol, handle.scale)
+
+
+@torch.no_grad()
+def tps_points(handle, points):
+    """The spline of a TPSHandle at M arbitrary points: points [B,M,nd] fp32 voxel coordinates (inside the volume or not) ->
+    [B,M,nd] fp32 displacements u(points), the kernel of ops.tps_flow with another position source.  No gradient.  A point
+    with a non-finite coordinate gives a non-finite row.  Raises before any launch on a shape or dtype that disagrees; a CPU
+    tensor raises the usual "no CPU fallback" error."""
+    what = "tps_points"
+    if not isinstance(handle, TPSHandle):
+        raise ValueError("%s: handle must be the TPSHandle of ops.tps_fit" % what)
+    coef, handle, B, K = _tps_args(handle, None, what)
+    nd = handle.nd
+    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != B or int(points.shape[2]) != nd \
+            or int(points.shape[1]) < 1:
+        raise DfmirHipError("%s: points mismatch (expected [B,M,nd] = [%d,M,%d] with M >= 1, got %s)"
+                            % (what, B, nd, tuple(points.shape) if torch.is_tensor(points) else type(points).__name__))
+    if points.dtype != torch.float32:
+        raise DfmirHipError("%s: fp32 tensors only (points is %s)" % (what, points.dtype))
+    if points.device != handle.ctrl.device:
+        raise DfmirHipError("%s: points on %s, control points on %s" % (what, points.device, handle.ctrl.device))
+    M = int(points.shape[1])
+    if B > 65535 or B * M * nd >= 2 ** 31:
+        raise DfmirHipError("%s: needs B <= 65535 and fewer than 2^31 coordinates, got %s" % (what, tuple(points.shape)))
+    points = _c(points)
+    out = torch.empty((B, M, nd), device=points.device, dtype=torch.float32)
+    check(lib().dfmir_tps_fwd(nd, _p(_c(coef.detach())), _p(handle.ctrl), _p(points), _p(out), B, K, M, 2, 2, 2,
+                              *_tps_zyx(nd, handle.scale, 1.0), _st()))
+    return out
+
+
 class MulFn(Function):
     """a * b element-wise, same shapes (`prediction * mask`, util/losses.py:120-121)."""
 

@@ -921,6 +921,33 @@ int dfmir_landmark_fwd(int nd, const float* flow, const float* fixed_pts, const 
 int dfmir_landmark_bwd(int nd, const float* flow, const float* fixed_pts, const float* moving_pts, const float* weight,
                        const float* gout, const float* wsum, float* dflow, float* ws, int B, int K, int D, int H, int W,
                        float hz, float hy, float hx, int penalty, void* stream);
+/* Thin-plate / polyharmonic spline interpolation of landmark displacements (build-defined: the reference has no landmark
+ * code; the fit itself is ops.tps_fit, a float64 solve in torch).  ctrl q: [B][K][nd] fp32 voxel coordinates of the control
+ * points, axis order (z,) y, x as a flow's channels, every entry finite (a padding entry is 0 with a zero coefficient);
+ * scale (sz, sy, sx) = h_a / L with L = max_a h_a (S_a - 1) (sz is not read when nd == 2): basis functions are evaluated in
+ * the normalised coordinates xh_a = scale_a x_a.  coef: [B][K + nd + 1][nd] float64 = [w (K rows); a_0; A (nd rows)].
+ *   u_a(x) = a_0[a] + sum_c xh_c A[c][a] + sum_k w[k][a] phi(|xh - qh_k|)
+ *   phi(r) = -r (nd == 3) or r^2 log r, computed as s log(s) / 2 from s = r^2 with phi(0) = 0 (nd == 2)
+ * dfmir_tps_fwd: points == NULL: out[b][a][(z)][y][x] = u_a at every voxel of the volume, a flow in the warp kernels'
+ * convention; points [B][M][nd] fp32 voxel coordinates: out[b][m][a] = u_a(points[b][m]) (D, H, W are not read; a non-finite
+ * coordinate gives a non-finite row).  One kernel body with two position sources.  The normalised coordinates are rounded to
+ * fp32 once from the double product, the squared distance and phi are fp32 (the accurate logf; the hardware square root,
+ * 1 ulp), the product with the coefficient and the sum over k are float64 FMAs in index order, rounded to fp32 once at the
+ * store.  A thread owns four voxels along x; the control points pass through LDS in chunks of 256.
+ * dfmir_tps_bwd_coef: the adjoint with respect to coef, float64: dcoef[b][k][a] = sum_x phi(|xh - qh_k|) g[b][a][x],
+ * dcoef[b][K][a] = sum_x g, dcoef[b][K + 1 + c][a] = sum_x xh_c g, g: [B][nd][(D)][H][W] fp32.  A thread owns one control
+ * point; the volume is cut into slabs (a number fixed by the shape alone) whose voxels pass through LDS in tiles of 256; a
+ * second launch adds the slabs' partials in slab order.  No atomics: dcoef is bit-identical from run to run.  No gradient is
+ * defined with respect to the control positions.  ws: dfmir_tps_ws_bytes BYTES (-1 for a refused shape), 8-byte aligned, need
+ * not be zeroed.
+ * Refused ("invalid argument", nothing is launched): nd outside {2, 3}, B outside [1, 65535], K outside [1, 4096], an extent
+ * < 2, B * nd * S >= 2^31 (point mode: M < 1 or B * M * nd >= 2^31), a scale that is not positive and finite, a NULL
+ * pointer other than `points`.  Nothing syncs, allocates or keeps state: the calls capture into a hipGraph. */
+long long dfmir_tps_ws_bytes(int nd, int B, int K, int D, int H, int W);
+int dfmir_tps_fwd(int nd, const double* coef, const float* ctrl, const float* points, float* out, int B, int K, long long M,
+                  int D, int H, int W, double sz, double sy, double sx, void* stream);
+int dfmir_tps_bwd_coef(int nd, const float* ctrl, const float* gout, double* dcoef, void* ws, int B, int K, int D, int H,
+                       int W, double sz, double sy, double sx, void* stream);
 /* NMI_Loss (util/losses.py:263-348): out[0] = -MI of the soft-binned (Parzen) joint histogram of y_true and y_pred, both
  * first clamped to [0, max_clip]; all n voxels (batch and channels included) form ONE histogram.  Per voxel
  * a_k = exp(-preterm (y_true - c_k)^2) normalised over k (b_k the same for y_pred), pab[i][j] = sum_v b[i] a[j] / V,
