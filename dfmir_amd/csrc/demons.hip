@@ -16,7 +16,8 @@
 //              e J and the upper triangle of J J^T are added IN DOUBLE -- 1 + 3 + 6 sums in 3-D, 1 + 2 + 3 in 2-D -- and the
 //              system is solved in closed form by its L D L^T factors, in double (dm_solve says why).  sum m s C and sum m
 //              leave as two double slots per workgroup.  No warped tensor, no e tensor, no atomics.
-//   dm_fin_k   (one workgroup) adds the slots of each sample in a fixed order: L_b and L.  Bit-identical from run to run.
+//   ws_fin_k   (ws_sample.h, shared with warpssd.hip, here without its scale output; one workgroup) adds the slots of each
+//              sample in a fixed order: L_b and L.  Bit-identical from run to run.
 // Nothing syncs with the host or keeps state.
 #include "ws_sample.h"
 
@@ -76,7 +77,10 @@ __device__ __forceinline__ void dm_solve(const double (&g)[3], const double (&h)
 }
 
 // part[2 wg] = sum m sum_c e^2, part[2 wg + 1] = sum m over the workgroup's voxels (m = 1 without a mask); dout = the force.
-// The staging is ws_fwd_k's (warpssd.hip), which see.
+// The walk over the workgroup's voxels -- thread geometry, prefetch, the 16-byte to one-voxel-per-lane staging in the wave's LDS
+// rows, the channel-group loop, the staged store and the two ordered sums -- repeats ws_fwd_k's (warpssd.hip), whose comments
+// explain it; only the per-voxel arithmetic differs.  The two stay separate kernels: profiles/walk_tile_ab.txt has the shared
+// forms that were tried and what they cost.
 template <int ND, int VPT>
 __global__ __launch_bounds__(WS_T) void dm_fwd_k(const float* __restrict__ mov, const float* __restrict__ fix,
                                                  const float* __restrict__ phi, const float* __restrict__ mask, WsGeom g,
@@ -196,28 +200,6 @@ __global__ __launch_bounds__(WS_T) void dm_fwd_k(const float* __restrict__ mov, 
   if (threadIdx.x == 0) { part[2LL * blockIdx.x] = acc; part[2LL * blockIdx.x + 1] = wsum; }
 }
 
-// per[b] = L_b, loss[0] = L
-__global__ __launch_bounds__(WS_T) void dm_fin_k(const double* __restrict__ part, int B, int nblk, double C,
-                                                 float* __restrict__ per, float* __restrict__ loss) {
-  __shared__ double red[WS_T / 64];
-  double total = 0.0, wtotal = 0.0;
-  for (int b = 0; b < B; ++b) {
-    double s = 0.0, w = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += WS_T) {
-      s += part[2 * ((long long)b * nblk + i)];
-      w += part[2 * ((long long)b * nblk + i) + 1];
-    }
-    s = block_sum_ordered<WS_T>(s, red);
-    w = block_sum_ordered<WS_T>(w, red);
-    if (threadIdx.x == 0) {
-      per[b] = w > 0.0 ? (float)(s / (C * w)) : 0.f;
-      total += s;
-      wtotal += w;
-    }
-  }
-  if (threadIdx.x == 0) loss[0] = wtotal > 0.0 ? (float)(total / (C * wtotal)) : 0.f;
-}
-
 }  // namespace
 
 extern "C" long long dfmir_demons_ws_floats(int nd, int B, int C, int D, int H, int W) {
@@ -245,7 +227,7 @@ extern "C" int dfmir_demons_force(int nd, const float* Mp, const float* F, const
   else { if (vpt == 4) DM_LAUNCH(2, 4); else DM_LAUNCH(2, 1); }
 #undef DM_LAUNCH
   DF_LAUNCH_CHECK();
-  dm_fin_k<<<1, WS_T, 0, st>>>(part, B, g.nblk, (double)C, per_sample, loss);
+  ws_fin_k<WS_T><<<1, WS_T, 0, st>>>(part, B, g.nblk, (double)C, mask ? 1 : 0, per_sample, loss, nullptr);
   DF_LAUNCH_CHECK();
   return 0;
 }

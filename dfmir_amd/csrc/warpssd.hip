@@ -23,8 +23,8 @@
 //              the corners are gathered, e^2 and e * dM are added.  sum m e^2 and sum m are added in double per thread and
 //              leave as two double slots per workgroup; the UNIT gradient (gout = 1; masked: still to be divided by sum m)
 //              is written when asked for.  No warped tensor, no e tensor, no atomics.
-//   ws_fin_k   (one workgroup) adds the slots of each sample in a fixed order: L_b, L and the gradient's scale (1, masked
-//              1 / sum m, 0 for an empty mask).  Bit-identical from run to run.
+//   ws_fin_k   (ws_sample.h, shared with demons.hip; one workgroup) adds the slots of each sample in a fixed order: L_b, L
+//              and the gradient's scale (1, masked 1 / sum m, 0 for an empty mask).  Bit-identical from run to run.
 //   ws_bwd_k   dflow = unit * gout * scale, both read on the device.
 // Nothing syncs with the host or keeps state.
 #include "ws_sample.h"
@@ -154,32 +154,6 @@ __global__ __launch_bounds__(WS_T) void ws_fwd_k(const float* __restrict__ mov, 
   if (threadIdx.x == 0) { part[2LL * blockIdx.x] = acc; part[2LL * blockIdx.x + 1] = wsum; }
 }
 
-// per[b] = L_b, loss[0] = L, scale[0] = what the unit gradient is still to be multiplied with besides gout
-__global__ __launch_bounds__(WS_T) void ws_fin_k(const double* __restrict__ part, int B, int nblk, double C, int masked,
-                                                 float* __restrict__ per, float* __restrict__ loss,
-                                                 float* __restrict__ scale) {
-  __shared__ double red[WS_T / 64];
-  double total = 0.0, wtotal = 0.0;
-  for (int b = 0; b < B; ++b) {
-    double s = 0.0, w = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += WS_T) {
-      s += part[2 * ((long long)b * nblk + i)];
-      w += part[2 * ((long long)b * nblk + i) + 1];
-    }
-    s = block_sum_ordered<WS_T>(s, red);
-    w = block_sum_ordered<WS_T>(w, red);
-    if (threadIdx.x == 0) {
-      per[b] = w > 0.0 ? (float)(s / (C * w)) : 0.f;
-      total += s;
-      wtotal += w;
-    }
-  }
-  if (threadIdx.x == 0) {
-    loss[0] = wtotal > 0.0 ? (float)(total / (C * wtotal)) : 0.f;
-    scale[0] = masked ? (wtotal > 0.0 ? (float)(1.0 / wtotal) : 0.f) : 1.f;
-  }
-}
-
 template <int V>
 __global__ __launch_bounds__(WS_T) void ws_bwd_k(const float* __restrict__ unit, const float* __restrict__ gout,
                                                  const float* __restrict__ scale, float* __restrict__ dflow, long long n) {
@@ -257,7 +231,7 @@ extern "C" int dfmir_warp_ssd_fwd_grad(int nd, const float* Mp, const float* M, 
   }
 #undef WS_LAUNCH
   DF_LAUNCH_CHECK();
-  ws_fin_k<<<1, WS_T, 0, st>>>(part, B, g.nblk, (double)C, mask ? 1 : 0, per_sample, loss, scale);
+  ws_fin_k<WS_T><<<1, WS_T, 0, st>>>(part, B, g.nblk, (double)C, mask ? 1 : 0, per_sample, loss, scale);
   DF_LAUNCH_CHECK();
   return 0;
 }

@@ -1,8 +1,9 @@
 // The cell and corner gather of the warped-feature SSD (warpssd.hip), shared with the affine system kernels (affine.hip):
 // the geometry of a feature volume, the cell floor() selects for a sample point with its guards (lin_cell.h's), the
 // gather of four channels of its corners from the voxel-major packed copy (or the channel-major tensor), and the
-// interpolant with its derivative.  Everything sits in an anonymous namespace: each file that includes this keeps its own
-// copy of the host helpers.
+// interpolant with its derivative.  The demons force (demons.hip) takes the same pieces, and shares with warpssd.hip the
+// kernel that finishes the per-sample sums (ws_fin_k).  Everything sits in an anonymous namespace: each file that includes
+// this keeps its own copy of the host helpers.
 #pragma once
 #include "lin_cell.h"
 
@@ -96,5 +97,34 @@ bool ws_geom(int nd, int B, int C, int D, int H, int W, int vpt, WsGeom* g) {
 }
 
 inline bool ws_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// (one workgroup of T threads) adds the two slots of each sample's workgroups in a fixed order: per[b] = L_b, loss[0] = L,
+// scale[0] (may be NULL) = what a unit gradient is still to be multiplied with: 1, masked 1 / sum m, 0 for an empty mask.
+// C = the channel count.  Bit-identical from run to run.  A template, so that only the files that launch it carry it.
+template <int T>
+static __global__ __launch_bounds__(T) void ws_fin_k(const double* __restrict__ part, int B, int nblk, double C, int masked,
+                                                     float* __restrict__ per, float* __restrict__ loss,
+                                                     float* __restrict__ scale) {
+  __shared__ double red[T / 64];
+  double total = 0.0, wtotal = 0.0;
+  for (int b = 0; b < B; ++b) {
+    double s = 0.0, w = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += T) {
+      s += part[2 * ((long long)b * nblk + i)];
+      w += part[2 * ((long long)b * nblk + i) + 1];
+    }
+    s = block_sum_ordered<T>(s, red);
+    w = block_sum_ordered<T>(w, red);
+    if (threadIdx.x == 0) {
+      per[b] = w > 0.0 ? (float)(s / (C * w)) : 0.f;
+      total += s;
+      wtotal += w;
+    }
+  }
+  if (threadIdx.x == 0) {
+    loss[0] = wtotal > 0.0 ? (float)(total / (C * wtotal)) : 0.f;
+    if (scale) scale[0] = masked ? (wtotal > 0.0 ? (float)(1.0 / wtotal) : 0.f) : 1.f;
+  }
+}
 
 }  // namespace

@@ -23,7 +23,7 @@ dfmir_demons_force: dm_fwd_k<ND, VPT>, VPT = 4 -- 16-byte accesses of the flow, 
 ws_fwd_k's, a workgroup owns 256 VPT voxels; the launch does not walk chunks, so tests/test_affine.py's large shape adds no path):
   <2-D, 1> (2,4,9,13)    <2-D, 4> (2,4,8,16)    <3-D, 4> (2,12,5,12,24) 1440 voxels = 2 workgroups per sample, three channel
   groups; (1,5,2,6,8) C = 5: a second group with one live channel    <3-D, 1> (2,1,3,7,9) C = 1
-dm_fin_k runs after every force.
+ws_fin_k (without its scale output) runs after every force.
 
 Flows of the force cases, a different one per sample (tests/test_affine.py's thetas, turned into dense fp32 fields): `zero`;
 `lattice` = smooth, offsets near integer + 0.5, every sample point at least 0.05 from a cell face (asserted on the fp32 field);
