@@ -186,6 +186,11 @@ _SIGS = {
     "dfmir_tps_ws_bytes": [c_int] * 6,
     "dfmir_tps_fwd": [c_int, P, P, P, P, c_int, c_int, c_longlong] + [c_int] * 3 + [c_double] * 3 + [P],
     "dfmir_tps_bwd_coef": [c_int, P, P, P, P] + [c_int] * 5 + [c_double] * 3 + [P],
+    "dfmir_keypoint_products": [c_int, P, P] + [c_int] * 4 + [c_float] * 3 + [P],
+    "dfmir_keypoint_response": [c_int, P, P] + [c_int] * 4 + [P],
+    "dfmir_keypoint_nms": [c_int, P, P, P] + [c_int] * 5 + [c_float, P],
+    "dfmir_keypoint_cost": [c_int, P, P, P, P] + [c_int] * 9 + [P],
+    "dfmir_keypoint_argmin": [c_int, P, P, c_float, P, P, c_longlong, c_int, c_int, P],
     "dfmir_nmi_ws_floats": [c_longlong, c_int],
     "dfmir_nmi_fwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P],
     "dfmir_nmi_bwd": [P, P, P, P, c_int, c_float, c_float, c_longlong, P, P, P, P, P],

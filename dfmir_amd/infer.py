@@ -718,3 +718,94 @@ def landmark_init(moving, fixed, fixed_pts, moving_pts, *, spacing=None, smoothi
     flow = ops.tps_flow(handle)
     tre = ops.landmark_distances(flow, fixed_pts, moving_pts, weight, spacing)[0]
     return dict(flow=flow, warped=_final_warp(moving.detach(), flow, interp), coef=handle.coef, tre=tre)
+
+
+@torch.no_grad()
+def keypoint_init(moving, fixed, *, features='mind', mind_radius=2, mind_dilation=2, num_keypoints=2048, sigma=1.5,
+                  nms_radius=3, mask=None, threshold=0.0, search_radius=8, search_step=2, patch=2, coeffs=CONVEX_COEFFS,
+                  smoothing=1e-3, spacing=None, interp='linear'):
+    """Stage 0 of the inference pipeline for a pair WITHOUT annotated keypoints (build-defined): detect distinctive points of
+    the fixed image, search a wide window around each one only, regularise the sparse displacements against a thin-plate
+    spline and interpolate -- the sparse answer to motion beyond convex_init's dense window (search_radius * search_step
+    voxels per axis, 16 at the defaults).  Returns dict(flow, warped, fixed_pts, moving_pts, weight, idx, tre).
+
+    moving, fixed: [B,1,*vol] fp32 images of one shape, 2-D or 3-D; features as in convex_init ('mind', 'intensity' or a pair
+    (moving features, fixed features) of [B,C,*vol] tensors, 1 <= C <= 16); num_keypoints: K in 1..ops.LANDMARK_MAX_K;
+    sigma, spacing: ops.foerstner_response's; nms_radius, mask, threshold: ops.local_maxima's; search_radius, search_step, patch:
+    ops.keypoint_cost's radius, step and patch (search_radius is clamped by nothing: 1..8 in 3-D, 1..16 in 2-D, the default 8
+    suits 3-D); coeffs: the coupling coefficients, finite floats >= 0, in the order they are applied; smoothing: the lambda
+    of every ops.tps_fit; interp: the final warp, as landmark_init.
+
+        q, w  = ops.select_keypoints(ops.local_maxima(ops.foerstner_response(fixed, sigma, spacing), nms_radius, mask,
+                                                      threshold), num_keypoints)
+        cost  = ops.keypoint_cost(Mf, Mm, q, search_radius, search_step, patch)          Mf, Mm: the fixed / moving features
+        disp  = ops.keypoint_argmin(cost, search_radius, search_step)[1]
+        for c in coeffs:
+            prior     = ops.tps_points(ops.tps_fit(q, q + disp, vol, spacing, smoothing, w), q)
+            idx, disp = ops.keypoint_argmin(cost, search_radius, search_step, prior, c)
+        p = q + disp
+
+    (ops.tps_points returns the spline's DISPLACEMENT at the points, which is the prior; nothing is subtracted.)
+        flow, warped, tre  exactly as landmark_init(moving, fixed, q, p, spacing=spacing, smoothing=smoothing, weight=w,
+                                                    interp=interp) returns them
+
+    fixed_pts = q, moving_pts = p [B,K,nd], weight = w [B,K] (the response at the keypoint; 0 and NaN coordinates mark the
+    padding of a sample with fewer than K peaks), idx = the index field of the last argmin, int32 [B,K].
+
+    Each ops.tps_fit syncs with the host once: len(coeffs) + 1 syncs per call; nothing else does.  Fewer than nd + 1 valid
+    keypoints in a sample surfaces as ops.tps_fit's ValueError (the spline system is singular).
+
+    The default `coeffs` are the numbers of the published coupled-convex schedule and `smoothing` is a borrowed number too:
+    the cost here is a mean over channels and patch, the displacements are in voxels and the prior is a spline, not a box
+    mean, so their scale is not the published one, and nobody has measured registration quality with them.
+
+    ValueError before any launch on an unknown interp, images that are not two [B,1,*vol] tensors of one shape (any channel
+    count with a feature pair), an unknown `features`, and every parameter the ops above refuse (num_keypoints, sigma,
+    spacing, nms_radius, mask, threshold, search_radius, search_step, patch, the staged extent, a coefficient that is
+    negative or not finite, smoothing)."""
+    what = "keypoint_init"
+    _check_interp(what, interp)
+    if not (torch.is_tensor(moving) and torch.is_tensor(fixed)) or moving.dim() not in (4, 5) \
+            or tuple(moving.shape) != tuple(fixed.shape):
+        raise ValueError("%s: moving and fixed must be two [B,1,*vol] tensors of one shape" % what)
+    nd = moving.dim() - 2
+    B, vol = int(moving.shape[0]), tuple(int(n) for n in moving.shape[2:])
+    _check_features(what, features, moving, nd, B, vol)
+    if fixed.shape[1] != 1:
+        raise ValueError("%s: the keypoints are detected on a single-channel fixed image, got %d channels" % (what, fixed.shape[1]))
+    ops._keypoint_int(num_keypoints, 1, ops.LANDMARK_MAX_K, what, "num_keypoints")
+    ops.bending_spacing(spacing, (nd,), what)
+    ops.gauss_radii(sigma, 3.0, nd, what)
+    ops._keypoint_int(nms_radius, 1, ops.KEYPOINT_NMS_MAX_RADIUS, what, "nms_radius")
+    if mask is not None and (not torch.is_tensor(mask) or tuple(mask.shape) != tuple(fixed.shape)
+                             or mask.dtype != torch.float32 or mask.requires_grad):
+        raise ValueError("%s: mask must be an fp32 tensor [B,1,*vol] = %s that does not require grad" % (what, tuple(fixed.shape)))
+    for name, t in (("moving", moving), ("fixed", fixed)):
+        if t.dtype != torch.float32:
+            raise ValueError("%s: fp32 tensors only (%s is %s)" % (what, name, t.dtype))
+    if not _finite_number(threshold):
+        raise ValueError("%s: threshold must be a finite number, got %r" % (what, threshold))
+    ops._keypoint_window(search_radius, search_step, nd, what)
+    ops._keypoint_int(patch, 0, ops.KEYPOINT_MAX_PATCH, what, "patch")
+    if 2 * (search_radius * search_step + patch) + 1 > ops.KEYPOINT_MAX_EXTENT:
+        raise ValueError("%s: the staged extent 2 (search_radius search_step + patch) + 1 exceeds ops.KEYPOINT_MAX_EXTENT = %d"
+                         % (what, ops.KEYPOINT_MAX_EXTENT))
+    try:
+        coeffs = tuple(float(c) for c in coeffs)
+    except (TypeError, ValueError):
+        raise ValueError("%s: coeffs must be a sequence of finite numbers >= 0, got %r" % (what, coeffs))
+    if not all(0.0 <= c < float('inf') for c in coeffs):
+        raise ValueError("%s: coeffs must be a sequence of finite numbers >= 0, got %r" % (what, coeffs))
+    if not _finite_number(smoothing) or smoothing < 0:
+        raise ValueError("%s: smoothing must be a finite number >= 0, got %r" % (what, smoothing))
+    Mm, Mf = _resolve_features(features, moving, fixed, mind_radius, mind_dilation)
+    peaks = ops.local_maxima(ops.foerstner_response(fixed.detach(), sigma, spacing), nms_radius, mask, threshold)
+    q, w = ops.select_keypoints(peaks, num_keypoints)
+    cost = ops.keypoint_cost(Mf, Mm, q, search_radius, search_step, patch)
+    idx, disp = ops.keypoint_argmin(cost, search_radius, search_step)
+    for c in coeffs:
+        prior = ops.tps_points(ops.tps_fit(q, q + disp, vol, spacing, smoothing, w), q)
+        idx, disp = ops.keypoint_argmin(cost, search_radius, search_step, prior, c)
+    p = q + disp
+    res = landmark_init(moving, fixed, q, p, spacing=spacing, smoothing=smoothing, weight=w, interp=interp)
+    return dict(flow=res['flow'], warped=res['warped'], fixed_pts=q, moving_pts=p, weight=w, idx=idx, tre=res['tre'])

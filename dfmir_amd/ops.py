@@ -3364,6 +3364,14 @@ def affine_lm_step(L, g, H, theta_acc, trial, state, hist, k, dof='affine', mu_u
 
 
 DSEARCH_MAX_RADIUS = {2: 8, 3: 4}           # dfmir_amd/csrc/dsearch.hip: what the cost kernel's staged window is sized for
+# dfmir_amd/csrc/keypoints.hip (the DFMIR_KEYPOINT_* of include/dfmir_hip.h): the limits of ops.local_maxima, ops.keypoint_cost
+# and ops.keypoint_argmin.  KEYPOINT_MAX_EXTENT bounds the staged extent E = 2 (radius step + patch) + 1 of the search region:
+# one plane of E^2 floats beside the largest fixed patch in 64 KB of LDS.
+KEYPOINT_NMS_MAX_RADIUS = 8
+KEYPOINT_MAX_RADIUS = {2: 16, 3: 8}
+KEYPOINT_MAX_STEP = 4
+KEYPOINT_MAX_PATCH = 3
+KEYPOINT_MAX_EXTENT = 96
 
 
 def _dsearch_radius(radius, nd, what):
@@ -3966,6 +3974,251 @@ def tps_points(handle, points):
     check(lib().dfmir_tps_fwd(nd, _p(_c(coef.detach())), _p(handle.ctrl), _p(points), _p(out), B, K, M, 2, 2, 2,
                               *_tps_zyx(nd, handle.scale, 1.0), _st()))
     return out
+
+
+def _keypoint_image(t, what, name, planes=1):
+    """(nd, B, D, H, W) of a [B,1,*vol] fp32 tensor after the checks a CPU tensor can fail (ValueError: nothing is launched);
+    `planes` = the most planes per voxel a kernel of the call forms from it."""
+    if not torch.is_tensor(t) or t.dim() not in (4, 5) or t.shape[1] != 1:
+        raise ValueError("%s: %s must be a [B,1,H,W] or [B,1,D,H,W] tensor, got %s"
+                         % (what, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    nd = t.dim() - 2
+    if t.shape[0] < 1 or min(t.shape[2:]) < 2:
+        raise ValueError("%s: %s needs B >= 1 and every extent >= 2, got %s" % (what, name, tuple(t.shape)))
+    if t.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (%s is %s)" % (what, name, t.dtype))
+    if t.numel() * planes >= 2 ** 31:
+        raise ValueError("%s: %s %s has 2^31 or more elements (times %d planes)" % (what, name, tuple(t.shape), planes))
+    if t.requires_grad:
+        raise ValueError("%s: %s requires grad, but the op has no gradient (detach it)" % (what, name))
+    D, H, W = (int(n) for n in (t.shape[2:] if nd == 3 else (1,) + tuple(t.shape[2:])))
+    return nd, int(t.shape[0]), D, H, W
+
+
+def _keypoint_int(v, lo, hi, what, name):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (what, name, lo, hi, v))
+    return v
+
+
+@torch.no_grad()
+def foerstner_response(I, sigma=1.5, spacing=None):
+    """The Foerstner structure-tensor response of an image (build-defined), the distinctiveness that keypoints are picked by:
+    I [B,1,*vol] fp32, 2-D or 3-D -> R [B,1,*vol].  Axis order (z,) y, x; S_a the extents.
+
+        g_a(x) = (I(min(x_a + 1, S_a - 1)) - I(max(x_a - 1, 0))) / (2 h_a)        h = `spacing`: nd positive numbers, None = 1
+        T_ab   = ops.gaussian_smooth(g_a g_b, sigma)                             nd (nd + 1) / 2 planes, fp32, renormalised at
+                                                                                 the faces: that op's definition exactly
+        R      = det(T) / trace(adj(T))   ( = 1 / trace(T^-1); in 2-D det / trace)
+
+    R is formed in DOUBLE from the fp32 planes and rounded once (the determinant of a near-singular T cancels), and is 0
+    where the denominator is not > 0 or anything is non-finite.  One kernel forms the products (a thread writes all planes
+    of its voxel from a staged tile), dfmir_gauss_smooth filters them, one kernel forms the response
+    (dfmir_amd/csrc/keypoints.hip).  Bit-identical from run to run; nothing syncs with the host.  No gradient: an input that
+    requires grad raises.  ValueError before any launch on a tensor that is not [B,1,*vol] fp32 with every extent >= 2, 2^31
+    or more elements in the stack of planes, a bad spacing (ops.bending_spacing) and what ops.gaussian_smooth refuses of
+    sigma; a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "foerstner_response"
+    nd, B, D, H, W = _keypoint_image(I, what, "I", planes=6 if torch.is_tensor(I) and I.dim() == 5 else 3)
+    hs = bending_spacing(spacing, (nd,), what)
+    hz, hy, hx = hs if nd == 3 else (1.0,) + hs
+    gauss_radii(sigma, 3.0, nd, what)
+    _need(I)
+    I = _c(I)
+    vol = tuple(I.shape[2:])
+    prod = torch.empty((B, nd * (nd + 1) // 2) + vol, device=I.device, dtype=torch.float32)
+    check(lib().dfmir_keypoint_products(nd, _p(I), _p(prod), B, D, H, W, hz, hy, hx, _st()))
+    T = gaussian_smooth(prod, sigma)
+    R = torch.empty((B, 1) + vol, device=I.device, dtype=torch.float32)
+    check(lib().dfmir_keypoint_response(nd, _p(T), _p(R), B, D, H, W, _st()))
+    return R
+
+
+@torch.no_grad()
+def local_maxima(R, radius, mask=None, threshold=0.0):
+    """Non-maximum suppression of a response map (build-defined): R [B,1,*vol] fp32, 2-D or 3-D -> [B,1,*vol] holding R(x)
+    where x is selected and 0 elsewhere.  x is selected iff R(x) > threshold, mask(x) != 0 (mask: [B,1,*vol] fp32 or None) and
+    for every other y of the (2 radius + 1)^nd window clipped to the volume R(y) < R(x), or R(y) == R(x) and y has the HIGHER
+    linear index -- the lowest index wins a plateau.  A NaN is never selected, and as a neighbour it compares as -inf; the mask
+    does not remove a voxel as a competitor.  radius: an integer in 1..KEYPOINT_NMS_MAX_RADIUS (8); threshold: a finite number.
+    One launch, tile plus halo in LDS and a direct walk of the window (dfmir_amd/csrc/keypoints.hip).  Bit-identical from run
+    to run; nothing syncs with the host; no gradient.  ValueError before any launch on tensors that are not [B,1,*vol] fp32 of
+    one shape with every extent >= 2, 2^31 or more elements, a tensor that requires grad, a radius outside its range and a
+    threshold that is not finite; a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "local_maxima"
+    nd, B, D, H, W = _keypoint_image(R, what, "R")
+    r = _keypoint_int(radius, 1, KEYPOINT_NMS_MAX_RADIUS, what, "radius")
+    if mask is not None:
+        if not torch.is_tensor(mask) or tuple(mask.shape) != tuple(R.shape):
+            raise ValueError("%s: mask must be [B,1,*vol] = %s, got %s"
+                             % (what, tuple(R.shape), tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__))
+        _keypoint_image(mask, what, "mask")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) \
+            or not abs(float(threshold)) <= float(np.finfo(np.float32).max):
+        raise ValueError("%s: threshold must be a finite number, got %r" % (what, threshold))
+    _need(R, mask)
+    if mask is not None and mask.device != R.device:
+        raise DfmirHipError("%s: R on %s, mask on %s" % (what, R.device, mask.device))
+    R = _c(R)
+    mask = None if mask is None else _c(mask)
+    out = torch.empty_like(R)
+    check(lib().dfmir_keypoint_nms(nd, _p(R), _p(mask), _p(out), B, D, H, W, r, float(threshold), _st()))
+    return out
+
+
+@torch.no_grad()
+def select_keypoints(peaks, K):
+    """The K strongest peaks of a suppressed response map as points (plain torch, plumbing only; it runs wherever `peaks`
+    lives): peaks [B,1,*vol], 2-D or 3-D, as ops.local_maxima returns it -> (pts [B,K,nd] fp32 voxel coordinates in axis order
+    (z,) y, x, weight [B,K] fp32 = the peaks' values).  Per sample the K largest POSITIVE entries in descending order, ties
+    broken by the lower linear index (a stable sort; torch.topk leaves the order of ties undefined).  A sample with fewer
+    positive entries is padded with NaN coordinates and weight 0, the padding ops.tps_fit honours.  K: an integer in
+    1..LANDMARK_MAX_K.  Nothing syncs with the host.  ValueError on a tensor that is not [B,1,*vol] floating point and on a K
+    outside its range."""
+    what = "select_keypoints"
+    if not torch.is_tensor(peaks) or peaks.dim() not in (4, 5) or peaks.shape[1] != 1 or not peaks.is_floating_point() \
+            or peaks.shape[0] < 1 or min(peaks.shape[2:]) < 1:
+        raise ValueError("%s: peaks must be a floating-point [B,1,H,W] or [B,1,D,H,W] tensor, got %s"
+                         % (what, tuple(peaks.shape) if torch.is_tensor(peaks) else type(peaks).__name__))
+    K = _keypoint_int(K, 1, LANDMARK_MAX_K, what, "K")
+    B, vol = int(peaks.shape[0]), tuple(int(n) for n in peaks.shape[2:])
+    flat = peaks.detach().reshape(B, -1).to(torch.float32)
+    flat = torch.where(flat > 0, flat, torch.zeros_like(flat))         # a NaN or a negative entry is no peak
+    val, lin = torch.sort(flat, dim=1, descending=True, stable=True)
+    val, lin = val[:, :K], lin[:, :K]
+    if val.shape[1] < K:
+        pad = K - val.shape[1]
+        val = torch.cat([val, val.new_zeros((B, pad))], 1)
+        lin = torch.cat([lin, lin.new_zeros((B, pad))], 1)
+    coords = []
+    for n in reversed(vol):
+        coords.append(lin % n)
+        lin = torch.div(lin, n, rounding_mode='floor')
+    pts = torch.stack(coords[::-1], -1).to(torch.float32)
+    pts = torch.where((val > 0)[..., None], pts, torch.full_like(pts, float('nan')))
+    return pts.contiguous(), val.contiguous()
+
+
+def _keypoint_window(radius, step, nd, what):
+    r = _keypoint_int(radius, 1, KEYPOINT_MAX_RADIUS[nd], what, "radius (%d-D)" % nd)
+    return r, _keypoint_int(step, 1, KEYPOINT_MAX_STEP, what, "step")
+
+
+def _keypoint_points(t, what, name, B, nd, K=None):
+    if not torch.is_tensor(t) or t.dim() != 3 or int(t.shape[0]) != B or int(t.shape[2]) != nd or int(t.shape[1]) < 1 \
+            or (K is not None and int(t.shape[1]) != K):
+        raise ValueError("%s: %s must be [B,K,nd] = [%d,%s,%d] with K >= 1, got %s"
+                         % (what, name, B, "K" if K is None else K, nd, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if t.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (%s is %s)" % (what, name, t.dtype))
+    if t.requires_grad:
+        raise ValueError("%s: %s requires grad, but the op has no gradient (detach it)" % (what, name))
+    return int(t.shape[1])
+
+
+@torch.no_grad()
+def keypoint_cost(fix, mov, pts, radius, step=1, patch=1):
+    """The windowed patch SSD around K points, the cost rows of a sparse displacement search (build-defined): fix, mov
+    [B,C,*vol] features (fp32, 1 <= C <= 16, 2-D or 3-D, one shape), pts [B,K,nd] fp32 voxel coordinates in axis order (z,) y,
+    x, as ops.landmark_distances takes them -> cost [B,K,D], D = (2 radius + 1)^nd.  With q_k = rint(pts[b,k]) (ties to even)
+    and P = (2 patch + 1)^nd,
+
+        cost[b,k,j] = 1/(C P) * sum_c sum_{o in {-patch..patch}^nd} ( fix[b,c,q+o] - mov[b,c,q+o+step*d_j] )^2
+
+    both sides reading 0 outside the volume; j enumerates d_j in {-radius .. radius}^nd in row-major order (dz,) dy, dx with
+    -radius first, exactly as ops.ssd_cost_volume does.  A row is all NaN where a coordinate of the point is non-finite or q_k
+    lies outside the volume.  Precision: the difference is fp32, its square and the sum are float64 in one fixed order for
+    every j, scaled in float64 and rounded once -- displacements whose reads all fall outside the volume tie bit for bit.
+    One workgroup per keypoint stages the fixed patch and, plane by plane, the moving search region in LDS
+    (dfmir_amd/csrc/keypoints.hip).  Bit-identical from run to run; nothing syncs with the host; no gradient.
+
+    Limits: radius 1..KEYPOINT_MAX_RADIUS[nd] (16 in 2-D, 8 in 3-D), step 1..KEYPOINT_MAX_STEP (4), patch
+    0..KEYPOINT_MAX_PATCH (3), the staged extent E = 2 (radius step + patch) + 1 <= KEYPOINT_MAX_EXTENT (96) -- a call beyond
+    it raises, there is no unstaged path --, B K D < 2^31, B <= 65535.  ValueError before any launch on these, on shapes that
+    disagree, and on what ops.pack_features refuses of the features (rank, C outside 1..16, dtype, 2^31 or more elements, a
+    tensor that requires grad); a CPU tensor raises the usual "no CPU fallback" error."""
+    what = "keypoint_cost"
+    geom = _features_geom(fix, what, "fix")
+    if not torch.is_tensor(mov) or tuple(mov.shape) != tuple(fix.shape):
+        raise ValueError("%s: fix %s / mov %s differ in shape"
+                         % (what, tuple(fix.shape), tuple(mov.shape) if torch.is_tensor(mov) else mov))
+    _features_geom(mov, what, "mov")
+    nd, B, C, D, H, W = geom
+    K = _keypoint_points(pts, what, "pts", B, nd)
+    r, step = _keypoint_window(radius, step, nd, what)
+    patch = _keypoint_int(patch, 0, KEYPOINT_MAX_PATCH, what, "patch")
+    E = 2 * (r * step + patch) + 1
+    if E > KEYPOINT_MAX_EXTENT:
+        raise ValueError("%s: the staged extent 2 (radius step + patch) + 1 = %d exceeds KEYPOINT_MAX_EXTENT = %d"
+                         % (what, E, KEYPOINT_MAX_EXTENT))
+    Dn = (2 * r + 1) ** nd
+    if B * K * Dn >= 2 ** 31:
+        raise ValueError("%s: the cost rows [%d,%d,%d] have 2^31 or more elements" % (what, B, K, Dn))
+    if B > 65535:
+        raise ValueError("%s: B must be <= 65535, got %s" % (what, tuple(fix.shape)))
+    _need(fix, mov, pts)
+    if mov.device != fix.device or pts.device != fix.device:
+        raise DfmirHipError("%s: fix on %s, mov on %s, pts on %s" % (what, fix.device, mov.device, pts.device))
+    fix, mov, pts = _c(fix), _c(mov), _c(pts)
+    cost = torch.empty((B, K, Dn), device=fix.device, dtype=torch.float32)
+    check(lib().dfmir_keypoint_cost(nd, _p(fix), _p(mov), _p(pts), _p(cost), B, C, K, D, H, W, r, step, patch, _st()))
+    return cost
+
+
+@torch.no_grad()
+def keypoint_argmin(cost, radius, step=1, prior=None, coeff=0.0):
+    """The sparse coupled argmin over each keypoint's cost row (build-defined) -> (idx int32 [B,K], disp fp32 [B,K,nd]):
+
+        idx[b,k] = argmin_j ( cost[b,k,j] + coeff * sum_a (step*d_j[a] - prior[b,k,a])^2 ),        disp[b,k] = step * d_idx
+
+    cost: [B,K,D] as ops.keypoint_cost lays it out, D = (2 radius + 1)^nd with nd = 2 or 3 (prior's last extent; without a
+    prior the one nd whose D matches, 3-D first); prior: [B,K,nd] fp32 in voxels, None = the plain argmin (coeff is then not
+    read); coeff: a finite float >= 0.  The lowest j wins a tie; only finite penalised values compete, so a NaN (or infinite)
+    entry is never selected, and a row without a finite entry gives idx 0 and disp NaN -- q + disp is then a padding point for
+    ops.tps_fit.  One wave per keypoint; the cross-lane reduction carries (value, j).  The squares are added in the order (z,)
+    y, x in fp32.  Nothing syncs with the host; no gradient.  ValueError before any launch on a cost that is not [B,K,D] fp32,
+    a radius or step outside KEYPOINT_MAX_RADIUS[nd] / KEYPOINT_MAX_STEP, a D that is no (2 radius + 1)^nd, a prior of another
+    shape, a coeff that is negative or not finite, 2^31 or more elements and a tensor that requires grad; a CPU tensor raises
+    the usual "no CPU fallback" error."""
+    what = "keypoint_argmin"
+    if not torch.is_tensor(cost) or cost.dim() != 3 or cost.shape[0] < 1 or cost.shape[1] < 1:
+        raise ValueError("%s: cost must be a [B,K,D] tensor, got %s"
+                         % (what, tuple(cost.shape) if torch.is_tensor(cost) else type(cost).__name__))
+    if cost.dtype != torch.float32:
+        raise ValueError("%s: fp32 tensors only (cost is %s)" % (what, cost.dtype))
+    if cost.requires_grad:
+        raise ValueError("%s: cost requires grad, but the op has no gradient (detach it)" % what)
+    if cost.numel() >= 2 ** 31:
+        raise ValueError("%s: cost %s has 2^31 or more elements" % (what, tuple(cost.shape)))
+    B, K, Dn = (int(n) for n in cost.shape)
+    if isinstance(radius, bool) or not isinstance(radius, int) or radius < 1:
+        raise ValueError("%s: radius must be an integer >= 1, got %r" % (what, radius))
+    if prior is not None:
+        if not torch.is_tensor(prior) or prior.dim() != 3 or int(prior.shape[2]) not in (2, 3):
+            raise ValueError("%s: prior must be [B,K,nd], got %s"
+                             % (what, tuple(prior.shape) if torch.is_tensor(prior) else type(prior).__name__))
+        nd = int(prior.shape[2])
+        _keypoint_points(prior, what, "prior", B, nd, K)
+    else:
+        nd = 3 if (2 * radius + 1) ** 3 == Dn else 2
+    r, step = _keypoint_window(radius, step, nd, what)
+    if (2 * r + 1) ** nd != Dn:
+        raise ValueError("%s: cost %s must have (2 radius + 1)^nd = %d entries per row" % (what, tuple(cost.shape), (2 * r + 1) ** nd))
+    try:
+        coeff = float(coeff)
+    except (TypeError, ValueError):
+        raise ValueError("%s: coeff must be a finite number >= 0, got %r" % (what, coeff))
+    if not 0.0 <= coeff < float('inf'):
+        raise ValueError("%s: coeff must be a finite number >= 0, got %r" % (what, coeff))
+    _need(cost, prior)
+    if prior is not None and prior.device != cost.device:
+        raise DfmirHipError("%s: cost on %s, prior on %s" % (what, cost.device, prior.device))
+    cost = _c(cost)
+    prior = None if prior is None else _c(prior)
+    idx = torch.empty((B, K), device=cost.device, dtype=torch.int32)
+    disp = torch.empty((B, K, nd), device=cost.device, dtype=torch.float32)
+    check(lib().dfmir_keypoint_argmin(nd, _p(cost), _p(prior), coeff, _p(idx), _p(disp), B * K, r, step, _st()))
+    return idx, disp
 
 
 class MulFn(Function):

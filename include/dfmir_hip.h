@@ -948,6 +948,56 @@ int dfmir_tps_fwd(int nd, const double* coef, const float* ctrl, const float* po
                   int D, int H, int W, double sz, double sy, double sx, void* stream);
 int dfmir_tps_bwd_coef(int nd, const float* ctrl, const float* gout, double* dcoef, void* ws, int B, int K, int D, int H,
                        int W, double sz, double sy, double sx, void* stream);
+/* Keypoint detection and sparse matching (build-defined: the reference has no keypoint code).  Everything fp32, nd = 2 or 3 (D
+ * is not read when nd == 2), axis order (z,) y, x, S = voxels per sample, every extent >= 2.
+ * dfmir_keypoint_products: I [B][(D)][H][W] -> T [B][NP][(D)][H][W], NP = nd (nd + 1) / 2 planes in the order zz, zy, zx, yy, yx,
+ *   xx (2-D: yy, yx, xx):  T_ab = g_a g_b  with  g_a(x) = (I(min(x_a + 1, S_a - 1)) - I(max(x_a - 1, 0))) / (2 h_a),  the
+ *   difference, 2 h_a, the quotient and the product each rounded to fp32; spacing h = (hz, hy, hx) positive and finite (hz is
+ *   not read when nd == 2).  A thread writes all planes of its voxel; the image is staged with its halo (stencil_tile.h).
+ * dfmir_keypoint_response: T as above, smoothed by the caller (dfmir_gauss_smooth over B NP planes) -> R [B][(D)][H][W]:
+ *   R = det(T) / trace(adj(T))  ( = 1 / trace(T^-1); 2-D: det / trace), formed in DOUBLE from the fp32 planes -- 3-D, with T =
+ *   [a b c; b d e; c e f]: A00 = d f - e e, A11 = a f - c c, A22 = a d - b b, det = a A00 - b (b f - c e) + c (b e - c d), trace
+ *   (adj) = (A00 + A11) + A22 -- and rounded once; 0 where the denominator is not > 0 or a plane or the quotient is not finite.
+ * dfmir_keypoint_nms: out[b][x] = R[b][x] where x is selected, else 0.  Selected: R(x) > threshold, mask[b][x] != 0 (mask [B][S]
+ *   or NULL) and for every other y of the (2 radius + 1)^nd window clipped to the volume R(y) < R(x), or R(y) == R(x) and y has
+ *   the HIGHER linear index: the lowest index wins a plateau.  A NaN is never selected and compares as -inf as a neighbour; the
+ *   mask does not remove a competitor.  radius in [1, DFMIR_KEYPOINT_NMS_MAX_RADIUS], threshold finite.  One launch: tile plus
+ *   halo in LDS, a direct window walk that leaves at the first neighbour that wins.
+ * dfmir_keypoint_cost: fix, mov [B][C][(D)][H][W], 1 <= C <= 16; pts [B][K][nd] voxel coordinates; cost [B][K][Dn], Dn = (2
+ *   radius + 1)^nd.  q = rint(pts[b][k]) (ties to even); a row whose point has a non-finite coordinate or a q outside the volume
+ *   is all NaN; otherwise, with P = (2 patch + 1)^nd,
+ *     cost[b][k][j] = 1 / (C P) sum_c sum_{o in {-patch .. patch}^nd} (fix[b][c][q + o] - mov[b][c][q + o + step d_j])^2
+ *   both sides reading 0 outside the volume, j enumerating d_j in {-radius .. radius}^nd in row-major order (dz,) dy, dx with
+ *   -radius first (dfmir_dsearch_cost's order).  The difference is fp32, its square and the sum are float64 in ONE order for
+ *   every j (oz, c, oy, ox), times 1 / (C P) in float64, rounded once: displacements whose reads all fall outside the volume tie
+ *   bit for bit.  One workgroup per keypoint; the fixed patch and, plane by plane, the moving search region pass through LDS.
+ *   radius in [1, DFMIR_KEYPOINT_MAX_RADIUS_3D] (nd = 3) or [1, .._2D] (nd = 2), step in [1, DFMIR_KEYPOINT_MAX_STEP], patch in
+ *   [0, DFMIR_KEYPOINT_MAX_PATCH], and the staged extent E = 2 (radius step + patch) + 1 <= DFMIR_KEYPOINT_MAX_EXTENT (one plane
+ *   of E^2 floats beside the largest patch in 64 KB of LDS): there is no unstaged path.
+ * dfmir_keypoint_argmin: cost [rows][Dn], prior [rows][nd] in voxels or NULL (= the plain argmin, coeff is then not read):
+ *     idx[row] = argmin_j ( cost[row][j] + coeff * sum_a (step d_j[a] - prior[row][a])^2 ),    disp[row][a] = step d_idx[a]
+ *   the squares added in the order (z,) y, x in fp32.  Only FINITE penalised values compete (a NaN or an infinite entry is never
+ *   selected); the lowest j wins a tie; a row without a finite value gives idx 0 and disp NaN.  One wave per row, the
+ *   cross-lane reduction carries (value, j).  coeff finite and >= 0.
+ * Refused ("invalid argument", nothing is launched): nd outside {2, 3}, B < 1, an extent < 2, C outside [1, 16], K < 1, B > 65535
+ * (cost), a parameter outside its range, a spacing or threshold that is not finite (spacing: and positive), 2^31 or more
+ * elements in any tensor, a NULL pointer other than mask / prior, out aliasing an input.  Nothing syncs, allocates or keeps
+ * state; no atomics: every output is bit-identical from run to run. */
+#define DFMIR_KEYPOINT_NMS_MAX_RADIUS 8
+#define DFMIR_KEYPOINT_MAX_RADIUS_3D 8
+#define DFMIR_KEYPOINT_MAX_RADIUS_2D 16
+#define DFMIR_KEYPOINT_MAX_STEP 4
+#define DFMIR_KEYPOINT_MAX_PATCH 3
+#define DFMIR_KEYPOINT_MAX_EXTENT 96
+int dfmir_keypoint_products(int nd, const float* I, float* T, int B, int D, int H, int W, float hz, float hy, float hx,
+                            void* stream);
+int dfmir_keypoint_response(int nd, const float* T, float* R, int B, int D, int H, int W, void* stream);
+int dfmir_keypoint_nms(int nd, const float* R, const float* mask, float* out, int B, int D, int H, int W, int radius,
+                       float threshold, void* stream);
+int dfmir_keypoint_cost(int nd, const float* fix, const float* mov, const float* pts, float* cost, int B, int C, int K, int D,
+                        int H, int W, int radius, int step, int patch, void* stream);
+int dfmir_keypoint_argmin(int nd, const float* cost, const float* prior, float coeff, int* idx, float* disp, long long rows,
+                          int radius, int step, void* stream);
 /* NMI_Loss (util/losses.py:263-348): out[0] = -MI of the soft-binned (Parzen) joint histogram of y_true and y_pred, both
  * first clamped to [0, max_clip]; all n voxels (batch and channels included) form ONE histogram.  Per voxel
  * a_k = exp(-preterm (y_true - c_k)^2) normalised over k (b_k the same for y_pred), pab[i][j] = sum_v b[i] a[j] / V,
